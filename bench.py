@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- minimum-snap trajectories/sec on N MI355X (one process per GPU).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -161,6 +161,9 @@ def parse():
     ap.add_argument("--backend", default="nccl", choices=("nccl", "gloo"),
                     help="nccl = RCCL over xGMI (default); gloo only to rehearse N > 1 on a 1-GPU box "
                          "(ranks then share device local_rank %% device_count, the all-gather runs on host copies)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write rank 0's outputs of the last timed step (coef, dur, status) "
+                         "as DIR/<name>.npy in float64, to compare two builds output for output")
     return ap.parse_args()
 
 
@@ -205,6 +208,28 @@ class GridBatch:
         rc = self._fn(*self._args)
         if rc != 0:
             raise RuntimeError(f"msnap_solve_grid_device failed: {rc}")
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, outputs, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: `outputs` maps a name to a tensor whose leading axis is the drone; each is written as
+    out_dir/<name>.npy in float64.  Above `limit` bytes in all, the same rows of every tensor are written for a
+    fixed seeded sample of the drones (identical from run to run for the same batch size), and the sampled drone
+    indices as drone_index.npy.  Returns the names written."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    n = next(iter(outputs.values())).shape[0]
+    per_drone = sum(8 * (x.numel() // n) for x in outputs.values())
+    if per_drone * n > limit:
+        idx = np.sort(np.random.default_rng(0).choice(n, size=limit // (per_drone + 8), replace=False))
+        sel = torch.from_numpy(idx)
+        outputs = {name: x.index_select(0, sel.to(x.device)) for name, x in outputs.items()}
+        outputs["drone_index"] = sel
+    for name, x in outputs.items():
+        np.save(os.path.join(out_dir, name + ".npy"), x.cpu().numpy().astype(np.float64))
+    return sorted(outputs)
 
 
 def timed_steps(torch, dist, batch, ctx, steps, warmup, use_graph, world):
@@ -946,6 +971,9 @@ def main():
     use_graph = not args.no_graph
     wall, dev_ms = timed_steps(torch, dist, batch, ctx, args.steps, args.warmup, use_graph, world)
     kname = ctx.last_kernel()       # the kernel instance libmsnap chose for this launch (msnap_last_kernel)
+    if args.dump_outputs and rank == 0:
+        # the K steps solve the same batch into the same buffers: they hold what the last timed step computed
+        dump_outputs(args.dump_outputs, {"coef": batch.coef, "dur": batch.dur, "status": batch.status})
     assert int(batch.status.abs().sum().item()) == 0, "solve reported per-drone failures"
     head_err, _ = oracle_parity(batch.coef, wp, t, order, np.arange(args.drones))
     wall_max, dev_ms_max, head_err = max_over_ranks(torch, dist, [wall, dev_ms, head_err], red_dev, use_pg)

@@ -65,14 +65,14 @@ def test_no_cpu_fallback_in_product():
 
 
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):
-    import importlib
+    # (monkeypatch restores the module's state; a reload would define a second MsnapError class, and every later
+    # `pytest.raises(MsnapError)` in the session would miss what the library raises)
     from drone_path_planning_python_amd import _lib
     monkeypatch.setattr(_lib, "_lib", None)
     monkeypatch.setattr(_lib, "LIB_PATH", str(tmp_path / "nope.so"))
     with pytest.raises(OSError):
         _lib.load()
     monkeypatch.undo()
-    importlib.reload(_lib)
 
 
 def test_prefetch_wait_counts_match_the_code_object():

@@ -36,7 +36,9 @@ def test_c_oracle_under_address_and_ub_sanitizers():
         pytest.skip("no gcc / libasan here")
     subprocess.run(["make", "-C", ORACLE, "sanitize"], check=True, capture_output=True)
     lib = os.path.join(ORACLE, "libmsnap_oracle_san.so")
-    env = dict(os.environ, LD_PRELOAD=asan, MSNAP_ORACLE_LIB=lib, OMP_NUM_THREADS="4",
+    # libasan first (the runtime must be the first library loaded), whatever the environment preloads kept behind it
+    preload = ":".join(p for p in (asan, os.environ.get("LD_PRELOAD")) if p)
+    env = dict(os.environ, LD_PRELOAD=preload, MSNAP_ORACLE_LIB=lib, OMP_NUM_THREADS="4",
                ASAN_OPTIONS="detect_leaks=0:abort_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
     # the C oracle against the reference-generated goldens, the order-9 extended-precision fixture and the
     # full-size formation fixtures (sampler + both collision passes), all through the sanitized library
@@ -68,8 +70,11 @@ def test_c_abi_host_side_under_address_and_ub_sanitizers(tmp_path):
         subprocess.run([hipcc, *extra, *SAN, *inc, "-c", src, "-o", obj], check=True, capture_output=True)
         objs.append(obj)
     subprocess.run([hipcc, *SAN, *objs, "-o", exe], check=True, capture_output=True)
+    # every device hidden: on a machine with a GPU msnap_create would otherwise get as far as the kernel-setup stand-in
+    # of host_stubs.cpp, which aborts; hidden, the program takes the no-device path it is written for everywhere
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1",
-               LSAN_OPTIONS="suppressions=" + os.path.join(ROOT, "tests", "c_abi", "lsan.supp"))
+               LSAN_OPTIONS="suppressions=" + os.path.join(ROOT, "tests", "c_abi", "lsan.supp"),
+               HIP_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="-1")
     r = subprocess.run([exe], env=env, capture_output=True, text=True)
     out = r.stdout + r.stderr
     assert r.returncode == 0 and "abi_args: 0 failure(s)" in r.stdout, out[-3000:]
