@@ -2840,6 +2840,48 @@ __device__ __forceinline__ double pt_tri_d2(double px, double py, double pz, con
   return ex * ex + ey * ey + ez * ez;
 }
 
+// Ericson's regions assume a triangle of nonzero area: with a repeated vertex they end in 0/0 (a NaN that never wins
+// the minimum), with three collinear vertices sign noise in va/vb/vc can pick the face region and a far too large
+// distance.  A triangle whose |ab x ac|^2 is below kTriDegenerate |ab|^2 |ac|^2 (sin^2 of the angle at a) is taken as
+// the union of its three closed edges: a segment or a point, exactly, when the area is zero, and within the triangle's
+// width (< 5e-6 x its longest edge) otherwise.  Both oracles restate this test and pt_degenerate_tri_d2.
+constexpr double kTriDegenerate = 1e-10;
+
+__device__ __forceinline__ bool tri_degenerate(const double *__restrict__ t) {
+#pragma clang fp contract(off)
+  const double abx = t[3] - t[0], aby = t[4] - t[1], abz = t[5] - t[2];
+  const double acx = t[6] - t[0], acy = t[7] - t[1], acz = t[8] - t[2];
+  const double nx = aby * acz - abz * acy, ny = abz * acx - abx * acz, nz = abx * acy - aby * acx;
+  const double nn = nx * nx + ny * ny + nz * nz;
+  const double ab2 = abx * abx + aby * aby + abz * abz, ac2 = acx * acx + acy * acy + acz * acz;
+  return nn <= kTriDegenerate * (ab2 * ac2);
+}
+
+// squared distance from p to the closed segment ab (a point when a == b)
+__device__ __forceinline__ double pt_seg_d2(double px, double py, double pz, double ax, double ay, double az,
+                                            double bx, double by, double bz) {
+#pragma clang fp contract(off)
+  const double ux = bx - ax, uy = by - ay, uz = bz - az;
+  const double wx = px - ax, wy = py - ay, wz = pz - az;
+  const double l2 = ux * ux + uy * uy + uz * uz;
+  double u = 0.0;
+  if (l2 > 0.0) {
+    u = (wx * ux + wy * uy + wz * uz) / l2;
+    u = (u > 0.0) ? u : 0.0;
+    u = (u < 1.0) ? u : 1.0;
+  }
+  const double ex = px - (ax + u * ux), ey = py - (ay + u * uy), ez = pz - (az + u * uz);
+  return ex * ex + ey * ey + ez * ez;
+}
+
+__device__ __forceinline__ double pt_degenerate_tri_d2(double px, double py, double pz, const double *__restrict__ t) {
+  double d = pt_seg_d2(px, py, pz, t[0], t[1], t[2], t[3], t[4], t[5]);
+  const double d_bc = pt_seg_d2(px, py, pz, t[3], t[4], t[5], t[6], t[7], t[8]);
+  d = (d_bc < d) ? d_bc : d;
+  const double d_ca = pt_seg_d2(px, py, pz, t[6], t[7], t[8], t[0], t[1], t[2]);
+  return (d_ca < d) ? d_ca : d;
+}
+
 // squared distance between the box [lo, hi] and the bounding box of triangle t: a lower bound of every
 // point-triangle distance between them
 __device__ __forceinline__ double box_tri_lb2(const double (&lo)[3], const double (&hi)[3], const double *__restrict__ t) {
@@ -2896,10 +2938,13 @@ mesh_sweep_kernel(const double *__restrict__ pos, int N, int S, const double *__
       // the triangle with the smallest bound first: it usually sets the distance the others have to beat
       const double m = uniform_f64(wave_min_f64(lb));
       if (!(m < wbest)) continue;                              // (also when the group has no triangle: every bound inf)
+      // the group's zero-area triangles, one bit per lane: a scalar, so the choice below is a uniform branch
+      const unsigned long long degen = __ballot(tl < n_tris && tri_degenerate(tris + (size_t)(tl < n_tris ? tl : 0) * 9));
       {
         const int sel = __builtin_ctzll(__ballot(lb == m));    // wave-uniform: the ballot is a scalar
         lb = (lane == sel) ? INFINITY : lb;
-        const double v = pt_tri_d2(px, py, pz, tris + (size_t)(t0 + sel) * 9);
+        const double *tri = tris + (size_t)(t0 + sel) * 9;
+        const double v = ((degen >> sel) & 1ULL) ? pt_degenerate_tri_d2(px, py, pz, tri) : pt_tri_d2(px, py, pz, tri);
         best = (v < best) ? v : best;
         wbest = uniform_f64(wave_min_f64(best));
         done += 1;
@@ -2911,7 +2956,8 @@ mesh_sweep_kernel(const double *__restrict__ pos, int N, int S, const double *__
       for (int k = 1; cand; ++k) {
         const int sel = __builtin_ctzll(cand);
         cand &= cand - 1;
-        const double v = pt_tri_d2(px, py, pz, tris + (size_t)(t0 + sel) * 9);
+        const double *tri = tris + (size_t)(t0 + sel) * 9;
+        const double v = ((degen >> sel) & 1ULL) ? pt_degenerate_tri_d2(px, py, pz, tri) : pt_tri_d2(px, py, pz, tri);
         best = (v < best) ? v : best;
         done += 1;
         if ((k & 3) == 0 && cand) {
@@ -2958,8 +3004,12 @@ int launch_mesh_sweep(msnap_ctx *ctx, int n_drones, int n_samples, const double 
 // whether it touches the environment mesh, src/RigidBodyPlanners/fcl_checker.py:93-100).
 // FCL is not vendored in the reference (parity unpinned): the predicate here is "some
 // robot triangle and some environment triangle intersect as closed sets", decided by the
-// 17-axis separating-axis test (2 face normals, 9 edge x edge, 6 edge x normal for the
-// coplanar case).  One wavefront per state, lanes stride the triangle pairs.
+// 23-axis separating-axis test (2 face normals, 9 edge x edge, 12 edge x normal for the
+// coplanar case: each triangle's edges crossed with both normals, so that a triangle of zero
+// area -- whose own normal is zero -- still meets the in-plane axes of its segment).  Complete
+// in exact arithmetic for every pair in which at least one triangle has nonzero area; two zero-area triangles on
+// one line or in one plane can be reported as touching when they are not (the safe side).
+// One wavefront per state, lanes stride the triangle pairs.
 // ------------------------------------------------------------------------------------
 __device__ __forceinline__ bool sat_separates(const double (&P)[3][3], const double (&Q)[3][3], double lx, double ly,
                                               double lz) {
@@ -3006,6 +3056,11 @@ __device__ __forceinline__ bool tri_tri_intersect(const double (&P)[3][3], const
     double lx = n1y * e[i][2] - n1z * e[i][1], ly = n1z * e[i][0] - n1x * e[i][2], lz = n1x * e[i][1] - n1y * e[i][0];
     if (sat_separates(P, Q, lx, ly, lz)) return false;
     lx = n2y * f[i][2] - n2z * f[i][1]; ly = n2z * f[i][0] - n2x * f[i][2]; lz = n2x * f[i][1] - n2y * f[i][0];
+    if (sat_separates(P, Q, lx, ly, lz)) return false;
+    // the other triangle's in-plane normals of these edges: the only in-plane axes left when n1 or n2 is zero
+    lx = n2y * e[i][2] - n2z * e[i][1]; ly = n2z * e[i][0] - n2x * e[i][2]; lz = n2x * e[i][1] - n2y * e[i][0];
+    if (sat_separates(P, Q, lx, ly, lz)) return false;
+    lx = n1y * f[i][2] - n1z * f[i][1]; ly = n1z * f[i][0] - n1x * f[i][2]; lz = n1x * f[i][1] - n1y * f[i][0];
     if (sat_separates(P, Q, lx, ly, lz)) return false;
   }
   return true;

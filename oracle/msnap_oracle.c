@@ -309,6 +309,39 @@ static double pt_tri_d2(const double *p, const double *t) {
   return ex * ex + ey * ey + ez * ez;
 }
 
+/* a zero-area triangle (|ab x ac|^2 <= 1e-10 |ab|^2 |ac|^2) as the union of its closed edges, as
+ * msnap_aux.hip tri_degenerate / pt_seg_d2 / pt_degenerate_tri_d2 */
+static int tri_degenerate(const double *t) {
+  const double abx = t[3] - t[0], aby = t[4] - t[1], abz = t[5] - t[2];
+  const double acx = t[6] - t[0], acy = t[7] - t[1], acz = t[8] - t[2];
+  const double nx = aby * acz - abz * acy, ny = abz * acx - abx * acz, nz = abx * acy - aby * acx;
+  const double nn = nx * nx + ny * ny + nz * nz;
+  const double ab2 = abx * abx + aby * aby + abz * abz, ac2 = acx * acx + acy * acy + acz * acz;
+  return nn <= 1e-10 * (ab2 * ac2);
+}
+
+static double pt_seg_d2(const double *p, const double *a, const double *b) {
+  const double ux = b[0] - a[0], uy = b[1] - a[1], uz = b[2] - a[2];
+  const double wx = p[0] - a[0], wy = p[1] - a[1], wz = p[2] - a[2];
+  const double l2 = ux * ux + uy * uy + uz * uz;
+  double u = 0.0;
+  if (l2 > 0.0) {
+    u = (wx * ux + wy * uy + wz * uz) / l2;
+    u = (u > 0.0) ? u : 0.0;
+    u = (u < 1.0) ? u : 1.0;
+  }
+  const double ex = p[0] - (a[0] + u * ux), ey = p[1] - (a[1] + u * uy), ez = p[2] - (a[2] + u * uz);
+  return ex * ex + ey * ey + ez * ez;
+}
+
+static double pt_degenerate_tri_d2(const double *p, const double *t) {
+  double d = pt_seg_d2(p, t, t + 3);
+  const double d_bc = pt_seg_d2(p, t + 3, t + 6);
+  d = (d_bc < d) ? d_bc : d;
+  const double d_ca = pt_seg_d2(p, t + 6, t);
+  return (d_ca < d) ? d_ca : d;
+}
+
 /* pos [N][S][3], tris [T][3][3]: min over samples and triangles of the point-triangle distance;
  * hit = min_dist < r */
 void msnap_oracle_mesh_sweep(int n, int n_samples, const double *pos, int n_tris, const double *tris,
@@ -323,7 +356,8 @@ void msnap_oracle_mesh_sweep(int n, int n_samples, const double *pos, int n_tris
     double best = INFINITY;
     for (int s = 0; s < n_samples; ++s)
       for (int t = 0; t < n_tris; ++t) {
-        const double v = pt_tri_d2(pos + ((size_t)i * n_samples + s) * 3, tris + (size_t)t * 9);
+        const double *tri = tris + (size_t)t * 9, *p = pos + ((size_t)i * n_samples + s) * 3;
+        const double v = tri_degenerate(tri) ? pt_degenerate_tri_d2(p, tri) : pt_tri_d2(p, tri);
         if (v < best) best = v;
       }
     min_dist[i] = sqrt(best);

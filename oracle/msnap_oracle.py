@@ -545,16 +545,57 @@ def point_triangle_dist2(p, a, b, c) -> float:
     return float(e @ e)
 
 
+TRI_DEGENERATE = 1e-10      # msnap_aux.hip kTriDegenerate
+
+
+def tri_degenerate(a, b, c) -> bool:
+    """msnap_aux.hip tri_degenerate: |ab x ac|^2 <= 1e-10 |ab|^2 |ac|^2 (zero area, up to rounding)."""
+    abx, aby, abz = float(b[0]) - float(a[0]), float(b[1]) - float(a[1]), float(b[2]) - float(a[2])
+    acx, acy, acz = float(c[0]) - float(a[0]), float(c[1]) - float(a[1]), float(c[2]) - float(a[2])
+    nx, ny, nz = aby * acz - abz * acy, abz * acx - abx * acz, abx * acy - aby * acx
+    nn = nx * nx + ny * ny + nz * nz
+    return nn <= TRI_DEGENERATE * ((abx * abx + aby * aby + abz * abz) * (acx * acx + acy * acy + acz * acz))
+
+
+def point_segment_dist2(p, a, b) -> float:
+    """msnap_aux.hip pt_seg_d2: squared distance from p to the closed segment ab (a point when a == b)."""
+    px, py, pz = (float(v) for v in p)
+    ax, ay, az = (float(v) for v in a)
+    ux, uy, uz = float(b[0]) - ax, float(b[1]) - ay, float(b[2]) - az
+    wx, wy, wz = px - ax, py - ay, pz - az
+    l2 = ux * ux + uy * uy + uz * uz
+    u = 0.0
+    if l2 > 0.0:
+        u = (wx * ux + wy * uy + wz * uz) / l2
+        u = u if u > 0.0 else 0.0
+        u = u if u < 1.0 else 1.0
+    ex, ey, ez = px - (ax + u * ux), py - (ay + u * uy), pz - (az + u * uz)
+    return ex * ex + ey * ey + ez * ez
+
+
+def point_degenerate_triangle_dist2(p, a, b, c) -> float:
+    """msnap_aux.hip pt_degenerate_tri_d2: a zero-area triangle as the union of its closed edges."""
+    d = point_segment_dist2(p, a, b)
+    d_bc = point_segment_dist2(p, b, c)
+    d = d_bc if d_bc < d else d
+    d_ca = point_segment_dist2(p, c, a)
+    return d_ca if d_ca < d else d
+
+
 def mesh_sweep(pos: np.ndarray, tris: np.ndarray, radius: float):
     """pos [N,S,3], tris [Tn,3,3] -> (min_dist [N], hit [N] bool: min_dist < r)."""
     N, S, _ = pos.shape
     mind = np.full(N, np.inf)
     tris = np.asarray(tris, dtype=np.float64)
+    degen = [tri_degenerate(t[0], t[1], t[2]) for t in tris]
     for i in range(N):
         best = np.inf
         for s in range(S):
-            for t in tris:
-                d2 = point_triangle_dist2(pos[i, s], t[0], t[1], t[2])
+            for t, dg in zip(tris, degen):
+                if dg:
+                    d2 = point_degenerate_triangle_dist2(pos[i, s], t[0], t[1], t[2])
+                else:
+                    d2 = point_triangle_dist2(pos[i, s], t[0], t[1], t[2])
                 if d2 < best:
                     best = d2
         mind[i] = math.sqrt(best)
@@ -574,7 +615,7 @@ def load_stl_binary(path: str) -> np.ndarray:
 # --------------------------------------------------------------------------
 # f4: batched isStateValid (RB_planning_sep_coll_check.py:208-226, fcl_checker.py:93-100).
 # python-fcl is not vendored: PARITY UNPINNED.  Predicate: closed triangles intersect,
-# by the 17-axis separating-axis test; same operation order as the kernel.
+# by the 23-axis separating-axis test; same operation order as the kernel.
 # --------------------------------------------------------------------------
 def _separates(P, Q, L):
     p = [P[v][0] * L[0] + P[v][1] * L[1] + P[v][2] * L[2] for v in range(3)]
@@ -605,6 +646,10 @@ def tri_tri_intersect(P, Q) -> bool:
         if _separates(P, Q, _cross(n1, e[i])):
             return False
         if _separates(P, Q, _cross(n2, f[i])):
+            return False
+        if _separates(P, Q, _cross(n2, e[i])):
+            return False
+        if _separates(P, Q, _cross(n1, f[i])):
             return False
     return True
 
