@@ -18,10 +18,10 @@ int record_hip_error(msnap_ctx *ctx, hipError_t e, const char *what) {
   return MSNAP_EHIP;
 }
 
-int handover_form(const msnap_ctx *ctx, const void *ptr, int n, int n_samples) {
+int handover_form(const msnap_ctx *ctx, const void *ptr, const void *pos, int n, int n_samples) {
   if (!ptr) return 0;
   for (const auto &h : ctx->handover)
-    if (h.ptr == ptr) return (h.n == n && h.s == n_samples) ? h.form : 0;
+    if (h.ptr == ptr) return (h.pos == pos && h.n == n && h.s == n_samples) ? h.form : 0;
   return 0;
 }
 
@@ -109,6 +109,7 @@ static int *option_slot(msnap_ctx *ctx, const char *name) {
   if (!strcmp(name, "collide_last_cull")) return &ctx->collide_last_cull;
   if (!strcmp(name, "collide_last_shares")) return &ctx->collide_last_shares;
   if (!strcmp(name, "collide_last_sym")) return &ctx->collide_last_sym;   // (read: what the last pass did)
+  if (!strcmp(name, "collide_last_handover")) return &ctx->collide_last_handover;
   if (!strcmp(name, "own_stream_priority")) return &ctx->own_stream_priority;   // (read side; set has its own branch)
   return nullptr;
 }
@@ -693,14 +694,15 @@ int msnap_formation_whole_pass_pays(msnap_ctx *ctx, int n_drones, int n_ranks, i
 
 // What the pass over these drones as a whole swarm will read from the sampler's second output, put on record for that
 // pass: behind the broad phase the boxes and sort keys (true: the sampler has the samples in LDS; the pass then needs
-// no key launch), otherwise the transposed row image (false).  A buffer seen before keeps its slot.
-static bool record_handover(msnap_ctx *ctx, const double *pos_t, int n_drones, int n_samples) {
+// no key launch), otherwise the transposed row image (false) -- paired with the positions `pos` they were computed
+// from.  A buffer seen before keeps its slot.
+static bool record_handover(msnap_ctx *ctx, const double *pos, const double *pos_t, int n_drones, int n_samples) {
   const bool keys = formation_collide_takes_broad_phase(ctx, n_drones, 0, n_drones, n_samples);
   msnap_ctx::Handover *rec = nullptr;
   for (auto &h : ctx->handover)
     if (h.ptr == (const void *)pos_t) rec = &h;
   if (!rec) rec = &ctx->handover[ctx->handover_next++ % 8];
-  *rec = {pos_t, n_drones, n_samples, keys ? 2 : 1};
+  *rec = {pos_t, pos, n_drones, n_samples, keys ? 2 : 1};
   return keys;
 }
 
@@ -712,7 +714,7 @@ int msnap_sample_collide_device(msnap_ctx *ctx, int n_drones, int n_seg, const d
   if (n_drones == 0 || n_samples == 0) return MSNAP_OK;
   if (!coef || !dur || !pos || !pos_t) return MSNAP_EINVAL;
   MSNAP_HIP(ctx, hipSetDevice(ctx->device));
-  const bool keys = record_handover(ctx, pos_t, n_drones, n_samples);
+  const bool keys = record_handover(ctx, pos, pos_t, n_drones, n_samples);
   return launch_sample(ctx, n_drones, n_seg, coef, dur, dt, n_samples, 3, pos, pos_t, keys);
 }
 
@@ -726,7 +728,7 @@ int msnap_solve_grid_sample_device(msnap_ctx *ctx, int n_drones, int n_seg, cons
   MSNAP_HIP(ctx, hipSetDevice(ctx->device));
   if (n_samples == 0) return launch_solve_grid(ctx, n_drones, wp, coef, dur, status);
   if (!pos) return MSNAP_EINVAL;
-  const bool keys = pos_t && record_handover(ctx, pos_t, n_drones, n_samples);
+  const bool keys = pos_t && record_handover(ctx, pos, pos_t, n_drones, n_samples);
   return launch_grid_sample(ctx, n_drones, wp, dt, n_samples, coef, dur, status, pos, pos_t, keys);
 }
 

@@ -1715,11 +1715,19 @@ collide_finish_groups_kernel(int N, const int32_t *__restrict__ oid, const int32
   const int lane = threadIdx.x & (kWave - 1), w = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
   int *sIt = sItAll[w];
   const int gq = blockIdx.x * kFinishWaves + w;
-  if (gq >= cg.nG || meta[kMetaGroups] > cg.cap) return;      // (more survivors than list slots: the share evaluator runs)
+  if (gq >= cg.nG) return;
   int pl[kChunks];
 #pragma unroll
   for (int c = 0; c < kChunks; ++c)
     pl[c] = (c * kWave < gq && c * kWave + lane < gq) ? cg.blist[(size_t)gq * cg.nG + c * kWave + lane] : 0;
+  if (meta[kMetaGroups] > cg.cap) {
+    // more survivors than list slots: the share evaluator runs.  The selection still filled the reverse lists of the
+    // first cap items -- cleared here as below, the next pass trusts them to be all-zero (blist_clean)
+#pragma unroll
+    for (int c = 0; c < kChunks; ++c)
+      if (pl[c] > 0) cg.blist[(size_t)gq * cg.nG + c * kWave + lane] = 0;
+    return;
+  }
   const int nA = cg.acnt[gq], sA = cg.astart[gq];
   // lane = 8 e + k: entry slot e, drone k of the group
   const int k = lane & (kColBlock - 1), e = lane >> 3;
@@ -2415,6 +2423,7 @@ int launch_formation_collide(msnap_ctx *ctx, int n_rows, int row_offset, int n_c
   g.I_lo = 0;
   g.I_hi = g.n_rb - 1;
   g.part = 0;
+  ctx->collide_last_handover = 0;
   if (n_cols == 0) {
     // nobody to collide with: the merge of nothing writes inf / -1 / 0
     g.os = g.oe = 0;
@@ -2514,7 +2523,8 @@ int launch_formation_collide(msnap_ctx *ctx, int n_rows, int row_offset, int n_c
     const long long all_groups = (long long)nJ * (nJ + 1) / 2;
     // Up to kCullGroupMaxDrones every group pair has a list slot; larger swarms get kGroupCapLarge slots and BOTH
     // evaluators are launched -- the share evaluator and its merge return at once unless the survivors overflowed the
-    // list (then the group launches did nothing): two empty launches on a pass of a quarter millisecond.
+    // list (then the group evaluator did nothing and the group fold only cleared the reverse-list entries the selection
+    // wrote for the first kGroupCapLarge items): two empty launches on a pass of a quarter millisecond.
     const bool all_fit = N <= kCullGroupMaxDrones;
     bool by_groups = false;
     if (ctx->collide_cull_mode == 2) {
@@ -2538,8 +2548,9 @@ int launch_formation_collide(msnap_ctx *ctx, int n_rows, int row_offset, int n_c
     const size_t entries = (by_groups && !both) ? 0 : (size_t)items_max * kRowBlock;
     const size_t centries = (by_groups && !both) ? 0 : (size_t)g.n_rb * spmax * N;
     const size_t gcap = !by_groups ? 0 : all_fit ? (size_t)all_groups : (size_t)kGroupCapLarge;
-    // the sampler's hand-over (msnap_sample_collide_device: boxes [N][6], then keys [N]) saves the key launch
-    const bool have_keys = handover_form(ctx, rows_t_in, N, n_samples) == 2;
+    // the sampler's hand-over (msnap_sample_collide_device: boxes [N][6], then keys [N]) saves the key launch -- when
+    // the sampler wrote it beside these positions
+    const bool have_keys = handover_form(ctx, rows_t_in, pos_cols, N, n_samples) == 2;
     // Buffers (doubles, then ints): sorted row image [E][Rp] | sorted columns [N][E] | box [N][6] | colbox [nJ][6] |
     // bound [N] | row-side entries | column-side slots | candidates [gcap][16] || entries (j) | slots (j, pre-filled -1) |
     // keys [N] | perm [N] | survivor list [shares] | cnt [n_rb] | meta | acnt, astart [nJ] | blist [nJ][nJ] (zeroed per
@@ -2562,7 +2573,8 @@ int launch_formation_collide(msnap_ctx *ctx, int n_rows, int row_offset, int n_c
     const double *box = have_keys ? rows_t_in : box_own;
     const unsigned *key = have_keys ? reinterpret_cast<const unsigned *>(rows_t_in + (size_t)N * 6) : key_own;
     CullGroups cg{glist, astart, acnt, blist, cand_d2, cand_j, (int)gcap, (int)nJ};
-    // the reverse lists are all-zero between passes (the fold zeroes what it read): they are cleared only when this
+    // the reverse lists are all-zero between passes (the fold zeroes what it read, also when the list overflowed and
+    // the share evaluator ran behind it -- the `both` launch of a larger swarm): they are cleared only when this
     // block has held something else since -- another layout, another evaluator, any other pass of the context -- and,
     // so that a graph replays whatever ran between its replays, always under stream capture
     // (nor is a block trusted that a graph may replay on between two eager passes)
@@ -2574,6 +2586,7 @@ int launch_formation_collide(msnap_ctx *ctx, int n_rows, int row_offset, int n_c
     ctx->collide_last_cull = 1;
     ctx->collide_last_by_groups = by_groups ? (all_fit ? 1 : 2) : 0;      // (2: while the survivors fit kGroupCapLarge)
     ctx->collide_last_n = N;
+    ctx->collide_last_handover = have_keys ? 2 : 0;
     if (!have_keys) {
       hipLaunchKernelGGL(collide_key_kernel, dim3((N + kKeyDrones - 1) / kKeyDrones), dim3(kWave * kKeyDrones), 0,
                          ctx->stream, pos_cols, N, n_samples, box_own, key_own);
@@ -2615,8 +2628,10 @@ int launch_formation_collide(msnap_ctx *ctx, int n_rows, int row_offset, int n_c
     return MSNAP_OK;
   }
   // (a row image is only what the sampler's record says it is: a hand-over in the keys form -- written for a whole-
-  // swarm pass that, by the options now in force, is not taken --, for other rows, or not on record is not one)
-  if (handover_form(ctx, rows_t_in, n_rows, n_samples) != 1) rows_t_in = nullptr;
+  // swarm pass that, by the options now in force, is not taken --, for other rows or other positions, or not on
+  // record is not one)
+  if (handover_form(ctx, rows_t_in, pos_rows, n_rows, n_samples) != 1) rows_t_in = nullptr;
+  ctx->collide_last_handover = rows_t_in ? 1 : 0;
   if (ctx->collide_sample_parts > 0) {
     g.sparts = ctx->collide_sample_parts < 8 ? ctx->collide_sample_parts : 8;
   } else if (ctx->collide_waves_per_cu == 0) {
@@ -2736,6 +2751,7 @@ int launch_formation_collide_part(msnap_ctx *ctx, int N, int n_samples, const do
   const size_t t_entries = (size_t)g.Rp * E;
   if ((part_entries + centries) * 12 > ((size_t)16 << 30)) return MSNAP_ENOMEM;
   ctx->collide_last_cull = 0;      // (the buffer the last broad-phase pass left its counts in is reused)
+  ctx->collide_last_handover = 0;
   ctx->collide_meta = nullptr;
   ctx->blist_clean = nullptr;      // (the block is about to hold this pass's buffers)
   int rc = ensure(ctx, ctx->stage[7],

@@ -113,14 +113,17 @@ struct msnap_ctx {
   // pass's choice of evaluator reads it without synchronising (csrc/msnap_aux.hip::cull_hint_pack)
   unsigned long long *cull_hint = nullptr;
   // what msnap_sample_collide_device left for the pairwise pass, and where (the last few buffers it wrote): 1 the
-  // transposed row image, 2 the per-drone boxes and sort keys of a whole-swarm pass behind the broad phase.  A buffer
-  // the pass is handed that is not on record -- or whose record does not fit the pass -- is ignored, never misread.
+  // transposed row image, 2 the per-drone boxes and sort keys of a whole-swarm pass behind the broad phase, each with
+  // the positions buffer the sampler wrote beside it.  A buffer the pass is handed that is not on record -- or whose
+  // record does not fit the pass, positions included -- is ignored, never misread.
   struct Handover {
     const void *ptr = nullptr;
+    const void *pos = nullptr;
     int n = 0, s = 0, form = 0;
   } handover[8];
   int handover_next = 0;
   int collide_last_sym = 0;     // "collide_last_sym" (read): 1 if the last msnap_formation_collide evaluated its own-range pairs once
+  int collide_last_handover = 0;   // "collide_last_handover" (read): the sampler's hand-over that pass read (0 none, 1 row image, 2 boxes and keys)
   int mesh_waves_per_cu = 0;    // "mesh_waves_per_cu": wavefronts per CU the mesh sweep's grid is capped at (0: one workgroup per drone)
   int own_stream_priority = 0;  // "own_stream_priority": 0 default, 1 lowest, 2 highest (re-creates own_stream)
   msnap::RetiredBuf *retired = nullptr;   // blocks kept alive for graphs captured before they were outgrown
@@ -133,8 +136,9 @@ namespace msnap {
 int record_hip_error(msnap_ctx *ctx, hipError_t e, const char *what);
 int ensure(msnap_ctx *ctx, DevBuf &b, size_t bytes);
 bool stream_is_capturing(const msnap_ctx *ctx);
-// form (1 row image, 2 boxes and keys; 0: not on record for n drones x n_samples) of a sampler hand-over buffer
-int handover_form(const msnap_ctx *ctx, const void *ptr, int n, int n_samples);
+// form (1 row image, 2 boxes and keys; 0: not on record for these positions, n drones x n_samples) of a sampler
+// hand-over buffer
+int handover_form(const msnap_ctx *ctx, const void *ptr, const void *pos, int n, int n_samples);
 // what the last broad-phase pass evaluated (device-side choice of collide_eval_kernel, restated on its counts)
 bool collide_counts_by_groups(const msnap_ctx *ctx, int n_drones, int shares_surviving, int group_pairs_surviving);
 

@@ -289,9 +289,14 @@ int msnap_formation_collide_device(msnap_ctx *ctx, int n_rows, int row_offset, i
  *     rows from it, 512 contiguous bytes per wave and load, and skips its own transposition pass), or
  *   - where the pass over the n_rows drones as a whole swarm runs behind the exact broad phase: every drone's path
  *     box and sort key (the sampler has the samples in LDS; the pass then starts with its sort, without a key launch).
- * The context remembers which of the two it last wrote and where; a buffer that is not that hand-over (or no longer
- * fits the options in force) is ignored, never misread.  Device pointers only: the pair exists to keep the formation
- * pipeline (sampler -> pairwise pass) on the GPU without the intermediate launch. */
+ * The context remembers which of the two it last wrote and where, as a pair (positions buffer pos, hand-over buffer
+ * pos_t): the pass reads the hand-over only when it is handed that same pair -- pos_rows (row image) or pos_cols (boxes
+ * and keys) the sampler's pos -- for the same drone and sample counts.  A buffer that is not that hand-over, comes with
+ * other positions or no longer fits the options in force is ignored, never misread: the pass computes its own image or
+ * keys.  A caller who rewrites the positions in place, without the sampler, must sample again; that case cannot be
+ * detected.  The read-only option "collide_last_handover" reports what the last pass read (0 nothing, 1 the row
+ * image, 2 the boxes and keys).  Device pointers only: the pair exists to keep the formation pipeline (sampler ->
+ * pairwise pass) on the GPU without the intermediate launch. */
 size_t msnap_collide_rows_t_doubles(int n_rows, int n_samples);
 /* 1 if msnap_formation_collide_t_device with these arguments reads the sampler's hand-over, 0 if not (paths shorter
  * than 6 samples take plain loops: the caller can then sample with msnap_sample and save the second output). */

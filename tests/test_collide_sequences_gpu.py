@@ -1,0 +1,262 @@
+"""Pairwise passes back to back on one context.
+
+A context carries state from one pairwise pass to the next, and some of it decides what the next pass trusts without
+checking: the group evaluator's reverse lists are taken to be all-zero ("blist_clean"), the previous pass's survivor
+counts pick the evaluator (read without synchronising), and the sampler's hand-over records say which buffers hold a
+row image or boxes and sort keys.  The single-pass parity tests cannot see any of it.  Every test here runs a sequence of
+passes on a context of its own and checks each pass, bit for bit, against the C oracle on the positions that pass got.
+"""
+from __future__ import annotations
+
+import functools
+
+import numpy as np
+import pytest
+
+import c_oracle
+from test_formation_full import _broad_phase_swarm
+
+R = 0.3
+GROUP_CAP_LARGE = 1 << 18      # list slots of a swarm above 8192 drones (csrc/msnap_aux.hip kGroupCapLarge)
+
+
+@functools.lru_cache(maxsize=None)
+def _swarm(kind, n, S):
+    """(positions, oracle) of one swarm, computed once per module."""
+    rng = np.random.default_rng([n, S, ("dense", "sparse", "teams").index(kind)])
+    pos = np.ascontiguousarray(_broad_phase_swarm(kind, n, S, rng))
+    return pos, c_oracle.formation_collide(pos, R)
+
+
+def _np(x):
+    return x.cpu().numpy() if hasattr(x, "cpu") else np.asarray(x)
+
+
+def _check(got, ref, what):
+    md, partner, hit = (_np(x) for x in got)
+    np.testing.assert_array_equal(md, ref[0], err_msg=f"min_dist, {what}")
+    np.testing.assert_array_equal(partner, ref[1], err_msg=f"partner, {what}")
+    np.testing.assert_array_equal(hit.astype(bool), ref[2], err_msg=f"hit, {what}")
+
+
+def _context():
+    from drone_path_planning_python_amd import Context
+    return Context(order=7, max_segments=16)
+
+
+def _host_pass(ctx, kind, n, S, what):
+    pos, ref = _swarm(kind, n, S)
+    _check(ctx.formation_collide(pos, pos, R), ref, what)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [9136, 16384])
+def test_group_list_overflow_leaves_the_reverse_lists_clean(n):
+    """Above 8192 drones the group evaluator has 2^18 list slots and the share evaluator is launched behind it.  A dense
+    swarm overflows the list; its selection still fills the reverse lists of the first 2^18 items, which the next group
+    pass of this size takes to be all-zero.  Dense then sparse is the order that goes wrong if they are not."""
+    S = 6
+    with _context() as ctx:
+        ctx.set_option("collide_cull_mode", 2)
+        for i, kind in enumerate(("dense", "sparse", "sparse", "dense", "dense", "sparse")):
+            what = f"pass {i} ({kind}, {n} drones)"
+            _host_pass(ctx, kind, n, S, what)
+            assert ctx.get_option("collide_last_cull") == 1, what
+            by_groups = ctx.get_option("collide_last_by_groups")
+            assert by_groups == (0 if kind == "dense" else 1), what
+            assert (ctx.get_option("collide_last_group_pairs") > GROUP_CAP_LARGE) == (kind == "dense"), what
+
+
+@pytest.mark.gpu
+def test_unsynchronised_passes_follow_a_hint_one_pass_old():
+    """"collide_cull_mode" 0 reads the previous pass's survivor counts without synchronising: passes queued back to back
+    choose their evaluator from counts that may be a pass old, so a pass after a dense one can still take the group
+    pairs -- on reverse lists the dense pass's overflow left.  Nothing between the four passes reads an option or
+    synchronises (either would refresh the counts)."""
+    import torch
+    n, S = 9136, 6
+    dev = torch.device("cuda", 0)
+    with _context() as ctx:
+        for i in range(2):      # host entry: synchronises, the next pass has this swarm's counts
+            _host_pass(ctx, "sparse", n, S, f"host pass {i}")
+        assert ctx.get_option("collide_last_cull") == 1
+        assert ctx.get_option("collide_last_by_groups") == 1       # a sparse swarm of this size takes the group pairs
+        kinds = ("dense", "sparse", "dense", "sparse")
+        pos = [torch.from_numpy(np.array(_swarm(k, n, S)[0])).to(dev) for k in kinds]
+        out = [(torch.full((n,), -1.0, dtype=torch.float64, device=dev), torch.full((n,), -7, dtype=torch.int32, device=dev),
+                torch.full((n,), -7, dtype=torch.int32, device=dev)) for _ in kinds]
+        torch.cuda.synchronize()
+        for p, (md, partner, hit) in zip(pos, out):
+            ctx.formation_collide_device(n, 0, n, S, p, p, R, md, partner, hit)
+        ctx.sync()
+        for i, (kind, o) in enumerate(zip(kinds, out)):
+            _check(o, _swarm(kind, n, S)[1], f"queued pass {i} ({kind})")
+
+
+def _interloper(ctx, what, n, S):
+    """One pass of another kind between two group passes at n drones."""
+    if what == "shares":
+        ctx.set_option("collide_cull_mode", 1)
+        try:
+            _host_pass(ctx, "teams", n, S, "shares pass")
+            assert ctx.get_option("collide_last_cull") == 1 and ctx.get_option("collide_last_by_groups") == 0
+        finally:
+            ctx.set_option("collide_cull_mode", 2)
+    elif what == "no_cull":
+        ctx.set_option("collide_no_cull", 1)
+        try:
+            _host_pass(ctx, "teams", n, S, "pass without the broad phase")
+            assert ctx.get_option("collide_last_cull") == 0
+        finally:
+            ctx.set_option("collide_no_cull", 0)
+    elif what == "grow":
+        _host_pass(ctx, "sparse", n + 1000, S, f"group pass at {n + 1000} drones")
+        assert ctx.get_option("collide_last_cull") == 1
+    elif what == "parts":
+        pos, ref = _swarm("teams", n, S)
+        blocks = np.stack([ctx.formation_collide_part(pos, p, 3) for p in range(3)])
+        _check(ctx.formation_collide_finish(blocks, n, R), ref, "parts and their fold")
+    elif what == "mesh":
+        pos = _swarm("teams", n, S)[0]
+        rng = np.random.default_rng(n)
+        tris = rng.uniform(-60.0, 60.0, size=(24, 3, 3))
+        md, hit = ctx.mesh_sweep(pos, tris, R)
+        rmd, rhit = c_oracle.mesh_sweep(pos, tris, R)
+        np.testing.assert_allclose(md, rmd, rtol=0, atol=1e-12)
+        np.testing.assert_array_equal(hit, rhit)
+    else:
+        raise ValueError(what)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("what", ["shares", "no_cull", "grow", "parts", "mesh"])
+@pytest.mark.parametrize("n", [3072, 8192])
+def test_group_passes_around_other_passes(n, what):
+    """Up to 8192 drones every group pair has a list slot and the fold clears the reverse lists it read.  A pass of
+    another kind between two group passes -- the shares, no broad phase (another layout of the same block), a larger
+    swarm (the block grows), the pass in parts, a mesh sweep -- leaves the next group pass exact."""
+    S = 7
+    with _context() as ctx:
+        ctx.set_option("collide_cull_mode", 2)
+        _host_pass(ctx, "dense", n, S, "first group pass")
+        assert ctx.get_option("collide_last_by_groups") == 1
+        _interloper(ctx, what, n, S)
+        for kind in ("sparse", "dense"):
+            _host_pass(ctx, kind, n, S, f"group pass ({kind}) after the {what} pass")
+            assert ctx.get_option("collide_last_cull") == 1 and ctx.get_option("collide_last_by_groups") == 1
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [3072, 8192])
+def test_group_pass_from_a_graph_between_eager_passes(n):
+    """A group pass captured in a graph never trusts the reverse lists; the eager passes after its replays share the
+    block with it.  All of them equal the oracle."""
+    import torch
+    S = 7
+    dev = torch.device("cuda", 0)
+    buf = torch.from_numpy(np.array(_swarm("dense", n, S)[0])).to(dev)
+    md = torch.empty((n,), dtype=torch.float64, device=dev)
+    partner = torch.empty((n,), dtype=torch.int32, device=dev)
+    hit = torch.empty((n,), dtype=torch.int32, device=dev)
+    side = torch.cuda.Stream()
+
+    def eager(kind, what):
+        buf.copy_(torch.from_numpy(np.array(_swarm(kind, n, S)[0])))
+        md.fill_(-1.0)
+        partner.fill_(-7)
+        ctx.formation_collide_device(n, 0, n, S, buf, buf, R, md, partner, hit)
+        side.synchronize()
+        _check((md, partner, hit), _swarm(kind, n, S)[1], what)
+
+    with _context() as ctx:
+        ctx.set_option("collide_cull_mode", 2)
+        with torch.cuda.stream(side):
+            ctx.set_stream(side.cuda_stream)
+            eager("dense", "eager pass before the capture")       # sizes the buffers
+            assert ctx.get_option("collide_last_by_groups") == 1
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, stream=side, capture_error_mode="thread_local"):
+                ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+                ctx.formation_collide_device(n, 0, n, S, buf, buf, R, md, partner, hit)
+            ctx.set_stream(side.cuda_stream)
+            for kind in ("sparse", "dense"):
+                buf.copy_(torch.from_numpy(np.array(_swarm(kind, n, S)[0])))
+                md.fill_(-1.0)
+                partner.fill_(-7)
+                g.replay()
+                side.synchronize()
+                _check((md, partner, hit), _swarm(kind, n, S)[1], f"replay ({kind})")
+            for kind in ("sparse", "dense", "sparse"):
+                eager(kind, f"eager pass ({kind}) after the replays")
+            del g
+            side.synchronize()
+        ctx.use_own_stream()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,by_groups_dense", [(8192, 1), (8193, 0)])
+def test_group_passes_at_the_list_capacity_boundary(n, by_groups_dense):
+    """8192 drones: the last size where every group pair has a list slot (only the group evaluator is launched);
+    8193: the first size with 2^18 slots and both evaluators.  A dense pass, then a sparse one, in mode 2."""
+    S = 6
+    with _context() as ctx:
+        ctx.set_option("collide_cull_mode", 2)
+        for kind in ("dense", "sparse"):
+            _host_pass(ctx, kind, n, S, f"{kind} pass at {n} drones")
+            assert ctx.get_option("collide_last_cull") == 1
+            assert ctx.get_option("collide_last_by_groups") == (by_groups_dense if kind == "dense" else 1)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,S,form", [(1000, 12, 1), (3072, 12, 2)])
+def test_hand_over_is_read_with_its_own_positions_only(n, S, form):
+    """The sampler's hand-over (form 1: the transposed row image; form 2: boxes and sort keys for the broad phase) is
+    tied to the positions it was written beside.  Handed over with other positions of the same shape it is ignored --
+    the pass computes its own -- and with its own positions it is still used ("collide_last_handover").  With
+    reused output buffers the same pair of buffers holds one swarm after the other.  B is A at half scale (a spread-out
+    swarm, its waypoints halved): A's boxes then overstate every gap of B, and a broad phase that read them would cull
+    true partners."""
+    import torch
+    from drone_path_planning_python_amd import swarm as sw
+    from drone_path_planning_python_amd.synthetic import swarm
+    dev = torch.device("cuda", 0)
+    with _context() as ctx:
+        comp = sw.DeviceCompute(ctx, torch)
+        try:
+            wp, t = swarm(51, n, 4)
+            rng = np.random.default_rng(n)
+            wp[..., :3] = 0.2 * wp[..., :3] + rng.uniform(-150.0, 150.0, size=(n, 1, 3)) * np.array([1.0, 1.0, 0.05])
+            wp_b = wp.copy()
+            wp_b[..., :3] *= 0.5
+            coefs = []
+            for w in (wp, wp_b):
+                coef, dur, status = comp.solve(torch.from_numpy(w).to(dev), torch.from_numpy(t).to(dev))
+                assert int(status.abs().sum()) == 0
+                coefs.append((coef, dur))
+            (pos_a, ho_a), (pos_b, ho_b) = (comp.sample_rows_t(c, d, 0.1, S, n_cols=n) for c, d in coefs)
+            assert ho_a is not None and ho_b is not None and ho_a.data_ptr() != ho_b.data_ptr()
+            ref_a, ref_b = (c_oracle.formation_collide(p.cpu().numpy(), R) for p in (pos_a, pos_b))
+            assert not np.array_equal(ref_a[0], ref_b[0])
+            _check(comp.collide(pos_b, 0, pos_b, R, rows_t=ho_a), ref_b, "B with A's hand-over")
+            assert ctx.get_option("collide_last_handover") == 0
+            _check(comp.collide(pos_a, 0, pos_a, R, rows_t=ho_a), ref_a, "A with its hand-over")
+            assert ctx.get_option("collide_last_handover") == form
+            _check(comp.collide(pos_b, 0, pos_b, R, rows_t=ho_b), ref_b, "B with its hand-over")
+            assert ctx.get_option("collide_last_handover") == form
+            assert ctx.get_option("collide_last_cull") == (1 if form == 2 else 0)
+        finally:
+            comp.close()
+        comp = sw.DeviceCompute(ctx, torch, reuse_outputs=True)
+        try:
+            pos, ho = comp.sample_rows_t(*coefs[0], 0.1, S, n_cols=n)
+            keep_a = pos.clone()
+            _check(comp.collide(pos, 0, pos, R, rows_t=ho), ref_a, "A in the reused buffers")
+            assert ctx.get_option("collide_last_handover") == form
+            pos2, ho2 = comp.sample_rows_t(*coefs[1], 0.1, S, n_cols=n)
+            assert pos2.data_ptr() == pos.data_ptr() and ho2.data_ptr() == ho.data_ptr()
+            _check(comp.collide(pos2, 0, pos2, R, rows_t=ho2), ref_b, "B sampled over A")
+            assert ctx.get_option("collide_last_handover") == form
+            _check(comp.collide(keep_a, 0, keep_a, R, rows_t=ho2), ref_a, "a copy of A with B's hand-over")
+            assert ctx.get_option("collide_last_handover") == 0
+        finally:
+            comp.close()

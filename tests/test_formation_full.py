@@ -285,14 +285,18 @@ def test_broad_phase_equals_the_full_pass(ctx7, kind, n, S):
 def test_large_swarm_group_list_overflow_falls_back_to_the_shares(ctx7):
     """Swarms above 8192 drones get 2^18 group-pair list slots and both evaluators are launched: the share evaluator and
     its merge return at once unless the survivors overflowed the list.  A sparse swarm goes through the group pairs, a
-    dense one (652 653 group pairs, all surviving) overflows -- both equal to the oracle."""
+    dense one (652 653 group pairs, all surviving) overflows -- both equal to the oracle, also the sparse pass after the
+    overflow (whose reverse lists the overflowing pass must leave clean)."""
     rng = np.random.default_rng(31)
     n, S = 9136, 6
+    swarms = {}
+    for kind in ("sparse", "dense"):
+        pos = _broad_phase_swarm(kind, n, S, rng)
+        swarms[kind] = (pos, c_oracle.formation_collide(pos, 0.3))
     ctx7.set_option("collide_cull_mode", 2)
     try:
-        for kind, by_groups in (("sparse", 1), ("dense", 0)):
-            pos = _broad_phase_swarm(kind, n, S, rng)
-            ref = c_oracle.formation_collide(pos, 0.3)
+        for kind, by_groups in (("sparse", 1), ("dense", 0), ("sparse", 1)):
+            pos, ref = swarms[kind]
             got = ctx7.formation_collide(pos, pos, 0.3)
             for a, b in zip(got, ref):
                 np.testing.assert_array_equal(a, b)
@@ -499,7 +503,8 @@ def test_read_only_options_and_last_pass_reports(ctx7):
     rng = np.random.default_rng(8)
     n, S = 3072, 12
     for name in ("collide_last_cull", "collide_last_shares", "collide_last_sym", "collide_last_survivors",
-                 "collide_last_group_pairs", "collide_last_by_groups", "collide_last_pairs_evaluated"):
+                 "collide_last_group_pairs", "collide_last_by_groups", "collide_last_pairs_evaluated",
+                 "collide_last_handover"):
         with pytest.raises(MsnapError):
             ctx7.set_option(name, 1)
     assert ctx7.collide_takes_broad_phase(n, 0, n, S) and not ctx7.collide_takes_broad_phase(n, 0, n + 1, S)
