@@ -57,6 +57,12 @@ SIGNATURES = {
     "msnap_eval_flat_device": (_I, [_VP, _I, _I, _VP, _VP, _I, _VP, _VP]),
     "msnap_snap_cost": (_I, [_VP, _I, _I, _VP, _VP, _VP]),
     "msnap_snap_cost_device": (_I, [_VP, _I, _I, _VP, _VP, _VP]),
+    "msnap_dynamic_peaks": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _VP]),
+    "msnap_dynamic_peaks_device": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _VP]),
+    "msnap_time_scale": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _VP]),
+    "msnap_time_scale_device": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _VP]),
+    "msnap_retime_to_limits": (_I, [_VP, _I, _I, _VP, _VP, _VP, _I, _VP, _VP, _VP]),
+    "msnap_retime_to_limits_device": (_I, [_VP, _I, _I, _VP, _VP, _VP, _I, _VP, _VP, _VP]),
     "msnap_formation_collide": (_I, [_VP, _I, _I, _I, _I, _VP, _VP, _D, _VP, _VP, _VP]),
     "msnap_formation_collide_device": (_I, [_VP, _I, _I, _I, _I, _VP, _VP, _D, _VP, _VP, _VP]),
     "msnap_collide_rows_t_doubles": (ctypes.c_size_t, [_I, _I]),

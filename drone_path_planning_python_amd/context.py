@@ -15,6 +15,7 @@ import numpy as np
 from . import _lib
 
 ST_OK, ST_SINGULAR, ST_TIMES, ST_NONFINITE = 0, 1, 2, 3
+RETIME_FIT, RETIME_COMMON = 1, 2      # msnap_retime_flags
 STATUS_TEXT = {
     ST_OK: "ok",
     ST_SINGULAR: "singular system",
@@ -350,6 +351,74 @@ class Context:
         with self._lock:
             self._ck(self._lib.msnap_snap_cost_device(self._h, int(n_drones), int(n_seg), _ptr(coef), _ptr(dur),
                                                      _ptr(cost)))
+
+    # ---- dynamic limits (include/msnap.h: certified peaks, uniform retiming) --------------
+    @staticmethod
+    def limits_array(v_max=0.0, a_max=0.0, j_max=0.0, yaw_rate_max=0.0):
+        """The limits[4] of msnap_retime_to_limits (0 or +inf: unconstrained) as a host array."""
+        return np.array([v_max, a_max, j_max, yaw_rate_max], dtype=np.float64)
+
+    @staticmethod
+    def retime_flags(fit=False, common=False) -> int:
+        return (RETIME_FIT if fit else 0) | (RETIME_COMMON if common else 0)
+
+    def dynamic_peaks(self, coef, dur):
+        """Certified peaks per drone: (peak [N, 4], t_peak [N, 4], status [N] int32); columns speed, acceleration,
+        jerk, yaw rate (msnap_dynamic_peaks)."""
+        coef, pc, dur, pd, N, M = self._coef_dur(coef, dur)
+        peak = np.empty((N, 4), dtype=np.float64)
+        t_peak = np.empty((N, 4), dtype=np.float64)
+        status = np.empty((N,), dtype=np.int32)
+        with self._lock:
+            self._ck(self._lib.msnap_dynamic_peaks(self._h, N, M, pc, pd, peak.ctypes.data_as(ctypes.c_void_p),
+                                                   t_peak.ctypes.data_as(ctypes.c_void_p),
+                                                   status.ctypes.data_as(ctypes.c_void_p)))
+        return peak, t_peak, status
+
+    def dynamic_peaks_device(self, n_drones, n_seg, coef, dur, peak, t_peak, status):
+        with self._lock:
+            self._ck(self._lib.msnap_dynamic_peaks_device(self._h, int(n_drones), int(n_seg), _ptr(coef), _ptr(dur),
+                                                          _ptr(peak), _ptr(t_peak), _ptr(status)))
+
+    def time_scale(self, coef, dur, scale):
+        """Run drone d `scale[d]` times slower (c_j -> c_j scale^-j, T -> scale T): (coef, dur) new arrays."""
+        coef, pc, dur, pd, N, M = self._coef_dur(coef, dur)
+        sc, psc = _host(scale, np.float64)
+        if sc.shape != (N,):
+            raise ValueError(f"scale must be [{N}]")
+        coef_out, dur_out = np.empty_like(coef), np.empty_like(dur)
+        with self._lock:
+            self._ck(self._lib.msnap_time_scale(self._h, N, M, pc, pd, psc, coef_out.ctypes.data_as(ctypes.c_void_p),
+                                                dur_out.ctypes.data_as(ctypes.c_void_p)))
+        return coef_out, dur_out
+
+    def time_scale_device(self, n_drones, n_seg, coef, dur, scale, coef_out, dur_out):
+        with self._lock:
+            self._ck(self._lib.msnap_time_scale_device(self._h, int(n_drones), int(n_seg), _ptr(coef), _ptr(dur),
+                                                       _ptr(scale), _ptr(coef_out), _ptr(dur_out)))
+
+    def retime_to_limits(self, coef, dur, v_max=0.0, a_max=0.0, j_max=0.0, yaw_rate_max=0.0, fit=False, common=False):
+        """Uniformly retimed (coef, dur) that meet the limits, and the per-drone scale [N] (msnap_retime_to_limits;
+        a limit of 0 or inf is no limit; `fit`: the scale may be below 1; `common`: one scale for the whole batch)."""
+        coef, pc, dur, pd, N, M = self._coef_dur(coef, dur)
+        lim, plim = _host(self.limits_array(v_max, a_max, j_max, yaw_rate_max), np.float64)
+        coef_out, dur_out = np.empty_like(coef), np.empty_like(dur)
+        scale = np.empty((N,), dtype=np.float64)
+        with self._lock:
+            self._ck(self._lib.msnap_retime_to_limits(
+                self._h, N, M, pc, pd, plim, self.retime_flags(fit, common), coef_out.ctypes.data_as(ctypes.c_void_p),
+                dur_out.ctypes.data_as(ctypes.c_void_p), scale.ctypes.data_as(ctypes.c_void_p)))
+        return coef_out, dur_out, scale
+
+    def retime_to_limits_device(self, n_drones, n_seg, coef, dur, limits, flags, coef_out, dur_out, scale):
+        """Device pointers; `limits` is a host sequence of 4 (speed, acceleration, jerk, yaw rate)."""
+        lim, plim = _host(limits, np.float64)
+        if lim.shape != (4,):
+            raise ValueError("limits must hold 4 values")
+        with self._lock:
+            self._ck(self._lib.msnap_retime_to_limits_device(self._h, int(n_drones), int(n_seg), _ptr(coef), _ptr(dur),
+                                                             plim, int(flags), _ptr(coef_out), _ptr(dur_out),
+                                                             _ptr(scale)))
 
     # ---- collision passes --------------------------------------------------------
     def formation_collide(self, pos_rows, pos_cols, radius: float, row_offset: int = 0):

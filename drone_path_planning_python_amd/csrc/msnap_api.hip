@@ -190,6 +190,7 @@ void msnap_destroy(msnap_ctx *ctx) {
   if (ctx->own_stream) (void)hipStreamSynchronize(ctx->own_stream);
   (void)msnap_release_graph_buffers(ctx, nullptr);
   if (ctx->scratch.p) (void)hipFree(ctx->scratch.p);
+  if (ctx->limits_work.p) (void)hipFree(ctx->limits_work.p);
   if (ctx->mesh_tests) (void)hipFree(ctx->mesh_tests);
   for (msnap::DevBuf *b : {&ctx->grid_t, &ctx->grid_wp, &ctx->grid_op, &ctx->grid_dur, &ctx->grid_status, &ctx->grid_frag})
     if (b->p) (void)hipFree(b->p);

@@ -7,7 +7,7 @@
 
 #include "../../include/msnap.h"
 
-#define MSNAP_VERSION_NUM 200  /* 0.2.0: n_seg on msnap_solve_grid[_device], msnap_grid_segments, graph-buffer retention */
+#define MSNAP_VERSION_NUM 300  /* 0.3.0: dynamic peaks, time scaling and retiming to limits (msnap_limits.hip) */
 /* int32 words of the pairwise pass's broad-phase hand-over block that msnap_get_option reads back */
 #define MSNAP_COLLIDE_META_SHARES 128
 #define MSNAP_COLLIDE_META_GROUPS 132
@@ -72,6 +72,7 @@ struct msnap_ctx {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   msnap::DevBuf scratch;   // global-memory scratch for n_seg too large for LDS
   msnap::DevBuf stage[8];  // device staging for the host-pointer entry points
+  msnap::DevBuf limits_work;   // msnap_limits.hip: per-(drone, segment, quantity) peaks, then the retiming's per-drone peaks
   // chunked host-pointer solves: two streams alternate H2D -> kernel -> D2H over chunks of drones,
   // each with its own staging set (wp, t, coef, dur, status)
   hipStream_t pipe_stream[2] = {nullptr, nullptr};

@@ -84,14 +84,22 @@ def paths_to_waypoints(paths: Sequence) -> tuple:
     return wp, path_time_grid(m)
 
 
-def paths_to_pols(paths: Sequence, ctx: Context | None = None):
-    """Batched path_to_pol: returns (matrix f32 [N, M, 33], coef, dur)."""
+def paths_to_pols(paths: Sequence, ctx: Context | None = None, limits=None, fit: bool = False):
+    """Batched path_to_pol: returns (matrix f32 [N, M, 33], coef, dur).
+
+    `limits` = (speed, acceleration, jerk, yaw rate), 0 = no limit: the batch is retimed with ONE common scale (these
+    drones fly one formation) so that every limit holds for the exact peaks of every drone (Context.retime_to_limits);
+    the matrix then carries the scaled durations.  Stretch only, unless `fit`: then the batch may also be sped up until
+    its tightest limit is met.  None (the default): the reference's timing, unchecked."""
     ctx = ctx or default_context(7)
     wp, t = paths_to_waypoints(paths)
     # every path of the node shares the uniform grid: one operator, one MFMA GEMM per batch
     coef, dur, status = ctx.solve_on_grid(t, wp)
     for k in range(len(paths)):
         raise_for_status(int(status[k]), t)
+    if limits is not None:
+        v_max, a_max, j_max, yaw_rate_max = (float(x) for x in limits)
+        coef, dur, _ = ctx.retime_to_limits(coef, dur, v_max, a_max, j_max, yaw_rate_max, fit=fit, common=True)
     return ctx.pack_pol_matrix(coef, dur), coef, dur
 
 
@@ -124,11 +132,13 @@ def save_pol_matrix(matrix: np.ndarray, cfid: int, out_dir: str | None = None) -
     return fn
 
 
-def path_to_pol(path, cfid: int, ctx: Context | None = None, out_dir: str | None = None, save: bool = True):
+def path_to_pol(path, cfid: int, ctx: Context | None = None, out_dir: str | None = None, save: bool = True,
+                limits=None):
     """One drone's Path -> polynomial pieces: solve, pack to float32, write the
-    CSV, publish on 'piece_pol' (reference :40-90).  Returns the message."""
+    CSV, publish on 'piece_pol' (reference :40-90).  Returns the message.
+    `limits` (speed, acceleration, jerk, yaw rate): stretch the timing until they hold (paths_to_pols)."""
     print("Path received...")
-    matrix, _, _ = paths_to_pols([path], ctx)
+    matrix, _, _ = paths_to_pols([path], ctx, limits=limits)
     matrix = matrix[0]
     if save:
         save_pol_matrix(matrix, cfid, out_dir)

@@ -157,6 +157,41 @@ class DeviceCompute:
             self.ctx.solve_grid_sample_device(n, M, wp, dt, n_samples, coef, dur, status, pos, pos_t)
         return coef, dur, status, pos, pos_t
 
+    # ---- dynamic limits (include/msnap.h) --------------------------------------------------------------------------
+    def dynamic_peaks(self, coef, dur):
+        """(peak [n, 4], t_peak [n, 4], status [n] int32): certified speed, acceleration, jerk and yaw-rate peaks."""
+        torch = self.torch
+        n, M = dur.shape
+        peak = self._out("dynamic_peaks.peak", (n, 4), torch.float64)
+        t_peak = self._out("dynamic_peaks.t_peak", (n, 4), torch.float64)
+        status = self._out("dynamic_peaks.status", (n,), torch.int32)
+        if n:
+            self.ctx.dynamic_peaks_device(n, M, coef, dur, peak, t_peak, status)
+        return peak, t_peak, status
+
+    def retime_to_limits(self, coef, dur, limits, fit=False, common=False):
+        """(coef, dur, scale [n]): the drones run uniformly slower (or, with `fit`, faster) so that the limits
+        (speed, acceleration, jerk, yaw rate; 0 = none) hold; `common`: one scale for the batch."""
+        torch = self.torch
+        n, M = dur.shape
+        coef_out = self._out("retime.coef", tuple(coef.shape), torch.float64)
+        dur_out = self._out("retime.dur", (n, M), torch.float64)
+        scale = self._out("retime.scale", (n,), torch.float64)
+        flags = self.ctx.retime_flags(fit, common)
+        if n:
+            self.ctx.retime_to_limits_device(n, M, coef, dur, limits, flags, coef_out, dur_out, scale)
+        return coef_out, dur_out, scale
+
+    def time_scale(self, coef, dur, scale):
+        """(coef, dur) of the drones run `scale[d]` times slower (a scale that is not finite and > 0 copies)."""
+        torch = self.torch
+        n, M = dur.shape
+        coef_out = self._out("time_scale.coef", tuple(coef.shape), torch.float64)
+        dur_out = self._out("time_scale.dur", (n, M), torch.float64)
+        if n:
+            self.ctx.time_scale_device(n, M, coef, dur, scale, coef_out, dur_out)
+        return coef_out, dur_out
+
     def collide(self, pos_rows, row_offset, pos_all, radius, rows_t=None):
         torch = self.torch
         r = pos_rows.shape[0]
@@ -433,6 +468,54 @@ def formation_pass_from_waypoints(compute, wp_local, n_total: int, world: int, r
                          status_local=status if check_status else None, mesh_tris=mesh_tris,
                          force_collectives=force_collectives, force_mode=force_mode, _sampled=(pos, rows_t))
     return res, coef, dur, status
+
+
+def check_limits(limits):
+    """The host-side check of msnap_retime_to_limits' limits: 4 values, none negative or NaN (0 / inf: no limit)."""
+    lim = np.asarray(limits, dtype=np.float64)
+    if lim.shape != (4,) or not bool(np.all(lim >= 0.0)):
+        raise ValueError(f"limits must be 4 values (speed, acceleration, jerk, yaw rate), none negative or NaN: {limits}")
+    return lim
+
+
+def retime_swarm(compute, coef_local, dur_local, limits, world: int, rank: int, dist=None, fit: bool = False,
+                 common: bool = True):
+    """Retime a swarm sharded over `world` ranks to the dynamic limits (speed, acceleration, jerk, yaw rate; 0 = none).
+
+    `common` (the default: a formation stays in step): every rank computes its drones' factors, one MAX all-reduce of a
+    single value gives the swarm's factor and `compute.time_scale` applies it -- the result equals one
+    `retime_to_limits(..., common=True)` over the whole swarm.  A rank without drones, or whose drones all failed,
+    contributes a neutral 0; failed drones (NaN coefficients) pass through with scale NaN.  Every rank enters the
+    collective whatever happened locally (a rank that raised would leave the others waiting); an error is re-raised
+    after it.  Returns (coef, dur, scale) of the local drones."""
+    if not common:
+        check_limits(limits)
+        return compute.retime_to_limits(coef_local, dur_local, limits, fit=fit, common=False)
+    import torch
+    n = dur_local.shape[0]
+    err, scale, k_local = None, None, None
+    try:
+        check_limits(limits)
+        if n:
+            _, _, scale = compute.retime_to_limits(coef_local, dur_local, limits, fit=fit, common=True)
+            k_local = torch.nan_to_num(scale, nan=0.0).amax().reshape(1)
+    except Exception as e:      # (entered the collective below all the same)
+        err = e
+    if k_local is None or err is not None:
+        k_local = torch.zeros(1, dtype=torch.float64)
+    if dist is not None and world > 1:
+        on_device = dist.get_backend() == "nccl"
+        k = k_local.to(dur_local.device) if on_device else k_local.cpu()
+        dist.all_reduce(k, op=dist.ReduceOp.MAX)
+    else:
+        k = k_local
+    if err is not None:
+        raise err
+    if not n:
+        return coef_local, dur_local, torch.zeros((0,), dtype=torch.float64, device=dur_local.device)
+    scale = torch.where(torch.isnan(scale), scale, k.to(scale.device).expand_as(scale)).contiguous()
+    coef_out, dur_out = compute.time_scale(coef_local, dur_local, scale)
+    return coef_out, dur_out, scale
 
 
 def default_sample_count(total_duration: float, dt: float) -> int:

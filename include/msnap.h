@@ -253,6 +253,59 @@ int msnap_snap_cost(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef,
 int msnap_snap_cost_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef,
                            const double *dur, double *cost);
 
+/* ---- dynamic limits: certified peaks and uniform retiming (new capability) ----
+ * The reference gives every path the grid t_i = i*10/n (scripts/drones_pols_generator.py:44-46,56) and checks the
+ * result against nothing.  For each drone, over the closed range [0, sum(dur)], each segment on its closed [0, T_i]:
+ *   q = 0  speed         max |p'(t)|    (Euclidean norm of the x, y, z derivative)
+ *   q = 1  acceleration  max |p''(t)|
+ *   q = 2  jerk          max |p'''(t)|
+ *   q = 3  yaw rate      max |psi'(t)|
+ *   peak   [n_drones][4]  a value the trajectory ATTAINS (SI units), at
+ *   t_peak [n_drones][4]  absolute time.  If S is the supremum for the exact real polynomials of the fp64
+ *                         coefficients: S (1 - 1e-9) - 1e-12 <= peak <= S (1 + 1e-12) + 1e-12.  Ties and near-ties:
+ *                         the larger value, then the earlier time.  A stationary drone reports peaks <= 1e-12.
+ *   status [n_drones]     msnap_status: MSNAP_ST_NONFINITE for a NaN / Inf coefficient or duration (what a failed
+ *                         solve leaves), else MSNAP_ST_TIMES for a duration <= 0; peak and t_peak are NaN then.
+ * A drone's results are bit-identical whatever its position in the batch, the batch size, or host versus device entry.
+ * Both orders, n_seg 1 .. max_segments.  (Method: branch and bound on Bernstein bounds of |.|^2 per segment.)
+ */
+int msnap_dynamic_peaks(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur, double *peak,
+                        double *t_peak, int32_t *status);
+int msnap_dynamic_peaks_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,
+                               double *peak, double *t_peak, int32_t *status);
+/* Uniform retiming.  Both orders impose homogeneous end conditions (derivatives 1..3 zero at order 7, 1..4 at order 9)
+ * and continuity of derivatives 1..6 (1..8) at the knots, so the solution for the times k t is the same path run k
+ * times slower: segment i keeps its polynomial with c_j -> c_j k^-j and T_i -> k T_i (derivative q scales by k^-q) --
+ * no second solve.
+ *   msnap_time_scale        applies a given scale [n_drones] (c_j times r^j with r = 1/k by repeated multiplication,
+ *                           T times k); a scale that is not finite and > 0 copies the drone unchanged.  The building
+ *                           block of a common scale over several ranks.
+ *   msnap_retime_to_limits  limits[4] = (speed, acceleration, jerk, yaw rate), a HOST array in both versions; 0 or
+ *                           +inf: unconstrained; negative or NaN: MSNAP_EINVAL.  Per drone, from peak (1 + 2e-9) (so
+ *                           that the limits hold for the true supremum):
+ *                             k = max(v / v_lim, sqrt(a / a_lim), cbrt(j / j_lim), yr / yr_lim)
+ *                           flags 0: stretch only, k = max(k, 1);  MSNAP_RETIME_FIT: k may be below 1 -- the fastest
+ *                           uniform retiming whose tightest limit is just met (k = 1 when nothing is constrained or
+ *                           every peak is 0);  MSNAP_RETIME_COMMON: one k for all drones of the call, their maximum
+ *                           (failed drones ignored, as fmax does): a formation stays in step.
+ *                           scale [n_drones] receives k; a failed drone (status != 0 above) passes through unchanged,
+ *                           with scale NaN.
+ * coef_out / dur_out may be coef / dur (in place).  Device versions only launch (no synchronisation).
+ */
+enum msnap_retime_flags {
+  MSNAP_RETIME_FIT = 1,
+  MSNAP_RETIME_COMMON = 2
+};
+int msnap_time_scale(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,
+                     const double *scale, double *coef_out, double *dur_out);
+int msnap_time_scale_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,
+                            const double *scale, double *coef_out, double *dur_out);
+int msnap_retime_to_limits(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,
+                           const double limits[4], int flags, double *coef_out, double *dur_out, double *scale);
+int msnap_retime_to_limits_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,
+                                  const double limits[4], int flags, double *coef_out, double *dur_out,
+                                  double *scale);
+
 /* ---- drone-vs-drone formation pass (new capability; no reference) -------
  * rows: the n_rows drones this caller owns (a shard), starting at global index
  * row_offset; cols: all n_cols drones (after the all-gather).  Spheres of `radius`.
