@@ -1,13 +1,12 @@
 // C-ABI of libmsnap.so (include/msnap.h): context management, host-pointer
-// wrappers, stream / timer plumbing.  All compute happens in the HIP kernels
-// of msnap_solve.hip / msnap_aux.hip; there is no CPU fallback.
+// wrappers, stream / timer plumbing.  All compute happens in the HIP kernels of
+// msnap_solve.hip / msnap_aux.hip / msnap_grid.hip / msnap_limits.hip; there is no CPU fallback.
+#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <new>
-
-#include <cstdarg>
-#include <cstdio>
 
 #include "msnap_internal.h"
 
@@ -70,6 +69,68 @@ static int check_seg(const msnap_ctx *ctx, int n_seg) {
   if (n_seg < 1 || n_seg > ctx->max_segments) return MSNAP_ESEGMENTS;
   return MSNAP_OK;
 }
+
+// An entry point and its _device twin share one argument check.  It returns MSNAP_OK to go on, an error code, or
+// kNoWork when the call has nothing to compute (the entry point then returns MSNAP_OK).
+constexpr int kNoWork = 1;
+
+// the start of such an entry point: anything but MSNAP_OK from the check is returned, then the device is selected
+#define MSNAP_ENTER(ctx, check)                                   \
+  do {                                                            \
+    const int rc__ = (check);                                     \
+    if (rc__) return rc__ == msnap::kNoWork ? MSNAP_OK : rc__;    \
+    MSNAP_HIP(ctx, hipSetDevice((ctx)->device));                  \
+  } while (0)
+
+// One host region of a host-pointer call: `in` is copied to the device before the launch, the device copy back to
+// `out` after it.  Either may be null; both set: the launch updates the region in place.
+struct Region {
+  const void *in;
+  void *out;
+  size_t bytes;
+};
+static Region upload(const void *h, size_t bytes) { return {h, nullptr, bytes}; }
+static Region download(void *h, size_t bytes) { return {nullptr, h, bytes}; }
+
+// a staged region's device address, for any pointer parameter of a launcher
+struct DevPtr {
+  void *p;
+  template <class T>
+  operator T *() const { return static_cast<T *>(p); }
+};
+
+// A host-pointer call.  The regions are carved, 256-byte aligned, out of the context's one staging arena (a region of
+// no bytes still gets a valid, non-null address); the inputs are copied in on ctx->stream, `launch` runs on their
+// device addresses, the outputs are copied back and the stream is synchronised once.  A failed launch returns its
+// code with nothing copied back.
+template <size_t K, class Launch>
+static int staged(msnap_ctx *ctx, const Region (&r)[K], Launch &&launch) {
+  size_t off[K], total = 0;
+  for (size_t k = 0; k < K; ++k) {
+    off[k] = total;
+    total += r[k].bytes ? (r[k].bytes + 255) & ~(size_t)255 : 256;
+  }
+  int rc = ensure(ctx, ctx->host_stage, total);
+  if (rc) return rc;
+  DevPtr d[K];
+  for (size_t k = 0; k < K; ++k) {
+    d[k].p = (char *)ctx->host_stage.p + off[k];
+    if (r[k].in && r[k].bytes)
+      MSNAP_HIP(ctx, hipMemcpyAsync(d[k].p, r[k].in, r[k].bytes, hipMemcpyHostToDevice, ctx->stream));
+  }
+  if ((rc = launch(d))) return rc;
+  for (size_t k = 0; k < K; ++k)
+    if (r[k].out && r[k].bytes)
+      MSNAP_HIP(ctx, hipMemcpyAsync(r[k].out, d[k].p, r[k].bytes, hipMemcpyDeviceToHost, ctx->stream));
+  MSNAP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return MSNAP_OK;
+}
+
+// bytes of a batch's coefficients [n_drones][n_seg][4][order + 1] and durations [n_drones][n_seg]
+static size_t coef_bytes(const msnap_ctx *ctx, int n_drones, int n_seg) {
+  return (size_t)n_drones * n_seg * 4 * (ctx->order + 1) * 8;
+}
+static size_t dur_bytes(int n_drones, int n_seg) { return (size_t)n_drones * n_seg * 8; }
 
 struct OptionName {
   const char *name, *env;
@@ -189,13 +250,10 @@ void msnap_destroy(msnap_ctx *ctx) {
   (void)hipSetDevice(ctx->device);
   if (ctx->own_stream) (void)hipStreamSynchronize(ctx->own_stream);
   (void)msnap_release_graph_buffers(ctx, nullptr);
-  if (ctx->scratch.p) (void)hipFree(ctx->scratch.p);
-  if (ctx->limits_work.p) (void)hipFree(ctx->limits_work.p);
   if (ctx->mesh_tests) (void)hipFree(ctx->mesh_tests);
-  for (msnap::DevBuf *b : {&ctx->grid_t, &ctx->grid_wp, &ctx->grid_op, &ctx->grid_dur, &ctx->grid_status, &ctx->grid_frag})
+  for (msnap::DevBuf *b : {&ctx->scratch, &ctx->limits_work, &ctx->host_stage, &ctx->collide_work, &ctx->grid_t,
+                           &ctx->grid_wp, &ctx->grid_op, &ctx->grid_dur, &ctx->grid_status, &ctx->grid_frag})
     if (b->p) (void)hipFree(b->p);
-  for (auto &b : ctx->stage)
-    if (b.p) (void)hipFree(b.p);
   for (int k = 0; k < 2; ++k) {
     if (ctx->pipe_stream[k]) (void)hipStreamSynchronize(ctx->pipe_stream[k]);
     for (auto &b : ctx->pipe[k])
@@ -408,8 +466,8 @@ static int solve_host(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp,
         ctx->bounce_cap = kBounceMax;
       }
     }
-    if (ctx->bounce && (rc = ensure(ctx, ctx->stage[5], kBounceMax)) == MSNAP_OK) {
-      char *hb = (char *)ctx->bounce, *db = (char *)ctx->stage[5].p;
+    if (ctx->bounce && (rc = ensure(ctx, ctx->host_stage, kBounceMax)) == MSNAP_OK) {
+      char *hb = (char *)ctx->bounce, *db = (char *)ctx->host_stage.p;
       memcpy(hb, wp, N * pd_wp);
       if (t) memcpy(hb + o_t, t, b_t);
       MSNAP_HIP(ctx, hipMemcpyAsync(db, hb, in_bytes, hipMemcpyHostToDevice, ctx->stream));
@@ -424,26 +482,10 @@ static int solve_host(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp,
       return MSNAP_OK;
     }
   }
-  if (N <= chunk || solve_uses_global_scratch(ctx, n_seg)) {
-    // one shot on the context's stream
-    if ((rc = ensure(ctx, ctx->stage[0], N * pd_wp))) return rc;
-    if (t && (rc = ensure(ctx, ctx->stage[1], (shared ? 1 : N) * pd_t))) return rc;
-    if ((rc = ensure(ctx, ctx->stage[2], N * pd_coef))) return rc;
-    if ((rc = ensure(ctx, ctx->stage[3], N * pd_dur))) return rc;
-    if ((rc = ensure(ctx, ctx->stage[4], N * pd_st))) return rc;
-    MSNAP_HIP(ctx, hipMemcpyAsync(ctx->stage[0].p, wp, N * pd_wp, hipMemcpyHostToDevice, ctx->stream));
-    if (t)
-      MSNAP_HIP(ctx, hipMemcpyAsync(ctx->stage[1].p, t, (shared ? 1 : N) * pd_t, hipMemcpyHostToDevice,
-                                    ctx->stream));
-    rc = launch(N, (const double *)ctx->stage[0].p, (const double *)ctx->stage[1].p, (double *)ctx->stage[2].p,
-                (double *)ctx->stage[3].p, (int32_t *)ctx->stage[4].p);
-    if (rc) return rc;
-    MSNAP_HIP(ctx, hipMemcpyAsync(coef, ctx->stage[2].p, N * pd_coef, hipMemcpyDeviceToHost, ctx->stream));
-    MSNAP_HIP(ctx, hipMemcpyAsync(dur, ctx->stage[3].p, N * pd_dur, hipMemcpyDeviceToHost, ctx->stream));
-    MSNAP_HIP(ctx, hipMemcpyAsync(status, ctx->stage[4].p, N * pd_st, hipMemcpyDeviceToHost, ctx->stream));
-    MSNAP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return MSNAP_OK;
-  }
+  if (N <= chunk || solve_uses_global_scratch(ctx, n_seg))      // one shot on the context's stream
+    return staged(ctx, {upload(wp, N * pd_wp), upload(t, b_t), download(coef, N * pd_coef), download(dur, N * pd_dur),
+                        download(status, N * pd_st)},
+                  [&](const DevPtr *d) { return launch(N, d[0], d[1], d[2], d[3], d[4]); });
 
   for (int k = 0; k < 2; ++k)
     if (!ctx->pipe_stream[k])
@@ -458,8 +500,8 @@ static int solve_host(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp,
     if ((rc = ensure(ctx, ctx->pipe[k][4], chunk * pd_st))) return rc;
   }
   if (t && shared) {
-    if ((rc = ensure(ctx, ctx->stage[1], pd_t))) return rc;
-    MSNAP_HIP(ctx, hipMemcpyAsync(ctx->stage[1].p, t, pd_t, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = ensure(ctx, ctx->host_stage, pd_t))) return rc;
+    MSNAP_HIP(ctx, hipMemcpyAsync(ctx->host_stage.p, t, pd_t, hipMemcpyHostToDevice, ctx->stream));
   }
   // the chunk streams start after whatever the context's stream holds (incl. the shared grid upload)
   MSNAP_HIP(ctx, hipEventRecord(ctx->pipe_start, ctx->stream));
@@ -484,7 +526,7 @@ static int solve_host(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp,
       PIPE_HIP(hipMemcpyAsync(b[1].p, (const char *)t + d0 * pd_t, n * pd_t, hipMemcpyHostToDevice, s));
     if (herr != hipSuccess) break;
     ctx->stream = s;   // the launchers enqueue on ctx->stream
-    rc = launch(n, (const double *)b[0].p, per_drone_t ? (const double *)b[1].p : (const double *)ctx->stage[1].p,
+    rc = launch(n, (const double *)b[0].p, per_drone_t ? (const double *)b[1].p : (const double *)ctx->host_stage.p,
                 (double *)b[2].p, (double *)b[3].p, (int32_t *)b[4].p);
     ctx->stream = user_stream;
     PIPE_HIP(hipMemcpyAsync((char *)coef + d0 * pd_coef, b[2].p, n * pd_coef, hipMemcpyDeviceToHost, s));
@@ -502,26 +544,26 @@ static int solve_host(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp,
   return MSNAP_OK;
 }
 
+// a batch of n_drones paths of n_seg segments whose every pointer is required
+static int batch_args(const msnap_ctx *ctx, int n_drones, int n_seg, std::initializer_list<const void *> ptrs) {
+  if (!ctx || n_drones < 0) return MSNAP_EINVAL;
+  if (int rc = check_seg(ctx, n_seg)) return rc;
+  if (n_drones == 0) return kNoWork;
+  for (const void *p : ptrs)
+    if (!p) return MSNAP_EINVAL;
+  return MSNAP_OK;
+}
+
 int msnap_solve_batch_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp,
                              const double *t, int shared_times, double *coef, double *dur,
                              int32_t *status) {
-  if (!ctx || n_drones < 0) return MSNAP_EINVAL;
-  int rc = check_seg(ctx, n_seg);
-  if (rc) return rc;
-  if (n_drones == 0) return MSNAP_OK;
-  if (!wp || !t || !coef || !dur || !status) return MSNAP_EINVAL;
-  MSNAP_HIP(ctx, hipSetDevice(ctx->device));
+  MSNAP_ENTER(ctx, batch_args(ctx, n_drones, n_seg, {wp, t, coef, dur, status}));
   return launch_solve(ctx, n_drones, n_seg, wp, t, shared_times ? 1 : 0, coef, dur, status);
 }
 
 int msnap_solve_batch(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, const double *t,
                       int shared_times, double *coef, double *dur, int32_t *status) {
-  if (!ctx || n_drones < 0) return MSNAP_EINVAL;
-  int rc = check_seg(ctx, n_seg);
-  if (rc) return rc;
-  if (n_drones == 0) return MSNAP_OK;
-  if (!wp || !t || !coef || !dur || !status) return MSNAP_EINVAL;
-  MSNAP_HIP(ctx, hipSetDevice(ctx->device));
+  MSNAP_ENTER(ctx, batch_args(ctx, n_drones, n_seg, {wp, t, coef, dur, status}));
   return solve_host(ctx, n_drones, n_seg, wp, t, shared_times ? 1 : 0, /*use_grid=*/false, coef, dur, status);
 }
 
@@ -550,93 +592,63 @@ int msnap_grid_segments(const msnap_ctx *ctx) {
   return ctx->grid_ready ? ctx->grid_seg : 0;
 }
 
-int msnap_solve_grid_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, double *coef, double *dur,
-                            int32_t *status) {
+static int grid_solve_args(const msnap_ctx *ctx, int n_drones, int n_seg, const void *wp, const void *coef,
+                           const void *dur, const void *status) {
   if (!ctx || n_drones < 0) return MSNAP_EINVAL;
   if (!ctx->grid_ready) return MSNAP_ENOGRID;
   if (n_seg != ctx->grid_seg) return MSNAP_ESEGMENTS;      // the caller's buffers are sized for another grid
-  if (n_drones == 0) return MSNAP_OK;
-  if (!wp || !coef || !dur || !status) return MSNAP_EINVAL;
-  MSNAP_HIP(ctx, hipSetDevice(ctx->device));
+  if (n_drones == 0) return kNoWork;
+  return (!wp || !coef || !dur || !status) ? MSNAP_EINVAL : MSNAP_OK;
+}
+
+int msnap_solve_grid_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, double *coef, double *dur,
+                            int32_t *status) {
+  MSNAP_ENTER(ctx, grid_solve_args(ctx, n_drones, n_seg, wp, coef, dur, status));
   return launch_solve_grid(ctx, n_drones, wp, coef, dur, status);
 }
 
 int msnap_solve_grid(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, double *coef, double *dur,
                      int32_t *status) {
-  if (!ctx || n_drones < 0) return MSNAP_EINVAL;
-  if (!ctx->grid_ready) return MSNAP_ENOGRID;
-  if (n_seg != ctx->grid_seg) return MSNAP_ESEGMENTS;
-  if (n_drones == 0) return MSNAP_OK;
-  if (!wp || !coef || !dur || !status) return MSNAP_EINVAL;
-  MSNAP_HIP(ctx, hipSetDevice(ctx->device));
+  MSNAP_ENTER(ctx, grid_solve_args(ctx, n_drones, n_seg, wp, coef, dur, status));
   return solve_host(ctx, n_drones, ctx->grid_seg, wp, nullptr, 1, /*use_grid=*/true, coef, dur, status);
 }
 
 // ------------------------------------------------------------------ pack
 int msnap_pack_pol_matrix_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef,
                                  const double *dur, float *out) {
-  if (!ctx || n_drones < 0) return MSNAP_EINVAL;
-  int rc = check_seg(ctx, n_seg);
-  if (rc) return rc;
-  if (n_drones == 0) return MSNAP_OK;
-  if (!coef || !dur || !out) return MSNAP_EINVAL;
-  MSNAP_HIP(ctx, hipSetDevice(ctx->device));
+  MSNAP_ENTER(ctx, batch_args(ctx, n_drones, n_seg, {coef, dur, out}));
   return launch_pack(ctx, n_drones, n_seg, coef, dur, out);
 }
 
 int msnap_pack_pol_matrix(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef,
                           const double *dur, float *out) {
-  if (!ctx || n_drones < 0) return MSNAP_EINVAL;
-  int rc = check_seg(ctx, n_seg);
-  if (rc) return rc;
-  if (n_drones == 0) return MSNAP_OK;
-  if (!coef || !dur || !out) return MSNAP_EINVAL;
-  MSNAP_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t N = n_drones, nc = ctx->order + 1;
-  const size_t b_coef = N * n_seg * 4 * nc * 8, b_dur = N * n_seg * 8, b_out = N * n_seg * (1 + 4 * nc) * 4;
-  if ((rc = ensure(ctx, ctx->stage[2], b_coef))) return rc;
-  if ((rc = ensure(ctx, ctx->stage[3], b_dur))) return rc;
-  if ((rc = ensure(ctx, ctx->stage[5], b_out))) return rc;
-  MSNAP_HIP(ctx, hipMemcpyAsync(ctx->stage[2].p, coef, b_coef, hipMemcpyHostToDevice, ctx->stream));
-  MSNAP_HIP(ctx, hipMemcpyAsync(ctx->stage[3].p, dur, b_dur, hipMemcpyHostToDevice, ctx->stream));
-  rc = launch_pack(ctx, n_drones, n_seg, (const double *)ctx->stage[2].p, (const double *)ctx->stage[3].p,
-                   (float *)ctx->stage[5].p);
-  if (rc) return rc;
-  MSNAP_HIP(ctx, hipMemcpyAsync(out, ctx->stage[5].p, b_out, hipMemcpyDeviceToHost, ctx->stream));
-  MSNAP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return MSNAP_OK;
+  MSNAP_ENTER(ctx, batch_args(ctx, n_drones, n_seg, {coef, dur, out}));
+  const size_t b_out = (size_t)n_drones * n_seg * (1 + 4 * (ctx->order + 1)) * 4;
+  return staged(ctx, {upload(coef, coef_bytes(ctx, n_drones, n_seg)), upload(dur, dur_bytes(n_drones, n_seg)),
+                      download(out, b_out)},
+                [&](const DevPtr *d) { return launch_pack(ctx, n_drones, n_seg, d[0], d[1], d[2]); });
 }
 
 // ------------------------------------------------------------------ formation transform
+static int transform_args(const msnap_ctx *ctx, int n_poses, int n_offsets, const void *rb_pose, const void *offsets,
+                          const void *out) {
+  if (!ctx || n_poses < 0 || n_offsets < 0) return MSNAP_EINVAL;
+  if (n_poses == 0 || n_offsets == 0) return kNoWork;
+  return (!rb_pose || !offsets || !out) ? MSNAP_EINVAL : MSNAP_OK;
+}
+
 int msnap_formation_transform_device(msnap_ctx *ctx, int n_poses, int n_offsets, const double *rb_pose,
                                      const double *offsets, double *out) {
-  if (!ctx || n_poses < 0 || n_offsets < 0) return MSNAP_EINVAL;
-  if (n_poses == 0 || n_offsets == 0) return MSNAP_OK;
-  if (!rb_pose || !offsets || !out) return MSNAP_EINVAL;
-  MSNAP_HIP(ctx, hipSetDevice(ctx->device));
+  MSNAP_ENTER(ctx, transform_args(ctx, n_poses, n_offsets, rb_pose, offsets, out));
   return launch_formation_transform(ctx, n_poses, n_offsets, rb_pose, offsets, out);
 }
 
 int msnap_formation_transform(msnap_ctx *ctx, int n_poses, int n_offsets, const double *rb_pose,
                               const double *offsets, double *out) {
-  if (!ctx || n_poses < 0 || n_offsets < 0) return MSNAP_EINVAL;
-  if (n_poses == 0 || n_offsets == 0) return MSNAP_OK;
-  if (!rb_pose || !offsets || !out) return MSNAP_EINVAL;
-  MSNAP_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t b_in = (size_t)n_poses * 7 * 8, b_off = (size_t)n_offsets * 3 * 8;
-  const size_t b_out = (size_t)n_offsets * n_poses * 7 * 8;
-  int rc;
-  if ((rc = ensure(ctx, ctx->stage[0], b_in))) return rc;
-  if ((rc = ensure(ctx, ctx->stage[1], b_off))) return rc;
-  if ((rc = ensure(ctx, ctx->stage[2], b_out))) return rc;
-  MSNAP_HIP(ctx, hipMemcpyAsync(ctx->stage[0].p, rb_pose, b_in, hipMemcpyHostToDevice, ctx->stream));
-  MSNAP_HIP(ctx, hipMemcpyAsync(ctx->stage[1].p, offsets, b_off, hipMemcpyHostToDevice, ctx->stream));
-  rc = launch_formation_transform(ctx, n_poses, n_offsets, (const double *)ctx->stage[0].p,
-                                  (const double *)ctx->stage[1].p, (double *)ctx->stage[2].p);
-  if (rc) return rc;
-  MSNAP_HIP(ctx, hipMemcpyAsync(out, ctx->stage[2].p, b_out, hipMemcpyDeviceToHost, ctx->stream));
-  MSNAP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return MSNAP_OK;
+  MSNAP_ENTER(ctx, transform_args(ctx, n_poses, n_offsets, rb_pose, offsets, out));
+  return staged(ctx, {upload(rb_pose, (size_t)n_poses * 7 * 8), upload(offsets, (size_t)n_offsets * 3 * 8),
+                      download(out, (size_t)n_offsets * n_poses * 7 * 8)},
+                [&](const DevPtr *d) { return launch_formation_transform(ctx, n_poses, n_offsets, d[0], d[1], d[2]); });
 }
 
 // ------------------------------------------------------------------ sampler
@@ -647,14 +659,17 @@ static int sample_args_ok(const msnap_ctx *ctx, int n_drones, int n_samples, int
   return 1;
 }
 
+static int sample_args(const msnap_ctx *ctx, int n_drones, int n_seg, const void *coef, const void *dur, double dt,
+                       int n_samples, int n_axes, const void *pos) {
+  if (!sample_args_ok(ctx, n_drones, n_samples, n_axes, dt)) return MSNAP_EINVAL;
+  if (int rc = check_seg(ctx, n_seg)) return rc;
+  if (n_drones == 0 || n_samples == 0) return kNoWork;
+  return (!coef || !dur || !pos) ? MSNAP_EINVAL : MSNAP_OK;
+}
+
 int msnap_sample_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,
                         double dt, int n_samples, int n_axes, double *pos) {
-  if (!sample_args_ok(ctx, n_drones, n_samples, n_axes, dt)) return MSNAP_EINVAL;
-  int rc = check_seg(ctx, n_seg);
-  if (rc) return rc;
-  if (n_drones == 0 || n_samples == 0) return MSNAP_OK;
-  if (!coef || !dur || !pos) return MSNAP_EINVAL;
-  MSNAP_HIP(ctx, hipSetDevice(ctx->device));
+  MSNAP_ENTER(ctx, sample_args(ctx, n_drones, n_seg, coef, dur, dt, n_samples, n_axes, pos));
   return launch_sample(ctx, n_drones, n_seg, coef, dur, dt, n_samples, n_axes, pos, nullptr, false);
 }
 
@@ -671,7 +686,7 @@ int msnap_formation_collide_reads_rows_t(const msnap_ctx *ctx, int n_rows, int r
 
 int msnap_formation_collide_takes_broad_phase(const msnap_ctx *ctx, int n_rows, int row_offset, int n_cols, int n_samples) {
   if (!ctx || n_rows <= 0 || n_cols <= 0 || n_samples < 1 || row_offset < 0) return 0;
-  return formation_collide_takes_broad_phase(ctx, n_rows, row_offset, n_cols, n_samples) ? 1 : 0;
+  return formation_collide_takes_broad_phase(ctx, n_rows, row_offset, n_cols, n_samples, ctx->collide_no_sym) ? 1 : 0;
 }
 
 int msnap_formation_whole_pass_pays(msnap_ctx *ctx, int n_drones, int n_ranks, int *pays) {
@@ -698,7 +713,7 @@ int msnap_formation_whole_pass_pays(msnap_ctx *ctx, int n_drones, int n_ranks, i
 // no key launch), otherwise the transposed row image (false) -- paired with the positions `pos` they were computed
 // from.  A buffer seen before keeps its slot.
 static bool record_handover(msnap_ctx *ctx, const double *pos, const double *pos_t, int n_drones, int n_samples) {
-  const bool keys = formation_collide_takes_broad_phase(ctx, n_drones, 0, n_drones, n_samples);
+  const bool keys = formation_collide_takes_broad_phase(ctx, n_drones, 0, n_drones, n_samples, ctx->collide_no_sym);
   msnap_ctx::Handover *rec = nullptr;
   for (auto &h : ctx->handover)
     if (h.ptr == (const void *)pos_t) rec = &h;
@@ -709,12 +724,8 @@ static bool record_handover(msnap_ctx *ctx, const double *pos, const double *pos
 
 int msnap_sample_collide_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,
                                 double dt, int n_samples, double *pos, double *pos_t) {
-  if (!sample_args_ok(ctx, n_drones, n_samples, 3, dt)) return MSNAP_EINVAL;
-  int rc = check_seg(ctx, n_seg);
-  if (rc) return rc;
-  if (n_drones == 0 || n_samples == 0) return MSNAP_OK;
-  if (!coef || !dur || !pos || !pos_t) return MSNAP_EINVAL;
-  MSNAP_HIP(ctx, hipSetDevice(ctx->device));
+  const int rc = sample_args(ctx, n_drones, n_seg, coef, dur, dt, n_samples, 3, pos);
+  MSNAP_ENTER(ctx, rc == MSNAP_OK && !pos_t ? MSNAP_EINVAL : rc);
   const bool keys = record_handover(ctx, pos, pos_t, n_drones, n_samples);
   return launch_sample(ctx, n_drones, n_seg, coef, dur, dt, n_samples, 3, pos, pos_t, keys);
 }
@@ -735,160 +746,97 @@ int msnap_solve_grid_sample_device(msnap_ctx *ctx, int n_drones, int n_seg, cons
 
 int msnap_sample(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur, double dt,
                  int n_samples, int n_axes, double *pos) {
-  if (!sample_args_ok(ctx, n_drones, n_samples, n_axes, dt)) return MSNAP_EINVAL;
-  int rc = check_seg(ctx, n_seg);
-  if (rc) return rc;
-  if (n_drones == 0 || n_samples == 0) return MSNAP_OK;
-  if (!coef || !dur || !pos) return MSNAP_EINVAL;
-  MSNAP_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t N = n_drones, nc = ctx->order + 1;
-  const size_t b_coef = N * n_seg * 4 * nc * 8, b_dur = N * n_seg * 8;
-  const size_t b_pos = N * (size_t)n_samples * n_axes * 8;
-  if ((rc = ensure(ctx, ctx->stage[2], b_coef))) return rc;
-  if ((rc = ensure(ctx, ctx->stage[3], b_dur))) return rc;
-  if ((rc = ensure(ctx, ctx->stage[6], b_pos))) return rc;
-  MSNAP_HIP(ctx, hipMemcpyAsync(ctx->stage[2].p, coef, b_coef, hipMemcpyHostToDevice, ctx->stream));
-  MSNAP_HIP(ctx, hipMemcpyAsync(ctx->stage[3].p, dur, b_dur, hipMemcpyHostToDevice, ctx->stream));
-  rc = launch_sample(ctx, n_drones, n_seg, (const double *)ctx->stage[2].p, (const double *)ctx->stage[3].p,
-                     dt, n_samples, n_axes, (double *)ctx->stage[6].p, nullptr, false);
-  if (rc) return rc;
-  MSNAP_HIP(ctx, hipMemcpyAsync(pos, ctx->stage[6].p, b_pos, hipMemcpyDeviceToHost, ctx->stream));
-  MSNAP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return MSNAP_OK;
+  MSNAP_ENTER(ctx, sample_args(ctx, n_drones, n_seg, coef, dur, dt, n_samples, n_axes, pos));
+  return staged(ctx, {upload(coef, coef_bytes(ctx, n_drones, n_seg)), upload(dur, dur_bytes(n_drones, n_seg)),
+                      download(pos, (size_t)n_drones * n_samples * n_axes * 8)},
+                [&](const DevPtr *d) {
+                  return launch_sample(ctx, n_drones, n_seg, d[0], d[1], dt, n_samples, n_axes, d[2], nullptr, false);
+                });
 }
 
 // ------------------------------------------------------------------ flatness evaluator
+static int eval_flat_args(const msnap_ctx *ctx, int n_drones, int n_seg, const void *coef, const void *dur,
+                          int n_samples, const void *ts, const void *out) {
+  if (!ctx || n_drones < 0 || n_samples < 0) return MSNAP_EINVAL;
+  if (int rc = check_seg(ctx, n_seg)) return rc;
+  if (n_drones == 0 || n_samples == 0) return kNoWork;
+  return (!coef || !dur || !ts || !out) ? MSNAP_EINVAL : MSNAP_OK;
+}
+
 int msnap_eval_flat_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,
                            int n_samples, const double *ts, double *out) {
-  if (!ctx || n_drones < 0 || n_samples < 0) return MSNAP_EINVAL;
-  int rc = check_seg(ctx, n_seg);
-  if (rc) return rc;
-  if (n_drones == 0 || n_samples == 0) return MSNAP_OK;
-  if (!coef || !dur || !ts || !out) return MSNAP_EINVAL;
-  MSNAP_HIP(ctx, hipSetDevice(ctx->device));
+  MSNAP_ENTER(ctx, eval_flat_args(ctx, n_drones, n_seg, coef, dur, n_samples, ts, out));
   return launch_eval_flat(ctx, n_drones, n_seg, coef, dur, n_samples, ts, out);
 }
 
 int msnap_eval_flat(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,
                     int n_samples, const double *ts, double *out) {
-  if (!ctx || n_drones < 0 || n_samples < 0) return MSNAP_EINVAL;
-  int rc = check_seg(ctx, n_seg);
-  if (rc) return rc;
-  if (n_drones == 0 || n_samples == 0) return MSNAP_OK;
-  if (!coef || !dur || !ts || !out) return MSNAP_EINVAL;
-  MSNAP_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t N = n_drones, nc = ctx->order + 1;
-  const size_t b_coef = N * n_seg * 4 * nc * 8, b_dur = N * n_seg * 8, b_ts = (size_t)n_samples * 8;
-  const size_t b_out = N * (size_t)n_samples * 13 * 8;
-  if ((rc = ensure(ctx, ctx->stage[2], b_coef))) return rc;
-  if ((rc = ensure(ctx, ctx->stage[3], b_dur))) return rc;
-  if ((rc = ensure(ctx, ctx->stage[1], b_ts))) return rc;
-  if ((rc = ensure(ctx, ctx->stage[6], b_out))) return rc;
-  MSNAP_HIP(ctx, hipMemcpyAsync(ctx->stage[2].p, coef, b_coef, hipMemcpyHostToDevice, ctx->stream));
-  MSNAP_HIP(ctx, hipMemcpyAsync(ctx->stage[3].p, dur, b_dur, hipMemcpyHostToDevice, ctx->stream));
-  MSNAP_HIP(ctx, hipMemcpyAsync(ctx->stage[1].p, ts, b_ts, hipMemcpyHostToDevice, ctx->stream));
-  rc = launch_eval_flat(ctx, n_drones, n_seg, (const double *)ctx->stage[2].p, (const double *)ctx->stage[3].p,
-                        n_samples, (const double *)ctx->stage[1].p, (double *)ctx->stage[6].p);
-  if (rc) return rc;
-  MSNAP_HIP(ctx, hipMemcpyAsync(out, ctx->stage[6].p, b_out, hipMemcpyDeviceToHost, ctx->stream));
-  MSNAP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return MSNAP_OK;
+  MSNAP_ENTER(ctx, eval_flat_args(ctx, n_drones, n_seg, coef, dur, n_samples, ts, out));
+  return staged(ctx, {upload(coef, coef_bytes(ctx, n_drones, n_seg)), upload(dur, dur_bytes(n_drones, n_seg)),
+                      upload(ts, (size_t)n_samples * 8), download(out, (size_t)n_drones * n_samples * 13 * 8)},
+                [&](const DevPtr *d) { return launch_eval_flat(ctx, n_drones, n_seg, d[0], d[1], n_samples, d[2], d[3]); });
 }
 
 // ------------------------------------------------------------------ snap cost
 int msnap_snap_cost_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,
                            double *cost) {
-  if (!ctx || n_drones < 0) return MSNAP_EINVAL;
-  int rc = check_seg(ctx, n_seg);
-  if (rc) return rc;
-  if (n_drones == 0) return MSNAP_OK;
-  if (!coef || !dur || !cost) return MSNAP_EINVAL;
-  MSNAP_HIP(ctx, hipSetDevice(ctx->device));
+  MSNAP_ENTER(ctx, batch_args(ctx, n_drones, n_seg, {coef, dur, cost}));
   return launch_snap_cost(ctx, n_drones, n_seg, coef, dur, cost);
 }
 
 int msnap_snap_cost(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur, double *cost) {
-  if (!ctx || n_drones < 0) return MSNAP_EINVAL;
-  int rc = check_seg(ctx, n_seg);
-  if (rc) return rc;
-  if (n_drones == 0) return MSNAP_OK;
-  if (!coef || !dur || !cost) return MSNAP_EINVAL;
-  MSNAP_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t N = n_drones, nc = ctx->order + 1;
-  const size_t b_coef = N * n_seg * 4 * nc * 8, b_dur = N * n_seg * 8, b_cost = N * 4 * 8;
-  if ((rc = ensure(ctx, ctx->stage[2], b_coef))) return rc;
-  if ((rc = ensure(ctx, ctx->stage[3], b_dur))) return rc;
-  if ((rc = ensure(ctx, ctx->stage[6], b_cost))) return rc;
-  MSNAP_HIP(ctx, hipMemcpyAsync(ctx->stage[2].p, coef, b_coef, hipMemcpyHostToDevice, ctx->stream));
-  MSNAP_HIP(ctx, hipMemcpyAsync(ctx->stage[3].p, dur, b_dur, hipMemcpyHostToDevice, ctx->stream));
-  rc = launch_snap_cost(ctx, n_drones, n_seg, (const double *)ctx->stage[2].p, (const double *)ctx->stage[3].p,
-                        (double *)ctx->stage[6].p);
-  if (rc) return rc;
-  MSNAP_HIP(ctx, hipMemcpyAsync(cost, ctx->stage[6].p, b_cost, hipMemcpyDeviceToHost, ctx->stream));
-  MSNAP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return MSNAP_OK;
+  MSNAP_ENTER(ctx, batch_args(ctx, n_drones, n_seg, {coef, dur, cost}));
+  return staged(ctx, {upload(coef, coef_bytes(ctx, n_drones, n_seg)), upload(dur, dur_bytes(n_drones, n_seg)),
+                      download(cost, (size_t)n_drones * 4 * 8)},
+                [&](const DevPtr *d) { return launch_snap_cost(ctx, n_drones, n_seg, d[0], d[1], d[2]); });
 }
 
 // ------------------------------------------------------------------ formation collide
+static int collide_args(const msnap_ctx *ctx, int n_rows, int row_offset, int n_cols, int n_samples,
+                        const void *pos_rows, const void *pos_cols, double radius, const void *min_dist,
+                        const void *partner, const void *hit) {
+  if (!ctx || n_rows < 0 || n_cols < 0 || n_samples < 1 || row_offset < 0 || !(radius >= 0.0)) return MSNAP_EINVAL;
+  if (n_rows == 0) return kNoWork;
+  return (!pos_rows || (n_cols > 0 && !pos_cols) || !min_dist || !partner || !hit) ? MSNAP_EINVAL : MSNAP_OK;
+}
+
 int msnap_formation_collide_device(msnap_ctx *ctx, int n_rows, int row_offset, int n_cols, int n_samples,
                                    const double *pos_rows, const double *pos_cols, double radius,
                                    double *min_dist, int32_t *partner, int32_t *hit) {
-  if (!ctx || n_rows < 0 || n_cols < 0 || n_samples < 1 || row_offset < 0 || !(radius >= 0.0))
-    return MSNAP_EINVAL;
-  if (n_rows == 0) return MSNAP_OK;
-  if (!pos_rows || (n_cols > 0 && !pos_cols) || !min_dist || !partner || !hit) return MSNAP_EINVAL;
-  MSNAP_HIP(ctx, hipSetDevice(ctx->device));
+  MSNAP_ENTER(ctx, collide_args(ctx, n_rows, row_offset, n_cols, n_samples, pos_rows, pos_cols, radius, min_dist,
+                                partner, hit));
   return launch_formation_collide(ctx, n_rows, row_offset, n_cols, n_samples, pos_rows, pos_cols, radius,
-                                  min_dist, partner, hit, nullptr);
+                                  min_dist, partner, hit, nullptr, ctx->collide_no_sym);
 }
 
 int msnap_formation_collide_t_device(msnap_ctx *ctx, int n_rows, int row_offset, int n_cols, int n_samples,
                                      const double *pos_rows_t, const double *pos_rows, const double *pos_cols,
                                      double radius, double *min_dist, int32_t *partner, int32_t *hit) {
-  if (!ctx || n_rows < 0 || n_cols < 0 || n_samples < 1 || row_offset < 0 || !(radius >= 0.0))
-    return MSNAP_EINVAL;
-  if (n_rows == 0) return MSNAP_OK;
-  if (!pos_rows_t || !pos_rows || (n_cols > 0 && !pos_cols) || !min_dist || !partner || !hit) return MSNAP_EINVAL;
-  MSNAP_HIP(ctx, hipSetDevice(ctx->device));
+  const int rc = collide_args(ctx, n_rows, row_offset, n_cols, n_samples, pos_rows, pos_cols, radius, min_dist,
+                              partner, hit);
+  MSNAP_ENTER(ctx, rc == MSNAP_OK && !pos_rows_t ? MSNAP_EINVAL : rc);
   return launch_formation_collide(ctx, n_rows, row_offset, n_cols, n_samples, pos_rows, pos_cols, radius,
-                                  min_dist, partner, hit, pos_rows_t);
+                                  min_dist, partner, hit, pos_rows_t, ctx->collide_no_sym);
 }
 
 int msnap_formation_collide(msnap_ctx *ctx, int n_rows, int row_offset, int n_cols, int n_samples,
                             const double *pos_rows, const double *pos_cols, double radius, double *min_dist,
                             int32_t *partner, int32_t *hit) {
-  if (!ctx || n_rows < 0 || n_cols < 0 || n_samples < 1 || row_offset < 0 || !(radius >= 0.0))
-    return MSNAP_EINVAL;
-  if (n_rows == 0) return MSNAP_OK;
-  if (!pos_rows || (n_cols > 0 && !pos_cols) || !min_dist || !partner || !hit) return MSNAP_EINVAL;
-  MSNAP_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t b_rows = (size_t)n_rows * n_samples * 3 * 8, b_cols = (size_t)n_cols * n_samples * 3 * 8;
-  int rc;
-  if ((rc = ensure(ctx, ctx->stage[0], b_rows))) return rc;
-  if ((rc = ensure(ctx, ctx->stage[1], b_cols + 8))) return rc;
-  if ((rc = ensure(ctx, ctx->stage[2], (size_t)n_rows * 8))) return rc;
-  if ((rc = ensure(ctx, ctx->stage[3], (size_t)n_rows * 4))) return rc;
-  if ((rc = ensure(ctx, ctx->stage[4], (size_t)n_rows * 4))) return rc;
-  MSNAP_HIP(ctx, hipMemcpyAsync(ctx->stage[0].p, pos_rows, b_rows, hipMemcpyHostToDevice, ctx->stream));
-  if (b_cols)
-    MSNAP_HIP(ctx, hipMemcpyAsync(ctx->stage[1].p, pos_cols, b_cols, hipMemcpyHostToDevice, ctx->stream));
+  MSNAP_ENTER(ctx, collide_args(ctx, n_rows, row_offset, n_cols, n_samples, pos_rows, pos_cols, radius, min_dist,
+                                partner, hit));
+  const size_t E = (size_t)n_samples * 3, b_rows = (size_t)n_rows * E * 8, R = n_rows;
   // The once-per-pair evaluation credits column-side minima to the ROW drones, which is only right when
   // pos_rows is the slice [row_offset, row_offset + n_rows) of pos_cols.  Host arrays can be compared: a
   // caller whose rows are some other set of drones gets the one-sided evaluation instead of wrong partners.
-  const int saved_no_sym = ctx->collide_no_sym;
-  if ((long long)row_offset + n_rows <= n_cols && pos_rows != pos_cols + (size_t)row_offset * n_samples * 3 &&
-      memcmp(pos_rows, pos_cols + (size_t)row_offset * n_samples * 3, b_rows) != 0)
-    ctx->collide_no_sym = 1;
-  rc = launch_formation_collide(ctx, n_rows, row_offset, n_cols, n_samples, (const double *)ctx->stage[0].p,
-                                (const double *)ctx->stage[1].p, radius, (double *)ctx->stage[2].p,
-                                (int32_t *)ctx->stage[3].p, (int32_t *)ctx->stage[4].p, nullptr);
-  ctx->collide_no_sym = saved_no_sym;
-  if (rc) return rc;
-  MSNAP_HIP(ctx, hipMemcpyAsync(min_dist, ctx->stage[2].p, (size_t)n_rows * 8, hipMemcpyDeviceToHost, ctx->stream));
-  MSNAP_HIP(ctx, hipMemcpyAsync(partner, ctx->stage[3].p, (size_t)n_rows * 4, hipMemcpyDeviceToHost, ctx->stream));
-  MSNAP_HIP(ctx, hipMemcpyAsync(hit, ctx->stage[4].p, (size_t)n_rows * 4, hipMemcpyDeviceToHost, ctx->stream));
-  MSNAP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return MSNAP_OK;
+  const bool no_sym = ctx->collide_no_sym ||
+                      ((long long)row_offset + n_rows <= n_cols && pos_rows != pos_cols + row_offset * E &&
+                       memcmp(pos_rows, pos_cols + row_offset * E, b_rows) != 0);
+  return staged(ctx, {upload(pos_rows, b_rows), upload(pos_cols, (size_t)n_cols * E * 8), download(min_dist, R * 8),
+                      download(partner, R * 4), download(hit, R * 4)},
+                [&](const DevPtr *d) {
+                  return launch_formation_collide(ctx, n_rows, row_offset, n_cols, n_samples, d[0], d[1], radius, d[2],
+                                                  d[3], d[4], nullptr, no_sym);
+                });
 }
 
 // ------------------------------------------------------------------ formation pass in parts (one per rank)
@@ -897,136 +845,166 @@ size_t msnap_formation_part_bytes(int n_drones) {
   return ((size_t)n_drones * (sizeof(double) + sizeof(int32_t)) + 7) & ~(size_t)7;
 }
 
+// (`device`: the parts are device memory, read as doubles: 8-byte aligned)
+static int part_args(const msnap_ctx *ctx, int n_drones, int n_samples, const void *pos_all, int part, int n_parts,
+                     const void *part_out, bool device) {
+  if (!ctx || n_drones < 0 || n_samples < 1 || n_parts < 1 || part < 0 || part >= n_parts) return MSNAP_EINVAL;
+  if (n_drones == 0) return kNoWork;
+  return (!pos_all || !part_out || (device && ((uintptr_t)part_out & 7))) ? MSNAP_EINVAL : MSNAP_OK;
+}
+
+static int finish_args(const msnap_ctx *ctx, int n_drones, int n_parts, const void *parts, int row_offset, int n_rows,
+                       double radius, const void *min_dist, const void *partner, const void *hit, bool device) {
+  if (!ctx || n_drones < 0 || n_parts < 1 || row_offset < 0 || n_rows < 0 || !(radius >= 0.0)) return MSNAP_EINVAL;
+  if ((long long)row_offset + n_rows > n_drones) return MSNAP_EINVAL;
+  if (n_rows == 0) return kNoWork;
+  return (!parts || !min_dist || !partner || !hit || (device && ((uintptr_t)parts & 7))) ? MSNAP_EINVAL : MSNAP_OK;
+}
+
 int msnap_formation_collide_part_device(msnap_ctx *ctx, int n_drones, int n_samples, const double *pos_all, int part,
                                         int n_parts, void *part_out) {
-  if (!ctx || n_drones < 0 || n_samples < 1 || n_parts < 1 || part < 0 || part >= n_parts) return MSNAP_EINVAL;
-  if (n_drones == 0) return MSNAP_OK;
-  if (!pos_all || !part_out || ((uintptr_t)part_out & 7)) return MSNAP_EINVAL;
-  MSNAP_HIP(ctx, hipSetDevice(ctx->device));
+  MSNAP_ENTER(ctx, part_args(ctx, n_drones, n_samples, pos_all, part, n_parts, part_out, true));
   return launch_formation_collide_part(ctx, n_drones, n_samples, pos_all, part, n_parts, (double *)part_out,
                                        (int32_t *)((unsigned char *)part_out + (size_t)n_drones * sizeof(double)));
 }
 
 int msnap_formation_collide_finish_device(msnap_ctx *ctx, int n_drones, int n_parts, const void *parts, int row_offset,
                                           int n_rows, double radius, double *min_dist, int32_t *partner, int32_t *hit) {
-  if (!ctx || n_drones < 0 || n_parts < 1 || row_offset < 0 || n_rows < 0 || !(radius >= 0.0)) return MSNAP_EINVAL;
-  if ((long long)row_offset + n_rows > n_drones) return MSNAP_EINVAL;
-  if (n_rows == 0) return MSNAP_OK;
-  if (!parts || !min_dist || !partner || !hit || ((uintptr_t)parts & 7)) return MSNAP_EINVAL;
-  MSNAP_HIP(ctx, hipSetDevice(ctx->device));
+  MSNAP_ENTER(ctx, finish_args(ctx, n_drones, n_parts, parts, row_offset, n_rows, radius, min_dist, partner, hit, true));
   return launch_formation_collide_finish(ctx, n_drones, n_parts, parts, msnap_formation_part_bytes(n_drones),
                                          row_offset, n_rows, radius, min_dist, partner, hit);
 }
 
 int msnap_formation_collide_part(msnap_ctx *ctx, int n_drones, int n_samples, const double *pos_all, int part,
                                  int n_parts, void *part_out) {
-  if (!ctx || n_drones < 0 || n_samples < 1 || n_parts < 1 || part < 0 || part >= n_parts) return MSNAP_EINVAL;
-  if (n_drones == 0) return MSNAP_OK;
-  if (!pos_all || !part_out) return MSNAP_EINVAL;
-  MSNAP_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t b_pos = (size_t)n_drones * n_samples * 3 * 8, b_out = msnap_formation_part_bytes(n_drones);
-  int rc;
-  if ((rc = ensure(ctx, ctx->stage[1], b_pos + 8))) return rc;
-  if ((rc = ensure(ctx, ctx->stage[2], b_out))) return rc;
-  MSNAP_HIP(ctx, hipMemcpyAsync(ctx->stage[1].p, pos_all, b_pos, hipMemcpyHostToDevice, ctx->stream));
-  rc = msnap_formation_collide_part_device(ctx, n_drones, n_samples, (const double *)ctx->stage[1].p, part, n_parts,
-                                           ctx->stage[2].p);
-  if (rc) return rc;
-  MSNAP_HIP(ctx, hipMemcpyAsync(part_out, ctx->stage[2].p, b_out, hipMemcpyDeviceToHost, ctx->stream));
-  MSNAP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return MSNAP_OK;
+  MSNAP_ENTER(ctx, part_args(ctx, n_drones, n_samples, pos_all, part, n_parts, part_out, false));
+  return staged(ctx, {upload(pos_all, (size_t)n_drones * n_samples * 3 * 8),
+                      download(part_out, msnap_formation_part_bytes(n_drones))},
+                [&](const DevPtr *d) {
+                  return msnap_formation_collide_part_device(ctx, n_drones, n_samples, d[0], part, n_parts, d[1]);
+                });
 }
 
 int msnap_formation_collide_finish(msnap_ctx *ctx, int n_drones, int n_parts, const void *parts, int row_offset,
                                    int n_rows, double radius, double *min_dist, int32_t *partner, int32_t *hit) {
-  if (!ctx || n_drones < 0 || n_parts < 1 || row_offset < 0 || n_rows < 0 || !(radius >= 0.0)) return MSNAP_EINVAL;
-  if ((long long)row_offset + n_rows > n_drones) return MSNAP_EINVAL;
-  if (n_rows == 0) return MSNAP_OK;
-  if (!parts || !min_dist || !partner || !hit) return MSNAP_EINVAL;
-  MSNAP_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t b_in = msnap_formation_part_bytes(n_drones) * (size_t)n_parts;
-  int rc;
-  if ((rc = ensure(ctx, ctx->stage[1], b_in + 8))) return rc;
-  if ((rc = ensure(ctx, ctx->stage[2], (size_t)n_rows * 8))) return rc;
-  if ((rc = ensure(ctx, ctx->stage[3], (size_t)n_rows * 4))) return rc;
-  if ((rc = ensure(ctx, ctx->stage[4], (size_t)n_rows * 4))) return rc;
-  MSNAP_HIP(ctx, hipMemcpyAsync(ctx->stage[1].p, parts, b_in, hipMemcpyHostToDevice, ctx->stream));
-  rc = msnap_formation_collide_finish_device(ctx, n_drones, n_parts, ctx->stage[1].p, row_offset, n_rows, radius,
-                                             (double *)ctx->stage[2].p, (int32_t *)ctx->stage[3].p,
-                                             (int32_t *)ctx->stage[4].p);
-  if (rc) return rc;
-  MSNAP_HIP(ctx, hipMemcpyAsync(min_dist, ctx->stage[2].p, (size_t)n_rows * 8, hipMemcpyDeviceToHost, ctx->stream));
-  MSNAP_HIP(ctx, hipMemcpyAsync(partner, ctx->stage[3].p, (size_t)n_rows * 4, hipMemcpyDeviceToHost, ctx->stream));
-  MSNAP_HIP(ctx, hipMemcpyAsync(hit, ctx->stage[4].p, (size_t)n_rows * 4, hipMemcpyDeviceToHost, ctx->stream));
-  MSNAP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return MSNAP_OK;
+  MSNAP_ENTER(ctx, finish_args(ctx, n_drones, n_parts, parts, row_offset, n_rows, radius, min_dist, partner, hit, false));
+  const size_t R = n_rows;
+  return staged(ctx, {upload(parts, msnap_formation_part_bytes(n_drones) * (size_t)n_parts), download(min_dist, R * 8),
+                      download(partner, R * 4), download(hit, R * 4)},
+                [&](const DevPtr *d) {
+                  return msnap_formation_collide_finish_device(ctx, n_drones, n_parts, d[0], row_offset, n_rows, radius,
+                                                               d[1], d[2], d[3]);
+                });
 }
 
 // ------------------------------------------------------------------ mesh sweep
+static int sweep_args(const msnap_ctx *ctx, int n_drones, int n_samples, const void *pos, int n_tris, const void *tris,
+                      double radius, const void *min_dist, const void *hit) {
+  if (!ctx || n_drones < 0 || n_samples < 1 || n_tris < 0 || !(radius >= 0.0)) return MSNAP_EINVAL;
+  if (n_drones == 0) return kNoWork;
+  return (!pos || (n_tris > 0 && !tris) || !min_dist || !hit) ? MSNAP_EINVAL : MSNAP_OK;
+}
+
 int msnap_mesh_sweep_device(msnap_ctx *ctx, int n_drones, int n_samples, const double *pos, int n_tris,
                             const double *tris, double radius, double *min_dist, int32_t *hit) {
-  if (!ctx || n_drones < 0 || n_samples < 1 || n_tris < 0 || !(radius >= 0.0)) return MSNAP_EINVAL;
-  if (n_drones == 0) return MSNAP_OK;
-  if (!pos || (n_tris > 0 && !tris) || !min_dist || !hit) return MSNAP_EINVAL;
-  MSNAP_HIP(ctx, hipSetDevice(ctx->device));
+  MSNAP_ENTER(ctx, sweep_args(ctx, n_drones, n_samples, pos, n_tris, tris, radius, min_dist, hit));
   return launch_mesh_sweep(ctx, n_drones, n_samples, pos, n_tris, tris, radius, min_dist, hit);
 }
 
 int msnap_mesh_sweep(msnap_ctx *ctx, int n_drones, int n_samples, const double *pos, int n_tris,
                      const double *tris, double radius, double *min_dist, int32_t *hit) {
-  if (!ctx || n_drones < 0 || n_samples < 1 || n_tris < 0 || !(radius >= 0.0)) return MSNAP_EINVAL;
-  if (n_drones == 0) return MSNAP_OK;
-  if (!pos || (n_tris > 0 && !tris) || !min_dist || !hit) return MSNAP_EINVAL;
-  MSNAP_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t b_pos = (size_t)n_drones * n_samples * 3 * 8, b_tri = (size_t)n_tris * 9 * 8;
-  int rc;
-  if ((rc = ensure(ctx, ctx->stage[0], b_pos))) return rc;
-  if ((rc = ensure(ctx, ctx->stage[1], b_tri + 8))) return rc;
-  if ((rc = ensure(ctx, ctx->stage[2], (size_t)n_drones * 8))) return rc;
-  if ((rc = ensure(ctx, ctx->stage[4], (size_t)n_drones * 4))) return rc;
-  MSNAP_HIP(ctx, hipMemcpyAsync(ctx->stage[0].p, pos, b_pos, hipMemcpyHostToDevice, ctx->stream));
-  if (b_tri) MSNAP_HIP(ctx, hipMemcpyAsync(ctx->stage[1].p, tris, b_tri, hipMemcpyHostToDevice, ctx->stream));
-  rc = launch_mesh_sweep(ctx, n_drones, n_samples, (const double *)ctx->stage[0].p, n_tris,
-                         (const double *)ctx->stage[1].p, radius, (double *)ctx->stage[2].p,
-                         (int32_t *)ctx->stage[4].p);
-  if (rc) return rc;
-  MSNAP_HIP(ctx, hipMemcpyAsync(min_dist, ctx->stage[2].p, (size_t)n_drones * 8, hipMemcpyDeviceToHost, ctx->stream));
-  MSNAP_HIP(ctx, hipMemcpyAsync(hit, ctx->stage[4].p, (size_t)n_drones * 4, hipMemcpyDeviceToHost, ctx->stream));
-  MSNAP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return MSNAP_OK;
+  MSNAP_ENTER(ctx, sweep_args(ctx, n_drones, n_samples, pos, n_tris, tris, radius, min_dist, hit));
+  return staged(ctx, {upload(pos, (size_t)n_drones * n_samples * 3 * 8), upload(tris, (size_t)n_tris * 9 * 8),
+                      download(min_dist, (size_t)n_drones * 8), download(hit, (size_t)n_drones * 4)},
+                [&](const DevPtr *d) {
+                  return launch_mesh_sweep(ctx, n_drones, n_samples, d[0], n_tris, d[1], radius, d[2], d[3]);
+                });
 }
 
 // ------------------------------------------------------------------ mesh-vs-mesh validity
+static int validity_args(const msnap_ctx *ctx, int n_states, const void *states, int n_rtris, const void *rtris,
+                         int n_etris, const void *etris, const void *valid) {
+  if (!ctx || n_states < 0 || n_rtris < 0 || n_etris < 0) return MSNAP_EINVAL;
+  if (n_states == 0) return kNoWork;
+  return (!states || !valid || (n_rtris > 0 && !rtris) || (n_etris > 0 && !etris)) ? MSNAP_EINVAL : MSNAP_OK;
+}
+
 int msnap_mesh_validity_device(msnap_ctx *ctx, int n_states, const double *states, int n_rtris, const double *rtris,
                                int n_etris, const double *etris, int32_t *valid) {
-  if (!ctx || n_states < 0 || n_rtris < 0 || n_etris < 0) return MSNAP_EINVAL;
-  if (n_states == 0) return MSNAP_OK;
-  if (!states || !valid || (n_rtris > 0 && !rtris) || (n_etris > 0 && !etris)) return MSNAP_EINVAL;
-  MSNAP_HIP(ctx, hipSetDevice(ctx->device));
+  MSNAP_ENTER(ctx, validity_args(ctx, n_states, states, n_rtris, rtris, n_etris, etris, valid));
   return launch_mesh_validity(ctx, n_states, states, n_rtris, rtris, n_etris, etris, valid);
 }
 
 int msnap_mesh_validity(msnap_ctx *ctx, int n_states, const double *states, int n_rtris, const double *rtris,
                         int n_etris, const double *etris, int32_t *valid) {
-  if (!ctx || n_states < 0 || n_rtris < 0 || n_etris < 0) return MSNAP_EINVAL;
-  if (n_states == 0) return MSNAP_OK;
-  if (!states || !valid || (n_rtris > 0 && !rtris) || (n_etris > 0 && !etris)) return MSNAP_EINVAL;
-  MSNAP_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t b_st = (size_t)n_states * 4 * 8, b_r = (size_t)n_rtris * 9 * 8, b_e = (size_t)n_etris * 9 * 8;
-  int rc;
-  if ((rc = ensure(ctx, ctx->stage[0], b_st))) return rc;
-  if ((rc = ensure(ctx, ctx->stage[1], b_r + 8))) return rc;
-  if ((rc = ensure(ctx, ctx->stage[2], b_e + 8))) return rc;
-  if ((rc = ensure(ctx, ctx->stage[4], (size_t)n_states * 4))) return rc;
-  MSNAP_HIP(ctx, hipMemcpyAsync(ctx->stage[0].p, states, b_st, hipMemcpyHostToDevice, ctx->stream));
-  if (b_r) MSNAP_HIP(ctx, hipMemcpyAsync(ctx->stage[1].p, rtris, b_r, hipMemcpyHostToDevice, ctx->stream));
-  if (b_e) MSNAP_HIP(ctx, hipMemcpyAsync(ctx->stage[2].p, etris, b_e, hipMemcpyHostToDevice, ctx->stream));
-  rc = launch_mesh_validity(ctx, n_states, (const double *)ctx->stage[0].p, n_rtris, (const double *)ctx->stage[1].p,
-                            n_etris, (const double *)ctx->stage[2].p, (int32_t *)ctx->stage[4].p);
-  if (rc) return rc;
-  MSNAP_HIP(ctx, hipMemcpyAsync(valid, ctx->stage[4].p, (size_t)n_states * 4, hipMemcpyDeviceToHost, ctx->stream));
-  MSNAP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  MSNAP_ENTER(ctx, validity_args(ctx, n_states, states, n_rtris, rtris, n_etris, etris, valid));
+  return staged(ctx, {upload(states, (size_t)n_states * 4 * 8), upload(rtris, (size_t)n_rtris * 9 * 8),
+                      upload(etris, (size_t)n_etris * 9 * 8), download(valid, (size_t)n_states * 4)},
+                [&](const DevPtr *d) { return launch_mesh_validity(ctx, n_states, d[0], n_rtris, d[1], n_etris, d[2], d[3]); });
+}
+
+// ------------------------------------------------------------------ dynamic limits (msnap_limits.hip)
+// `limits_rc`: check_limits of a retiming (limits is a host array in both versions), which comes after the shape and
+// before an empty batch returns
+static int limits_args(const msnap_ctx *ctx, int n_drones, int n_seg, std::initializer_list<const void *> ptrs,
+                       int limits_rc = MSNAP_OK) {
+  if (int rc = check_limits_args(ctx, n_drones, n_seg)) return rc;
+  if (limits_rc) return limits_rc;
+  if (n_drones == 0) return kNoWork;
+  for (const void *p : ptrs)
+    if (!p) return MSNAP_EINVAL;
   return MSNAP_OK;
+}
+
+int msnap_dynamic_peaks_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,
+                               double *peak, double *t_peak, int32_t *status) {
+  MSNAP_ENTER(ctx, limits_args(ctx, n_drones, n_seg, {coef, dur, peak, t_peak, status}));
+  const int rc = ensure(ctx, ctx->limits_work, lane_doubles(n_drones, n_seg) * sizeof(double));
+  if (rc) return rc;
+  return launch_peaks(ctx, n_drones, n_seg, coef, dur, (double *)ctx->limits_work.p, peak, t_peak, status);
+}
+
+int msnap_dynamic_peaks(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur, double *peak,
+                        double *t_peak, int32_t *status) {
+  MSNAP_ENTER(ctx, limits_args(ctx, n_drones, n_seg, {coef, dur, peak, t_peak, status}));
+  const size_t b_pk = (size_t)n_drones * 4 * 8;
+  return staged(ctx, {upload(coef, coef_bytes(ctx, n_drones, n_seg)), upload(dur, dur_bytes(n_drones, n_seg)),
+                      download(peak, b_pk), download(t_peak, b_pk), download(status, (size_t)n_drones * 4)},
+                [&](const DevPtr *d) {
+                  return msnap_dynamic_peaks_device(ctx, n_drones, n_seg, d[0], d[1], d[2], d[3], d[4]);
+                });
+}
+
+int msnap_time_scale_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,
+                            const double *scale, double *coef_out, double *dur_out) {
+  MSNAP_ENTER(ctx, limits_args(ctx, n_drones, n_seg, {coef, dur, scale, coef_out, dur_out}));
+  return launch_time_scale(ctx, n_drones, n_seg, coef, dur, scale, coef_out, dur_out);
+}
+
+// (the host versions stage coef and dur once and scale them in place)
+int msnap_time_scale(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,
+                     const double *scale, double *coef_out, double *dur_out) {
+  MSNAP_ENTER(ctx, limits_args(ctx, n_drones, n_seg, {coef, dur, scale, coef_out, dur_out}));
+  return staged(ctx, {{coef, coef_out, coef_bytes(ctx, n_drones, n_seg)}, {dur, dur_out, dur_bytes(n_drones, n_seg)},
+                      upload(scale, (size_t)n_drones * 8)},
+                [&](const DevPtr *d) { return launch_time_scale(ctx, n_drones, n_seg, d[0], d[1], d[2], d[0], d[1]); });
+}
+
+int msnap_retime_to_limits_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,
+                                  const double limits[4], int flags, double *coef_out, double *dur_out,
+                                  double *scale) {
+  MSNAP_ENTER(ctx, limits_args(ctx, n_drones, n_seg, {coef, dur, coef_out, dur_out, scale}, check_limits(limits, flags)));
+  return launch_retime(ctx, n_drones, n_seg, coef, dur, limits, flags, coef_out, dur_out, scale);
+}
+
+int msnap_retime_to_limits(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,
+                           const double limits[4], int flags, double *coef_out, double *dur_out, double *scale) {
+  MSNAP_ENTER(ctx, limits_args(ctx, n_drones, n_seg, {coef, dur, coef_out, dur_out, scale}, check_limits(limits, flags)));
+  return staged(ctx, {{coef, coef_out, coef_bytes(ctx, n_drones, n_seg)}, {dur, dur_out, dur_bytes(n_drones, n_seg)},
+                      download(scale, (size_t)n_drones * 8)},
+                [&](const DevPtr *d) {
+                  return launch_retime(ctx, n_drones, n_seg, d[0], d[1], limits, flags, d[0], d[1], d[2]);
+                });
 }
 
 }  // extern "C"

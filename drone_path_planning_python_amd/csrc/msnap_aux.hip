@@ -2399,8 +2399,9 @@ bool collide_counts_by_groups(const msnap_ctx *ctx, int n_drones, int shares_sur
 
 // whether a pass with these arguments runs behind the exact broad phase (which builds its own, spatially sorted, row
 // image: a caller-provided one is then not read -- msnap_formation_collide_reads_rows_t)
-bool formation_collide_takes_broad_phase(const msnap_ctx *ctx, int n_rows, int row_offset, int n_cols, int n_samples) {
-  if (n_samples < kSampleChunk || n_rows != n_cols || row_offset != 0 || ctx->collide_no_cull || ctx->collide_no_sym) return false;
+bool formation_collide_takes_broad_phase(const msnap_ctx *ctx, int n_rows, int row_offset, int n_cols, int n_samples,
+                                         bool no_sym) {
+  if (n_samples < kSampleChunk || n_rows != n_cols || row_offset != 0 || ctx->collide_no_cull || no_sym) return false;
   const int cull_min = ctx->collide_cull_min_drones > 0 ? ctx->collide_cull_min_drones : kCullMinDrones;
   return n_rows >= cull_min && n_rows >= 2 * kRowBlock && n_rows <= kCullMaxDrones;
 }
@@ -2409,7 +2410,7 @@ bool formation_collide_takes_broad_phase(const msnap_ctx *ctx, int n_rows, int r
 // second output, msnap_sample_collide); nullptr: built here from pos_rows
 int launch_formation_collide(msnap_ctx *ctx, int n_rows, int row_offset, int n_cols, int n_samples,
                              const double *pos_rows, const double *pos_cols, double radius, double *min_dist,
-                             int32_t *partner, int32_t *hit, const double *rows_t_in) {
+                             int32_t *partner, int32_t *hit, const double *rows_t_in, bool no_sym) {
   CollideGeom g;
   g.R = n_rows;
   g.ro = row_offset;
@@ -2451,9 +2452,10 @@ int launch_formation_collide(msnap_ctx *ctx, int n_rows, int row_offset, int n_c
   g.oe = rows_in_cols ? row_offset + n_rows : n_cols;
   const size_t cpart_entries = (size_t)g.n_rb * n_rows;
   // (the column-side partial buffer is bounded at 2 GB: 170 k rows on one GPU; beyond that, and for callers whose
-  // rows are not the slice of the columns -- "collide_no_sym" -- every pair of the range is evaluated from both
+  // rows are not the slice of the columns -- no_sym: "collide_no_sym", or msnap_formation_collide's comparison of its
+  // host arrays -- every pair of the range is evaluated from both
   // sides; msnap_get_option("collide_last_sym") reports which way the last pass went)
-  g.sym = (rows_in_cols && n_rows > kRowBlock && !ctx->collide_no_sym && cpart_entries * 12 <= ((size_t)2 << 30)) ? 1 : 0;
+  g.sym = (rows_in_cols && n_rows > kRowBlock && !no_sym && cpart_entries * 12 <= ((size_t)2 << 30)) ? 1 : 0;
   ctx->collide_last_sym = g.sym;
   g.upw = 1;
   g.total = collide_ustart(g, g.n_rb);
@@ -2501,7 +2503,7 @@ int launch_formation_collide(msnap_ctx *ctx, int n_rows, int row_offset, int n_c
   // (below some 3000 drones the six small launches in front of the pass cost more than a sparse swarm saves:
   // 2048 x 91 dense 91 -> 121 us, sparse 92 -> 84; 4096 x 91 dense 243 -> 282, sparse 243 -> 122, the formation
   // fixture 243 -> 105)
-  const bool cull = g.sym && formation_collide_takes_broad_phase(ctx, n_rows, row_offset, n_cols, n_samples);
+  const bool cull = g.sym && formation_collide_takes_broad_phase(ctx, n_rows, row_offset, n_cols, n_samples, no_sym);
   // (what the last pass did: the broad-phase fields are set together, once its buffer exists)
   ctx->collide_last_cull = 0;
   ctx->collide_meta = nullptr;
@@ -2558,9 +2560,9 @@ int launch_formation_collide(msnap_ctx *ctx, int n_rows, int row_offset, int n_c
     const size_t doubles = (size_t)g.Rp * E + (size_t)N * E + (size_t)N * 6 + nJ * 6 + (size_t)N + entries + centries + gcap * 16;
     const size_t ints = entries + centries + (size_t)N + (size_t)N + (size_t)shares + g.n_rb + kMetaWords + 2 * nJ + gcap +
                         gcap * 16 + (by_groups ? nJ * nJ : 0);
-    int rc = ensure(ctx, ctx->stage[7], doubles * sizeof(double) + ints * sizeof(int32_t) + 64);
+    int rc = ensure(ctx, ctx->collide_work, doubles * sizeof(double) + ints * sizeof(int32_t) + 64);
     if (rc) return rc;
-    double *rows_t = (double *)ctx->stage[7].p;
+    double *rows_t = (double *)ctx->collide_work.p;
     double *psorted = rows_t + (size_t)g.Rp * E, *box_own = psorted + (size_t)N * E, *colbox = box_own + (size_t)N * 6;
     unsigned long long *bound = (unsigned long long *)(colbox + nJ * 6);
     double *pd = (double *)(bound + N), *cd = pd + entries;
@@ -2578,7 +2580,7 @@ int launch_formation_collide(msnap_ctx *ctx, int n_rows, int row_offset, int n_c
     // block has held something else since -- another layout, another evaluator, any other pass of the context -- and,
     // so that a graph replays whatever ran between its replays, always under stream capture
     // (nor is a block trusted that a graph may replay on between two eager passes)
-    const bool trust = by_groups && !stream_is_capturing(ctx) && !ctx->stage[7].in_graph;
+    const bool trust = by_groups && !stream_is_capturing(ctx) && !ctx->collide_work.in_graph;
     const bool blist_clean = trust && ctx->blist_clean == (const void *)blist && ctx->blist_clean_n == (int)nJ;
     ctx->blist_clean = trust ? (const void *)blist : nullptr;
     ctx->blist_clean_n = (int)nJ;
@@ -2643,10 +2645,10 @@ int launch_formation_collide(msnap_ctx *ctx, int n_rows, int row_offset, int n_c
   const size_t centries = g.sym ? cpart_entries * g.sparts : 0;
   const size_t t_entries = rows_t_in ? 0 : (size_t)g.Rp * E;
   ctx->blist_clean = nullptr;      // (the block is about to hold this pass's buffers)
-  int rc = ensure(ctx, ctx->stage[7],
+  int rc = ensure(ctx, ctx->collide_work,
                   t_entries * sizeof(double) + (part_entries + centries) * (sizeof(double) + sizeof(int32_t)) + 64);
   if (rc) return rc;
-  double *rows_t = (double *)ctx->stage[7].p;
+  double *rows_t = (double *)ctx->collide_work.p;
   double *pd = rows_t + t_entries;
   double *cd = pd + part_entries;
   int32_t *pj = (int32_t *)(cd + centries);
@@ -2754,10 +2756,10 @@ int launch_formation_collide_part(msnap_ctx *ctx, int N, int n_samples, const do
   ctx->collide_last_handover = 0;
   ctx->collide_meta = nullptr;
   ctx->blist_clean = nullptr;      // (the block is about to hold this pass's buffers)
-  int rc = ensure(ctx, ctx->stage[7],
+  int rc = ensure(ctx, ctx->collide_work,
                   t_entries * sizeof(double) + (part_entries + centries) * (sizeof(double) + sizeof(int32_t)) + 64);
   if (rc) return rc;
-  double *rows_t = (double *)ctx->stage[7].p;
+  double *rows_t = (double *)ctx->collide_work.p;
   double *pd = rows_t + t_entries;
   double *cd = pd + part_entries;
   int32_t *pj = (int32_t *)(cd + centries);

@@ -71,7 +71,9 @@ struct msnap_ctx {
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   msnap::DevBuf scratch;   // global-memory scratch for n_seg too large for LDS
-  msnap::DevBuf stage[8];  // device staging for the host-pointer entry points
+  msnap::DevBuf host_stage;    // the host-pointer entry points' staging arena (msnap_api.hip, staged()); also the device
+                               // side of solve_host's bounce buffer and its shared time grid when chunked
+  msnap::DevBuf collide_work;  // the pairwise pass's working set (msnap_aux.hip, launch_formation_collide[_part])
   msnap::DevBuf limits_work;   // msnap_limits.hip: per-(drone, segment, quantity) peaks, then the retiming's per-drone peaks
   // chunked host-pointer solves: two streams alternate H2D -> kernel -> D2H over chunks of drones,
   // each with its own staging set (wp, t, coef, dur, status)
@@ -99,7 +101,7 @@ struct msnap_ctx {
   void *mesh_tests = nullptr;   // "mesh_count_tests": device counter of the point-triangle tests evaluated (not culled)
   int collide_waves_per_cu = 0; // "collide_waves_per_cu": shares per CU of the pairwise pass (0: one column block per share)
   int collide_sample_parts = 0; // "collide_sample_parts": waves per share of the pairwise pass (0: chosen per launch)
-  int collide_no_sym = 0;       // "collide_no_sym": 1 = the rows of msnap_formation_collide are NOT the slice of the columns at row_offset: one-sided evaluation
+  int collide_no_sym = 0;       // "collide_no_sym": 1 = the rows of msnap_formation_collide[_device] are NOT the slice of the columns at row_offset: one-sided evaluation
   int collide_no_cull = 0;      // "collide_no_cull": 1 = whole-swarm passes without the exact broad phase (A/B, dense swarms)
   int collide_cull_mode = 0;         // "collide_cull_mode": evaluator behind the broad phase: 0 chosen per pass, 1 surviving shares, 2 surviving group pairs
   int collide_cull_min_drones = 0;   // "collide_cull_min_drones": smallest whole swarm that takes the broad phase (0: default 3072)
@@ -164,10 +166,12 @@ int launch_sample(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, c
 int launch_eval_flat(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,
                      int n_samples, const double *ts, double *out);
 int launch_snap_cost(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur, double *cost);
+// no_sym: the rows are not the slice of the columns at row_offset (one-sided evaluation, no broad phase)
 int launch_formation_collide(msnap_ctx *ctx, int n_rows, int row_offset, int n_cols, int n_samples,
                              const double *pos_rows, const double *pos_cols, double radius,
-                             double *min_dist, int32_t *partner, int32_t *hit, const double *rows_t);
-bool formation_collide_takes_broad_phase(const msnap_ctx *ctx, int n_rows, int row_offset, int n_cols, int n_samples);
+                             double *min_dist, int32_t *partner, int32_t *hit, const double *rows_t, bool no_sym);
+bool formation_collide_takes_broad_phase(const msnap_ctx *ctx, int n_rows, int row_offset, int n_cols, int n_samples,
+                                         bool no_sym);
 int launch_formation_collide_part(msnap_ctx *ctx, int n_drones, int n_samples, const double *pos_all, int part,
                                   int n_parts, double *out_d2, int32_t *out_j);
 int launch_formation_collide_finish(msnap_ctx *ctx, int n_drones, int n_parts, const void *parts, size_t part_stride,
@@ -189,5 +193,28 @@ bool grid_gemm_supported(const msnap_ctx *ctx, int n_seg);
 int grid_frag_ks_pitch(const msnap_ctx *ctx, int n_seg);
 int launch_grid_sample(msnap_ctx *ctx, int n_drones, const double *wp, double dt, int n_samples, double *coef,
                        double *dur, int32_t *status, double *pos, double *pos_t, bool keys_form);
+
+// dynamic limits (msnap_limits.hip): one lane per (drone, segment, quantity), kLimitsThreads lanes per block
+constexpr int kLimitsThreads = 256;
+inline int check_limits_args(const msnap_ctx *ctx, int n_drones, int n_seg) {
+  if (!ctx || n_drones < 0) return MSNAP_EINVAL;
+  if (n_seg < 1 || n_seg > ctx->max_segments) return MSNAP_ESEGMENTS;
+  if (((size_t)n_drones * n_seg * 4 + kLimitsThreads - 1) / kLimitsThreads > 0x7fffffffu) return MSNAP_EINVAL;   // grid size
+  return MSNAP_OK;
+}
+inline int check_limits(const double *limits, int flags) {
+  if (!limits || (flags & ~(MSNAP_RETIME_FIT | MSNAP_RETIME_COMMON))) return MSNAP_EINVAL;
+  for (int q = 0; q < 4; ++q)
+    if (!(limits[q] >= 0.0)) return MSNAP_EINVAL;      // negative or NaN
+  return MSNAP_OK;
+}
+// ctx->limits_work: per-lane results [N M 4][2], then (retiming) peak [N][4], t_peak [N][4], status [N]
+inline size_t lane_doubles(int N, int M) { return (size_t)N * M * 4 * 2; }
+int launch_peaks(msnap_ctx *ctx, int N, int M, const double *coef, const double *dur, double *work, double *peak,
+                 double *t_peak, int32_t *status);
+int launch_time_scale(msnap_ctx *ctx, int N, int M, const double *coef, const double *dur, const double *scale,
+                      double *coef_out, double *dur_out);
+int launch_retime(msnap_ctx *ctx, int N, int M, const double *coef, const double *dur, const double *limits, int flags,
+                  double *coef_out, double *dur_out, double *scale);
 
 }  // namespace msnap

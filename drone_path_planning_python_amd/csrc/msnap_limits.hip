@@ -28,7 +28,7 @@ constexpr int kMaxDepth = 40;            // sub-intervals of 2^-40: below that t
 constexpr int kMaxNodes = 4096;          // nodes per lane: a guard on the loop, never met by a smooth g
 constexpr double kPruneRel = 1e-9;       // on g = |.|^2: 5e-10 on the norm (contract: 1e-9)
 constexpr double kPruneAbs = 1e-26;      // on g: 1e-13 on the norm (contract: 1e-12)
-constexpr int kThreads = 256;
+constexpr int kThreads = kLimitsThreads;
 
 constexpr double binom(int n, int k) {
   double r = 1.0;
@@ -318,24 +318,7 @@ time_scale_kernel(const double *coef, const double *dur, const double *__restric
 
 unsigned blocks_of(size_t items, int threads) { return (unsigned)((items + threads - 1) / threads); }
 
-bool grid_fits(size_t items) { return (items + kThreads - 1) / kThreads <= 0x7fffffffu; }
-
-int check_args(const msnap_ctx *ctx, int n_drones, int n_seg) {
-  if (!ctx || n_drones < 0) return MSNAP_EINVAL;
-  if (n_seg < 1 || n_seg > ctx->max_segments) return MSNAP_ESEGMENTS;
-  if (!grid_fits((size_t)n_drones * n_seg * 4)) return MSNAP_EINVAL;
-  return MSNAP_OK;
-}
-
-int check_limits(const double *limits, int flags) {
-  if (!limits || (flags & ~(MSNAP_RETIME_FIT | MSNAP_RETIME_COMMON))) return MSNAP_EINVAL;
-  for (int q = 0; q < 4; ++q)
-    if (!(limits[q] >= 0.0)) return MSNAP_EINVAL;      // negative or NaN
-  return MSNAP_OK;
-}
-
-// the context's work block: per-lane results [N M 4][2], then (retiming) peak [N][4], t_peak [N][4], status [N]
-size_t lane_doubles(int N, int M) { return (size_t)N * M * 4 * 2; }
+}  // namespace
 
 int launch_peaks(msnap_ctx *ctx, int N, int M, const double *coef, const double *dur, double *work, double *peak,
                  double *t_peak, int32_t *status) {
@@ -386,116 +369,4 @@ int launch_retime(msnap_ctx *ctx, int N, int M, const double *coef, const double
   return launch_time_scale(ctx, N, M, coef, dur, scale, coef_out, dur_out);
 }
 
-}  // namespace
 }  // namespace msnap
-
-using namespace msnap;
-
-// ------------------------------------------------------------------ dynamic peaks
-int msnap_dynamic_peaks_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,
-                               double *peak, double *t_peak, int32_t *status) {
-  int rc = check_args(ctx, n_drones, n_seg);
-  if (rc) return rc;
-  if (n_drones == 0) return MSNAP_OK;
-  if (!coef || !dur || !peak || !t_peak || !status) return MSNAP_EINVAL;
-  MSNAP_HIP(ctx, hipSetDevice(ctx->device));
-  if ((rc = ensure(ctx, ctx->limits_work, lane_doubles(n_drones, n_seg) * sizeof(double)))) return rc;
-  return launch_peaks(ctx, n_drones, n_seg, coef, dur, (double *)ctx->limits_work.p, peak, t_peak, status);
-}
-
-int msnap_dynamic_peaks(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur, double *peak,
-                        double *t_peak, int32_t *status) {
-  int rc = check_args(ctx, n_drones, n_seg);
-  if (rc) return rc;
-  if (n_drones == 0) return MSNAP_OK;
-  if (!coef || !dur || !peak || !t_peak || !status) return MSNAP_EINVAL;
-  MSNAP_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t N = n_drones, nc = ctx->order + 1;
-  const size_t b_coef = N * n_seg * 4 * nc * 8, b_dur = N * n_seg * 8, b_pk = N * 4 * 8, b_st = N * 4;
-  if ((rc = ensure(ctx, ctx->stage[2], b_coef))) return rc;
-  if ((rc = ensure(ctx, ctx->stage[3], b_dur))) return rc;
-  if ((rc = ensure(ctx, ctx->stage[6], 2 * b_pk + b_st))) return rc;
-  if ((rc = ensure(ctx, ctx->limits_work, lane_doubles(n_drones, n_seg) * sizeof(double)))) return rc;
-  char *out = (char *)ctx->stage[6].p;
-  MSNAP_HIP(ctx, hipMemcpyAsync(ctx->stage[2].p, coef, b_coef, hipMemcpyHostToDevice, ctx->stream));
-  MSNAP_HIP(ctx, hipMemcpyAsync(ctx->stage[3].p, dur, b_dur, hipMemcpyHostToDevice, ctx->stream));
-  rc = launch_peaks(ctx, n_drones, n_seg, (const double *)ctx->stage[2].p, (const double *)ctx->stage[3].p,
-                    (double *)ctx->limits_work.p, (double *)out, (double *)(out + b_pk), (int32_t *)(out + 2 * b_pk));
-  if (rc) return rc;
-  MSNAP_HIP(ctx, hipMemcpyAsync(peak, out, b_pk, hipMemcpyDeviceToHost, ctx->stream));
-  MSNAP_HIP(ctx, hipMemcpyAsync(t_peak, out + b_pk, b_pk, hipMemcpyDeviceToHost, ctx->stream));
-  MSNAP_HIP(ctx, hipMemcpyAsync(status, out + 2 * b_pk, b_st, hipMemcpyDeviceToHost, ctx->stream));
-  MSNAP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return MSNAP_OK;
-}
-
-// ------------------------------------------------------------------ uniform time scaling
-int msnap_time_scale_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,
-                            const double *scale, double *coef_out, double *dur_out) {
-  int rc = check_args(ctx, n_drones, n_seg);
-  if (rc) return rc;
-  if (n_drones == 0) return MSNAP_OK;
-  if (!coef || !dur || !scale || !coef_out || !dur_out) return MSNAP_EINVAL;
-  MSNAP_HIP(ctx, hipSetDevice(ctx->device));
-  return launch_time_scale(ctx, n_drones, n_seg, coef, dur, scale, coef_out, dur_out);
-}
-
-int msnap_time_scale(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,
-                     const double *scale, double *coef_out, double *dur_out) {
-  int rc = check_args(ctx, n_drones, n_seg);
-  if (rc) return rc;
-  if (n_drones == 0) return MSNAP_OK;
-  if (!coef || !dur || !scale || !coef_out || !dur_out) return MSNAP_EINVAL;
-  MSNAP_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t N = n_drones, nc = ctx->order + 1;
-  const size_t b_coef = N * n_seg * 4 * nc * 8, b_dur = N * n_seg * 8, b_sc = N * 8;
-  if ((rc = ensure(ctx, ctx->stage[2], b_coef))) return rc;
-  if ((rc = ensure(ctx, ctx->stage[3], b_dur))) return rc;
-  if ((rc = ensure(ctx, ctx->stage[6], b_sc))) return rc;
-  MSNAP_HIP(ctx, hipMemcpyAsync(ctx->stage[2].p, coef, b_coef, hipMemcpyHostToDevice, ctx->stream));
-  MSNAP_HIP(ctx, hipMemcpyAsync(ctx->stage[3].p, dur, b_dur, hipMemcpyHostToDevice, ctx->stream));
-  MSNAP_HIP(ctx, hipMemcpyAsync(ctx->stage[6].p, scale, b_sc, hipMemcpyHostToDevice, ctx->stream));
-  double *c = (double *)ctx->stage[2].p, *t = (double *)ctx->stage[3].p;
-  if ((rc = launch_time_scale(ctx, n_drones, n_seg, c, t, (const double *)ctx->stage[6].p, c, t))) return rc;
-  MSNAP_HIP(ctx, hipMemcpyAsync(coef_out, c, b_coef, hipMemcpyDeviceToHost, ctx->stream));
-  MSNAP_HIP(ctx, hipMemcpyAsync(dur_out, t, b_dur, hipMemcpyDeviceToHost, ctx->stream));
-  MSNAP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return MSNAP_OK;
-}
-
-// ------------------------------------------------------------------ retiming to limits
-int msnap_retime_to_limits_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,
-                                  const double limits[4], int flags, double *coef_out, double *dur_out,
-                                  double *scale) {
-  int rc = check_args(ctx, n_drones, n_seg);
-  if (rc) return rc;
-  if ((rc = check_limits(limits, flags))) return rc;
-  if (n_drones == 0) return MSNAP_OK;
-  if (!coef || !dur || !coef_out || !dur_out || !scale) return MSNAP_EINVAL;
-  MSNAP_HIP(ctx, hipSetDevice(ctx->device));
-  return launch_retime(ctx, n_drones, n_seg, coef, dur, limits, flags, coef_out, dur_out, scale);
-}
-
-int msnap_retime_to_limits(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,
-                           const double limits[4], int flags, double *coef_out, double *dur_out, double *scale) {
-  int rc = check_args(ctx, n_drones, n_seg);
-  if (rc) return rc;
-  if ((rc = check_limits(limits, flags))) return rc;
-  if (n_drones == 0) return MSNAP_OK;
-  if (!coef || !dur || !coef_out || !dur_out || !scale) return MSNAP_EINVAL;
-  MSNAP_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t N = n_drones, nc = ctx->order + 1;
-  const size_t b_coef = N * n_seg * 4 * nc * 8, b_dur = N * n_seg * 8, b_sc = N * 8;
-  if ((rc = ensure(ctx, ctx->stage[2], b_coef))) return rc;
-  if ((rc = ensure(ctx, ctx->stage[3], b_dur))) return rc;
-  if ((rc = ensure(ctx, ctx->stage[6], b_sc))) return rc;
-  MSNAP_HIP(ctx, hipMemcpyAsync(ctx->stage[2].p, coef, b_coef, hipMemcpyHostToDevice, ctx->stream));
-  MSNAP_HIP(ctx, hipMemcpyAsync(ctx->stage[3].p, dur, b_dur, hipMemcpyHostToDevice, ctx->stream));
-  double *c = (double *)ctx->stage[2].p, *t = (double *)ctx->stage[3].p;
-  if ((rc = launch_retime(ctx, n_drones, n_seg, c, t, limits, flags, c, t, (double *)ctx->stage[6].p))) return rc;
-  MSNAP_HIP(ctx, hipMemcpyAsync(coef_out, c, b_coef, hipMemcpyDeviceToHost, ctx->stream));
-  MSNAP_HIP(ctx, hipMemcpyAsync(dur_out, t, b_dur, hipMemcpyDeviceToHost, ctx->stream));
-  MSNAP_HIP(ctx, hipMemcpyAsync(scale, ctx->stage[6].p, b_sc, hipMemcpyDeviceToHost, ctx->stream));
-  MSNAP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return MSNAP_OK;
-}

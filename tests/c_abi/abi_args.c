@@ -96,6 +96,12 @@ int main(void) {
   EXPECT(msnap_mesh_sweep_device(NULL, 1, 2, d, 1, d, 0.1, d, i) == MSNAP_EINVAL);
   EXPECT(msnap_mesh_validity(NULL, 1, d, 1, d, 1, d, i) == MSNAP_EINVAL);
   EXPECT(msnap_mesh_validity_device(NULL, 1, d, 1, d, 1, d, i) == MSNAP_EINVAL);
+  EXPECT(msnap_dynamic_peaks(NULL, 1, 1, d, d, d, d, i) == MSNAP_EINVAL);
+  EXPECT(msnap_dynamic_peaks_device(NULL, 1, 1, d, d, d, d, i) == MSNAP_EINVAL);
+  EXPECT(msnap_time_scale(NULL, 1, 1, d, d, d, d, d) == MSNAP_EINVAL);
+  EXPECT(msnap_time_scale_device(NULL, 1, 1, d, d, d, d, d) == MSNAP_EINVAL);
+  EXPECT(msnap_retime_to_limits(NULL, 1, 1, d, d, d, 0, d, d, d) == MSNAP_EINVAL);
+  EXPECT(msnap_retime_to_limits_device(NULL, 1, 1, d, d, d, 0, d, d, d) == MSNAP_EINVAL);
 
   printf("abi_args: %d failure(s)\n", fails);
   return fails ? 1 : 0;

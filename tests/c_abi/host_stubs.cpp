@@ -17,9 +17,9 @@ int launch_sample(msnap_ctx *, int, int, const double *, const double *, double,
 int launch_eval_flat(msnap_ctx *, int, int, const double *, const double *, int, const double *, double *) { return unreachable(); }
 int launch_snap_cost(msnap_ctx *, int, int, const double *, const double *, double *) { return unreachable(); }
 int launch_formation_collide(msnap_ctx *, int, int, int, int, const double *, const double *, double, double *, int32_t *,
-                             int32_t *, const double *) { return unreachable(); }
+                             int32_t *, const double *, bool) { return unreachable(); }
 int launch_formation_collide_part(msnap_ctx *, int, int, const double *, int, int, double *, int32_t *) { return unreachable(); }
-bool formation_collide_takes_broad_phase(const msnap_ctx *, int, int, int, int) { return false; }
+bool formation_collide_takes_broad_phase(const msnap_ctx *, int, int, int, int, bool) { return false; }
 bool collide_counts_by_groups(const msnap_ctx *, int, int, int) { return false; }
 int launch_formation_collide_finish(msnap_ctx *, int, int, const void *, size_t, int, int, double, double *, int32_t *,
                                     int32_t *) { return unreachable(); }
@@ -31,5 +31,8 @@ int launch_grid_prepare(msnap_ctx *, int, const double *, int) { return unreacha
 int launch_solve_grid(msnap_ctx *, int, const double *, double *, double *, int32_t *) { return unreachable(); }
 int launch_grid_sample(msnap_ctx *, int, const double *, double, int, double *, double *, int32_t *, double *, double *, bool) { return unreachable(); }
 bool grid_gemm_supported(const msnap_ctx *, int) { return unreachable() != 0; }
+int launch_peaks(msnap_ctx *, int, int, const double *, const double *, double *, double *, double *, int32_t *) { return unreachable(); }
+int launch_time_scale(msnap_ctx *, int, int, const double *, const double *, const double *, double *, double *) { return unreachable(); }
+int launch_retime(msnap_ctx *, int, int, const double *, const double *, const double *, int, double *, double *, double *) { return unreachable(); }
 
 }  // namespace msnap

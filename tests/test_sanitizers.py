@@ -56,7 +56,9 @@ def test_c_oracle_under_address_and_ub_sanitizers():
     assert r.stdout.strip().endswith("True"), r.stdout + r.stderr
 
 
-def test_c_abi_host_side_under_address_and_ub_sanitizers(tmp_path):
+def test_c_abi_host_side_incl_limits_under_address_and_ub_sanitizers(tmp_path):
+    """Every C-ABI entry point, the dynamic-limits ones included (csrc/msnap_api.hip hosts them all; the stand-ins
+    of tests/c_abi/host_stubs.cpp follow the launcher declarations of csrc/msnap_internal.h)."""
     hipcc = "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         pytest.skip("no hipcc here")
