@@ -137,7 +137,7 @@ struct OptionName {
 };
 static const OptionName kOptions[] = {
     {"solve_grid_waves", "MSNAP_SOLVE_GRID_WAVES"}, {"gemm_grid_waves", "MSNAP_GEMM_GRID_WAVES"},
-    {"twist_max_drones", "MSNAP_TWIST_MAX_DRONES"}, {"no_twist", "MSNAP_NO_TWIST"},
+    {"twist_max_drones", "MSNAP_TWIST_MAX_DRONES"}, {"no_twist", "MSNAP_NO_TWIST"}, {"twist_waves", "MSNAP_TWIST_WAVES"},
     {"collide_waves_per_cu", "MSNAP_COLLIDE_WAVES_PER_CU"}, {"pipe_chunk_mb", "MSNAP_PIPE_CHUNK_MB"},
     {"collide_sample_parts", "MSNAP_COLLIDE_SAMPLE_PARTS"}, {"no_twin", "MSNAP_NO_TWIN"}, {"no_grid_sample", "MSNAP_NO_GRID_SAMPLE"}, {"gemm_stream_waves_per_cu", "MSNAP_GEMM_STREAM_WAVES_PER_CU"}, {"mesh_waves_per_cu", "MSNAP_MESH_WAVES_PER_CU"}, {"collide_no_cull", "MSNAP_COLLIDE_NO_CULL"}, {"collide_cull_min_drones", "MSNAP_COLLIDE_CULL_MIN_DRONES"}, {"collide_cull_mode", "MSNAP_COLLIDE_CULL_MODE"}, {"twin_max_drones", "MSNAP_TWIN_MAX_DRONES"},
 };
@@ -156,6 +156,7 @@ static int *option_slot(msnap_ctx *ctx, const char *name) {
   if (!strcmp(name, "gemm_grid_waves")) return &ctx->gemm_grid_waves;
   if (!strcmp(name, "twist_max_drones")) return &ctx->twist_max_drones;
   if (!strcmp(name, "no_twist")) return &ctx->no_twist;
+  if (!strcmp(name, "twist_waves")) return &ctx->twist_waves;
   if (!strcmp(name, "no_twin")) return &ctx->no_twin;
   if (!strcmp(name, "no_grid_sample")) return &ctx->no_grid_sample;
   if (!strcmp(name, "gemm_stream_waves_per_cu")) return &ctx->gemm_stream_waves_per_cu;
@@ -335,6 +336,7 @@ int msnap_set_option(msnap_ctx *ctx, const char *name, long value) {
     return MSNAP_OK;
   }
   if (option_is_read_only(name)) return MSNAP_EINVAL;      // "collide_last_*": what the last pass did
+  if (!strcmp(name, "twist_waves") && value != 0 && value != 1 && value != 2 && value != 4) return MSNAP_EINVAL;
   int *slot = option_slot(ctx, name);
   if (!slot) return MSNAP_EINVAL;
   *slot = (int)value;

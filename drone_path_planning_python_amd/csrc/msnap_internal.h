@@ -96,6 +96,7 @@ struct msnap_ctx {
   int no_twin = 0;             // "no_twin": batches keep solve_kernel_reg where solve_kernel_twin would run (A/B timing)
   int twin_max_drones = 0;      // "twin_max_drones": largest batch that takes solve_kernel_twin (0: default per order)
   int twist_max_drones = 0;     // "twist_max_drones": batches up to this size take the small-batch kernel (0: default)
+  int twist_waves = 0;          // "twist_waves": waves per 8-drone tile of the small-batch kernel: 1, 2, 4 (0: chosen per launch)
   int solve_grid_waves = 0;     // "solve_grid_waves": cap on solve_kernel_reg's persistent grid (0: default)
   int gemm_grid_waves = 0;      // "gemm_grid_waves": cap on the shared-grid GEMM's persistent grid (0: default)
   void *mesh_tests = nullptr;   // "mesh_count_tests": device counter of the point-triangle tests evaluated (not culled)

@@ -421,7 +421,8 @@ __device__ __forceinline__ void store_segment_quad8(double *__restrict__ seg_bas
 }
 
 // dur[d][i] = t[d][i+1] - t[d][i] for the whole tile, one contiguous sweep
-template <int MAXCNT = 0>   // compile-time bound of drones x segments per tile (0: not known, scalar loop)
+// (`lane` runs over STRIDE threads: a wave, or the whole workgroup of a multi-wave instance)
+template <int MAXCNT = 0, int STRIDE = kWave>   // MAXCNT: compile-time bound of drones x segments per tile (0: not known, scalar loop)
 __device__ __forceinline__ void store_durations(const double *sTraw, int shared_times, int tpitch, int M,
                                                 int nvalid, int lane, double *__restrict__ dur_tile) {
   // The trip count is WAVE-UNIFORM (a scalar loop around a predicated body), not `for (e = lane; e < cnt; e += 64)`:
@@ -441,9 +442,9 @@ __device__ __forceinline__ void store_durations(const double *sTraw, int shared_
   };
   if constexpr (MAXCNT > 0) {      // straight-line instances: two or three predicated rounds, no loop at all
 #pragma unroll
-    for (int e0 = 0; e0 < MAXCNT; e0 += kWave) one(e0 + lane);
+    for (int e0 = 0; e0 < MAXCNT; e0 += STRIDE) one(e0 + lane);
   } else {
-    for (int e0 = 0; e0 < cnt; e0 += kWave) one(e0 + lane);
+    for (int e0 = 0; e0 < cnt; e0 += STRIDE) one(e0 + lane);
   }
 }
 
@@ -1469,14 +1470,15 @@ constexpr int kTwistDrones = 8;
 constexpr int kTwistFenceHalf = 9;   // instances with this many knots per side fence the scheduler per knot
 
 #ifdef MSNAP_TOOLS_TIMELINE
-// phase timestamps of the twisted kernel (s_memrealtime, 100 MHz, and s_memtime): tools/twist_timeline.py
+// phase timestamps of the twisted kernel (s_memrealtime, 100 MHz, and s_memtime): tools/twist_timeline.py.
+// One row of 32 words per WAVE (row = tile * NW + wave): points 0..4 in words 0..9.
 __device__ unsigned long long g_timeline[1024 * 32];
 #define MSNAP_TL(k)                                                                       \
   do {                                                                                    \
-    const int it__ = (tl_tile - (int)blockIdx.x) / (int)gridDim.x;                        \
-    if (lane == 0 && blockIdx.x < 1024 && it__ < 2) {                                     \
-      g_timeline[blockIdx.x * 32 + 16 * it__ + 2 * (k)] = wall_clock64();                 \
-      g_timeline[blockIdx.x * 32 + 16 * it__ + 2 * (k) + 1] = clock64();                  \
+    const int row__ = (int)blockIdx.x * NW + wave;                                        \
+    if (lane == 0 && row__ < 1024) {                                                      \
+      g_timeline[row__ * 32 + 2 * (k)] = wall_clock64();                                  \
+      g_timeline[row__ * 32 + 2 * (k) + 1] = clock64();                                   \
     }                                                                                     \
   } while (0)
 #else
@@ -1486,11 +1488,27 @@ __device__ unsigned long long g_timeline[1024 * 32];
 // One instance per (order, segment count M); MAXH = knots of the longer side.  Every loop bound is
 // a constant, so the whole solve is straight-line code that the scheduler interleaves across knots
 // (a run-time M costs block boundaries with dozens of register copies each: 6.2 vs 5.3 us at M = 10).
-template <int K, int MAXH, int M>
-__global__ void __launch_bounds__(kWave)
+//
+// NW waves per tile (1, 2 or 4; option "twist_waves").  The launcher's default takes NW > 1 only while the batch has
+// at most one tile per two (NW = 2) or four (NW = 4) CUs, where each wave of a workgroup can have a SIMD, and its
+// issue port, to itself; a forced "twist_waves" holds at any tile count, the tiles then share SIMDs (correct, slower:
+// the sweeps run NW times on them).  Every wave runs the same sweeps and the same merge (redundantly: no second
+// barrier, every wave holds the knot states), then the
+// back-substitution and the recovery are split by segment: wave w recovers the pieces it in [lo(w), hi(w)] of
+// both sides, and back-substitutes from the meeting knot only as far out as lo(w).  The waves with the longest
+// back-substitution recover the fewest pieces.  Every value is computed by the same code from the same
+// operands as at NW = 1: the outputs are bitwise those of the one-wave form.
+// Contract: grid == tile count (one workgroup per 8-drone tile; the launcher starts exactly that many).
+template <int S, int NW>   // S pieces per side (it = 0 .. S-1): the chunk of wave w, larger chunks at the high end
+__device__ __forceinline__ constexpr int twist_chunk_lo(int w) {
+  return w * (S / NW) + (w > NW - S % NW ? w - (NW - S % NW) : 0);
+}
+template <int K, int MAXH, int M, int NW>
+__global__ void __launch_bounds__(kWave * NW)
 solve_kernel_twist(const double *__restrict__ wp, const double *__restrict__ tt, int shared_times,
                    int N, double *__restrict__ coef, double *__restrict__ dur,
-                   int32_t *__restrict__ status, int ntiles) {
+                   int32_t *__restrict__ status) {
+  static_assert(NW == 1 || NW == 2 || NW == 4, "one, two or four waves per tile");
   using SW = Sweep<K>;
   constexpr int NU = SW::NU, NC = SW::NC, NS = SW::NS;
   // M - 1 interior knots = nL (side 0) + the meeting knot + nR (side 1), nL <= nR <= nL + 1
@@ -1500,7 +1518,10 @@ solve_kernel_twist(const double *__restrict__ wp, const double *__restrict__ tt,
 
   extern __shared__ __attribute__((aligned(16))) double lds[];
 
-  const int lane = threadIdx.x;
+  const int tid = threadIdx.x;
+  const int lane = NW > 1 ? tid & (kWave - 1) : tid;
+  // the wave index in a scalar register: every branch on it is a scalar branch (exec stays whole)
+  const int wave = NW > 1 ? __builtin_amdgcn_readfirstlane(tid / kWave) : 0;
   const int a = lane & 3;
   const int side = (lane >> 2) & 1;
   const int dl = lane >> 3;           // drone inside the tile
@@ -1514,20 +1535,17 @@ solve_kernel_twist(const double *__restrict__ wp, const double *__restrict__ tt,
 #pragma unroll
   for (int r = 0; r < NU; ++r) dsg[r] = (r & 1) ? 1.0 : -1.0;
 
-  // ONE tile per wave, no tile loop: the launcher starts exactly one wave per tile (launch_solve_k: grid = nt8).  With
-  // a loop around the body the compiler hoisted ~130 loop-invariant instructions (constants, lane-derived indices) into
-  // its preheader -- IN FRONT of the tile's input loads, a quarter of a microsecond of a 3.6 us kernel (round 4)
-  // (and no `tile < ntiles` test: it made the kernel fetch `ntiles` alone, wait, branch, and only then fetch its other
-  //  arguments -- two dependent scalar-cache round trips in front of the first load; gridDim.x == ntiles by construction)
+  // ONE tile per workgroup, no tile loop: the launcher starts exactly one workgroup per tile (launch_solve_k:
+  // grid = nt8).  With a loop around the body the compiler hoisted ~130 loop-invariant instructions (constants,
+  // lane-derived indices) into its preheader -- IN FRONT of the tile's input loads, a quarter of a microsecond of a
+  // 3.6 us kernel (round 4).  Nor is there a `tile < ntiles` test (and no tile-count argument at all): it made the
+  // kernel fetch the count alone, wait, branch, and only then fetch its other arguments -- two dependent
+  // scalar-cache round trips in front of the first load.
   const int tile = blockIdx.x;
-  (void)ntiles;
   // (pinning the three output pointers in SGPRs at the top -- the compiler re-fetches each right in front of its first
   //  use, a scalar-cache hit on the dependent chain -- was measured and LOST: 4.52 against 4.38 us per step; the kernel
   //  holds ~60 fp64 constants in scalar registers and six more live ones push some of them out)
   {
-#ifdef MSNAP_TOOLS_TIMELINE
-    const int tl_tile = tile;
-#endif
     MSNAP_TL(0);
     const int d_raw = tile * kTwistDrones + dl;
     const bool live = d_raw < N;
@@ -1535,24 +1553,25 @@ solve_kernel_twist(const double *__restrict__ wp, const double *__restrict__ tt,
     const int left = N - tile * kTwistDrones;
     const int nvalid = left < kTwistDrones ? left : kTwistDrones;
 
-    {   // stage the 8 drones' inputs (one flight)
+    {   // stage the 8 drones' inputs (one flight; at NW > 1 every wave loads its share)
+      constexpr int NT = kWave * NW;
       const double2 *wsrc = reinterpret_cast<const double2 *>(wp + (size_t)tile * kTwistDrones * wpitch);
       double2 *wdst = reinterpret_cast<double2 *>(sWraw);
       const int wcnt = nvalid * wpitch / 2;
       const double *tsrc = shared_times ? tt : tt + (size_t)tile * kTwistDrones * tpitch;
       const int tcnt = shared_times ? tpitch : nvalid * tpitch;
-      constexpr int UW = (kTwistDrones * wpitch / 2 + kWave - 1) / kWave;
-      constexpr int UT = (kTwistDrones * tpitch + kWave - 1) / kWave;
+      constexpr int UW = (kTwistDrones * wpitch / 2 + NT - 1) / NT;
+      constexpr int UT = (kTwistDrones * tpitch + NT - 1) / NT;
       double2 vw[UW];
       double vt[UT];
 #pragma unroll
       for (int u = 0; u < UW; ++u) {
-        const int e = u * kWave + lane;
+        const int e = u * NT + tid;
         vw[u] = wsrc[e < wcnt ? e : wcnt - 1];
       }
 #pragma unroll
       for (int u = 0; u < UT; ++u) {
-        const int f = u * kWave + lane;
+        const int f = u * NT + tid;
         vt[u] = tsrc[f < tcnt ? f : tcnt - 1];
       }
 #pragma unroll
@@ -1561,12 +1580,12 @@ solve_kernel_twist(const double *__restrict__ wp, const double *__restrict__ tt,
       for (int u = 0; u < UT; ++u) asm volatile("" : "+v"(vt[u]));
 #pragma unroll
       for (int u = 0; u < UW; ++u) {
-        const int e = u * kWave + lane;
+        const int e = u * NT + tid;
         if (e < wcnt) wdst[e] = vw[u];
       }
 #pragma unroll
       for (int u = 0; u < UT; ++u) {
-        const int f = u * kWave + lane;
+        const int f = u * NT + tid;
         if (f < tcnt) sTraw[f] = vt[u];
       }
     }
@@ -1586,9 +1605,9 @@ solve_kernel_twist(const double *__restrict__ wp, const double *__restrict__ tt,
     // long paths keep z_i in LDS (one slot per lane) so the instance fits the register file
     constexpr bool kZReg = MAXH * NU < 3 * kTwistFenceHalf;
     double wreg[HA + 2], xreg[HA + 1], zreg[kZReg ? HA : 1][NU];
-    double *sZ = sTraw + kTwistDrones * tpitch + lane;      // [knot][r][64 lanes]
-    // a launch of this kernel never has more than two waves per CU: the G_i blocks stay in
-    // registers (overflowing into AGPRs on long paths) -- no LDS round trip on the dependent chain
+    double *sZ = sTraw + kTwistDrones * tpitch + wave * (HA * NU * kWave) + lane;   // per wave: [knot][r][64 lanes]
+    // the G_i blocks stay in registers (overflowing into AGPRs on long paths: the instance is built for one wave per
+    // SIMD, whatever NW, and the hardware places no more) -- no LDS round trip on the dependent chain
     double Greg[HA][NU][NU];
     const double t0 = lt[0];
     wreg[0] = Wown(0);
@@ -1691,11 +1710,13 @@ solve_kernel_twist(const double *__restrict__ wp, const double *__restrict__ tt,
     const bool f_time = ((__ballot(badtime) >> gsh) & 0xFFull) != 0;
     const bool f_sing = ((__ballot(singular) >> gsh) & 0xFFull) != 0;
     const int st = f_nonfinite ? MSNAP_ST_NONFINITE : f_time ? MSNAP_ST_TIMES : f_sing ? MSNAP_ST_SINGULAR : MSNAP_ST_OK;
-    if (live && (lane & 7) == 0) status[d] = st;      // (moved to the end with the durations: no gain, 4.30 against 4.28 us)
+    if (live && (lane & 7) == 0 && wave == NW - 1) status[d] = st;   // (moved to the end with the durations: no gain, 4.30 against 4.28 us)
     const bool bad = st != 0;
 
     MSNAP_TL(3);
-    // ---- outward back-substitution + recovery: side s owns its segments 0 .. mside ----
+    // ---- outward back-substitution + recovery: side s owns its segments 0 .. mside; this wave recovers the
+    // pieces lo .. hi of each side and back-substitutes out to lo (scalar bounds: wave-uniform branches) ----
+    const int lo = twist_chunk_lo<MAXH + 1, NW>(wave), hi = twist_chunk_lo<MAXH + 1, NW>(wave + 1) - 1;
     // A failed drone's outputs are NaN: poison what every coefficient is computed from once
     // (waypoints -> c0 and the end-side block, knot states -> c1..) instead of selecting per piece.
     const double qnan = __builtin_nan("");
@@ -1707,6 +1728,7 @@ solve_kernel_twist(const double *__restrict__ wp, const double *__restrict__ tt,
     for (int r = 0; r < NU; ++r) un[r] = bad ? qnan : um[r];
 #pragma unroll
     for (int it = MAXH; it >= 0; --it) {
+      if (NW > 1 && (it < lo || hi < lo)) break;     // (no piece of this wave further out)
       if (it <= nL || side) {    // only side 1 owns segment nR when nL < nR
         double u[NU];
         if (it >= 1) {
@@ -1723,6 +1745,7 @@ solve_kernel_twist(const double *__restrict__ wp, const double *__restrict__ tt,
 #pragma unroll
           for (int r = 0; r < NU; ++r) u[r] = zero_or_nan;
         }
+        if (NW == 1 || it <= hi) {   // (beyond hi: back-substitution only, the piece is another wave's)
         // Side 1 holds the piece in reversed time, q(s) with p(t) = q(T - t).  Its endpoint states in
         // forward time are the reversed ones with the odd derivatives negated, so the forward
         // coefficients come from the same recovery with the two ends swapped -- no Taylor shift.
@@ -1748,15 +1771,18 @@ solve_kernel_twist(const double *__restrict__ wp, const double *__restrict__ tt,
 #pragma unroll
           for (int m = 0; m < NC; m += 2) *reinterpret_cast<double2 *>(o + m) = make_double2(c[m], c[m + 1]);
         }
+        }
 #pragma unroll
         for (int r = 0; r < NU; ++r) un[r] = u[r];
       }
       if constexpr (MAXH * NU >= 3 * kTwistFenceHalf) __builtin_amdgcn_sched_barrier(0);
     }
     // the durations leave LAST: in front of the sweeps they cost the fetch of their pointer and ~40 instructions on the
-    // dependent chain; the staged times are still in LDS (the z stash lives behind them, nothing aliases the inputs)
+    // dependent chain; the staged times are still in LDS (the z stash lives behind them, nothing aliases the inputs;
+    // at NW > 1 the whole workgroup shares the rounds)
     __builtin_amdgcn_sched_barrier(0);
-    store_durations<kTwistDrones * M>(sTraw, shared_times, tpitch, M, nvalid, lane, dur + (size_t)tile * kTwistDrones * M);
+    store_durations<kTwistDrones * M, kWave * NW>(sTraw, shared_times, tpitch, M, nvalid, tid,
+                                                  dur + (size_t)tile * kTwistDrones * M);
     MSNAP_TL(4);
   }
 }
@@ -1798,13 +1824,23 @@ static int launch_solve_k(msnap_ctx *ctx, int N, int M, const double *wp, const 
     // small batch: at most one wavefront per SIMD -- halve the dependent chain instead
     const int nt8 = (N + kTwistDrones - 1) / kTwistDrones;
     const int nR = (M - 2) - (M - 2) / 2;
-    // inputs + z stash (64 lanes x NU per knot; used by the long-path instances only)
-    const size_t lds_bytes = ((size_t)kTwistDrones * (M + 1) * 5 + (size_t)64 * (K - 1) * nR) * sizeof(double);
+    // waves per tile (msnap_set_option admits 0, 1, 2 and 4 only).  Measured on 256 CUs, us per step, one / two /
+    // four waves (profiles/r05_twist_waves.txt): 256 x 10 (32 tiles) 4.41 / 4.31 / 4.30, 300 x 20 (38) 7.67 / 7.21 /
+    // 7.08, order 9 256 x 10 6.03 / 5.78 / 5.82 -- but 1024 x 24 (128 tiles) 9.85 / 9.59 / 9.85 and 2048 x 10 (256
+    // tiles) 5.71 / 5.89 / 6.06: four waves up to a quarter of the CUs' count in tiles, two up to half, one above
+    const int nw = ctx->twist_waves > 0 ? ctx->twist_waves : nt8 * 4 <= ctx->n_cu ? 4 : nt8 * 2 <= ctx->n_cu ? 2 : 1;
+    // inputs + z stash per wave (64 lanes x NU per knot; used by the long-path instances only, 4 x 16.5 KiB at M = 24)
+    const size_t lds_bytes = ((size_t)kTwistDrones * (M + 1) * 5 + (size_t)nw * 64 * (K - 1) * nR) * sizeof(double);
+    // grid == tile count: one workgroup of nw waves per 8-drone tile (the kernel has no tile loop and no tile guard)
+#define MSNAP_TWIST_NW(MM, NWV)                                                                                    \
+  hipLaunchKernelGGL((solve_kernel_twist<K, (MM - 2) - (MM - 2) / 2, MM, NWV>), dim3(nt8), dim3(kWave * NWV),      \
+                     lds_bytes, ctx->stream, wp, t, shared, N, coef, dur, status)
 #define MSNAP_TWIST_EXACT(MM)                                                                          \
   case MM:                                                                                             \
     note_kernel(ctx, "msnap::solve_kernel_twist<%d, %d, %d>", K, (MM - 2) - (MM - 2) / 2, MM);         \
-    hipLaunchKernelGGL((solve_kernel_twist<K, (MM - 2) - (MM - 2) / 2, MM>), dim3(nt8), dim3(kWave),   \
-                       lds_bytes, ctx->stream, wp, t, shared, N, coef, dur, status, nt8);             \
+    if (nw == 4) MSNAP_TWIST_NW(MM, 4);                                                                \
+    else if (nw == 2) MSNAP_TWIST_NW(MM, 2);                                                           \
+    else MSNAP_TWIST_NW(MM, 1);                                                                        \
     break;
     if constexpr (K == 4) {
       switch (M) {   // 2 <= M <= kTwistMaxSeg
@@ -1825,6 +1861,7 @@ static int launch_solve_k(msnap_ctx *ctx, int N, int M, const double *wp, const 
       }
     }
 #undef MSNAP_TWIST_EXACT
+#undef MSNAP_TWIST_NW
     MSNAP_HIP(ctx, hipGetLastError());
     return MSNAP_OK;
   }

@@ -106,6 +106,8 @@ int msnap_host_free(void *ptr);
  *   "no_grid_sample"       1: msnap_solve_grid_sample_device runs the two kernels where it would fuse (A/B timing)
  *   "twist_max_drones"     largest batch that takes the small-batch two-sided kernel (0 = default)
  *   "no_twist"             1: small batches stay on the one-sided kernels
+ *   "twist_waves"          waves per 8-drone tile of the small-batch kernel: 1, 2 or 4 (0 = default: 4 up to
+ *                          one tile per four CUs, 2 up to one per two, 1 above); outputs are bitwise the same
  *   "twin_max_drones"      largest batch that takes the two-sided column-split throughput kernel (0 = default:
  *                          order 7 up to 128 drones per CU, order 9 any size)
  *   "no_twin"             1: order-9 batches stay on the one-sided throughput kernel where the two-sided
