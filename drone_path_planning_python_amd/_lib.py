@@ -57,6 +57,11 @@ SIGNATURES = {
     "msnap_eval_flat_device": (_I, [_VP, _I, _I, _VP, _VP, _I, _VP, _VP]),
     "msnap_snap_cost": (_I, [_VP, _I, _I, _VP, _VP, _VP]),
     "msnap_snap_cost_device": (_I, [_VP, _I, _I, _VP, _VP, _VP]),
+    "msnap_snap_cost_grad": (_I, [_VP, _I, _I, _VP, _VP, _VP]),
+    "msnap_snap_cost_grad_device": (_I, [_VP, _I, _I, _VP, _VP, _VP]),
+    "msnap_optimize_times": (_I, [_VP, _I, _I, _VP, _VP, _I, _VP, _D, _I, _D, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "msnap_optimize_times_device": (_I, [_VP, _I, _I, _VP, _VP, _I, _VP, _D, _I, _D, _VP, _VP, _VP, _VP, _VP, _VP,
+                                         _VP]),
     "msnap_dynamic_peaks": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _VP]),
     "msnap_dynamic_peaks_device": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _VP]),
     "msnap_time_scale": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _VP]),

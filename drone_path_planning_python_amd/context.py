@@ -352,6 +352,64 @@ class Context:
             self._ck(self._lib.msnap_snap_cost_device(self._h, int(n_drones), int(n_seg), _ptr(coef), _ptr(dur),
                                                      _ptr(cost)))
 
+    # ---- time allocation (include/msnap.h: segment times optimised per drone) ---------------
+    def snap_cost_grad(self, coef, dur):
+        """-E per drone, segment and axis -> [N, M, 4] (msnap_snap_cost_grad): the derivative of the optimal cost
+        by each duration when `coef` is the solve's result for `dur`."""
+        coef, pc, dur, pd, N, M = self._coef_dur(coef, dur)
+        grad = np.empty((N, M, 4), dtype=np.float64)
+        with self._lock:
+            self._ck(self._lib.msnap_snap_cost_grad(self._h, N, M, pc, pd, grad.ctypes.data_as(ctypes.c_void_p)))
+        return grad
+
+    def snap_cost_grad_device(self, n_drones, n_seg, coef, dur, grad):
+        with self._lock:
+            self._ck(self._lib.msnap_snap_cost_grad_device(self._h, int(n_drones), int(n_seg), _ptr(coef), _ptr(dur),
+                                                           _ptr(grad)))
+
+    def optimize_times(self, wp, t, weights=(1, 1, 1, 1), min_fraction=0.1, max_iter=200, tol=1e-4):
+        """Per-drone optimisation of the interior knot times, waypoints and total duration kept
+        (msnap_optimize_times): wp [N, m, 4], t [N, m] or shared [m] with t[0] == 0 ->
+        (t_out [N, m], coef [N, M, 4, ncoef], dur [N, M], status [N] int32, info) with info = {"cost": [N, 2] (at
+        the input times, at t_out), "pg": [N] stopping measure, "iters": [N] accepted steps}."""
+        wp, pwp = _host(wp, np.float64)
+        t, pt = _host(t, np.float64)
+        if wp.ndim != 3 or wp.shape[2] != 4:
+            raise ValueError("wp must be [N, m, 4]")
+        N, m, _ = wp.shape
+        shared = int(t.ndim == 1)
+        if (shared and t.shape != (m,)) or (not shared and t.shape != (N, m)):
+            raise ValueError("t must be [N, m] or [m]")
+        w, pw = _host(weights, np.float64)
+        if w.shape != (4,):
+            raise ValueError("weights must hold 4 values")
+        M = m - 1
+        t_out = np.empty((N, m), dtype=np.float64)
+        coef = np.empty((N, max(M, 0), 4, self.ncoef), dtype=np.float64)
+        dur = np.empty((N, max(M, 0)), dtype=np.float64)
+        status = np.empty((N,), dtype=np.int32)
+        cost = np.empty((N, 2), dtype=np.float64)
+        pg = np.empty((N,), dtype=np.float64)
+        iters = np.empty((N,), dtype=np.int32)
+        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)   # noqa: E731
+        with self._lock:
+            self._ck(self._lib.msnap_optimize_times(
+                self._h, N, M, pwp, pt, shared, pw, float(min_fraction), int(max_iter), float(tol), vp(t_out),
+                vp(coef), vp(dur), vp(status), vp(cost), vp(pg), vp(iters)))
+        return t_out, coef, dur, status, {"cost": cost, "pg": pg, "iters": iters}
+
+    def optimize_times_device(self, n_drones, n_seg, wp, t, shared_times, weights, min_fraction, max_iter, tol,
+                              t_out, coef, dur, status, cost=None, pg=None, iters=None):
+        """Device pointers, asynchronous; `weights` is a host sequence of 4 (x, y, z, yaw)."""
+        w, pw = _host(weights, np.float64)
+        if w.shape != (4,):
+            raise ValueError("weights must hold 4 values")
+        with self._lock:
+            self._ck(self._lib.msnap_optimize_times_device(
+                self._h, int(n_drones), int(n_seg), _ptr(wp), _ptr(t), int(bool(shared_times)), pw,
+                float(min_fraction), int(max_iter), float(tol), _ptr(t_out), _ptr(coef), _ptr(dur), _ptr(status),
+                _ptr(cost), _ptr(pg), _ptr(iters)))
+
     # ---- dynamic limits (include/msnap.h: certified peaks, uniform retiming) --------------
     @staticmethod
     def limits_array(v_max=0.0, a_max=0.0, j_max=0.0, yaw_rate_max=0.0):

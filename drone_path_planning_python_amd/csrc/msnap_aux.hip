@@ -6,6 +6,7 @@
 #include <cstdlib>
 
 #include "msnap_internal.h"
+#include "msnap_energy.h"
 
 namespace msnap {
 
@@ -875,6 +876,36 @@ int launch_snap_cost(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef
     hipLaunchKernelGGL((snap_cost_kernel<8>), dim3(blocks), dim3(256), 0, ctx->stream, coef, dur, n_drones, n_seg, cost);
   else
     hipLaunchKernelGGL((snap_cost_kernel<10>), dim3(blocks), dim3(256), 0, ctx->stream, coef, dur, n_drones, n_seg, cost);
+  MSNAP_HIP(ctx, hipGetLastError());
+  return MSNAP_OK;
+}
+
+// -E per (drone, segment, axis), E the Ostrogradsky energy of the segment's polynomial at its start (msnap_sweep.h):
+// the derivative of the optimal snap cost by the segment's duration when coef is the solve's result.  Streaming: one
+// lane per (drone, segment, axis) reads its own coefficients.
+template <int NC>
+__global__ void __launch_bounds__(256)
+snap_cost_grad_kernel(const double *__restrict__ coef, size_t total, double *__restrict__ grad) {
+  for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
+    double c[NC];
+#pragma unroll
+    for (int j = 0; j < NC; j += 2) {
+      const double2 v = *reinterpret_cast<const double2 *>(coef + idx * NC + j);
+      c[j] = v.x;
+      c[j + 1] = v.y;
+    }
+    grad[idx] = -ostrogradsky_energy<NC / 2>(c);
+  }
+}
+
+int launch_snap_cost_grad(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, double *grad) {
+  const size_t total = (size_t)n_drones * n_seg * 4;
+  size_t blocks = (total + 255) / 256;
+  if (blocks > (size_t)ctx->n_cu * 16) blocks = (size_t)ctx->n_cu * 16;
+  if (ctx->order == 7)
+    hipLaunchKernelGGL((snap_cost_grad_kernel<8>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, coef, total, grad);
+  else
+    hipLaunchKernelGGL((snap_cost_grad_kernel<10>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, coef, total, grad);
   MSNAP_HIP(ctx, hipGetLastError());
   return MSNAP_OK;
 }

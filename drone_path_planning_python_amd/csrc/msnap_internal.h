@@ -7,7 +7,7 @@
 
 #include "../../include/msnap.h"
 
-#define MSNAP_VERSION_NUM 300  /* 0.3.0: dynamic peaks, time scaling and retiming to limits (msnap_limits.hip) */
+#define MSNAP_VERSION_NUM 400  /* 0.4.0: segment-time optimisation (msnap_timeopt.hip), snap-cost gradient */
 /* int32 words of the pairwise pass's broad-phase hand-over block that msnap_get_option reads back */
 #define MSNAP_COLLIDE_META_SHARES 128
 #define MSNAP_COLLIDE_META_GROUPS 132
@@ -131,6 +131,7 @@ struct msnap_ctx {
   int mesh_waves_per_cu = 0;    // "mesh_waves_per_cu": wavefronts per CU the mesh sweep's grid is capped at (0: one workgroup per drone)
   int own_stream_priority = 0;  // "own_stream_priority": 0 default, 1 lowest, 2 highest (re-creates own_stream)
   msnap::RetiredBuf *retired = nullptr;   // blocks kept alive for graphs captured before they were outgrown
+  int timeopt_ready = 0;        // msnap_timeopt.hip: its kernels' dynamic-LDS limit has been raised on this context's device
   char hip_err[256] = {0};
   char last_kernel[96] = {0};   // msnap_last_kernel: the solve kernel instance the last solve entry point launched
 };
@@ -167,6 +168,12 @@ int launch_sample(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, c
 int launch_eval_flat(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,
                      int n_samples, const double *ts, double *out);
 int launch_snap_cost(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur, double *cost);
+int launch_snap_cost_grad(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, double *grad);
+// time allocation (msnap_timeopt.hip): the whole iteration of a batch in one launch; cost, pg, iters may be null
+int launch_optimize_times(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, const double *t, int shared_times,
+                          const double *weights, double min_fraction, int max_iter, double tol, double *t_out,
+                          double *coef, double *dur, int32_t *status, double *cost, double *pg, int32_t *iters);
+int timeopt_max_segments(int khalf);   // largest n_seg whose per-tile state fits LDS (80 at order 7, 58 at order 9)
 // no_sym: the rows are not the slice of the columns at row_offset (one-sided evaluation, no broad phase)
 int launch_formation_collide(msnap_ctx *ctx, int n_rows, int row_offset, int n_cols, int n_samples,
                              const double *pos_rows, const double *pos_cols, double radius,

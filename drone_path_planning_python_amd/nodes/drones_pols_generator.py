@@ -84,8 +84,14 @@ def paths_to_waypoints(paths: Sequence) -> tuple:
     return wp, path_time_grid(m)
 
 
-def paths_to_pols(paths: Sequence, ctx: Context | None = None, limits=None, fit: bool = False):
+def paths_to_pols(paths: Sequence, ctx: Context | None = None, limits=None, fit: bool = False,
+                  optimize_times: bool = False):
     """Batched path_to_pol: returns (matrix f32 [N, M, 33], coef, dur).
+
+    `optimize_times`: each path's interior waypoint times are optimised from the node's grid, per drone, before
+    packing (Context.optimize_times: lower snap cost, same waypoints, same total duration; `limits` then retimes as
+    below).  The drones no longer share one grid afterwards: a formation that must pass its waypoints in step needs
+    one grid for all drones, which this does not give.  False (the default): the node's output is unchanged.
 
     `limits` = (speed, acceleration, jerk, yaw rate), 0 = no limit: the batch is retimed with ONE common scale (these
     drones fly one formation) so that every limit holds for the exact peaks of every drone (Context.retime_to_limits);
@@ -93,8 +99,11 @@ def paths_to_pols(paths: Sequence, ctx: Context | None = None, limits=None, fit:
     its tightest limit is met.  None (the default): the reference's timing, unchecked."""
     ctx = ctx or default_context(7)
     wp, t = paths_to_waypoints(paths)
-    # every path of the node shares the uniform grid: one operator, one MFMA GEMM per batch
-    coef, dur, status = ctx.solve_on_grid(t, wp)
+    if optimize_times:
+        _, coef, dur, status, _ = ctx.optimize_times(wp, t)
+    else:
+        # every path of the node shares the uniform grid: one operator, one MFMA GEMM per batch
+        coef, dur, status = ctx.solve_on_grid(t, wp)
     for k in range(len(paths)):
         raise_for_status(int(status[k]), t)
     if limits is not None:
@@ -133,12 +142,13 @@ def save_pol_matrix(matrix: np.ndarray, cfid: int, out_dir: str | None = None) -
 
 
 def path_to_pol(path, cfid: int, ctx: Context | None = None, out_dir: str | None = None, save: bool = True,
-                limits=None):
+                limits=None, optimize_times: bool = False):
     """One drone's Path -> polynomial pieces: solve, pack to float32, write the
     CSV, publish on 'piece_pol' (reference :40-90).  Returns the message.
-    `limits` (speed, acceleration, jerk, yaw rate): stretch the timing until they hold (paths_to_pols)."""
+    `limits` (speed, acceleration, jerk, yaw rate): stretch the timing until they hold (paths_to_pols).
+    `optimize_times`: optimise the interior waypoint times first (paths_to_pols; default off)."""
     print("Path received...")
-    matrix, _, _ = paths_to_pols([path], ctx, limits=limits)
+    matrix, _, _ = paths_to_pols([path], ctx, limits=limits, **({"optimize_times": True} if optimize_times else {}))
     matrix = matrix[0]
     if save:
         save_pol_matrix(matrix, cfid, out_dir)

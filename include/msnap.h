@@ -308,6 +308,66 @@ int msnap_retime_to_limits_device(msnap_ctx *ctx, int n_drones, int n_seg, const
                                   const double limits[4], int flags, double *coef_out, double *dur_out,
                                   double *scale);
 
+/* ---- time allocation: segment times optimised per drone (new capability) ----
+ * Everything above takes the waypoint times as given (the reference's grid t_i = i*10/n,
+ * scripts/drones_pols_generator.py:44-46,56).  msnap_optimize_times moves the interior knot times of each drone,
+ * independently, to lower its cost with the waypoints and the total duration kept.
+ *
+ * Per drone: wp [n_seg+1][4], t [n_seg+1] absolute with t[0] == 0 (t may be one grid shared by the batch:
+ * shared_times != 0), weights[4] >= 0 for x, y, z, yaw (a HOST array in both versions), min_fraction in (0, 1],
+ * max_iter >= 0, tol >= 0.  With M = n_seg and T_i the durations:
+ *   objective   J(T) = sum_a weights[a] * J_a, J_a the msnap_snap_cost (crackle at order 9) of the solve for T;
+ *   feasible    sum T_i = t[M] and T_i >= T_min = min_fraction * t[M] / M.  Input durations below T_min are raised to it
+ *               and every other duration becomes T_min + (T_i - T_min) * f with the one factor
+ *               f = 1 - (sum of the raises) / (sum of the other durations' excess over T_min), which keeps the sum;
+ *               an input with no duration below T_min is taken bit for bit;
+ *   t_out [M+1] t_out[0] = 0 and t_out[M] = t[M] bit for bit;  dur[i] = t_out[i+1] - t_out[i] as the solve entries form
+ *               it, coef [M][4][order+1] the solution for t_out (the arithmetic of msnap_solve_batch's kernels);
+ *   cost  [2]   J at the (raised) input times and at t_out;  pg [1] the stopping measure at t_out;
+ *   iters [1]   accepted steps.  cost, pg, iters may be NULL.
+ * Guarantees: every dur[i] >= T_min (1 - 1e-12);  cost[1] <= cost[0] (only decreasing steps are accepted: max_iter = 0
+ * returns the input times and cost[1] == cost[0]);  the run ends when
+ *               |P g|_2 * t[M] / (sqrt(M) * J) <= tol,
+ * after max_iter accepted steps, or when the line search cannot lower J any more.  g_i = dJ/dT_i, and P removes the
+ * mean over the free segments (a segment within T_min (1 + 1e-9) whose descent direction points below T_min is not
+ * free).  The measure has no unit, and every quantity of the iteration scales by a power of two when the waypoints
+ * do: t_out, dur, iters, pg are then bit-identical.  A drone's outputs are bit-identical whatever its position in the
+ * batch, the batch size, or host versus device entry.
+ * status [n_drones]: MSNAP_ST_NONFINITE for NaN / Inf in wp or t; MSNAP_ST_TIMES for times not strictly increasing or
+ * t[0] != 0 (the solve entries evaluate segment 0's start rows at local time t[0], the reference's quirk; the gradient
+ * below does not hold then); MSNAP_ST_SINGULAR for a non-positive pivot, or a cost that is not finite, at the input
+ * times.  A failed drone gets NaN coef, t_out, dur, cost, pg and iters 0.  A trial point whose solve fails is a rejected
+ * step, not a failed drone.
+ * Method: projected gradient descent with Armijo backtracking, the whole iteration of the batch in one launch.
+ * Direction -P g; first proposal 0.25 * min T / max |P g|; the step is the proposal cut so that no T_i passes T_min;
+ * accepted when J_new <= J - 1e-4 * step * |P g|^2, after which the proposal is twice the step (the same proposal again
+ * when the step had been cut); rejected otherwise, the proposal then half the step, at most 30 times in a row.  The
+ * trial knots are the running sum of max(T_i + step * d_i, T_min) from 0, the last one t[M].
+ * n_seg: 1 (returns the input) .. 80 at order 7, .. 58 at order 9 (what one tile's state leaves of the LDS), and at most
+ * max_segments; MSNAP_ESEGMENTS above.  MSNAP_EINVAL: a weight that is negative or not finite, min_fraction outside
+ * (0, 1], negative max_iter or tol.  The device version only launches (no synchronisation, no context buffer).
+ *
+ * msnap_snap_cost_grad: grad [n_drones][n_seg][4] = -E per segment and axis, E the Ostrogradsky energy of the
+ * segment's polynomial at its start, with x^(q)(0) = q! c_q and k = (order + 1) / 2:
+ *   E = (x^(k))^2 + 2 sum_{m=1..k-1} (-1)^m x^(k-m) x^(k+m)
+ *     = 576 c4^2 - 1440 c3 c5 + 2880 c2 c6 - 10080 c1 c7                                              (order 7)
+ *     = 14400 c5^2 - 34560 c4 c6 + 60480 c3 c7 - 161280 c2 c8 + 725760 c1 c9                          (order 9)
+ * For a minimiser between fixed end states E is constant along the segment, and by the envelope theorem
+ * dJ_a/dT_i = grad[.][i][a] -- but ONLY when coef is the solve's result for dur; for any other coefficients grad is
+ * just this expression.  dur is not read (it names the point the derivative belongs to).
+ */
+int msnap_snap_cost_grad(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,
+                         double *grad);
+int msnap_snap_cost_grad_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,
+                                double *grad);
+int msnap_optimize_times(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, const double *t, int shared_times,
+                         const double weights[4], double min_fraction, int max_iter, double tol, double *t_out,
+                         double *coef, double *dur, int32_t *status, double *cost, double *pg, int32_t *iters);
+int msnap_optimize_times_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, const double *t,
+                                int shared_times, const double weights[4], double min_fraction, int max_iter,
+                                double tol, double *t_out, double *coef, double *dur, int32_t *status, double *cost,
+                                double *pg, int32_t *iters);
+
 /* ---- drone-vs-drone formation pass (new capability; no reference) -------
  * rows: the n_rows drones this caller owns (a shard), starting at global index
  * row_offset; cols: all n_cols drones (after the all-gather).  Spheres of `radius`.

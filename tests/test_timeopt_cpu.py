@@ -1,0 +1,159 @@
+"""Time allocation without a GPU: the C-ABI names, the closed-form gradient against central differences of the
+oracle's solve + cost, the fixture's own invariants, the NumPy restatement's guarantees, and the node's default path."""
+import inspect
+import math
+import os
+import re
+import sys
+
+import numpy as np
+import pytest
+
+from conftest import GOLDEN_DIR, ROOT
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import msnap_oracle as oracle  # noqa: E402
+import timeopt_ref as R  # noqa: E402
+
+NEW = ["msnap_optimize_times", "msnap_optimize_times_device", "msnap_snap_cost_grad", "msnap_snap_cost_grad_device"]
+
+
+def test_new_names_in_the_header_and_the_binding_table():
+    from drone_path_planning_python_amd import _lib
+    with open(os.path.join(ROOT, "include", "msnap.h")) as f:
+        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+    declared = set(re.findall(r"\b(msnap_[a-z0-9_]+)\s*\(", text))
+    for name in NEW:
+        assert name in declared, name
+        assert name in _lib.SIGNATURES, name
+    assert sorted(_lib.SIGNATURES) == sorted(declared)
+    # argument counts of the binding against the declarations
+    for name in NEW:
+        m = re.search(r"\b%s\s*\(([^;]*?)\)\s*;" % name, text, flags=re.S)
+        assert m and len(m.group(1).split(",")) == len(_lib.SIGNATURES[name][1]), name
+    lib = _lib.load()
+    assert lib.msnap_version() >= 400
+    for name in NEW:
+        assert hasattr(lib, name)
+    # argument errors need no device
+    assert lib.msnap_optimize_times(None, 1, 3, None, None, 0, None, 0.1, 1, 1e-4, None, None, None, None, None, None,
+                                    None) == -1
+    assert lib.msnap_snap_cost_grad(None, 1, 3, None, None, None) == -1
+
+
+def _walk(seed, m):
+    rng = np.random.default_rng(seed)
+    wp = np.cumsum(rng.normal(size=(m + 1, 4)), axis=0)
+    t = np.concatenate([[0.0], np.cumsum(rng.uniform(0.5, 1.5, size=m))])
+    return wp, t
+
+
+@pytest.mark.parametrize("ncoef,bound", [(8, 1e-7), (10, 1e-7)])
+def test_closed_form_gradient_against_central_differences(ncoef, bound):
+    """dJ*/dT_i = -sum_a E_i,a on the oracle's coefficients; the differences' own error is about 1e-9."""
+    wp, t = _walk(3, 10)
+    J, g, _ = R.evaluate(wp, t, (1, 1, 1, 1), ncoef)
+    T = np.diff(t)
+    for i in range(10):
+        h = 1e-5 * T[i]
+        Jpm = []
+        for s in (+1, -1):
+            T2 = T.copy()
+            T2[i] += s * h
+            Jpm.append(R.evaluate(wp, np.concatenate([[0.0], np.cumsum(T2)]), (1, 1, 1, 1), ncoef)[0])
+        fd = (Jpm[0] - Jpm[1]) / (2 * h)
+        assert abs(fd - g[i]) <= bound * np.abs(g).max(), (i, fd, g[i])
+
+
+def test_energy_is_constant_along_a_solved_segment():
+    """E evaluated from the segment's polynomial shifted to its end equals E at its start (Ostrogradsky)."""
+    wp, t = _walk(4, 6)
+    coef, dur = oracle.solve_batch_fast(wp[None], t[None], 8)
+    for i in range(6):
+        for a in range(4):
+            p = np.polynomial.Polynomial(coef[0, i, a])
+            shifted = np.array([p.deriv(q)(dur[0, i]) / math.factorial(q) for q in range(8)])
+            e0 = -R.snap_cost_grad(coef[0, i, a])
+            e1 = -R.snap_cost_grad(shifted)
+            assert abs(e0 - e1) <= 1e-7 * np.abs(R.energy_terms(coef[0, i, a])).sum(), (i, a, e0, e1)
+
+
+def test_fast_cost_is_the_oracle_cost():
+    wp, t = _walk(5, 7)
+    for nc in (8, 10):
+        coef, dur = oracle.solve_batch_fast(wp[None], t[None], nc)
+        np.testing.assert_allclose(R.fast_cost(coef[0], dur[0]), oracle.snap_cost(coef[0], dur[0]), rtol=1e-11)
+
+
+def test_fixture_invariants():
+    path = os.path.join(GOLDEN_DIR, "timeopt_golden.npz")
+    assert os.path.getsize(path) < 100 * 1024
+    z = np.load(path)
+    n = int(z["n"])
+    assert 20 <= n <= 30
+    assert set(z["order"].tolist()) == {7, 9}
+    segs = {z[f"t_{k}"].shape[0] - 1 for k in range(n)}
+    assert {4, 10, 20} <= segs
+    half = z["min_fraction"] == 0.5
+    assert half.sum() >= 3 and (z["active"][half] > 0).sum() >= 2
+    assert (np.abs(z["J_slsqp"] - z["J_descent"]) <= 1e-6 * z["J_ref"]).sum() >= 20
+    assert np.array_equal(z["J_ref"], np.minimum(z["J_slsqp"], z["J_descent"]))
+    assert (z["J_ref"] < z["J0"]).all() and (z["gap4"] >= -1e-12).all() and z["gap4"].max() < 1e-6
+    for k in range(n):
+        t = z[f"t_{k}"]
+        assert t[0] == 0.0 and (np.diff(t) > 0).all() and z[f"wp_{k}"].shape == (t.shape[0], 4)
+    # the recorded start cost is the oracle's
+    k = 6
+    Tmin = R.floor_of(z[f"t_{k}"], float(z["min_fraction"][k]))
+    coef, dur = oracle.solve_batch_fast(z[f"wp_{k}"][None], R.start_times(z[f"t_{k}"], Tmin)[None], int(z["order"][k]) + 1)
+    assert abs(R.weighted(oracle.snap_cost(coef[0], dur[0]), (1, 1, 1, 1)) - float(z["J0"][k])) <= 1e-12 * float(z["J0"][k])
+
+
+def test_restatement_keeps_the_contract():
+    wp, t = _walk(8, 8)
+    t[3] = t[2] + 1e-3                              # one duration far below the floor
+    Tmin = R.floor_of(t, 0.5)
+    ts = R.start_times(t, Tmin)
+    assert ts[0] == 0.0 and ts[-1] == t[-1] and (np.diff(ts) >= Tmin * (1 - 1e-12)).all()
+    assert np.array_equal(R.start_times(ts, Tmin * 0.5), ts)      # a feasible input is taken as it is
+    r = R.optimize(wp, t, (1, 1, 1, 1), 0.5, 100, 1e-4, 8, R.fast_cost)
+    assert r["cost"] <= r["cost0"] and (np.diff(r["t_out"]) >= Tmin * (1 - 1e-12)).all()
+    assert r["t_out"][0] == 0.0 and r["t_out"][-1] == t[-1]
+    r0 = R.optimize(wp, ts, (1, 1, 1, 1), 0.5, 0, 1e-4, 8, R.fast_cost)
+    assert r0["iters"] == 0 and np.array_equal(r0["t_out"], ts) and r0["cost"] == r0["cost0"]
+    # the measure has no unit: waypoints times 4 take the same steps
+    r4 = R.optimize(4.0 * wp, t, (1, 1, 1, 1), 0.5, 100, 1e-4, 8, R.fast_cost)
+    assert r4["iters"] == r["iters"] and np.allclose(r4["t_out"], r["t_out"], rtol=0, atol=1e-9)
+
+
+def test_node_default_does_not_touch_the_new_path():
+    from drone_path_planning_python_amd.nodes import drones_pols_generator as G
+    from drone_path_planning_python_amd.nodes import msgs
+    assert inspect.signature(G.paths_to_pols).parameters["optimize_times"].default is False
+    assert inspect.signature(G.path_to_pol).parameters["optimize_times"].default is False
+
+    class Ctx:
+        calls = []
+
+        def solve_on_grid(self, t, wp):
+            self.calls.append("solve_on_grid")
+            n, m = wp.shape[0], wp.shape[1] - 1
+            return np.zeros((n, m, 4, 8)), np.ones((n, m)), np.zeros(n, dtype=np.int32)
+
+        def optimize_times(self, wp, t):
+            self.calls.append("optimize_times")
+            n, m = wp.shape[0], wp.shape[1] - 1
+            return np.tile(t, (n, 1)), np.zeros((n, m, 4, 8)), np.ones((n, m)), np.zeros(n, dtype=np.int32), {}
+
+        def pack_pol_matrix(self, coef, dur):
+            self.calls.append("pack")
+            return np.zeros(dur.shape + (33,), dtype=np.float32)
+
+    pos = np.cumsum(np.ones((6, 3)), axis=0)
+    path = msgs.path_from_arrays(pos, np.tile([0.0, 0.0, 0.0, 1.0], (6, 1)))
+    ctx = Ctx()
+    G.paths_to_pols([path, path], ctx)
+    assert ctx.calls == ["solve_on_grid", "pack"]
+    ctx.calls.clear()
+    G.paths_to_pols([path, path], ctx, optimize_times=True)
+    assert ctx.calls == ["optimize_times", "pack"]
