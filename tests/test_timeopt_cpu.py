@@ -157,3 +157,70 @@ def test_node_default_does_not_touch_the_new_path():
     ctx.calls.clear()
     G.paths_to_pols([path, path], ctx, optimize_times=True)
     assert ctx.calls == ["optimize_times", "pack"]
+
+
+def test_wide_fixture_invariants():
+    """The conditions tests/golden/make_timeopt_wide_golden.py builds the second fixture for, on the committed file."""
+    path = os.path.join(GOLDEN_DIR, "timeopt_wide_golden.npz")
+    assert os.path.getsize(path) < 100 * 1024
+    z = np.load(path)
+    cases = R.unpack_cases(z)
+    n = int(z["n"])
+    assert n == len(cases) and z["wp"].dtype == np.float32
+    seg = np.array([len(c["t"]) - 1 for c in cases])
+    order = np.array([c["order"] for c in cases])
+    # every 8-drone-tile size, the last 16-drone-tile sizes, and per order a group of a full tile and a tail of 3
+    for o, td8, last16 in ((7, (41, 49, 72, 80), 40), (9, (30, 58), 29)):
+        have = set(seg[order == o].tolist())
+        assert set(td8) <= have and last16 in have, (o, have)
+        assert max(np.bincount(z["group"][(order == o) & np.isin(seg, td8)])) >= 11
+    assert (z["top_active"] >= 64).sum() >= 2
+    assert (z["n_below"] >= 3).sum() >= 4
+    assert (z["gap4"] >= -1e-12).all()
+    assert np.array_equal(z["J_ref"], np.minimum(z["J_slsqp"], z["J_descent"])) and (z["J_ref"] < z["J0"]).all()
+    agree = np.abs(z["J_slsqp"] - z["J_descent"]) <= 1e-6 * z["J_ref"]
+    for k in np.flatnonzero(~agree):
+        print(f"drone {k}: J_slsqp {z['J_slsqp'][k]:.12g} J_descent {z['J_descent'][k]:.12g}")
+    assert agree.sum() >= 0.8 * n
+    # the prefix: at most a tenth of the drones left out, a tolerance for every drone that takes part
+    left_out = z["p_margin"] < 1e-3
+    assert left_out.any(axis=1).sum() <= 0.1 * n
+    assert np.isfinite(z["prefix_sens"][~left_out]).all() and (z["prefix_sens"][~left_out] > 0).all()
+    assert (z["p_iters"] <= np.array([1, 3])).all() and (z["p_trials"] >= z["p_iters"]).all()
+    # one group with a shared grid at 10 and at 49 segments, six drones each; one group with mixed weights
+    shared = [c for c in cases if c["shared"]]
+    assert sorted({len(c["t"]) - 1 for c in shared}) == [10, 49] and len(shared) == 12
+    for c in shared:
+        first = next(s for s in shared if s["group"] == c["group"])
+        assert np.array_equal(c["t"], first["t"])
+    assert {c["weights"] for c in cases} == {(1.0, 1.0, 1.0, 1.0), (2.0, 0.5, 1.0, 3.0)}
+    for c in cases:
+        k, t = c["k"], c["t"]
+        Tmin = R.floor_of(t, c["min_fraction"])
+        assert t[0] == 0.0 and (np.diff(t) > 0).all() and c["wp"].shape == (t.shape[0], 4)
+        assert int((np.diff(t) < Tmin).sum()) == int(z["n_below"][k])
+        for p in c["p_t"]:
+            assert p.shape == t.shape and p[0] == 0.0 and p[-1] == t[-1] and (np.diff(p) >= Tmin * (1 - 1e-12)).all()
+    # the recorded costs are the oracle's: the start cost of a squeezed drone, the prefix cost of a weighted one
+    k = int(np.argmax(z["n_below"]))
+    c = cases[k]
+    ts = R.start_times(c["t"], R.floor_of(c["t"], c["min_fraction"]))
+    coef, dur = oracle.solve_batch_fast(c["wp"][None], ts[None], c["order"] + 1)
+    assert abs(R.weighted(oracle.snap_cost(coef[0], dur[0]), c["weights"]) - float(z["J0"][k])) <= 1e-12 * float(z["J0"][k])
+    c = next(c for c in cases if c["weights"] != (1.0, 1.0, 1.0, 1.0))
+    coef, dur = oracle.solve_batch_fast(c["wp"][None], c["p_t"][0][None], c["order"] + 1)
+    got = R.weighted(oracle.snap_cost(coef[0], dur[0]), c["weights"])
+    assert abs(got - float(z["p_cost"][c["k"], 0])) <= 1e-12 * got
+
+
+def test_trace_leaves_the_restatement_unchanged():
+    z = np.load(os.path.join(GOLDEN_DIR, "timeopt_golden.npz"))
+    for k in (0, 13, 20):
+        wp, t, mf, nc = z[f"wp_{k}"], z[f"t_{k}"], float(z["min_fraction"][k]), int(z["order"][k]) + 1
+        a = R.optimize(wp, t, (1, 1, 1, 1), mf, 40, 1e-4, nc, R.fast_cost)
+        trace = []
+        b = R.optimize(wp, t, (1, 1, 1, 1), mf, 40, 1e-4, nc, R.fast_cost, trace=trace)
+        assert np.array_equal(a["t_out"], b["t_out"])
+        assert all(a[key] == b[key] for key in ("cost0", "cost", "pg", "iters", "solves"))
+        assert len(trace) == b["solves"] - 1 and sum(acc for _, acc, _ in trace) == b["iters"]
+        assert all(s > 0 and m >= 0 for s, _, m in trace)

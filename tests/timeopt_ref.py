@@ -118,8 +118,10 @@ def measure(n2, J, ttotal, M):
     return math.sqrt(n2) * ttotal / (math.sqrt(M) * J) if J > 0 else 0.0
 
 
-def optimize(wp, t, weights=(1, 1, 1, 1), min_fraction=0.1, max_iter=200, tol=1e-4, ncoef=8, cost_fn=None):
-    """-> dict(t_out, cost0, cost, pg, iters, solves); the input must be a valid one (t[0] == 0, increasing)."""
+def optimize(wp, t, weights=(1, 1, 1, 1), min_fraction=0.1, max_iter=200, tol=1e-4, ncoef=8, cost_fn=None, trace=None):
+    """-> dict(t_out, cost0, cost, pg, iters, solves); the input must be a valid one (t[0] == 0, increasing).
+    `trace`, a list, receives one (step, accepted, margin) per trial, margin = |J_new - (J - ARMIJO step |P g|^2)| / J:
+    how far the trial was from the other decision (inf when its solve failed).  It changes nothing else."""
     wp = np.asarray(wp, dtype=np.float64)
     t = np.asarray(t, dtype=np.float64)
     w = [float(x) for x in weights]
@@ -142,6 +144,8 @@ def optimize(wp, t, weights=(1, 1, 1, 1), min_fraction=0.1, max_iter=200, tol=1e
         ev = evaluate(wp, tt, w, ncoef, cost_fn)
         solves += 1
         accept = ev is not None and ev[0] <= J - ARMIJO * step * n2
+        if trace is not None:
+            trace.append((step, accept, abs(ev[0] - (J - ARMIJO * step * n2)) / J if ev is not None else math.inf))
         capped = step >= cap
         if accept:
             J, g, _ = ev
@@ -161,3 +165,17 @@ def optimize(wp, t, weights=(1, 1, 1, 1), min_fraction=0.1, max_iter=200, tol=1e
         step, prop = nxt, nprop
         run = not done
     return {"t_out": tc, "cost0": J0, "cost": J, "pg": pg, "iters": iters, "solves": solves}
+
+
+def unpack_cases(z):
+    """The drones of tests/golden/timeopt_wide_golden.npz (flat arrays) as a list of dicts: k, group, order,
+    min_fraction, weights, shared, wp [M+1, 4] float64, t [M+1], and the prefix knots p_t (max_iter 1, 3)."""
+    out = []
+    for k in range(int(z["n"])):
+        g = int(z["group"][k])
+        lo, hi = int(z["off"][k]), int(z["off"][k + 1])
+        out.append({"k": k, "group": g, "order": int(z["order"][g]), "min_fraction": float(z["min_fraction"][g]),
+                    "weights": tuple(float(x) for x in z["weights"][g]), "shared": bool(z["shared"][g]),
+                    "wp": z["wp"][lo:hi].astype(np.float64), "t": z["t"][lo:hi],
+                    "p_t": (z["p_t1"][lo:hi], z["p_t3"][lo:hi])})
+    return out
