@@ -1,7 +1,8 @@
 // C-ABI of libmsnap.so (include/msnap.h): context management, host-pointer
 // wrappers, stream / timer plumbing.  All compute happens in the HIP kernels of
-// msnap_solve.hip / msnap_aux.hip / msnap_grid.hip / msnap_limits.hip / msnap_timeopt.hip (which also hosts the
-// time-allocation entry points, on the helpers of msnap_api_util.h); there is no CPU fallback.
+// msnap_solve.hip / msnap_aux.hip / msnap_sample.hip / msnap_collide.hip / msnap_grid.hip / msnap_limits.hip /
+// msnap_timeopt.hip (which also hosts the time-allocation entry points, on the helpers of msnap_api_util.h); there is
+// no CPU fallback.
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -11,6 +12,7 @@
 
 #include "msnap_internal.h"
 #include "msnap_api_util.h"
+#include "msnap_collide.h"
 
 namespace msnap {
 
@@ -303,12 +305,12 @@ int msnap_get_option(const msnap_ctx *ctx, const char *name, long *value) {
     if (culled) {
       if (stream_is_capturing(ctx)) return MSNAP_ECAPTURE;
       if (hipSetDevice(ctx->device) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess ||
-          hipMemcpy(&shares, ctx->collide_meta + MSNAP_COLLIDE_META_SHARES, sizeof shares, hipMemcpyDeviceToHost) != hipSuccess ||
-          hipMemcpy(&groups, ctx->collide_meta + MSNAP_COLLIDE_META_GROUPS, sizeof groups, hipMemcpyDeviceToHost) != hipSuccess)
+          hipMemcpy(&shares, ctx->collide_meta + kMetaTotal, sizeof shares, hipMemcpyDeviceToHost) != hipSuccess ||
+          hipMemcpy(&groups, ctx->collide_meta + kMetaGroups, sizeof groups, hipMemcpyDeviceToHost) != hipSuccess)
         return MSNAP_EHIP;
     }
-    // (a large swarm's group evaluator ran only if its survivors fit the list: 1 << 18 slots, csrc/msnap_aux.hip)
-    const bool by_groups = culled && (ctx->collide_last_by_groups == 1 || (ctx->collide_last_by_groups == 2 && groups <= (1 << 18)));
+    // (a large swarm's group evaluator ran only if its survivors fit the list: kGroupCapLarge slots)
+    const bool by_groups = culled && (ctx->collide_last_by_groups == 1 || (ctx->collide_last_by_groups == 2 && groups <= kGroupCapLarge));
     if (!strcmp(name, "collide_last_group_pairs")) *value = groups;
     else if (!strcmp(name, "collide_last_survivors")) *value = shares;
     else if (!strcmp(name, "collide_last_by_groups")) *value = by_groups ? 1 : 0;
@@ -602,7 +604,7 @@ int msnap_sample_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *c
 
 size_t msnap_collide_rows_t_doubles(int n_rows, int n_samples) {
   if (n_rows <= 0 || n_samples <= 0) return 0;
-  return ((size_t)n_rows + 127) / 128 * 128 * (size_t)n_samples * 3;
+  return ((size_t)n_rows + kRowBlock - 1) / kRowBlock * kRowBlock * (size_t)n_samples * 3;
 }
 
 int msnap_formation_collide_reads_rows_t(const msnap_ctx *ctx, int n_rows, int row_offset, int n_cols, int n_samples) {

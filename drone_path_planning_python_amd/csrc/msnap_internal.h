@@ -8,9 +8,6 @@
 #include "../../include/msnap.h"
 
 #define MSNAP_VERSION_NUM 400  /* 0.4.0: segment-time optimisation (msnap_timeopt.hip), snap-cost gradient */
-/* int32 words of the pairwise pass's broad-phase hand-over block that msnap_get_option reads back */
-#define MSNAP_COLLIDE_META_SHARES 128
-#define MSNAP_COLLIDE_META_GROUPS 132
 
 namespace msnap {
 
@@ -73,7 +70,7 @@ struct msnap_ctx {
   msnap::DevBuf scratch;   // global-memory scratch for n_seg too large for LDS
   msnap::DevBuf host_stage;    // the host-pointer entry points' staging arena (msnap_api.hip, staged()); also the device
                                // side of solve_host's bounce buffer and its shared time grid when chunked
-  msnap::DevBuf collide_work;  // the pairwise pass's working set (msnap_aux.hip, launch_formation_collide[_part])
+  msnap::DevBuf collide_work;  // the pairwise pass's working set (msnap_collide.hip, launch_formation_collide[_part])
   msnap::DevBuf limits_work;   // msnap_limits.hip: per-(drone, segment, quantity) peaks, then the retiming's per-drone peaks
   // chunked host-pointer solves: two streams alternate H2D -> kernel -> D2H over chunks of drones,
   // each with its own staging set (wp, t, coef, dur, status)
@@ -114,7 +111,7 @@ struct msnap_ctx {
   const void *blist_clean = nullptr;   // the group evaluator's reverse lists at this address (for blist_clean_n groups) are all-zero
   int blist_clean_n = 0;
   // one 64-bit word in page-locked host memory the broad phase's evaluator writes its survivor counts to: the next
-  // pass's choice of evaluator reads it without synchronising (csrc/msnap_aux.hip::cull_hint_pack)
+  // pass's choice of evaluator reads it without synchronising (csrc/msnap_collide.hip::cull_hint_pack)
   unsigned long long *cull_hint = nullptr;
   // what msnap_sample_collide_device left for the pairwise pass, and where (the last few buffers it wrote): 1 the
   // transposed row image, 2 the per-drone boxes and sort keys of a whole-swarm pass behind the broad phase, each with
@@ -144,8 +141,6 @@ bool stream_is_capturing(const msnap_ctx *ctx);
 // form (1 row image, 2 boxes and keys; 0: not on record for these positions, n drones x n_samples) of a sampler
 // hand-over buffer
 int handover_form(const msnap_ctx *ctx, const void *ptr, const void *pos, int n, int n_samples);
-// what the last broad-phase pass evaluated (device-side choice of collide_eval_kernel, restated on its counts)
-bool collide_counts_by_groups(const msnap_ctx *ctx, int n_drones, int shares_surviving, int group_pairs_surviving);
 
 // records the kernel instance a solve launcher chose (msnap_last_kernel; bench.py labels its rooflines with it)
 void note_kernel(msnap_ctx *ctx, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
@@ -174,17 +169,7 @@ int launch_optimize_times(msnap_ctx *ctx, int n_drones, int n_seg, const double 
                           const double *weights, double min_fraction, int max_iter, double tol, double *t_out,
                           double *coef, double *dur, int32_t *status, double *cost, double *pg, int32_t *iters);
 int timeopt_max_segments(int khalf);   // largest n_seg whose per-tile state fits LDS (80 at order 7, 58 at order 9)
-// no_sym: the rows are not the slice of the columns at row_offset (one-sided evaluation, no broad phase)
-int launch_formation_collide(msnap_ctx *ctx, int n_rows, int row_offset, int n_cols, int n_samples,
-                             const double *pos_rows, const double *pos_cols, double radius,
-                             double *min_dist, int32_t *partner, int32_t *hit, const double *rows_t, bool no_sym);
-bool formation_collide_takes_broad_phase(const msnap_ctx *ctx, int n_rows, int row_offset, int n_cols, int n_samples,
-                                         bool no_sym);
-int launch_formation_collide_part(msnap_ctx *ctx, int n_drones, int n_samples, const double *pos_all, int part,
-                                  int n_parts, double *out_d2, int32_t *out_j);
-int launch_formation_collide_finish(msnap_ctx *ctx, int n_drones, int n_parts, const void *parts, size_t part_stride,
-                                    int row_offset, int n_rows, double radius, double *min_dist, int32_t *partner,
-                                    int32_t *hit);
+// (the pairwise pass: msnap_collide.h)
 int launch_mesh_sweep(msnap_ctx *ctx, int n_drones, int n_samples, const double *pos, int n_tris,
                       const double *tris, double radius, double *min_dist, int32_t *hit);
 int launch_mesh_validity(msnap_ctx *ctx, int n_states, const double *states, int n_rtris, const double *rtris,

@@ -1,0 +1,58 @@
+// Cross-lane helpers of a 64-lane wave for fp64 values: shared by the sampler, the pairwise pass and the mesh sweep.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+namespace msnap {
+
+// v of lane (lane xor mask)
+__device__ __forceinline__ double shfl_xor_f64(double v, int mask) {
+  const int lo = __shfl_xor(__double2loint(v), mask);
+  const int hi = __shfl_xor(__double2hiint(v), mask);
+  return __hiloint2double(hi, lo);
+}
+
+// fp64 min / max over the 64 lanes of a wave (every lane gets the result): four DPP stages inside
+// the rows of 16 (lane xor 1, xor 2, mirror of 8, mirror of 16), two exchanges across the rows
+template <int CTRL>
+__device__ __forceinline__ double dpp_f64(double v) {
+  const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xF, 0xF, true);
+  const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xF, 0xF, true);
+  return __hiloint2double(hi, lo);
+}
+template <bool MAX>
+__device__ __forceinline__ double wave_minmax_f64(double v) {
+  auto fold = [](double a, double b) { return MAX ? ((b > a) ? b : a) : ((b < a) ? b : a); };
+  v = fold(v, dpp_f64<0xB1>(v));     // quad_perm [1,0,3,2]
+  v = fold(v, dpp_f64<0x4E>(v));     // quad_perm [2,3,0,1]
+  v = fold(v, dpp_f64<0x141>(v));    // row_half_mirror
+  v = fold(v, dpp_f64<0x140>(v));    // row_mirror
+  v = fold(v, __shfl_xor(v, 16));
+  v = fold(v, __shfl_xor(v, 32));
+  return v;
+}
+__device__ __forceinline__ double wave_min_f64(double v) { return wave_minmax_f64<false>(v); }
+__device__ __forceinline__ double wave_max_f64(double v) { return wave_minmax_f64<true>(v); }
+// The same butterflies with IEEE minNum / maxNum: a NaN operand is ignored, so a wave that mixes NaN and finite
+// values ends with the extreme of the finite ones in EVERY lane (with the compare-and-select fold a lane holding
+// NaN keeps it and its partner drops that subtree: the lanes would disagree); all-NaN stays NaN.
+template <bool MAX>
+__device__ __forceinline__ double wave_minmax_num_f64(double v) {
+  auto fold = [](double a, double b) { return MAX ? __builtin_fmax(a, b) : __builtin_fmin(a, b); };
+  v = fold(v, dpp_f64<0xB1>(v));
+  v = fold(v, dpp_f64<0x4E>(v));
+  v = fold(v, dpp_f64<0x141>(v));
+  v = fold(v, dpp_f64<0x140>(v));
+  v = fold(v, __shfl_xor(v, 16));
+  v = fold(v, __shfl_xor(v, 32));
+  return v;
+}
+
+// the value of lane 0 as a compiler-visible wave-uniform value (after a wave reduction every lane holds
+// the same number, but only this makes the branches and triangle loads that depend on it scalar)
+__device__ __forceinline__ double uniform_f64(double v) {
+  return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)),
+                          __builtin_amdgcn_readfirstlane(__double2loint(v)));
+}
+
+}  // namespace msnap

@@ -96,12 +96,14 @@ def test_no_register_pressure_copy_under_a_reduced_exec_mask():
     base + 16 * garbage."""
     import subprocess
     import sys
-    objs = [os.path.join(ROOT, "drone_path_planning_python_amd", "csrc", f) for f in ("msnap_solve.o", "msnap_aux.o", "msnap_grid.o")]
+    objs = [os.path.join(ROOT, "drone_path_planning_python_amd", "csrc", f)
+            for f in ("msnap_solve.o", "msnap_aux.o", "msnap_sample.o", "msnap_collide.o", "msnap_grid.o", "msnap_limits.o",
+                      "msnap_timeopt.o")]
     if not all(os.path.exists(o) for o in objs) or not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-objdump"):
         pytest.skip("no object files / ROCm LLVM tools here")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "check_exec_isa.py")] + objs, capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
-    assert r.stdout.count("none under a reduced exec mask") == 3, r.stdout
+    assert r.stdout.count("none under a reduced exec mask") == len(objs), r.stdout
 
 
 def test_the_exec_check_sees_the_round_4_fault_pattern():

@@ -17,7 +17,7 @@ import c_oracle
 from test_formation_full import _broad_phase_swarm
 
 R = 0.3
-GROUP_CAP_LARGE = 1 << 18      # list slots of a swarm above 8192 drones (csrc/msnap_aux.hip kGroupCapLarge)
+GROUP_CAP_LARGE = 1 << 18      # list slots of a swarm above 8192 drones (csrc/msnap_collide.h kGroupCapLarge)
 
 
 @functools.lru_cache(maxsize=None)

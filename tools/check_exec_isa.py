@@ -17,7 +17,8 @@ Second rule, for kernels without such copies (an ordinary v_mov placed the same 
 the latch of a loop that runs until no lane is left (`s_cbranch_execnz` backwards) exec is zero on EVERY execution until
 it is written again, so any vector instruction there is reported -- it can only be one the compiler misplaced.
 
-    python tools/check_exec_isa.py [object files ...]        (default: csrc/msnap_solve.o msnap_aux.o msnap_grid.o msnap_limits.o msnap_timeopt.o)
+    python tools/check_exec_isa.py [object files ...]        (default: csrc/msnap_solve.o msnap_aux.o msnap_sample.o msnap_collide.o msnap_grid.o
+                                                              msnap_limits.o msnap_timeopt.o)
 """
 from __future__ import annotations
 
@@ -166,8 +167,8 @@ def check(obj):
 
 
 def main():
-    objs = sys.argv[1:] or [os.path.join(CSRC, f) for f in ("msnap_solve.o", "msnap_aux.o", "msnap_grid.o", "msnap_limits.o",
-                                                             "msnap_timeopt.o")]
+    objs = sys.argv[1:] or [os.path.join(CSRC, f) for f in ("msnap_solve.o", "msnap_aux.o", "msnap_sample.o", "msnap_collide.o",
+                                                             "msnap_grid.o", "msnap_limits.o", "msnap_timeopt.o")]
     rc = 0
     for obj in objs:
         n_kernels, n_spill, bad = check(obj)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Registers, LDS and scratch of the kernels in one object file of the library (code-object metadata).
-    python tools/kernel_meta.py [msnap_aux.o] [name substring]"""
+    python tools/kernel_meta.py [msnap_aux.o | msnap_sample.o | msnap_collide.o | ...] [name substring]"""
 import os
 import re
 import subprocess
