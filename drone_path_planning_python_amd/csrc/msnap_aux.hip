@@ -21,13 +21,12 @@ pack_kernel(const double *__restrict__ coef, const double *__restrict__ dur, flo
             size_t n_rows /* N*M */, int nc) {
   const int ncol = 1 + 4 * nc;
   const size_t total = n_rows * (size_t)ncol;
-  for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
-       idx += (size_t)gridDim.x * blockDim.x) {
+  uniform_for<size_t>(threadIdx.x, total, (size_t)gridDim.x * blockDim.x, [&](size_t idx) {
     const size_t row = idx / ncol;
     const int col = (int)(idx - row * ncol);
     const double v = (col == 0) ? dur[row] : coef[row * (size_t)(4 * nc) + (col - 1)];
     out[idx] = (float)v;
-  }
+  }, (size_t)blockIdx.x * blockDim.x);
 }
 
 int launch_pack(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur, float *out) {
@@ -269,7 +268,7 @@ snap_cost_kernel(const double *__restrict__ coef, const double *__restrict__ dur
                  double *__restrict__ cost) {
   constexpr int K = NC / 2;
   const int total = N * 4;
-  for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
+  uniform_for<int>(threadIdx.x, total, gridDim.x * blockDim.x, [&](int idx) {
     const int d = idx >> 2, a = idx & 3;
     double J = 0.0;
     for (int i = 0; i < M; ++i) {
@@ -295,7 +294,7 @@ snap_cost_kernel(const double *__restrict__ coef, const double *__restrict__ dur
       J += acc;
     }
     cost[idx] = J;
-  }
+  }, blockIdx.x * blockDim.x);
 }
 
 int launch_snap_cost(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur, double *cost) {
@@ -316,7 +315,7 @@ int launch_snap_cost(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef
 template <int NC>
 __global__ void __launch_bounds__(256)
 snap_cost_grad_kernel(const double *__restrict__ coef, size_t total, double *__restrict__ grad) {
-  for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
+  uniform_for<size_t>(threadIdx.x, total, (size_t)gridDim.x * blockDim.x, [&](size_t idx) {
     double c[NC];
 #pragma unroll
     for (int j = 0; j < NC; j += 2) {
@@ -325,7 +324,7 @@ snap_cost_grad_kernel(const double *__restrict__ coef, size_t total, double *__r
       c[j + 1] = v.y;
     }
     grad[idx] = -ostrogradsky_energy<NC / 2>(c);
-  }
+  }, (size_t)blockIdx.x * blockDim.x);
 }
 
 int launch_snap_cost_grad(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, double *grad) {

@@ -336,14 +336,14 @@ collide_transpose_kernel(const double *__restrict__ prow, int R, int Rp, int E, 
   __shared__ double tile[64][TE + 1];
   if ((int)blockIdx.y >= ny) {
     const size_t stride = (size_t)(gridDim.y - ny) * gridDim.x * 256;
-    for (size_t i = ((size_t)(blockIdx.y - ny) * gridDim.x + blockIdx.x) * 256 + threadIdx.x; i < fill_n; i += stride)
-      fill[i] = -1;
+    uniform_for<size_t>(threadIdx.x, fill_n, stride, [&](size_t i) { fill[i] = -1; },
+                        ((size_t)(blockIdx.y - ny) * gridDim.x + blockIdx.x) * 256);
     return;
   }
   const int r0 = blockIdx.x * 64, e0 = blockIdx.y * TE;
   {
     const int tx = threadIdx.x & (TE - 1), ty = threadIdx.x / TE;
-#pragma unroll
+#pragma unroll      // (compile-time bounds, the same trips for every lane: not a loop in the code)
     for (int i = ty; i < 64; i += 256 / TE) {
       const int r = min(r0 + i, R - 1), e = e0 + tx;
       const double v = e < E ? prow[(size_t)(perm ? perm[r] : r) * E + e] : 0.0;
@@ -353,7 +353,7 @@ collide_transpose_kernel(const double *__restrict__ prow, int R, int Rp, int E, 
   }
   __syncthreads();
   const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-#pragma unroll
+#pragma unroll      // (as above)
   for (int i = ty; i < TE; i += 4) {
     const int e = e0 + i;
     if (e < E) prow_t[(size_t)e * Rp + r0 + tx] = tile[tx][i];
@@ -543,7 +543,7 @@ collide_select_kernel(int N, int n_rb, CollideCull cu, const double *__restrict_
   __shared__ double sBox[kStageGroups * 6];
   {
     const int nG = (N + kColBlock - 1) / kColBlock;
-    for (int gq = threadIdx.x; gq < nG; gq += kSelThreads) {
+    uniform_for<int>(threadIdx.x, nG, kSelThreads, [&](int gq) {
       double m = 0.0;
 #pragma unroll
       for (int d = 0; d < kColBlock; ++d) {
@@ -551,7 +551,7 @@ collide_select_kernel(int N, int n_rb, CollideCull cu, const double *__restrict_
         m = fmax(m, bound[r < N ? r : N - 1]);
       }
       sCmax[gq] = m;
-    }
+    });
     if constexpr (kStage) {      // (one flight: six loads per thread at most)
       double bv[kStageGroups * 6 / kSelThreads];
 #pragma unroll
@@ -1290,7 +1290,8 @@ collide_rank_kernel(const unsigned *__restrict__ key, int N, int32_t *__restrict
   __shared__ int cnt[kRankWaves][kRankTile];
   {
     const int gid = blockIdx.x * (kWave * kRankWaves) + threadIdx.x;
-    for (int z = gid; z < n_zero; z += gridDim.x * (kWave * kRankWaves)) zero[z] = 0;
+    uniform_for<int>(threadIdx.x, n_zero, gridDim.x * (kWave * kRankWaves), [&](int z) { zero[z] = 0; },
+                     blockIdx.x * (kWave * kRankWaves));
     if (gid == 0) {      // (the selection adds its survivors)
       meta[kMetaTotal] = 0;
       meta[kMetaGroups] = 0;
@@ -1374,7 +1375,7 @@ collide_gather_kernel(const double *__restrict__ pos, int N, int Rp, int E, doub
   const int nb = (int)blockIdx.x - nx * ny;
   if (nb >= n_box) {
     const size_t stride = (size_t)(gridDim.x - nx * ny - n_box) * 256;
-    for (size_t i = (size_t)(nb - n_box) * 256 + tid; i < fill_n; i += stride) fill[i] = -1;
+    uniform_for<size_t>(tid, fill_n, stride, [&](size_t i) { fill[i] = -1; }, (size_t)(nb - n_box) * 256);
     return;
   }
   if (nb >= 0) {
@@ -1426,7 +1427,7 @@ collide_gather_kernel(const double *__restrict__ pos, int N, int Rp, int E, doub
   lds_barrier();      // (not __syncthreads(): that would sit out the round trip of the stores above)
   {
     const int tx = tid & 63, ty = tid >> 6;
-    for (int i = ty; i < ne; i += 4) prow_t[(size_t)(e0 + i) * Rp + r0 + tx] = tile[tx * kTilePitch + i];
+    uniform_for<int>(ty, ne, 4, [&](int i) { prow_t[(size_t)(e0 + i) * Rp + r0 + tx] = tile[tx * kTilePitch + i]; });
   }
   {
     // pair (row, row + k) over the tile's samples, one thread each

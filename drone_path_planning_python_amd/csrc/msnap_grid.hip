@@ -31,6 +31,7 @@
 #include <cstdlib>
 
 #include "msnap_internal.h"
+#include "msnap_wave.h"
 
 namespace msnap {
 
@@ -43,12 +44,12 @@ constexpr int kGridMaxKS = 4;   // k steps (4 waypoints each): M + 1 <= 16
 __global__ void __launch_bounds__(256)
 unit_wp_kernel(double *__restrict__ wp, int P, int m) {
   const int total = P * m * 4;
-  for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
+  uniform_for<int>(threadIdx.x, total, gridDim.x * blockDim.x, [&](int idx) {
     const int a = idx & 3;
     const int i = (idx >> 2) % m;
     const int p = (idx >> 2) / m;
     wp[idx] = (i == 4 * p + a) ? 1.0 : 0.0;
-  }
+  }, blockIdx.x * blockDim.x);
 }
 
 // Gop in MFMA B-fragment order: frag[(ct*nks + ks)*64 + lane] = Gop[j = 4*ks + lane>>4][c = 16*ct + lane&15]
@@ -66,13 +67,6 @@ pack_gop_kernel(const double *__restrict__ gop /* [P][M][4][NC] */, int M, int N
     v = gop[(((size_t)(j >> 2) * M + seg) * 4 + (j & 3)) * NC + kc];
   }
   frag[(size_t)blockIdx.x * kWave + lane] = v;
-}
-
-template <int CTRL>
-__device__ __forceinline__ double dpp_quad_f64(double v) {
-  const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xF, 0xF, true);
-  const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xF, 0xF, true);
-  return __hiloint2double(hi, lo);
 }
 
 #ifdef MSNAP_TOOLS_TIMELINE
@@ -173,8 +167,8 @@ grid_gemm_kernel(const double *__restrict__ wp, const double *__restrict__ gop /
       // pair exchange (lanes l, l^1 hold adjacent columns): afterwards an even lane owns
       // columns (c, c+1) of drones 0 and 2, an odd lane the same columns of drones 1 and 3,
       // so every lane issues two 16-byte stores instead of four 8-byte ones
-      const double s0 = dpp_quad_f64<0xB1>(odd ? acc[ct][0] : acc[ct][1]);
-      const double s1 = dpp_quad_f64<0xB1>(odd ? acc[ct][2] : acc[ct][3]);
+      const double s0 = dpp_f64<0xB1>(odd ? acc[ct][0] : acc[ct][1]);
+      const double s1 = dpp_f64<0xB1>(odd ? acc[ct][2] : acc[ct][3]);
       const double lo0 = odd ? s0 : acc[ct][0], hi0 = odd ? acc[ct][1] : s0;   // drone (odd ? 1 : 0)
       const double lo1 = odd ? s1 : acc[ct][2], hi1 = odd ? acc[ct][3] : s1;   // drone (odd ? 3 : 2)
       const int c = 16 * ct + (col & ~1);
@@ -272,8 +266,8 @@ grid_gemm_stream_kernel(const double *__restrict__ wp, const double *__restrict_
         const int d0 = (g * RT + rt) * 4;
         // pair exchange as in grid_gemm_kernel: even lanes end up with columns (c, c+1) of drones
         // 0 and 2, odd lanes with those of drones 1 and 3 -> 16-byte stores
-        const double s0 = dpp_quad_f64<0xB1>(odd ? acc[rt][0] : acc[rt][1]);
-        const double s1 = dpp_quad_f64<0xB1>(odd ? acc[rt][2] : acc[rt][3]);
+        const double s0 = dpp_f64<0xB1>(odd ? acc[rt][0] : acc[rt][1]);
+        const double s1 = dpp_f64<0xB1>(odd ? acc[rt][2] : acc[rt][3]);
         const double lo0 = odd ? s0 : acc[rt][0], hi0 = odd ? acc[rt][1] : s0;
         const double lo1 = odd ? s1 : acc[rt][2], hi1 = odd ? acc[rt][3] : s1;
         if (c < ncols) {
@@ -294,6 +288,8 @@ grid_gemm_stream_kernel(const double *__restrict__ wp, const double *__restrict_
     if (blockIdx.y == 0) {   // durations and status once per row group
       const int d0 = g * RT * 4;
       const int nd = N - d0 < RT * 4 ? N - d0 : RT * 4;
+      // (lane by lane on purpose: through uniform_for of msnap_wave.h the register allocation of the whole kernel moves
+      // and the 4096 x 20 solve stage measured 11.7 against 11.4 us -- DESIGN.md 9.3; the census test pins this loop)
       for (int e = lane; e < nd * M; e += kWave) dur[(size_t)d0 * M + e] = gdur[e % M];
 #pragma unroll
       for (int rt = 0; rt < RT; ++rt) {

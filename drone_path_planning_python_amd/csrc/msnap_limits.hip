@@ -20,6 +20,7 @@
 #include <math.h>
 
 #include "msnap_internal.h"
+#include "msnap_wave.h"
 
 namespace msnap {
 namespace {
@@ -275,7 +276,7 @@ __global__ void __launch_bounds__(1024)
 retime_common_kernel(int N, double *__restrict__ scale) {
   __shared__ double part[1024];
   double m = __builtin_nan("");
-  for (int d = threadIdx.x; d < N; d += blockDim.x) m = fmax(m, scale[d]);
+  uniform_for<int>(threadIdx.x, N, blockDim.x, [&](int d) { m = fmax(m, scale[d]); });
   part[threadIdx.x] = m;
   __syncthreads();
   for (int w = blockDim.x / 2; w > 0; w >>= 1) {
@@ -283,8 +284,9 @@ retime_common_kernel(int N, double *__restrict__ scale) {
     __syncthreads();
   }
   const double k = part[0];
-  for (int d = threadIdx.x; d < N; d += blockDim.x)
+  uniform_for<int>(threadIdx.x, N, blockDim.x, [&](int d) {
     if (!isnan(scale[d])) scale[d] = k;
+  });
 }
 
 // one thread per (drone, segment, axis): c_j -> c_j r^j with r = 1/k, T -> k T; a scale that is not finite and

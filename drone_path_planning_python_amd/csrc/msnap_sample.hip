@@ -46,8 +46,7 @@ __global__ void __launch_bounds__(256)
 sample_generic_kernel(const double *__restrict__ coef, const double *__restrict__ dur, double dt, int N, int M, int S,
                       int naxes, double *__restrict__ pos) {
   const size_t total = (size_t)N * S;
-  for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
-       idx += (size_t)gridDim.x * blockDim.x) {
+  uniform_for<size_t>(threadIdx.x, total, (size_t)gridDim.x * blockDim.x, [&](size_t idx) {
     const int d = (int)(idx / S);
     const int s = (int)(idx - (size_t)d * S);
     for (int a = 0; a < naxes; ++a) {
@@ -55,7 +54,7 @@ sample_generic_kernel(const double *__restrict__ coef, const double *__restrict_
       sample_point_generic<NC>(coef + (size_t)d * M * 4 * NC, dur + (size_t)d * M, M, (double)s * dt, a, x);
       pos[idx * naxes + a] = x;
     }
-  }
+  }, (size_t)blockIdx.x * blockDim.x);
 }
 
 // Fast form: one thread per (drone, piece, axis).  The reference's search `t < acc + T_i` over the
@@ -107,6 +106,9 @@ __device__ __forceinline__ void sample_image_out(const double *sImg, int tid, in
   double *out = pos + (size_t)d0 * per_drone;
   const bool aligned = ((size_t)d0 * per_drone & 1) == 0;
   if (aligned) {
+    // (these two copies and the box fold below keep the lane-by-lane form on purpose: through uniform_for the 4096 x 10
+    // sampler stage measured 12.4 against 11.9 us, the fold two thirds of it -- DESIGN.md 9.3; the exec check guards
+    // them, and the census test pins their count)
     for (size_t e = (size_t)tid * 2; e + 1 < words; e += (size_t)nthreads * 2)
       *reinterpret_cast<double2 *>(out + e) = *reinterpret_cast<const double2 *>(sImg + e);
     if ((words & 1) && tid == 0) out[words - 1] = sImg[words - 1];
@@ -119,10 +121,10 @@ __device__ __forceinline__ void sample_image_out(const double *sImg, int tid, in
   // over the finished positions
   if (pos_t != nullptr) {
     const int runs = (int)per_drone;              // (sample, axis) pairs; naxes == 3 (checked by the launcher)
-    for (int e = tid; e < runs * nd; e += nthreads) {
+    uniform_for<int>(tid, runs * nd, nthreads, [&](int e) {
       const int sk = e / nd, dl = e - sk * nd;
       pos_t[(size_t)sk * Rp + d0 + dl] = sImg[(size_t)dl * per_drone + sk];
-    }
+    });
   }
   // third output, for a whole-swarm pass behind the exact broad phase: what collide_key_kernel would compute from
   // the finished positions -- the box of the drone's finite samples and its sort key -- while the samples sit in
@@ -132,7 +134,7 @@ __device__ __forceinline__ void sample_image_out(const double *sImg, int tid, in
     double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
     if (dl < nd) {
       const double *img = sImg + (size_t)dl * per_drone;
-      for (int sq = part; sq < S; sq += 16)
+      for (int sq = part; sq < S; sq += 16) {      // (lane by lane, as the copies above: measured)
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
           const double v = img[(size_t)sq * 3 + k];
@@ -141,6 +143,7 @@ __device__ __forceinline__ void sample_image_out(const double *sImg, int tid, in
             hi[k] = v > hi[k] ? v : hi[k];
           }
         }
+      }
     }
 #pragma unroll
     for (int m = 1; m < 16; m <<= 1)
@@ -197,7 +200,7 @@ sample_kernel(const double *__restrict__ coef, const double *__restrict__ dur, d
     }
     __syncthreads();
     const int items = nd * M * naxes;
-    for (int it = tid; it < items; it += blockDim.x) {
+    uniform_for<int>(tid, items, blockDim.x, [&](int it) {
       const int dl = div_by(it, inv_piece), rem = it - dl * (naxes * M);
       const int i = div_by(rem, inv_axes), a = rem - i * naxes;
       const double *cbase = coef + (size_t)(d0 + dl) * M * 4 * NC;
@@ -206,7 +209,7 @@ sample_kernel(const double *__restrict__ coef, const double *__restrict__ dur, d
         if (i == 0)       // rare: one thread per axis walks the whole path with the reference's own loop
           for (int sq = 0; sq < S; ++sq)
             sample_point_generic<NC>(cbase, dur + (size_t)(d0 + dl) * M, M, (double)sq * dt, a, img[(size_t)sq * naxes + a]);
-        continue;
+        return;
       }
       const double *crow = cbase + ((size_t)i * 4 + a) * NC;
       sample_piece<NC>(sB[dl * (M + 1) + i], sB[dl * (M + 1) + i + 1], i, M, S, dt, img, naxes, a, [&](double (&c)[NC]) {
@@ -217,7 +220,7 @@ sample_kernel(const double *__restrict__ coef, const double *__restrict__ dur, d
           c[q + 1] = v.y;
         }
       });
-    }
+    });
     __syncthreads();
     sample_image_out(sImg, tid, blockDim.x, nd, d0, per_drone, S, pos, pos_t, Rp, kbox, kkey);
     __syncthreads();
@@ -307,7 +310,7 @@ grid_sample_kernel(const double *__restrict__ wp, const double *__restrict__ fra
     }
     sBad[DW] = ranges ? 0 : 1;
   }
-  for (int e = tid; e < rows16 * wpitch; e += blockDim.x) sW[e] = 0.0;
+  uniform_for<int>(tid, rows16 * wpitch, blockDim.x, [&](int e) { sW[e] = 0.0; });
 
   for (int d0 = blockIdx.x * DW; d0 < N; d0 += gridDim.x * DW) {
     const int nd = N - d0 < DW ? N - d0 : DW;
@@ -391,22 +394,22 @@ grid_sample_kernel(const double *__restrict__ wp, const double *__restrict__ fra
       for (int dl = wave; dl < nd; dl += 4) {
         const bool bad = grid_st != 0 || sBad[dl] != 0;
         double *cout = coef + (size_t)(d0 + dl) * M * 4 * NC;
-        for (int e = lane; e < ppd; e += kWave) {
+        uniform_for<int>(lane, ppd, kWave, [&](int e) {
           const int g = 2 * e;
           const int kc = g % NC, q = g / NC;
           const int a = q & 3, seg = q >> 2;
           double2 v = *reinterpret_cast<const double2 *>(sC + (size_t)(dl * 4 + a) * cpitch + seg * NC + kc);
           if (bad) v = make_double2(__builtin_nan(""), __builtin_nan(""));
           *reinterpret_cast<double2 *>(cout + g) = v;
-        }
+        });
       }
-      for (int e = tid; e < nd * M; e += blockDim.x) dur[(size_t)d0 * M + e] = gdur[e % M];
+      uniform_for<int>(tid, nd * M, blockDim.x, [&](int e) { dur[(size_t)d0 * M + e] = gdur[e % M]; });
       if (tid < nd) status[d0 + tid] = sBad[tid] ? MSNAP_ST_NONFINITE : grid_st;
     }
     MSNAP_GSTL(4);
     const int items = nd * M * 3;
     const bool generic = sBad[DW] != 0;
-    for (int it = tid; it < items; it += blockDim.x) {
+    uniform_for<int>(tid, items, blockDim.x, [&](int it) {
       const int dl = div_by(it, inv_piece), rem = it - dl * (3 * M);
       const int i = rem / 3, a = rem - i * 3;
       double *img = sImg + (size_t)dl * per_drone;
@@ -420,7 +423,7 @@ grid_sample_kernel(const double *__restrict__ wp, const double *__restrict__ fra
             if (!bad) sample_point_generic<NC>(cbase, gdur, M, (double)sq * dt, a, x, NC, cpitch);
             img[(size_t)sq * 3 + a] = x;
           }
-        continue;
+        return;
       }
       const double *crow = cbase + (size_t)a * cpitch + i * NC;
       sample_piece<NC>(sB[i], sB[i + 1], i, M, S, dt, img, 3, a, [&](double (&c)[NC]) {
@@ -431,7 +434,7 @@ grid_sample_kernel(const double *__restrict__ wp, const double *__restrict__ fra
           c[q + 1] = v.y;
         }
       });
-    }
+    });
     lds_barrier();
     MSNAP_GSTL(5);
     sample_image_out(sImg, tid, blockDim.x, nd, d0, per_drone, S, pos, pos_t, Rp, kbox, kkey);

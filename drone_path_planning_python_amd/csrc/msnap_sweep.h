@@ -6,6 +6,7 @@
 #include "msnap_consts.h"
 #include "msnap_internal.h"
 #include "msnap_energy.h"
+#include "msnap_wave.h"
 
 namespace msnap {
 
@@ -394,12 +395,9 @@ __device__ __forceinline__ void store_segment_quad8(double *__restrict__ seg_bas
 template <int MAXCNT = 0, int STRIDE = kWave>   // MAXCNT: compile-time bound of drones x segments per tile (0: not known, scalar loop)
 __device__ __forceinline__ void store_durations(const double *sTraw, int shared_times, int tpitch, int M,
                                                 int nvalid, int lane, double *__restrict__ dur_tile) {
-  // The trip count is WAVE-UNIFORM (a scalar loop around a predicated body), not `for (e = lane; e < cnt; e += 64)`:
-  // a loop the lanes leave one by one ends with exec == 0, and the compiler put register-pressure copies of values
-  // that live across it (v_accvgpr_write_b32 of lane + 64 / lane + 128, solve_kernel_twin<5, 20>; the scratch spills of
-  // round 3's two-sided 16-segment instance) into that exit block IN FRONT of the instruction that restores exec --
-  // they wrote no lane, the next tile's prefetch indices were garbage: "Memory access fault by GPU" (DESIGN.md 9.3;
-  // tools/check_exec_isa.py now refuses a build with such a copy under a reduced exec mask)
+  // The loop whose lane-by-lane form `for (e = lane; e < cnt; e += 64)` faulted (uniform_for, msnap_wave.h, has the
+  // account): the same wave-uniform scalar loop around a predicated body, written out here because the helper's
+  // inlining order moves instructions in ten solve kernels and the headline kernels are held instruction for instruction
   const int cnt = nvalid * M;
   auto one = [&](int e) {
     if (e < cnt) {

@@ -324,8 +324,8 @@ timeopt_kernel(const TimeoptArgs p) {
   {
     const int cnt = nvalid * tpitch;
     double *dst = p.t_out + (size_t)tile * TD * tpitch;
-    for (int e0 = 0; e0 < cnt; e0 += kWave) {
-      const int e = e0 + lane;
+    for (int e0 = 0; e0 < cnt; e0 += kWave) {      // (uniform_for of msnap_wave.h written out, as store_durations is:
+      const int e = e0 + lane;                      // the helper's inlining order moves instructions in this kernel)
       if (e < cnt) dst[e] = sTraw[e];
     }
   }

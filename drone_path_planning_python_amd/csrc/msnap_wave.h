@@ -1,4 +1,5 @@
-// Cross-lane helpers of a 64-lane wave for fp64 values: shared by the sampler, the pairwise pass and the mesh sweep.
+// Cross-lane helpers of a 64-lane wave for fp64 values (the sampler, the pairwise pass, the mesh sweep, the GEMM) and
+// the counted loop of every kernel whose lanes make different numbers of trips (uniform_for).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -46,6 +47,24 @@ __device__ __forceinline__ double wave_minmax_num_f64(double v) {
   v = fold(v, __shfl_xor(v, 16));
   v = fold(v, __shfl_xor(v, 32));
   return v;
+}
+
+// body(e) for e = base + first, base + first + stride, ... while e < count: THE counted loop of this library whenever
+// the lanes' trip counts differ (lane-, thread- and grid-strided sweeps).  `count`, `stride` and `base` are
+// wave-uniform, `first` < stride is the lane's offset (base: 0 for a workgroup-strided loop, the block's first element
+// for a grid-stride one).  The loop variable and the trip test are WAVE-UNIFORM -- a scalar loop around a predicated
+// body -- not `for (e = first; e < count; e += stride)`: a loop the lanes leave one by one ends with exec == 0, and
+// the compiler put register-pressure copies of values that live across it (v_accvgpr_write_b32 of lane + 64 /
+// lane + 128, solve_kernel_twin<5, 20>; the scratch spills of round 3's two-sided 16-segment instance) into that exit
+// block IN FRONT of the instruction that restores exec -- they wrote no lane, the next tile's prefetch indices were
+// garbage: "Memory access fault by GPU" (tools/check_exec_isa.py refuses a build with such a copy, and
+// tests/test_abi.py one with a new loop of that shape).  `continue` in the body is `return`.
+template <class I, class Body>
+__device__ __forceinline__ void uniform_for(I first, I count, I stride, Body &&body, I base = 0) {
+  for (I e0 = base; e0 < count; e0 += stride) {
+    const I e = e0 + first;
+    if (e < count) body(e);
+  }
 }
 
 // the value of lane 0 as a compiler-visible wave-uniform value (after a wave reduction every lane holds

@@ -106,6 +106,58 @@ def test_no_register_pressure_copy_under_a_reduced_exec_mask():
     assert r.stdout.count("none under a reduced exec mask") == len(objs), r.stdout
 
 
+def test_lane_retiring_loops_are_only_the_allow_listed_ones():
+    """tools/check_exec_isa.lane_latches on the objects of this build: a loop the lanes leave one by one (a backward
+    `s_cbranch_execnz` behind `s_andn2_b64 exec, exec, ..`) is what a counted loop `for (e = lane; e < n; e += 64)` compiles
+    to, and its exit block is where the round-4 copies sat.  Counted loops go through uniform_for
+    (csrc/msnap_wave.h); what is left are loops whose trip count is a per-lane RESULT, listed here by kernel."""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import check_exec_isa as chk
+    allowed = {      # kernel -> loops per instance: a further `for (e = lane; ..)` in one of these raises its count
+        # sample_piece (msnap_sample.hip): the two correction `while`s of first_at and the sample-range loop
+        # `for (sq = s_lo; sq < s_hi; ++sq)` -- s_lo, s_hi come out of a division per (drone, piece); and
+        # sample_image_out: the 16-byte and 8-byte copies and the box fold `for (sq = part; sq < S; sq += 16)`, slower
+        # through uniform_for (DESIGN.md 9.3 has the measurement)
+        "msnap::sample_kernel": 6,
+        "msnap::grid_sample_kernel": 6,      # the same sample_piece and sample_image_out, inlined into the fused launch
+        # the duration store `for (e = lane; e < nd * M; e += kWave)`: through uniform_for the whole kernel's register
+        # allocation moves and the 4096 x 20 solve stage was 2.5 % slower (DESIGN.md 9.3)
+        "msnap::grid_gemm_stream_kernel": 1,
+    }
+    if not all(os.path.exists(o) for o in chk.DEFAULT_OBJS) or not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-objdump"):
+        pytest.skip("no object files / ROCm LLVM tools here")
+    found = {}
+    for obj in chk.DEFAULT_OBJS:
+        found.update(chk.lane_latches(obj))
+    assert found, "the census found no loop at all: the disassembly was not understood"
+    extra = sorted((k, n) for k, n in found.items() if n > allowed.get(k.split("<")[0], 0))
+    assert not extra, f"lane-retiring loops outside the allow-list (use uniform_for of msnap_wave.h): {extra}"
+
+
+def test_the_exec_check_tells_a_loop_latch_from_an_if_and_from_an_always_taken_branch():
+    """exec_latch on the three shapes a backward `s_cbranch_execnz` has in these objects: behind `s_andn2_b64 exec` the
+    latch of a lane-retiring loop; behind a saveexec an if-block laid out in front of its test; in a block that does not
+    write exec, or only restores it, the folded `vcc = exec & -1` branch of a uniform loop nest, which never falls through."""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import check_exec_isa as chk
+
+    def kind(lines):
+        body = [(ln, 0x1000 + 4 * i, 0x1000) if ln.startswith("s_cbranch_execnz") else
+                (ln, 0x1000 + 4 * i, 0x1000 + 4 * (len(lines) - 1) if ln.startswith(("s_branch", "s_cbranch_scc1")) else None)
+                for i, ln in enumerate(lines)]
+        at = {a: i for i, (_, a, _) in enumerate(body)}
+        return chk.exec_latch(body, at, len(lines) - 1)
+
+    assert kind(["global_store_dwordx2 v[0:1], v[4:5], off", "s_andn2_b64 exec, exec, s[6:7]", "s_cbranch_execnz 65501"]) == "loop"
+    assert kind(["v_mov_b32_e32 v1, v2", "s_and_saveexec_b64 s[4:5], vcc", "s_xor_b64 s[4:5], exec, s[4:5]",
+                 "s_cbranch_execnz 65501"]) == "if"
+    assert kind(["v_mov_b32_e32 v1, v2", "s_andn2_b64 exec, exec, s[6:7]", "s_cbranch_scc1 3", "global_store_dwordx2 v[0:1], v[4:5], off",
+                 "s_branch 65516", "s_cbranch_execnz 65503"]) is None
+    assert kind(["s_andn2_b64 exec, exec, s[14:15]", "s_or_b64 exec, exec, s[12:13]", "s_cbranch_execnz 65507"]) is None
+
+
 def test_the_exec_check_sees_the_round_4_fault_pattern():
     """tools/check_exec_isa.walk on the instruction shapes of the faulty build (solve_kernel_twin<5, 20>, round 4): a
     loop the lanes leave one by one, the copies in its exit block in front of the restore -- reported; the same copies

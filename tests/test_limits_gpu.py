@@ -139,6 +139,23 @@ def test_edge_cases(ctx7, ctx9):
         assert np.array_equal(co[1:3], c[1:3], equal_nan=True) and np.array_equal(do[1:3], d[1:3])
 
 
+def test_common_scale_over_more_drones_than_the_fold_has_threads(ctx7):
+    """retime_common_kernel is one workgroup of 1024 threads: 1029 drones are a second, partial round of both of its
+    loops.  The common scale is the exact maximum of the drones' own scales (a maximum does not round) -- here a drone
+    of the partial round holds it -- and failed drones keep NaN."""
+    _, _, coef, dur = _solved(ctx7, 1029, 1029, 2)
+    coef, dur = coef.copy(), dur.copy()
+    coef[1027] *= 64.0                        # 64 x the speed and acceleration: the largest factor of the batch
+    coef[5, 0, 0, 0] = np.nan
+    dur[1028, 1] = -0.5
+    own = ctx7.retime_to_limits(coef, dur, 1.0, 1.0, fit=True, common=False)[2]
+    bad = np.isnan(own)
+    assert bad.nonzero()[0].tolist() == [5, 1028] and int(np.nanargmax(own)) == 1027
+    co, do, com = ctx7.retime_to_limits(coef, dur, 1.0, 1.0, fit=True, common=True)
+    assert np.isnan(com[bad]).all() and (com[~bad] == own[1027]).all()
+    assert np.array_equal(co[bad], coef[bad], equal_nan=True) and np.array_equal(do[bad], dur[bad])
+
+
 @pytest.mark.parametrize("order,tol", [(7, 1e-10), (9, 1e-9)])
 def test_retiming_equals_a_fresh_solve_on_scaled_times(ctx7, ctx9, order, tol):
     ctx = ctx7 if order == 7 else ctx9

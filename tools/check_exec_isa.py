@@ -19,6 +19,7 @@ it is written again, so any vector instruction there is reported -- it can only 
 
     python tools/check_exec_isa.py [object files ...]        (default: csrc/msnap_solve.o msnap_aux.o msnap_sample.o msnap_collide.o msnap_grid.o
                                                               msnap_limits.o msnap_timeopt.o)
+    python tools/check_exec_isa.py --latches [object files ...]      the kernels that still hold such a loop, with their latch counts
 """
 from __future__ import annotations
 
@@ -42,6 +43,10 @@ NARROW = re.compile(r"^s_(?:andn2|and)_b64 exec, exec,")       # lanes leave (lo
 EXEC_WRITE = re.compile(r"^s_\w+_saveexec_b64|^s_\w+ exec\b|^v_cmpx")
 VECTOR = re.compile(r"^(v_(?!readlane|readfirstlane|writelane)|ds_|global_|flat_|buffer_|scratch_)")
 OTHER_EXEC = re.compile(r"^s_\w+ exec\b|^v_cmpx")               # any other writer of exec: treated as narrowing
+
+
+DEFAULT_OBJS = [os.path.join(CSRC, f) for f in ("msnap_solve.o", "msnap_aux.o", "msnap_sample.o", "msnap_collide.o",
+                                                "msnap_grid.o", "msnap_limits.o", "msnap_timeopt.o")]
 
 
 def disassemble(obj):
@@ -79,12 +84,58 @@ def kernels_of(text):
     return out
 
 
+def exec_latch(body, at, i, targets=None):
+    """What a backward `s_cbranch_execnz` at instruction i is, from the write of exec in front of it in its own block:
+    "loop" behind `s_andn2_b64 exec, exec, ..` -- the latch of a loop the lanes leave one by one; "if" behind a
+    saveexec -- an if-block the compiler laid out in front of its test; None for any other instruction, and for a
+    branch whose block does not write exec at all or only restores it (`s_or_b64 exec, exec, pair`): the compiler's
+    form of a uniform branch that is always taken (`s_and_b64 vcc, exec, -1` + `s_cbranch_vccnz`, folded), which never
+    falls through.  (The write of exec is looked for in the latch's own block only: LLVM ends a lane-retiring loop
+    with the pair `s_andn2_b64 exec, exec, ..; s_cbranch_execnz`, never with the branch alone in a block of its own.  A
+    compiler that split the pair over two blocks would go unseen by this rule and by the census; the first rule of the
+    walk -- copies under a narrowed mask -- does not depend on it.)  `targets`: the set of branch targets, when the
+    caller has it."""
+    ins, _, target = body[i]
+    if ins.split()[0] != "s_cbranch_execnz" or target is None or target not in at or at[target] > i:
+        return None
+    if targets is None:
+        targets = {t for _, _, t in body if t is not None}
+    for k in range(i - 1, -1, -1):
+        prev, addr, _ = body[k]
+        if prev.startswith(("s_branch", "s_cbranch", "s_endpgm")):
+            return None
+        if OR_EXEC.match(prev):      # a restore: exec is the wider mask again, not empty
+            return None
+        if NARROW.match(prev):
+            return "loop"
+        if EXEC_WRITE.match(prev):
+            return "if"
+        if addr in targets:
+            return None
+    return None
+
+
+def lane_latches(obj):
+    """kernel name (without its argument list) -> number of "loop" latches, for every kernel of the object that has
+    one: the census of the loops whose trip count differs between lanes (tests/test_abi.py holds the allow-list)"""
+    out = {}
+    for name, body in kernels_of(disassemble(obj)).items():
+        at = {addr: i for i, (_, addr, _) in enumerate(body)}
+        targets = {t for _, _, t in body if t is not None}
+        n = sum(1 for i in range(len(body)) if exec_latch(body, at, i, targets) == "loop")
+        if n:
+            key = name.replace("(anonymous namespace)", "{anon}").split("(")[0].replace("void ", "")
+            out[key] = out.get(key, 0) + n
+    return out
+
+
 def walk(body):
     """Abstract interpretation of exec over the kernel's control-flow graph.  State: the stack of SGPR pairs that hold
     a saved (wider) mask, plus `narrow` (lanes have left through s_andn2 exec since the last restore).  Structured
     control flow as LLVM emits it: s_*_saveexec pushes, `s_or_b64 exec, exec, pair` pops down to that pair.
     Returns the list of (instruction, state) for register-pressure copies executed with a possibly reduced mask."""
     at = {addr: i for i, (_, addr, _) in enumerate(body)}
+    targets = {t for _, _, t in body if t is not None}
     seen, bad, work = set(), [], [(0, (), False, False)]
     while work:
         i, stack, narrow, zero = work.pop()
@@ -143,8 +194,8 @@ def walk(body):
                 continue
             if op.startswith("s_cbranch") and target is not None and target in at:
                 work.append((at[target], stack, narrow, zero))
-                if op == "s_cbranch_execnz" and at[target] <= i:      # the latch of a loop the lanes leave one by one:
-                    zero = True                                        # behind it exec is zero on EVERY execution
+                if exec_latch(body, at, i, targets):      # behind it exec is zero on EVERY execution
+                    zero = True
             i += 1
     visited = {i for i, _, _, _ in seen}
     missed = [body[i][0] for i in range(len(body)) if i not in visited and SPILL.match(body[i][0])]
@@ -167,8 +218,14 @@ def check(obj):
 
 
 def main():
-    objs = sys.argv[1:] or [os.path.join(CSRC, f) for f in ("msnap_solve.o", "msnap_aux.o", "msnap_sample.o", "msnap_collide.o",
-                                                             "msnap_grid.o", "msnap_limits.o", "msnap_timeopt.o")]
+    if sys.argv[1:2] == ["--latches"]:      # the census: one line per kernel with a lane-retiring loop
+        for obj in sys.argv[2:] or DEFAULT_OBJS:
+            found = lane_latches(obj)
+            print(f"check_exec_isa: {os.path.basename(obj)}: {sum(found.values())} lane-retiring loop latches in {len(found)} kernels")
+            for k, n in sorted(found.items()):
+                print(f"    {n:3d}  {k}")
+        return 0
+    objs = sys.argv[1:] or DEFAULT_OBJS
     rc = 0
     for obj in objs:
         n_kernels, n_spill, bad = check(obj)
