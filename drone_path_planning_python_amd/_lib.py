@@ -68,6 +68,8 @@ SIGNATURES = {
     "msnap_time_scale_device": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _VP]),
     "msnap_retime_to_limits": (_I, [_VP, _I, _I, _VP, _VP, _VP, _I, _VP, _VP, _VP]),
     "msnap_retime_to_limits_device": (_I, [_VP, _I, _I, _VP, _VP, _VP, _I, _VP, _VP, _VP]),
+    "msnap_pair_clearance": (_I, [_VP, _I, _I, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP]),
+    "msnap_pair_clearance_device": (_I, [_VP, _I, _I, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP]),
     "msnap_formation_collide": (_I, [_VP, _I, _I, _I, _I, _VP, _VP, _D, _VP, _VP, _VP]),
     "msnap_formation_collide_device": (_I, [_VP, _I, _I, _I, _I, _VP, _VP, _D, _VP, _VP, _VP]),
     "msnap_collide_rows_t_doubles": (ctypes.c_size_t, [_I, _I]),

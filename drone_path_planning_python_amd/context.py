@@ -14,13 +14,14 @@ import numpy as np
 
 from . import _lib
 
-ST_OK, ST_SINGULAR, ST_TIMES, ST_NONFINITE = 0, 1, 2, 3
+ST_OK, ST_SINGULAR, ST_TIMES, ST_NONFINITE, ST_PAIR = 0, 1, 2, 3, 4
 RETIME_FIT, RETIME_COMMON = 1, 2      # msnap_retime_flags
 STATUS_TEXT = {
     ST_OK: "ok",
     ST_SINGULAR: "singular system",
     ST_TIMES: "times not strictly increasing",
     ST_NONFINITE: "non-finite waypoint or time",
+    ST_PAIR: "pair index out of range, or a drone paired with itself",
 }
 
 
@@ -477,6 +478,33 @@ class Context:
             self._ck(self._lib.msnap_retime_to_limits_device(self._h, int(n_drones), int(n_seg), _ptr(coef), _ptr(dur),
                                                              plim, int(flags), _ptr(coef_out), _ptr(dur_out),
                                                              _ptr(scale)))
+
+    # ---- pairwise clearance in continuous time (include/msnap.h) --------------------------
+    def pair_clearance(self, coef, dur, pairs):
+        """Certified distance of the listed pairs of drones while both fly: (min_dist [P], t_min [P], lower [P],
+        status [P] int32) with lower <= infimum <= min_dist, min_dist attained at t_min (msnap_pair_clearance).
+        `pairs`: [P, 2] drone indices into the batch."""
+        coef, pc, dur, pd, N, M = self._coef_dur(coef, dur)
+        pr, ppr = _host(pairs, np.int32)
+        if pr.ndim != 2 or pr.shape[1] != 2:
+            raise ValueError("pairs must be [P, 2]")
+        P = pr.shape[0]
+        md = np.empty((P,), dtype=np.float64)
+        tm = np.empty((P,), dtype=np.float64)
+        lower = np.empty((P,), dtype=np.float64)
+        status = np.empty((P,), dtype=np.int32)
+        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)      # noqa: E731
+        with self._lock:
+            self._ck(self._lib.msnap_pair_clearance(self._h, N, M, pc, pd, P, ppr, vp(md), vp(tm), vp(lower),
+                                                    vp(status)))
+        return md, tm, lower, status
+
+    def pair_clearance_device(self, n_drones, n_seg, coef, dur, n_pairs, pairs, min_dist, t_min, lower, status):
+        """Device pointers (pairs int32 [n_pairs, 2]), asynchronous on the context's stream."""
+        with self._lock:
+            self._ck(self._lib.msnap_pair_clearance_device(self._h, int(n_drones), int(n_seg), _ptr(coef), _ptr(dur),
+                                                           int(n_pairs), _ptr(pairs), _ptr(min_dist), _ptr(t_min),
+                                                           _ptr(lower), _ptr(status)))
 
     # ---- collision passes --------------------------------------------------------
     def formation_collide(self, pos_rows, pos_cols, radius: float, row_offset: int = 0):

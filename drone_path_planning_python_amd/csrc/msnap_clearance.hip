@@ -1,0 +1,400 @@
+// Pairwise clearance in continuous time: the certified minimum distance of two drones of one batch while both fly
+// (include/msnap.h, "pairwise clearance").
+//
+// Window.  Knot times are the running sums acc = acc + T of each drone (as peaks_fold_kernel and msnap_eval_flat form
+// them); the window of a pair is [0, W], W = min of the two totals.  A drone that has landed is NOT held at its end
+// point: what happens after the shorter path ends is out of scope here.
+//
+// Intervals.  Between consecutive knots of the two drones |p_a(t) - p_b(t)|^2 is one polynomial.  The end points
+// inside the window are the M - 1 interior knots of a, the M - 1 interior knots of b and W itself: 2 M - 1 slots, one
+// lane per (pair, slot).  The lane's interval ends at its end point and starts at the largest end point below it, ties
+// ordered a's knots < b's knots < W -- so coincident knots (a shared grid) leave the later slot empty, a slot whose end
+// point lies beyond W is dead, and every live interval is found exactly once whichever drone is called a.  Both are
+// found with uniform loops over the M durations (every lane of a pair loads the same addresses).
+//
+// Lane.  Per axis x, y, z: Taylor shift of each drone's polynomial to its local offset at the interval's start, the
+// DIFFERENCE of the two (before any square: near a minimum the distance carries the rounding of the difference, not
+// of the positions), scaled by h^j to u in [0, 1].  g(u) = sum of the three squares, degree 2 order.  Then the walk of
+// peaks_lane_kernel (msnap_limits.hip) turned to a minimum: dyadic sub-intervals, Taylor shift and exact scaling by
+// 2^-lvl, the smallest Bernstein coefficient of g as a lower bound, g at both ends and the middle as attained values
+// (smaller value, then earlier time), a node pruned when bound >= L (1 - kPruneRel) - kPruneAbs.  The lane carries the
+// minimum of the bounds of every node it pruned or stopped at (depth cap), and of the root's bound if the node guard
+// ends the walk early: exactly what the walk proved.  Stackless and wave-uniform: the loop runs while any lane of the
+// wave is active, every per-lane decision is a select.
+//
+// Fold.  One thread per pair over its slots: smallest attained value, then earliest absolute time; smallest bound.
+// The attained value is evaluated again at t_min in the t domain -- msnap_eval_flat's segment lookup and Horner, the
+// formation pass's fma(dz, dz, fma(dy, dy, dx dx)) -- so that eval_flat at t_min reproduces min_dist.  Nothing crosses
+// lanes but the trip count: a pair's outputs do not depend on its place in the list, and (b, a) gives the bits of
+// (a, b) (the difference changes sign exactly, every later quantity is even in it).
+#include <math.h>
+
+#include "msnap_api_util.h"
+#include "msnap_wave.h"
+
+namespace msnap {
+namespace {
+
+constexpr int kMaxDepth = 40;            // sub-intervals of 2^-40 (msnap_limits.hip)
+constexpr int kMaxNodes = 4096;          // nodes per lane: a guard on the loop
+constexpr double kPruneRel = 2e-9;       // on g = |.|^2: 1e-9 on the distance
+constexpr double kPruneAbs = 1e-18;      // on g: A^2 with A = 1e-9 m (DESIGN.md §5 K9 has the depth arithmetic)
+constexpr int kThreads = kClearanceThreads;
+
+constexpr double binom(int n, int k) {
+  double r = 1.0;
+  for (int j = 1; j <= k; ++j) r = r * (double)(n - k + j) / (double)j;
+  return r;
+}
+
+// power basis -> Bernstein basis of degree n on [0, 1]: b_i = sum_{k <= i} C(i, k) / C(n, k) a_k
+template <int n>
+struct BernsteinWeights {
+  double w[n + 1][n + 1];
+  constexpr BernsteinWeights() : w() {
+    for (int i = 0; i <= n; ++i)
+      for (int k = 0; k <= i; ++k) w[i][k] = binom(i, k) / binom(n, k);
+  }
+};
+
+// one thread per (drone, segment): 2 for a non-finite coefficient (any axis) or duration, else 1 for a duration <= 0
+template <int NC>
+__global__ void __launch_bounds__(kThreads)
+clearance_flags_kernel(const double *__restrict__ coef, const double *__restrict__ dur, size_t segs,
+                       int32_t *__restrict__ flags) {
+  const size_t seg = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (seg >= segs) return;
+  const double T = dur[seg];
+  bool finite = isfinite(T);
+#pragma unroll
+  for (int j = 0; j < 4 * NC; ++j) finite = finite && isfinite(coef[seg * 4 * NC + j]);
+  flags[seg] = !finite ? 2 : (T > 0.0 ? 0 : 1);
+}
+
+__device__ __forceinline__ bool pair_in_range(int a, int b, int N) {
+  return a >= 0 && b >= 0 && a < N && b < N && a != b;
+}
+
+// one lane per (pair, slot): work[3 item] = smallest attained g of the slot's interval (+inf: an empty or dead slot, or
+// a failed pair), [3 item + 1] = its absolute time, [3 item + 2] = the proven lower bound of g there (+inf likewise)
+template <int NC>
+__global__ void __launch_bounds__(kThreads)
+clearance_lane_kernel(const double *__restrict__ coef, const double *__restrict__ dur,
+                      const int32_t *__restrict__ flags, int N, int M, int n_pairs, const int32_t *__restrict__ pairs,
+                      double *__restrict__ work) {
+  constexpr int D = NC - 1;       // degree of the positions
+  constexpr int n = 2 * D;        // degree of g
+  constexpr BernsteinWeights<n> W{};
+  const double inf = __builtin_inf();
+  const int slots = 2 * M - 1;
+  const size_t total = (size_t)n_pairs * slots;
+  const size_t item = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool in_range = item < total;
+  const size_t p = in_range ? item / (size_t)slots : 0;
+  const int k = (int)(item - p * (size_t)slots);
+  const int a0 = in_range ? pairs[2 * p] : 0, b0 = in_range ? pairs[2 * p + 1] : 0;
+  const bool pair_ok = in_range && pair_in_range(a0, b0, N);
+  const size_t da = pair_ok ? (size_t)a0 * M : 0, db = pair_ok ? (size_t)b0 * M : 0;
+  // the slot's end point: an interior knot of a (kind 0), of b (kind 1), or the window's end (kind 2)
+  const int kind = k < M - 1 ? 0 : (k < 2 * M - 2 ? 1 : 2);
+  const int own = kind == 0 ? k : k - (M - 1);
+
+  // first pass over the durations: the totals, the slot's end point, the drones' flags
+  double accA = 0.0, accB = 0.0, E = 0.0;
+  int bad = 0;
+  for (int i = 0; i < M; ++i) {
+    const double Ta = pair_ok ? dur[da + i] : 1.0, Tb = pair_ok ? dur[db + i] : 1.0;
+    bad |= pair_ok ? (flags[da + i] | flags[db + i]) : 0;
+    accA = accA + Ta;
+    accB = accB + Tb;
+    if (kind == 0 && i == own) E = accA;
+    if (kind == 1 && i == own) E = accB;
+  }
+  const double Wend = fmin(accA, accB);
+  if (kind == 2) E = Wend;
+  const bool valid = pair_ok && bad == 0;
+
+  // second pass: the interval's start (the largest end point below E; ties: a's knots < b's knots < the window's
+  // end) and the segment of each drone that holds it, by msnap_eval_flat's lookup (first i with E <= acc_i)
+  double start = 0.0, offA = 0.0, offB = 0.0;
+  int segA = M - 1, segB = M - 1;
+  bool foundA = false, foundB = false;
+  accA = 0.0;
+  accB = 0.0;
+  for (int i = 0; i < M; ++i) {
+    const double Ta = valid ? dur[da + i] : 1.0, Tb = valid ? dur[db + i] : 1.0;
+    const double prevA = accA, prevB = accB;
+    accA = accA + Ta;
+    accB = accB + Tb;
+    const bool interior = i < M - 1;
+    const bool belowA = kind == 0 ? accA < E : accA <= E;
+    const bool belowB = kind == 2 ? accB <= E : accB < E;
+    if (interior && belowA) start = fmax(start, accA);
+    if (interior && belowB) start = fmax(start, accB);
+    if (!foundA && E <= accA) { segA = i; offA = prevA; foundA = true; }
+    if (!foundB && E <= accB) { segB = i; offB = prevB; foundB = true; }
+  }
+  const double h = E - start;
+  const bool ok = valid && E <= Wend && h > 0.0;
+
+  // e[s][j]: the difference polynomial of axis s on the interval, in u
+  double e[3][D + 1];
+  {
+    const double la = start - offA, lb = start - offB;
+    const double *ca = coef + (da + segA) * 4 * NC, *cb = coef + (db + segB) * 4 * NC;
+#pragma unroll
+    for (int s = 0; s < 3; ++s) {
+      double pa[NC], pb[NC];
+#pragma unroll
+      for (int j = 0; j < NC; ++j) {
+        pa[j] = ok ? ca[s * NC + j] : 0.0;
+        pb[j] = ok ? cb[s * NC + j] : 0.0;
+      }
+#pragma unroll
+      for (int kk = 0; kk < D; ++kk)
+#pragma unroll
+        for (int j = D - 1; j >= kk; --j) {
+          pa[j] = fma(la, pa[j + 1], pa[j]);
+          pb[j] = fma(lb, pb[j + 1], pb[j]);
+        }
+      double hp = 1.0;
+#pragma unroll
+      for (int j = 0; j <= D; ++j) {
+        e[s][j] = ok ? (pa[j] - pb[j]) * hp : 0.0;
+        hp *= h;
+      }
+    }
+  }
+
+  // branch and bound over the dyadic sub-intervals; every lane runs the body while any lane is active
+  double best = inf, best_u = 0.0, low = inf, root = inf;
+  unsigned long long idx = 0;
+  int lvl = 0, nodes = 0;
+  bool active = ok;
+  while (__ballot(active) != 0) {
+    const double hh = ldexp(1.0, -lvl);
+    const double a = (double)idx * hh;
+    // f_s(x) = e_s(a + hh x): Taylor shift to a, then the exact scaling by hh = 2^-lvl
+    double f[3][D + 1];
+#pragma unroll
+    for (int s = 0; s < 3; ++s) {
+#pragma unroll
+      for (int j = 0; j <= D; ++j) f[s][j] = e[s][j];
+#pragma unroll
+      for (int kk = 0; kk < D; ++kk)
+#pragma unroll
+        for (int j = D - 1; j >= kk; --j) f[s][j] = fma(a, f[s][j + 1], f[s][j]);
+      double hp = hh;
+#pragma unroll
+      for (int j = 1; j <= D; ++j) {
+        f[s][j] *= hp;
+        hp *= hh;
+      }
+    }
+    // g on the sub-interval (power basis in x), then its Bernstein bound
+    double G[n + 1];
+#pragma unroll
+    for (int j = 0; j <= n; ++j) G[j] = 0.0;
+#pragma unroll
+    for (int s = 0; s < 3; ++s)
+#pragma unroll
+      for (int i = 0; i <= D; ++i)
+#pragma unroll
+        for (int j = 0; j <= D; ++j) G[i + j] = fma(f[s][i], f[s][j], G[i + j]);
+    double bound = G[0];
+#pragma unroll
+    for (int i = 1; i <= n; ++i) {
+      double b = 0.0;
+#pragma unroll
+      for (int j = 0; j <= i; ++j) b = fma(W.w[i][j], G[j], b);
+      bound = fmin(bound, b);
+    }
+    // attained values at x = 0, 1/2, 1 (earlier first: a tie keeps the earlier time)
+    double g0 = 0.0, gm = 0.0, g1 = 0.0;
+#pragma unroll
+    for (int s = 0; s < 3; ++s) {
+      double vm = 0.0, v1 = 0.0;
+#pragma unroll
+      for (int j = D; j >= 0; --j) {
+        vm = fma(vm, 0.5, f[s][j]);
+        v1 = v1 + f[s][j];
+      }
+      g0 = fma(f[s][0], f[s][0], g0);
+      gm = fma(vm, vm, gm);
+      g1 = fma(v1, v1, g1);
+    }
+    double nb = best, nu = best_u;
+    if (g0 < nb || (g0 == nb && a < nu)) { nb = g0; nu = a; }
+    const double um = fma(0.5, hh, a), u1 = a + hh;
+    if (gm < nb || (gm == nb && um < nu)) { nb = gm; nu = um; }
+    if (g1 < nb || (g1 == nb && u1 < nu)) { nb = g1; nu = u1; }
+    if (active) { best = nb; best_u = nu; }
+    // next node: a child, or (pruned / at the depth cap) the next sibling of the deepest ancestor that has one
+    const bool split = bound < fma(-kPruneRel, best, best) - kPruneAbs && lvl < kMaxDepth;
+    const int up = __builtin_ctzll(~idx);           // trailing ones of idx: levels to climb (idx < 2^lvl: up <= lvl)
+    const unsigned long long idx_next = split ? idx << 1 : (idx >> up) + 1;
+    const int lvl_next = split ? lvl + 1 : lvl - up;
+    const bool first = nodes == 0;
+    ++nodes;
+    const bool finished = !split && up == lvl;
+    const bool guard = !finished && nodes >= kMaxNodes;      // nodes are left unvisited: only the root's bound holds
+    if (active) {
+      root = first ? bound : root;
+      low = split ? low : fmin(low, bound);
+      low = guard ? fmin(low, root) : low;
+      idx = idx_next;
+      lvl = lvl_next;
+    }
+    active = active && !(finished || guard);
+  }
+
+  if (!in_range) return;
+  const double tm = fmin(fma(h, best_u, start), E);
+  work[3 * item] = ok ? best : inf;
+  work[3 * item + 1] = ok ? tm : 0.0;
+  work[3 * item + 2] = ok ? low : inf;
+}
+
+// position of one drone at absolute time t: msnap_eval_flat's lookup (first segment with t <= acc + T) and Horner
+template <int NC>
+__device__ __forceinline__ void position_at(const double *__restrict__ coef, const double *__restrict__ dur, size_t d0,
+                                            int M, double t, double &x, double &y, double &z) {
+#pragma clang fp contract(off)
+  double acc = 0.0;
+  int seg = -1;
+  for (int i = 0; i < M; ++i) {
+    const double Ti = dur[d0 + i];
+    if (seg < 0) {
+      if (t <= acc + Ti) seg = i;
+      else acc = acc + Ti;
+    }
+  }
+  seg = seg < 0 ? M - 1 : seg;
+  const double tl = t - acc;
+  const double *c = coef + (d0 + seg) * 4 * NC;
+  x = y = z = 0.0;
+#pragma unroll
+  for (int j = NC - 1; j >= 0; --j) {
+    x = x * tl + c[j];
+    y = y * tl + c[NC + j];
+    z = z * tl + c[2 * NC + j];
+  }
+}
+
+// one thread per pair: fold the slots (smaller value, then earlier time; smallest bound), status, the attained value
+// again in the t domain
+template <int NC>
+__global__ void __launch_bounds__(kThreads)
+clearance_fold_kernel(const double *__restrict__ coef, const double *__restrict__ dur,
+                      const int32_t *__restrict__ flags, const double *__restrict__ work, int N, int M, int n_pairs,
+                      const int32_t *__restrict__ pairs, double *__restrict__ min_dist, double *__restrict__ t_min,
+                      double *__restrict__ lower, int32_t *__restrict__ status) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n_pairs) return;
+  const double nan = __builtin_nan("");
+  const int a = pairs[2 * (size_t)p], b = pairs[2 * (size_t)p + 1];
+  int st = MSNAP_ST_OK;
+  if (!pair_in_range(a, b, N)) {
+    st = MSNAP_ST_PAIR;
+  } else {
+    int bad = 0;
+    for (int i = 0; i < M; ++i) bad |= flags[(size_t)a * M + i] | flags[(size_t)b * M + i];
+    st = (bad & 2) ? MSNAP_ST_NONFINITE : ((bad & 1) ? MSNAP_ST_TIMES : MSNAP_ST_OK);
+  }
+  double md = nan, tm = nan, lo = nan;
+  if (st == MSNAP_ST_OK) {
+    const int slots = 2 * M - 1;
+    const double *w = work + (size_t)p * slots * 3;
+    double best = __builtin_inf(), bt = 0.0, low = __builtin_inf();
+    for (int k = 0; k < slots; ++k) {
+      const double g = w[3 * k], t = w[3 * k + 1];
+      if (g < best || (g == best && t < bt)) {
+        best = g;
+        bt = t;
+      }
+      low = fmin(low, w[3 * k + 2]);
+    }
+    double xa, ya, za, xb, yb, zb;
+    position_at<NC>(coef, dur, (size_t)a * M, M, bt, xa, ya, za);
+    position_at<NC>(coef, dur, (size_t)b * M, M, bt, xb, yb, zb);
+    const double dx = xa - xb, dy = ya - yb, dz = za - zb;
+    md = sqrt(fma(dz, dz, fma(dy, dy, dx * dx)));
+    tm = bt;
+    lo = fmin(sqrt(fmax(low, 0.0)), md);      // (an attained value bounds the infimum too)
+  }
+  min_dist[p] = md;
+  t_min[p] = tm;
+  lower[p] = lo;
+  status[p] = st;
+}
+
+unsigned blocks_of(size_t items, int threads) { return (unsigned)((items + threads - 1) / threads); }
+
+template <int NC>
+int launch(msnap_ctx *ctx, int N, int M, const double *coef, const double *dur, int n_pairs, const int32_t *pairs,
+           void *scratch, double *min_dist, double *t_min, double *lower, int32_t *status) {
+  const size_t lanes = clearance_lanes(n_pairs, M), segs = (size_t)N * M;
+  double *work = (double *)scratch;
+  int32_t *flags = (int32_t *)(work + 3 * lanes);
+  if (segs) {
+    hipLaunchKernelGGL((clearance_flags_kernel<NC>), dim3(blocks_of(segs, kThreads)), dim3(kThreads), 0, ctx->stream,
+                       coef, dur, segs, flags);
+    MSNAP_HIP(ctx, hipGetLastError());
+  }
+  hipLaunchKernelGGL((clearance_lane_kernel<NC>), dim3(blocks_of(lanes, kThreads)), dim3(kThreads), 0, ctx->stream,
+                     coef, dur, (const int32_t *)flags, N, M, n_pairs, pairs, work);
+  MSNAP_HIP(ctx, hipGetLastError());
+  hipLaunchKernelGGL((clearance_fold_kernel<NC>), dim3(blocks_of(n_pairs, kThreads)), dim3(kThreads), 0, ctx->stream,
+                     coef, dur, (const int32_t *)flags, (const double *)work, N, M, n_pairs, pairs, min_dist, t_min,
+                     lower, status);
+  MSNAP_HIP(ctx, hipGetLastError());
+  return MSNAP_OK;
+}
+
+int launch_pair_clearance(msnap_ctx *ctx, int N, int M, const double *coef, const double *dur, int n_pairs,
+                          const int32_t *pairs, double *min_dist, double *t_min, double *lower, int32_t *status) {
+  const int rc = ensure(ctx, ctx->clearance_work, clearance_work_bytes(N, M, n_pairs));
+  if (rc) return rc;
+  void *scratch = ctx->clearance_work.p;
+  return ctx->order == 7
+             ? launch<8>(ctx, N, M, coef, dur, n_pairs, pairs, scratch, min_dist, t_min, lower, status)
+             : launch<10>(ctx, N, M, coef, dur, n_pairs, pairs, scratch, min_dist, t_min, lower, status);
+}
+
+}  // namespace
+}  // namespace msnap
+
+using namespace msnap;
+
+extern "C" {
+
+// the entry points live beside their launcher, as msnap_timeopt.hip's do
+static int clearance_args(const msnap_ctx *ctx, int n_drones, int n_seg, int n_pairs,
+                          std::initializer_list<const void *> ptrs) {
+  if (int rc = check_clearance_args(ctx, n_drones, n_seg, n_pairs)) return rc;
+  if (n_pairs == 0) return kNoWork;
+  for (const void *p : ptrs)
+    if (!p) return MSNAP_EINVAL;
+  return MSNAP_OK;
+}
+
+int msnap_pair_clearance_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,
+                                int n_pairs, const int32_t *pairs, double *min_dist, double *t_min, double *lower,
+                                int32_t *status) {
+  MSNAP_ENTER(ctx, clearance_args(ctx, n_drones, n_seg, n_pairs, {coef, dur, pairs, min_dist, t_min, lower, status}));
+  return launch_pair_clearance(ctx, n_drones, n_seg, coef, dur, n_pairs, pairs, min_dist, t_min, lower, status);
+}
+
+int msnap_pair_clearance(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur, int n_pairs,
+                         const int32_t *pairs, double *min_dist, double *t_min, double *lower, int32_t *status) {
+  MSNAP_ENTER(ctx, clearance_args(ctx, n_drones, n_seg, n_pairs, {coef, dur, pairs, min_dist, t_min, lower, status}));
+  const size_t b_out = (size_t)n_pairs * 8;
+  return staged(ctx, {upload(coef, coef_bytes(ctx, n_drones, n_seg)), upload(dur, dur_bytes(n_drones, n_seg)),
+                      upload(pairs, (size_t)n_pairs * 2 * 4), download(min_dist, b_out), download(t_min, b_out),
+                      download(lower, b_out), download(status, (size_t)n_pairs * 4)},
+                [&](const DevPtr *d) {
+                  return launch_pair_clearance(ctx, n_drones, n_seg, d[0], d[1], n_pairs, d[2], d[3], d[4], d[5], d[6]);
+                });
+}
+
+}  // extern "C"

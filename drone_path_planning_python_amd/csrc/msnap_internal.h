@@ -7,7 +7,7 @@
 
 #include "../../include/msnap.h"
 
-#define MSNAP_VERSION_NUM 400  /* 0.4.0: segment-time optimisation (msnap_timeopt.hip), snap-cost gradient */
+#define MSNAP_VERSION_NUM 500  /* 0.5.0: pairwise clearance in continuous time (msnap_clearance.hip) */
 
 namespace msnap {
 
@@ -72,6 +72,7 @@ struct msnap_ctx {
                                // side of solve_host's bounce buffer and its shared time grid when chunked
   msnap::DevBuf collide_work;  // the pairwise pass's working set (msnap_collide.hip, launch_formation_collide[_part])
   msnap::DevBuf limits_work;   // msnap_limits.hip: per-(drone, segment, quantity) peaks, then the retiming's per-drone peaks
+  msnap::DevBuf clearance_work;   // msnap_clearance.hip: per-(pair, slot) results, then the per-(drone, segment) flags
   // chunked host-pointer solves: two streams alternate H2D -> kernel -> D2H over chunks of drones,
   // each with its own staging set (wp, t, coef, dur, status)
   hipStream_t pipe_stream[2] = {nullptr, nullptr};
@@ -210,4 +211,18 @@ int launch_time_scale(msnap_ctx *ctx, int N, int M, const double *coef, const do
 int launch_retime(msnap_ctx *ctx, int N, int M, const double *coef, const double *dur, const double *limits, int flags,
                   double *coef_out, double *dur_out, double *scale);
 
+// pairwise clearance (msnap_clearance.hip): one lane per (pair, slot), 2 n_seg - 1 slots per pair
+constexpr int kClearanceThreads = 256;
+inline size_t clearance_lanes(int n_pairs, int M) { return (size_t)n_pairs * (size_t)(2 * M - 1); }
+// ctx->clearance_work: per-lane results [lanes][3] doubles, then the flags [N M] int32
+inline size_t clearance_work_bytes(int N, int M, int n_pairs) {
+  return clearance_lanes(n_pairs, M) * 3 * sizeof(double) + (size_t)N * M * sizeof(int32_t);
+}
+inline int check_clearance_args(const msnap_ctx *ctx, int n_drones, int n_seg, int n_pairs) {
+  if (!ctx || n_drones < 0 || n_pairs < 0) return MSNAP_EINVAL;
+  if (n_seg < 1 || n_seg > ctx->max_segments) return MSNAP_ESEGMENTS;
+  if ((clearance_lanes(n_pairs, n_seg) + kClearanceThreads - 1) / kClearanceThreads > 0x7fffffffu) return MSNAP_EINVAL;   // grid size
+  if (((size_t)n_drones * n_seg + kClearanceThreads - 1) / kClearanceThreads > 0x7fffffffu) return MSNAP_EINVAL;
+  return MSNAP_OK;
+}
 }  // namespace msnap

@@ -192,6 +192,23 @@ class DeviceCompute:
             self.ctx.time_scale_device(n, M, coef, dur, scale, coef_out, dur_out)
         return coef_out, dur_out
 
+    # ---- pairwise clearance in continuous time (include/msnap.h) -----------------------------------------------------
+    def pair_clearance(self, coef, dur, pairs):
+        """(min_dist [P], t_min [P], lower [P], status [P] int32) of the listed pairs (int32 [P, 2], drone indices into
+        the batch): the certified distance while both fly, lower <= infimum <= min_dist."""
+        torch = self.torch
+        n, M = dur.shape
+        P = pairs.shape[0]
+        if pairs.dim() != 2 or pairs.shape[1] != 2 or pairs.dtype != torch.int32:
+            raise ValueError("pair_clearance: pairs must be an int32 tensor [P, 2]")
+        md = self._out("pair_clearance.md", (P,), torch.float64)
+        tm = self._out("pair_clearance.tm", (P,), torch.float64)
+        lower = self._out("pair_clearance.lower", (P,), torch.float64)
+        status = self._out("pair_clearance.status", (P,), torch.int32)
+        if P:
+            self.ctx.pair_clearance_device(n, M, coef, dur, P, pairs.contiguous(), md, tm, lower, status)
+        return md, tm, lower, status
+
     def collide(self, pos_rows, row_offset, pos_all, radius, rows_t=None):
         torch = self.torch
         r = pos_rows.shape[0]
@@ -522,3 +539,122 @@ def default_sample_count(total_duration: float, dt: float) -> int:
     """len(np.arange(0, duration, dt)) -- the reference's sampling loop
     (src/trajectory_visualising/visualization.py:53)."""
     return int(len(np.arange(0.0, total_duration, dt)))
+
+
+# ---- certified clearance of a swarm: the sampled pass decides what it can, the exact kernel sees the rest ------------
+PEAK_MARGIN = 2e-9       # V_i = peak (1 + 2e-9): the peaks' contract (include/msnap.h), so that V_i bounds the true speed
+COMPARE_MARGIN = 1e-9    # relative margin of the fp64 compares against 2 radius + (V_i + V_j) gap
+
+
+def sample_gap(dt: float, n_samples: int, totals) -> float:
+    """The largest distance from a time at which a drone flies to the nearest sample at which it still flies: dt / 2
+    inside the grid, more at the end of a path the grid stops short of (`default_sample_count` stops one step early: a
+    10 s path sampled at 0.1 s ends at 9.9 s, gap 0.1 s).  Per drone with total duration T the samples are s dt,
+    s < n_samples, s dt <= T (a sample beyond T reads the extrapolated last piece, which the certified speed does not
+    bound); the result is the maximum over the drones (`totals`: their total durations)."""
+    totals = np.asarray(totals, dtype=np.float64).reshape(-1)
+    if n_samples < 1 or not dt > 0.0:
+        raise ValueError("sample_gap: n_samples >= 1 and dt > 0")
+    if totals.size == 0:
+        return 0.5 * dt
+    k = np.minimum(np.floor(totals / dt), n_samples - 1)
+    k = np.where(k * dt > totals, k - 1, k)
+    tail = totals - k * dt
+    inner = np.where(k >= 1, 0.5 * dt, 0.0)
+    return float(np.maximum(inner, tail).max())
+
+
+@dataclass
+class ClearanceResult:
+    certified_lower: object   # [N] a proven lower bound of the drone's distance to every other drone while both fly
+    hit: object               # [N] bool: some pair of the drone ATTAINS a distance below 2 radius (definite)
+    undecided: object         # [N] bool: no hit, but a pair with lower < 2 radius <= min_dist (a search that met its caps)
+    cleared_by_sampling: object   # [N] bool: the sampled pass and the speed peaks alone prove >= 2 radius
+    sampled_min_dist: object  # [N] the sampled pass, for comparison
+    sampled_partner: object
+    sampled_hit: object
+    pairs: object             # [P, 2] int32: the pairs that went through msnap_pair_clearance
+    pair_min_dist: object     # [P]
+    pair_t_min: object
+    pair_lower: object
+    gap: float
+    n_uncertain: int          # |U|: drones the sampled pass could not clear
+
+
+def uncertain_pairs(pos_u, idx_u, v_u, radius: float, gap: float, torch, budget: int = 1 << 22):
+    """Among the drones idx_u (positions pos_u [U, S, 3], speeds v_u [U]) the pairs (i < j, global indices, int32
+    [P, 2]) whose sampled distance is below (2 radius + (V_i + V_j) gap) (1 + COMPARE_MARGIN)."""
+    U, S = pos_u.shape[0], pos_u.shape[1]
+    out = []
+    rows = max(1, budget // max(1, U * S))
+    for r0 in range(0, U, rows):
+        r1 = min(U, r0 + rows)
+        d = pos_u[r0:r1, None] - pos_u[None]                       # [rows, U, S, 3]
+        dist = (d * d).sum(dim=-1).amin(dim=-1).sqrt()             # [rows, U]
+        lim = (2.0 * radius + (v_u[r0:r1, None] + v_u[None, :]) * gap) * (1.0 + COMPARE_MARGIN)
+        keep = dist < lim
+        ii, jj = torch.nonzero(keep, as_tuple=True)
+        ii = ii + r0
+        sel = ii < jj
+        out.append(torch.stack([idx_u[ii[sel]], idx_u[jj[sel]]], dim=1))
+    if not out:
+        return torch.zeros((0, 2), dtype=torch.int32, device=pos_u.device)
+    return torch.cat(out, dim=0).to(torch.int32).contiguous()
+
+
+def certify_clearance(compute, coef, dur, radius: float, dt: float, n_samples: int, status=None, world: int = 1,
+                      rank: int = 0) -> ClearanceResult:
+    """Certify the drone-vs-drone clearance of a swarm in continuous time.
+
+    1. the sampled pass as `formation_pass` runs it, and the certified speed peaks V_i = peak (1 + 2e-9);
+    2. gap = `sample_gap`;
+    3. a drone whose sampled minimum distance d_i is at least 2 radius + (V_i + V_max) gap is cleared by sampling: a
+       pair that truly comes within 2 radius has a sample within gap of that moment, at which both of its drones fail
+       this test;
+    4. among the other drones U, the pairs whose sampled distance is below 2 radius + (V_i + V_j) gap
+    5. go through `compute.pair_clearance` (msnap_pair_clearance_device).
+
+    One rank only: several ranks would need a gather of the uncertain drones' coefficients, which is not built --
+    `world > 1` raises.  Drones whose solve failed (`status` != 0) are refused, as `formation_pass` does."""
+    import torch
+    if world != 1 or rank != 0:
+        raise NotImplementedError("certify_clearance runs on one rank: the gather of the uncertain drones' "
+                                  "coefficients over several ranks is not built")
+    if not (radius >= 0.0):
+        raise ValueError("certify_clearance: radius >= 0")
+    n = dur.shape[0]
+    res = formation_pass(compute, coef, dur, n, 1, 0, dt, n_samples, radius, status_local=status)
+    peak, _, pst = compute.dynamic_peaks(coef, dur)
+    if int(pst.abs().sum()) != 0:
+        raise ValueError("certify_clearance: drones with non-finite coefficients or durations <= 0 cannot be certified")
+    d = res.min_dist
+    v = peak[:, 0] * (1.0 + PEAK_MARGIN)
+    gap = sample_gap(dt, n_samples, dur.sum(dim=1).cpu().numpy())
+    v_max = v.max() if n else 0.0
+    reach = (v + v_max) * gap
+    cleared = d >= (2.0 * radius + reach) * (1.0 + COMPARE_MARGIN)
+    idx_u = torch.nonzero(~cleared, as_tuple=True)[0]
+    pairs = uncertain_pairs(res.positions_all[idx_u], idx_u, v[idx_u], radius, gap, torch)
+    # everything that is not a kept pair is at least 2 radius apart: a cleared drone by its own bound d_i - reach_i
+    # (which covers all of its pairs), a pair of U that was not kept by d_ij - (V_i + V_j) gap >= 2 radius
+    lip = torch.where(cleared, (d - reach) * (1.0 - COMPARE_MARGIN), torch.full_like(d, 2.0 * radius))
+    certified = lip.clone()
+    hit = torch.zeros((n,), dtype=torch.bool, device=d.device)
+    undecided = torch.zeros((n,), dtype=torch.bool, device=d.device)
+    P = pairs.shape[0]
+    if P:
+        md, tm, lower, pstat = compute.pair_clearance(coef, dur, pairs)
+        if int(pstat.abs().sum()) != 0:
+            raise ValueError("certify_clearance: msnap_pair_clearance reported failed pairs")
+        md, tm, lower = md.clone(), tm.clone(), lower.clone()
+        both = pairs.to(torch.int64).reshape(-1)                      # a0 b0 a1 b1 ...
+        certified.scatter_reduce_(0, both, lower.repeat_interleave(2), reduce="amin", include_self=True)
+        p_hit = md < 2.0 * radius
+        p_und = (~p_hit) & (lower < 2.0 * radius)
+        hit[both[p_hit.repeat_interleave(2)]] = True
+        undecided[both[p_und.repeat_interleave(2)]] = True
+        undecided &= ~hit
+    else:
+        md = tm = lower = torch.zeros((0,), dtype=torch.float64, device=d.device)
+    return ClearanceResult(certified, hit, undecided, cleared, d, res.partner, res.hit, pairs, md, tm, lower, gap,
+                           int(idx_u.numel()))

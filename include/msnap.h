@@ -69,7 +69,8 @@ enum msnap_status {       /* per-drone, written to status[]                   */
   MSNAP_ST_OK = 0,
   MSNAP_ST_SINGULAR = 1,  /* a pivot of the block LDL^T was <= 0 or not finite */
   MSNAP_ST_TIMES = 2,     /* times not strictly increasing (or t[1] <= 2 t[0]) */
-  MSNAP_ST_NONFINITE = 3  /* NaN / Inf in the waypoints or times               */
+  MSNAP_ST_NONFINITE = 3, /* NaN / Inf in the waypoints or times               */
+  MSNAP_ST_PAIR = 4       /* msnap_pair_clearance: a drone index outside [0, n_drones), or a == b */
 };
 
 int msnap_version(void);                       /* 10000*major + 100*minor + patch */
@@ -307,6 +308,38 @@ int msnap_retime_to_limits(msnap_ctx *ctx, int n_drones, int n_seg, const double
 int msnap_retime_to_limits_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,
                                   const double limits[4], int flags, double *coef_out, double *dur_out,
                                   double *scale);
+
+/* ---- pairwise clearance in continuous time (new capability) ----
+ * The formation pass takes its minimum distance on the sampling grid and can miss a crossing between two samples.
+ * msnap_pair_clearance certifies the distance of listed pairs of drones of ONE coef / dur batch (same order, same n_seg,
+ * per-drone durations) between the samples as well.  For pair p = (a, b) = pairs[p][0..1] the window is
+ * [0, min(sum dur_a, sum dur_b)] -- while both fly; a drone that has landed is NOT held at its end point, what happens
+ * after the shorter path ends is out of scope.  D is the infimum of |p_a(t) - p_b(t)| over the window for the exact
+ * real polynomials of the fp64 coefficients.
+ *   min_dist [n_pairs]  a distance the pair ATTAINS, at
+ *   t_min    [n_pairs]  absolute time, 0 <= t_min <= window (smaller value, then the earlier time): msnap_eval_flat of
+ *                       the two drones at t_min gives positions whose distance is min_dist;
+ *   lower    [n_pairs]  a proven lower bound:  lower <= D <= min_dist, each up to rounding (ten times the worst
+ *                       deviation measured against an exact reference):
+ *                         lower <= D (1 + 1e-13) + 1e-13   and   D <= min_dist (1 + 1e-13) + 1e-13
+ *                       When the search closes (always, short of its caps: 40 bisections of an interval between knots,
+ *                       4096 nodes per interval):  lower >= min_dist (1 - 1e-9) - 1e-9  -- the absolute term A = 1e-9 m
+ *                       is what lets a crossing (D = 0) close.  A pair that meets a cap still gets a valid lower, only
+ *                       further from min_dist; no status is raised for it.
+ *   status   [n_pairs]  msnap_status: MSNAP_ST_PAIR for an index outside [0, n_drones) or a == b (nothing is read for
+ *                       such a pair), else MSNAP_ST_NONFINITE for a NaN / Inf coefficient or duration of either drone,
+ *                       else MSNAP_ST_TIMES for a duration <= 0.  min_dist, t_min and lower of a failed pair are NaN.
+ * A pair's outputs are bit-identical whatever its place in the list, the list's length, host versus device entry, and
+ * for (b, a) in place of (a, b).  n_pairs == 0 is a no-op.  The device version only launches; its scratch is a buffer
+ * of the context under the capture rules above (MSNAP_ECAPTURE: run the call once outside the capture first).
+ * (Method: per interval between consecutive knots of the two drones, branch and bound on Bernstein bounds of the
+ * squared norm of the DIFFERENCE polynomial.)
+ */
+int msnap_pair_clearance(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur, int n_pairs,
+                         const int32_t *pairs, double *min_dist, double *t_min, double *lower, int32_t *status);
+int msnap_pair_clearance_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,
+                                int n_pairs, const int32_t *pairs, double *min_dist, double *t_min, double *lower,
+                                int32_t *status);
 
 /* ---- time allocation: segment times optimised per drone (new capability) ----
  * Everything above takes the waypoint times as given (the reference's grid t_i = i*10/n,

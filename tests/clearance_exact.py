@@ -1,0 +1,290 @@
+"""References for the pairwise clearance (include/msnap.h, "pairwise clearance"), test side only.
+
+exact_clearance: the coefficients and the fp64 knot times (running sums, as the library forms them) taken as exact
+Fractions; the merged knots with the window's end included; on every interval g = |p_a - p_b|^2 as an exact rational
+polynomial in the time since the interval's start, the real roots of g' from mpmath.polyroots at 60 digits, g there and
+at both ends; D = sqrt of the minimum.
+fp64_clearance: a plain NumPy fp64 restatement of the kernel's walk (csrc/msnap_clearance.hip), vectorised over the
+(pair, interval) lanes -- for large lists, for the node counts, and for measuring the rounding of the fp64 method
+against exact_clearance.  Not bit-exact with the kernel (no fused multiply-add here)."""
+from __future__ import annotations
+
+from fractions import Fraction
+from math import comb
+
+import mpmath
+import numpy as np
+
+DPS = 60
+# include/msnap.h, "pairwise clearance"
+REL_CLOSE = 1e-9        # lower >= min_dist (1 - REL_CLOSE) - ABS_CLOSE when the walk closes
+ABS_CLOSE = 1e-9
+REL_ROUND = 1e-13       # lower <= D (1 + REL_ROUND) + ABS_ROUND,  D <= min_dist (1 + REL_ROUND) + ABS_ROUND
+ABS_ROUND = 1e-13
+# csrc/msnap_clearance.hip
+MAX_DEPTH = 40
+MAX_NODES = 4096
+PRUNE_REL = 2e-9
+PRUNE_ABS = 1e-18
+
+
+def knots(dur):
+    """fp64 running sums acc = acc + T of one drone's durations (the library's knot times), as floats."""
+    out, acc = [], 0.0
+    for T in dur:
+        acc = acc + float(T)
+        out.append(acc)
+    return out
+
+
+def _shift(c, a):
+    """Exact Taylor shift: coefficients (ascending) of c(x + a)."""
+    c = list(c)
+    n = len(c)
+    for k in range(n - 1):
+        for j in range(n - 2, k - 1, -1):
+            c[j] = c[j] + a * c[j + 1]
+    return c
+
+
+def _mpf(x):
+    return mpmath.mpf(x.numerator) / x.denominator
+
+
+def exact_interval_min(ga, t0, t1):
+    """min over tau in [0, t1 - t0] of the exact polynomial ga (ascending Fractions): (value, tau) as mpf."""
+    with mpmath.workdps(DPS):
+        h = _mpf(t1 - t0)
+        cands = [mpmath.mpf(0), h]
+        gp = [(i + 1) * ga[i + 1] for i in range(len(ga) - 1)]
+        while gp and gp[-1] == 0:
+            gp.pop()
+        if len(gp) >= 2:
+            coeffs = [_mpf(x) for x in reversed(gp)]
+            try:
+                roots = mpmath.polyroots(coeffs, maxsteps=200, extraprec=DPS)
+            except mpmath.libmp.NoConvergence:
+                roots = mpmath.polyroots(coeffs, maxsteps=4000, extraprec=20 * DPS)
+            for z in roots:
+                z = mpmath.mpc(z)
+                if abs(z.imag) <= mpmath.mpf(10) ** (-DPS // 2) * (1 + abs(z.real)):
+                    cands.append(min(max(z.real, mpmath.mpf(0)), h))
+        gm = [_mpf(x) for x in reversed(ga)]
+        best, bt = None, None
+        for t in cands:
+            v = mpmath.polyval(gm, t)
+            if best is None or v < best or (v == best and t < bt):
+                best, bt = v, t
+        return best, bt
+
+
+def exact_clearance(coef_a, dur_a, coef_b, dur_b, candidates=None):
+    """coef [M, 4, nc], dur [M] of two drones -> (D, t, window) as mpf: the infimum of |p_a - p_b| over [0, window],
+    window = min of the two totals, and a time at which it is attained.  `candidates`: the start times (floats) of the
+    intervals that can hold the infimum (default: all) -- candidate_intervals tells them from the fp64 bounds."""
+    ka, kb = knots(dur_a), knots(dur_b)
+    W = min(ka[-1], kb[-1])
+    cuts = sorted({Fraction(0)} | {Fraction(x) for x in ka + kb if x <= W})
+    assert cuts[-1] == Fraction(W)
+    starts_a, starts_b = [0.0] + ka[:-1], [0.0] + kb[:-1]
+    best, bt = None, None
+    with mpmath.workdps(DPS):
+        for t0, t1 in zip(cuts[:-1], cuts[1:]):
+            if candidates is not None and float(t0) not in candidates:
+                continue
+            ia = next(i for i, x in enumerate(ka) if t1 <= Fraction(x))
+            ib = next(i for i, x in enumerate(kb) if t1 <= Fraction(x))
+            g = [Fraction(0)]
+            for ax in range(3):
+                pa = _shift([Fraction(float(x)) for x in coef_a[ia, ax]], t0 - Fraction(starts_a[ia]))
+                pb = _shift([Fraction(float(x)) for x in coef_b[ib, ax]], t0 - Fraction(starts_b[ib]))
+                d = [x - y for x, y in zip(pa, pb)]
+                sq = [Fraction(0)] * (2 * len(d) - 1)
+                for i, x in enumerate(d):
+                    if x:
+                        for j, y in enumerate(d):
+                            sq[i + j] += x * y
+                g = [(g[i] if i < len(g) else 0) + sq[i] for i in range(len(sq))]
+            v, tau = exact_interval_min(g, t0, t1)
+            if best is None or v < best:
+                best, bt = v, _mpf(t0) + tau
+        return mpmath.sqrt(max(best, mpmath.mpf(0))), bt, mpmath.mpf(W)
+
+
+def exact_distance_at(coef_a, dur_a, coef_b, dur_b, t):
+    """|p_a(t) - p_b(t)| as mpf at an absolute time t (a float or an mpf) inside the window."""
+    with mpmath.workdps(DPS):
+        t = mpmath.mpf(t)
+        s = mpmath.mpf(0)
+        pos = []
+        for coef, dur in ((coef_a, dur_a), (coef_b, dur_b)):
+            k = knots(dur)
+            i = next((i for i, x in enumerate(k) if t <= x), len(k) - 1)
+            tl = t - ([0.0] + k)[i]
+            pos.append([mpmath.polyval([mpmath.mpf(float(x)) for x in coef[i, ax][::-1]], tl) for ax in range(3)])
+        for x, y in zip(*pos):
+            s += (x - y) ** 2
+        return mpmath.sqrt(s)
+
+
+def contract_violations(min_dist, lower, D, closed=True):
+    """The inequalities of include/msnap.h that (min_dist, lower) break against the exact D (an mpf): a list of text."""
+    D = float(D)
+    bad = []
+    if not lower <= D * (1 + REL_ROUND) + ABS_ROUND:
+        bad.append(f"lower {lower!r} above D {D!r}")
+    if not D <= min_dist * (1 + REL_ROUND) + ABS_ROUND:
+        bad.append(f"min_dist {min_dist!r} below D {D!r}")
+    if closed and not lower >= min_dist * (1 - REL_CLOSE) - ABS_CLOSE - ABS_ROUND:
+        bad.append(f"lower {lower!r} not within the closed-walk bound of min_dist {min_dist!r}")
+    return bad
+
+
+# ------------------------------------------------------------------------------------------------ fp64 restatement
+def _bernstein_weights(n):
+    w = np.zeros((n + 1, n + 1))
+    for i in range(n + 1):
+        for k in range(i + 1):
+            w[i, k] = comb(i, k) / comb(n, k)
+    return w
+
+
+def _taylor(c, a):
+    """c [L, D + 1] (ascending) -> coefficients of c(x + a), a [L]; in place on a copy."""
+    c = c.copy()
+    D = c.shape[1] - 1
+    for k in range(D):
+        for j in range(D - 1, k - 1, -1):
+            c[:, j] = a * c[:, j + 1] + c[:, j]
+    return c
+
+
+def _positions(coef, dur, d, t):
+    """msnap_eval_flat's lookup and Horner: positions [P, 3] of drones d [P] at absolute times t [P]."""
+    K = np.add.accumulate(dur[d], axis=1)
+    seg = np.minimum((t[:, None] > K).sum(axis=1), dur.shape[1] - 1)
+    off = np.concatenate([np.zeros((len(d), 1)), K], axis=1)[np.arange(len(d)), seg]
+    tl = t - off
+    c = coef[d, seg, :3, :]                       # [P, 3, nc]
+    v = np.zeros((len(d), 3))
+    for j in range(c.shape[2] - 1, -1, -1):
+        v = v * tl[:, None] + c[:, :, j]
+    return v
+
+
+def fp64_clearance(coef, dur, pairs, stats=None):
+    """coef [N, M, 4, nc], dur [N, M], pairs [P, 2] (valid, finite) -> (min_dist [P], t_min [P], lower [P]) by the
+    kernel's method in NumPy fp64.  `stats` (a dict) receives the nodes per live lane ("nodes") and the lanes that met
+    the depth cap or the node guard ("capped")."""
+    coef = np.asarray(coef, dtype=np.float64)
+    dur = np.asarray(dur, dtype=np.float64)
+    pairs = np.asarray(pairs, dtype=np.int64)
+    P, M, nc = len(pairs), dur.shape[1], coef.shape[3]
+    D, n = nc - 1, 2 * (nc - 1)
+    Wt = _bernstein_weights(n)
+    a_i, b_i = pairs[:, 0], pairs[:, 1]
+    KA, KB = np.add.accumulate(dur[a_i], axis=1), np.add.accumulate(dur[b_i], axis=1)
+    Wend = np.minimum(KA[:, -1], KB[:, -1])
+    ends = np.concatenate([KA[:, :M - 1], KB[:, :M - 1], Wend[:, None]], axis=1)          # [P, 2M - 1]
+    ends = np.sort(np.minimum(ends, Wend[:, None]), axis=1)
+    starts = np.concatenate([np.zeros((P, 1)), ends[:, :-1]], axis=1)
+    h_all = ends - starts
+    live = h_all > 0
+    pi, si = np.nonzero(live)
+    E, t0, h = ends[pi, si], starts[pi, si], h_all[pi, si]
+    L = len(pi)
+    e = np.zeros((L, 3, D + 1))
+    for drone, K, sign in ((a_i[pi], KA[pi], 1.0), (b_i[pi], KB[pi], -1.0)):
+        seg = np.minimum((E[:, None] > K).sum(axis=1), M - 1)
+        off = np.concatenate([np.zeros((L, 1)), K], axis=1)[np.arange(L), seg]
+        for ax in range(3):
+            e[:, ax, :] += sign * _taylor(coef[drone, seg, ax, :], t0 - off)
+    e *= (h[:, None] ** np.arange(D + 1))[:, None, :]
+
+    best = np.full(L, np.inf)
+    best_u = np.zeros(L)
+    low = np.full(L, np.inf)
+    root = np.full(L, np.inf)
+    idx = np.zeros(L, dtype=np.uint64)
+    lvl = np.zeros(L, dtype=np.int64)
+    nodes = np.zeros(L, dtype=np.int64)
+    capped = np.zeros(L, dtype=bool)
+    act = np.arange(L)
+    while len(act):
+        hh = np.ldexp(1.0, -lvl[act])
+        a = idx[act].astype(np.float64) * hh
+        G = np.zeros((len(act), n + 1))
+        g0 = np.zeros(len(act))
+        gm = np.zeros(len(act))
+        g1 = np.zeros(len(act))
+        scale = hh[:, None] ** np.arange(D + 1)
+        for s in range(3):
+            f = _taylor(e[act, s, :], a) * scale
+            for i in range(D + 1):
+                G[:, i:i + D + 1] += f[:, i:i + 1] * f
+            vm = np.zeros(len(act))
+            for j in range(D, -1, -1):
+                vm = vm * 0.5 + f[:, j]
+            v1 = f[:, ::-1].cumsum(axis=1)[:, -1]
+            g0 += f[:, 0] ** 2
+            gm += vm ** 2
+            g1 += v1 ** 2
+        bound = (G @ Wt.T).min(axis=1)
+        nb, nu = best[act].copy(), best_u[act].copy()
+        for gv, uv in ((g0, a), (gm, a + 0.5 * hh), (g1, a + hh)):
+            take = (gv < nb) | ((gv == nb) & (uv < nu))
+            nb = np.where(take, gv, nb)
+            nu = np.where(take, uv, nu)
+        best[act], best_u[act] = nb, nu
+        at_cap = lvl[act] >= MAX_DEPTH
+        split = (bound < nb - PRUNE_REL * nb - PRUNE_ABS) & ~at_cap
+        ix = idx[act]
+        up = np.zeros(len(act), dtype=np.int64)
+        tmp = ix.copy()
+        while True:                                   # trailing ones of idx
+            m = (tmp & np.uint64(1)) == 1
+            if not m.any():
+                break
+            up += m
+            tmp = np.where(m, tmp >> np.uint64(1), tmp)
+        first = nodes[act] == 0
+        root[act] = np.where(first, bound, root[act])
+        nodes[act] += 1
+        finished = ~split & (up == lvl[act])
+        guard = ~finished & (nodes[act] >= MAX_NODES)
+        lw = np.where(split, low[act], np.minimum(low[act], bound))
+        low[act] = np.where(guard, np.minimum(lw, root[act]), lw)
+        capped[act] |= guard | (~split & at_cap & (bound < nb - PRUNE_REL * nb - PRUNE_ABS))
+        idx[act] = np.where(split, ix << np.uint64(1), (ix >> up.astype(np.uint64)) + np.uint64(1))
+        lvl[act] = np.where(split, lvl[act] + 1, lvl[act] - up)
+        act = act[~(finished | guard)]
+
+    tm = np.minimum(h * best_u + t0, E)
+    g_pair = np.full(P, np.inf)
+    np.minimum.at(g_pair, pi, best)
+    t_pair = np.full(P, np.inf)
+    winners = best == g_pair[pi]
+    np.minimum.at(t_pair, pi[winners], tm[winners])
+    low_pair = np.full(P, np.inf)
+    np.minimum.at(low_pair, pi, low)
+    diff = _positions(coef, dur, a_i, t_pair) - _positions(coef, dur, b_i, t_pair)
+    md = np.sqrt(diff[:, 2] ** 2 + (diff[:, 1] ** 2 + diff[:, 0] ** 2))
+    lower = np.minimum(np.sqrt(np.maximum(low_pair, 0.0)), md)
+    if stats is not None:
+        stats["lane_pair"], stats["lane_start"], stats["lane_low"], stats["pair_best"] = pi, t0, low, g_pair
+        stats["nodes"] = nodes
+        stats["capped"] = capped
+        stats["lanes"] = L
+    return md, t_pair, lower
+
+
+def candidate_intervals(coef, dur, pairs, rel=1e-6):
+    """Per pair, the start times of the intervals whose fp64 lower bound of g is within `rel` (on the distance) of the
+    pair's smallest attained value: the only ones that can hold the infimum (exact_clearance's `candidates`)."""
+    st = {}
+    fp64_clearance(coef, dur, pairs, stats=st)
+    out = [set() for _ in range(len(pairs))]
+    keep = st["lane_low"] <= st["pair_best"][st["lane_pair"]] * (1 + rel) ** 2 + 1e-12
+    for p, t0 in zip(st["lane_pair"][keep], st["lane_start"][keep]):
+        out[int(p)].add(float(t0))
+    return out

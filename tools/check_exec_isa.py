@@ -18,7 +18,7 @@ the latch of a loop that runs until no lane is left (`s_cbranch_execnz` backward
 it is written again, so any vector instruction there is reported -- it can only be one the compiler misplaced.
 
     python tools/check_exec_isa.py [object files ...]        (default: csrc/msnap_solve.o msnap_aux.o msnap_sample.o msnap_collide.o msnap_grid.o
-                                                              msnap_limits.o msnap_timeopt.o)
+                                                              msnap_limits.o msnap_timeopt.o msnap_clearance.o)
     python tools/check_exec_isa.py --latches [object files ...]      the kernels that still hold such a loop, with their latch counts
 """
 from __future__ import annotations
@@ -46,7 +46,7 @@ OTHER_EXEC = re.compile(r"^s_\w+ exec\b|^v_cmpx")               # any other writ
 
 
 DEFAULT_OBJS = [os.path.join(CSRC, f) for f in ("msnap_solve.o", "msnap_aux.o", "msnap_sample.o", "msnap_collide.o",
-                                                "msnap_grid.o", "msnap_limits.o", "msnap_timeopt.o")]
+                                                "msnap_grid.o", "msnap_limits.o", "msnap_timeopt.o", "msnap_clearance.o")]
 
 
 def disassemble(obj):
