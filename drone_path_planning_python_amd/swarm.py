@@ -566,7 +566,11 @@ def sample_gap(dt: float, n_samples: int, totals) -> float:
 
 @dataclass
 class ClearanceResult:
-    certified_lower: object   # [N] a proven lower bound of the drone's distance to every other drone while both fly
+    # [N] a proven lower bound of the drone's distance to every other drone while both fly, up to the rounding allowance
+    # of msnap_pair_clearance (include/msnap.h): certified_lower <= D (1 + 1e-13) + 1e-13 + C_ROUND 2^-52 R for the
+    # exact infimum D of each of the drone's pairs, R the largest sum_k |c_k| T_i^k over x, y, z, the two drones and
+    # the segments that meet the pair's window -- an ulp of the coordinates, which far from the origin exceeds 1e-13 m
+    certified_lower: object
     hit: object               # [N] bool: some pair of the drone ATTAINS a distance below 2 radius (definite)
     undecided: object         # [N] bool: no hit, but a pair with lower < 2 radius <= min_dist (a search that met its caps)
     cleared_by_sampling: object   # [N] bool: the sampled pass and the speed peaks alone prove >= 2 radius

@@ -321,11 +321,19 @@ int msnap_retime_to_limits_device(msnap_ctx *ctx, int n_drones, int n_seg, const
  *                       the two drones at t_min gives positions whose distance is min_dist;
  *   lower    [n_pairs]  a proven lower bound:  lower <= D <= min_dist, each up to rounding (ten times the worst
  *                       deviation measured against an exact reference):
- *                         lower <= D (1 + 1e-13) + 1e-13   and   D <= min_dist (1 + 1e-13) + 1e-13
+ *                         lower <= D (1 + 1e-13) + r   and   D <= min_dist (1 + 1e-13) + r,
+ *                         r = 1e-13 + C_ROUND * 2^-52 * R   [m],   C_ROUND = 8
+ *                       R is the size of what the pair's positions are computed from: the largest value of
+ *                       sum_k |c_k| T_i^k over x, y, z, both drones and every segment i that starts before the window
+ *                       ends (c_k the segment's coefficients, T_i its duration).  The positions of the two drones are
+ *                       rounded to an ulp of the coordinate, not of the distance: two drones 1 m apart at 5000 m from
+ *                       the origin carry 1e-12 m of it, and a rest-to-rest segment of 2000 m has R = 4e5 m whatever
+ *                       its duration.  A caller computes R from coef and dur alone.
  *                       When the search closes (always, short of its caps: 40 bisections of an interval between knots,
- *                       4096 nodes per interval):  lower >= min_dist (1 - 1e-9) - 1e-9  -- the absolute term A = 1e-9 m
- *                       is what lets a crossing (D = 0) close.  A pair that meets a cap still gets a valid lower, only
- *                       further from min_dist; no status is raised for it.
+ *                       4096 nodes per interval):  lower >= min_dist (1 - 1e-9) - 1e-9 - r  -- the absolute term
+ *                       A = 1e-9 m is what lets a crossing (D = 0) close.  A pair that meets a cap still gets a valid
+ *                       lower, only further from min_dist; no status is raised for it (two drones that cross at
+ *                       560 m/s on one 11 s segment of order 9 meet the depth cap).
  *   status   [n_pairs]  msnap_status: MSNAP_ST_PAIR for an index outside [0, n_drones) or a == b (nothing is read for
  *                       such a pair), else MSNAP_ST_NONFINITE for a NaN / Inf coefficient or duration of either drone,
  *                       else MSNAP_ST_TIMES for a duration <= 0.  min_dist, t_min and lower of a failed pair are NaN.

@@ -1,0 +1,392 @@
+"""Seeded edge inputs of the pairwise clearance, shared by tests/test_clearance_edges_gpu.py, the CPU twins in
+tests/test_clearance_cpu.py and tools/clearance_rounding.py.  Every builder takes `solve(wp, t, nc) -> (coef, dur)` (the
+GPU solve or the C oracle) where it needs one and returns fp64 arrays coef [N, M, 4, nc], dur [N, M].  The check_*
+functions are the bodies of the tests: they take `ctx`, a Context of the right order or clearance_exact.RestatedContext."""
+from __future__ import annotations
+
+import itertools
+
+import numpy as np
+
+import clearance_exact as CE
+from drone_path_planning_python_amd.synthetic import swarm
+
+QUANTUM = 2.0 ** -35      # c0 on this grid: moving it by an integer below 2^17 m is exact in fp64
+SCALES = [(1e-3, 1.0), (1.0, 1e6), (50.0, 1e-4), (1e-2, 1e3)]      # tests/test_solve_gpu.py::test_extreme_scales
+# far-from-origin offsets: +-1000 m and +-5000 m, on one axis only and on all three
+OFFSETS = {
+    "x+1000": (1000.0, 0.0, 0.0), "y-1000": (0.0, -1000.0, 0.0), "all+1000": (1000.0,) * 3, "all-1000": (-1000.0,) * 3,
+    "z+5000": (0.0, 0.0, 5000.0), "x-5000": (-5000.0, 0.0, 0.0), "all+5000": (5000.0,) * 3, "all-5000": (-5000.0,) * 3,
+    "all+1e5": (1e5,) * 3,        # beyond the issue's list: the offset at which the allowance without R fails
+}
+
+
+def all_pairs(n):
+    return np.array(list(itertools.combinations(range(n), 2)), dtype=np.int32)
+
+
+def quantised(coef):
+    """coef with the x, y, z constant terms rounded to QUANTUM, so that `moved` is exact."""
+    c = np.array(coef, dtype=np.float64)
+    c[:, :, :3, 0] = np.round(c[:, :, :3, 0] / QUANTUM) * QUANTUM
+    return c
+
+
+def moved(coef, offset, drones=None):
+    """coef with `offset` (x, y, z) added to the constant terms of `drones` (default: all).  Exact on `quantised`
+    coefficients: the moved swarm is the same set of real polynomials, translated."""
+    c = np.array(coef, dtype=np.float64)
+    sel = slice(None) if drones is None else drones
+    new = c[sel, :, :3, 0] + np.asarray(offset, dtype=np.float64)
+    assert np.array_equal(new - np.asarray(offset, dtype=np.float64), c[sel, :, :3, 0])
+    c[sel, :, :3, 0] = new
+    return c
+
+
+def far_base(solve, nc, n=7):
+    """The swarm the far cases move: synthetic.swarm(7011, n, 4) solved once, constant terms quantised."""
+    wp, t = swarm(7011, n, 4)
+    coef, dur = solve(wp, t, nc)
+    return quantised(coef), dur
+
+
+def with_loner(coef, k=5):
+    """The swarm at +5000 m with drone k at -8000 m on all axes (the loner of tests/test_formation_full.py's far swarm)."""
+    c = moved(coef, (5000.0,) * 3)
+    others = [i for i in range(c.shape[0]) if i != k]
+    c[k] = moved(coef, (-8000.0,) * 3)[k]
+    return c, np.array([(i, k) for i in others], dtype=np.int32)
+
+
+def scaled(solve, nc, scale_t, scale_w, n=6, m=10):
+    wp, t = swarm(600, n, m)
+    return solve(wp * scale_w, t * scale_t, nc)
+
+
+def crossing(solve, nc, half=1000.0, total=1.1):
+    """Two rest-to-rest drones crossing at right angles, +-half m in `total` s: both at the origin at total / 2."""
+    wp = np.zeros((2, 2, 4))
+    wp[0, :, 0] = [-half, half]
+    wp[1, :, 1] = [-half, half]
+    return solve(wp, np.array([0.0, total]), nc)
+
+
+def long_paths(solve, nc, m, n=6, cfg=7349, unequal=False):
+    wp, t = swarm(cfg + m, n, m)
+    if unequal:
+        t = t.copy()
+        t[0] *= 0.63
+    return solve(wp, t, nc)
+
+
+def stacked(solve, nc, m_total, n=3, piece=64):
+    """n drones of m_total segments each, made of solved `piece`-segment paths laid end to end (the path jumps at every
+    `piece`-th knot: the clearance takes any piecewise polynomial)."""
+    assert m_total % piece == 0
+    k = m_total // piece
+    wp, t = swarm(7400 + m_total, n * k, piece)
+    coef, dur = solve(wp, t, nc)
+    return coef.reshape(n, m_total, 4, nc).copy(), dur.reshape(n, m_total).copy()
+
+
+def _knots(d):
+    out, acc = [], 0.0
+    for T in d:
+        acc = acc + float(T)
+        out.append(acc)
+    return np.array(out)
+
+
+def near_knots(solve, nc, kind, m=5):
+    """Drones 0 and 1 on one time grid, then drone 1's durations changed so that its knots (the running sums) sit
+    next to drone 0's:  "ulp" -- interior knots within a few ulp and not all equal;  "rel" -- moved by a relative
+    1e-12;  "short" -- the same interior knots, the total one ulp shorter (the window ends one ulp before a's knot)."""
+    wp, t = swarm(7520, 2, m)
+    t = np.broadcast_to(t[0], t.shape).copy()
+    coef, dur = solve(wp, t, nc)
+    dur = dur.copy()
+    ka = _knots(dur[0])
+    if kind == "ulp":
+        dur[1, 0] = np.nextafter(dur[1, 0], np.inf)
+        kb = _knots(dur[1])
+        assert (kb[:-1] != ka[:-1]).any() and (np.abs(kb - ka) <= 4 * np.spacing(ka)).all()
+    elif kind == "rel":
+        dur[1] = dur[1] * (1.0 + 1e-12)
+        kb = _knots(dur[1])
+        assert (kb != ka).all() and (np.abs(kb / ka - 1.0) <= 2e-12).all()
+    elif kind == "short":
+        want = np.nextafter(ka[-1], 0.0)
+        for _ in range(64):
+            if _knots(dur[1])[-1] <= want:
+                break
+            dur[1, -1] = np.nextafter(dur[1, -1], 0.0)
+        kb = _knots(dur[1])
+        assert kb[-1] == want and np.array_equal(kb[:-1], ka[:-1])
+    else:
+        raise ValueError(kind)
+    return coef, dur
+
+
+def hand(polys, durs, nc):
+    """coef / dur from per-drone lists of segments, each segment the (x, y, z) ascending coefficient lists."""
+    n, m = len(polys), len(polys[0])
+    coef = np.zeros((n, m, 4, nc))
+    for d, segs in enumerate(polys):
+        for s, axes in enumerate(segs):
+            for ax, c in enumerate(axes):
+                coef[d, s, ax, :len(c)] = c
+    return coef, np.array(durs, dtype=np.float64)
+
+
+def hover(point, m, nc, T=1.0):
+    """A drone that stays at `point` for m segments: coefficients set by hand (c0 = point, the rest zero)."""
+    return hand([[[[point[0]], [point[1]], [point[2]]]] * m], [[T] * m], nc)
+
+
+def fast_crossing(solve, nc, dz=0.0):
+    """The input of the CPU search for the walk's caps: two rest-to-rest drones on one 11 s segment
+    from -900 m to +1100 m, at right angles, `dz` apart in height -- a relative speed of 560 m/s through a point that
+    is no dyadic fraction of the interval.  At order 9 the restatement meets the depth cap of 40 bisections for
+    dz <= 1e-5 m; at order 7 the walk closes at depth 40 (81 nodes, the most the search found)."""
+    wp = np.zeros((2, 2, 4))
+    wp[0, :, 0] = [-900.0, 1100.0]
+    wp[1, :, 1] = [-900.0, 1100.0]
+    wp[1, :, 2] = dz
+    return solve(wp, np.array([0.0, 11.0]), nc)
+
+
+def ends_case(nc):
+    """Hand-made drones of two segments (durations 1 + 1) against a hover at the origin (drone 0):
+    1 leaves:        x = 1 + t, then 2 + t                    closest at t = 0
+    2 arrives:       x = 3 - t, then 2 - t / 2                closest at the window's end, t = 2
+    3 out and back:  x = 1 + t, then 2 - t                    g(0) = g(2) = 1 exactly: the tie goes to t = 0
+    4 hump:          one polynomial 1 + t (2 - t) cut in two  the same tie with curvature
+    5 hovers at the origin for 0.5 + 0.75 s: against drone 2 the window ends at 1.25 s, inside 2's second segment"""
+    zero = [[0.0], [0.0], [0.0]]
+    polys = [
+        [zero] * 2,
+        [[[1.0, 1.0], [0.0], [0.0]], [[2.0, 1.0], [0.0], [0.0]]],
+        [[[3.0, -1.0], [0.0], [0.0]], [[2.0, -0.5], [0.0], [0.0]]],
+        [[[1.0, 1.0], [0.0], [0.0]], [[2.0, -1.0], [0.0], [0.0]]],
+        [[[1.0, 2.0, -1.0], [0.0], [0.0]], [[2.0, 0.0, -1.0], [0.0], [0.0]]],
+        [zero] * 2,
+    ]
+    return hand(polys, [[1.0, 1.0]] * 5 + [[0.5, 0.75]], nc)
+
+
+# ------------------------------------------------------------------------------------------------ test bodies
+def exact_of(coef, dur, pairs):
+    cands = CE.candidate_intervals(coef, dur, pairs)
+    out = []
+    for k, (a, b) in enumerate(pairs):
+        D, _, W = CE.exact_clearance(coef[a], dur[a], coef[b], dur[b], cands[k])
+        out.append((D, W))
+    return out
+
+
+def run(ctx, coef, dur, pairs=((0, 1),)):
+    md, tm, lower, status = ctx.pair_clearance(coef, dur, np.array(pairs, dtype=np.int32))
+    assert (status == 0).all()
+    return md, tm, lower
+
+
+def far_origin(ctx, solve, nc, n_pairs=None):
+    """The base swarm (constant terms on a grid, so that moving them is exact), its exact D -- which hold for every
+    translate -- and the outputs at the origin."""
+    coef, dur = far_base(solve, nc)
+    pairs = all_pairs(coef.shape[0])[:n_pairs]
+    exact = exact_of(coef, dur, pairs)
+    md, tm, lower, _ = CE.check_contract(ctx, coef, dur, pairs, with_R=True, exact=exact)
+    return coef, dur, pairs, exact, md, lower, tm
+
+
+def check_far(ctx, origin, name):
+    coef, dur, pairs, exact, md0, lower0, tm0 = origin
+    c = moved(coef, OFFSETS[name])
+    md, tm, lower, _ = CE.check_contract(ctx, c, dur, pairs, with_R=True, exact=exact)
+    # translation invariance: the same real polynomials, so the two answers bracket one D.  Where both walks stop at
+    # the same time the two min_dist are one exact value rounded twice: they agree within the rounding allowance.
+    # Elsewhere each is an attained value somewhere in [D - r, D (1 + 1e-9) + A + r] -- rounding moves the prune
+    # decisions, so the walks may stop at different nodes -- and the closing slack is all that ties them; `lower`
+    # always carries that slack.
+    for k, (a, b) in enumerate(pairs):
+        r = CE.round_terms(CE.pair_R(c[a], dur[a], c[b], dur[b])) + CE.round_terms(CE.pair_R(coef[a], dur[a], coef[b], dur[b]))
+        if tm[k] == tm0[k]:
+            assert abs(md[k] - md0[k]) <= 2 * CE.REL_ROUND * md0[k] + r, (a, b, md[k], md0[k])
+        assert abs(md[k] - md0[k]) <= CE.REL_CLOSE * md0[k] + CE.ABS_CLOSE + r, (a, b, md[k], md0[k])
+        assert abs(lower[k] - lower0[k]) <= CE.REL_CLOSE * md0[k] + CE.ABS_CLOSE + r, (a, b, lower[k], lower0[k])
+        assert lower[k] <= md0[k] * (1 + CE.REL_ROUND) + r and lower0[k] <= md[k] * (1 + CE.REL_ROUND) + r
+
+
+def check_loner(ctx, origin, n_pairs=None):
+    c, pairs = with_loner(origin[0])
+    md, _, _, _ = CE.check_contract(ctx, c, origin[1], pairs[:n_pairs], with_R=True)
+    assert (md > 13000.0 * np.sqrt(3.0) - 20.0).all()
+
+
+def check_crossing(ctx, solve, nc, total):
+    """+-1000 m at right angles: exact D = 0 at total / 2, coefficient sums of 4e5 m (order 7) and 3e6 m (order 9)."""
+    coef, dur = crossing(solve, nc, 1000.0, total)
+    md, tm, lower, _ = CE.check_contract(ctx, coef, dur, [(0, 1)], with_R=True, crossing=True)
+    assert abs(tm[0] - total / 2) <= 1e-9 * total
+
+
+def check_knots(ctx, solve, nc, kind):
+    coef, dur = near_knots(solve, nc, kind)
+    md, tm, lower, _ = CE.check_contract(ctx, coef, dur, [(0, 1), (1, 0)], with_R=True)
+    assert md[0] == md[1] and tm[0] == tm[1] and lower[0] == lower[1]
+
+
+def check_copies(ctx, solve, nc):
+    coef, dur = far_base(solve, nc, n=1)
+    c = np.concatenate([coef, coef, moved(coef, (0.5, 0.0, 0.0))])
+    d = np.concatenate([dur] * 3)
+    md, tm, lower = run(ctx, c, d, [(0, 1), (0, 2), (2, 1)])
+    assert md[0] == 0.0 and tm[0] == 0.0 and lower[0] == 0.0
+    assert md[1] == 0.5 and tm[1] == 0.0 and md[2] == 0.5 and tm[2] == 0.0
+    assert 0.5 * (1 - CE.REL_CLOSE) - CE.ABS_CLOSE <= lower[1] <= 0.5 and lower[2] == lower[1]
+    # the same with constant terms that are not on a grid: x + 0.5 rounds, the difference is what fp64 makes of it
+    raw, rd = solve(*swarm(7011, 1, 4), nc)
+    c = np.concatenate([raw, raw])
+    c[1, :, 0, 0] += 0.5
+    md, tm, lower = run(ctx, c, np.concatenate([rd, rd]))
+    assert md[0] == abs(c[1, 0, 0, 0] - c[0, 0, 0, 0]) and tm[0] == 0.0
+
+
+def check_hovering(ctx, nc, m):
+    ca, da = hover((1.0, 2.0, 3.0), m, nc)
+    cb, db = hover((4.0, 6.0, 3.0), m, nc, T=0.75)
+    md, tm, lower = run(ctx, np.concatenate([ca, cb]), np.concatenate([da, db]))
+    assert md[0] == 5.0 and tm[0] == 0.0 and lower[0] == 5.0
+    # far from the origin and on top of each other
+    ca, _ = hover((5000.0, -8000.0, 1e5), m, nc)
+    md, tm, lower = run(ctx, np.concatenate([ca, ca]), np.concatenate([da, db]))
+    assert md[0] == 0.0 and tm[0] == 0.0 and lower[0] == 0.0
+
+
+def check_hover_against_moving(ctx, solve, nc):
+    """The moving drone leaves (0, 0, 0) along +x, rest to rest over three segments; the hovering one waits at
+    (-2, 0, 0) and, in a second pair, at (3, 4, 0) beside the path."""
+    wp = np.zeros((1, 4, 4))
+    wp[0, :, 0] = [0.0, 1.0, 2.5, 6.0]
+    coef, dur = solve(wp, np.array([[0.0, 1.0, 2.0, 3.5]]), nc)
+    coef = coef.copy()
+    coef[0, 0, :3, 0] = 0.0                                   # the start exactly at the origin
+    h = [hover(p, 3, nc)[0] for p in ((-2.0, 0.0, 0.0), (3.0, 4.0, 0.0))]
+    c = np.concatenate([coef] + h)
+    d = np.concatenate([dur, np.ones((2, 3))])
+    md, tm, lower = run(ctx, c, d, [(0, 1), (1, 0)])
+    assert md[0] == 2.0 and tm[0] == 0.0 and md[1] == 2.0 and tm[1] == 0.0 and lower[0] == lower[1]
+    md, tm, lower, _ = CE.check_contract(ctx, c, d, [(0, 1), (0, 2)], with_R=True)
+    assert 4.0 * (1 - 1e-9) <= md[1] <= 4.0 * (1 + 1e-9) and 1.0 < tm[1] < 3.0
+
+
+def check_ends_by_hand(ctx, nc):
+    coef, dur = ends_case(nc)
+    pairs = [(0, 1), (0, 2), (0, 3), (0, 4), (5, 2), (2, 5)]
+    md, tm, lower = run(ctx, coef, dur, pairs)
+    print(md, tm, lower)
+    assert md.tolist() == [1.0, 1.5, 1.0, 1.0, 1.875, 1.875]
+    assert tm.tolist() == [0.0, 2.0, 0.0, 0.0, 1.25, 1.25]
+    assert (lower <= md).all() and (lower >= md * (1 - CE.REL_CLOSE) - CE.ABS_CLOSE).all()
+    CE.check_contract(ctx, coef, dur, pairs, with_R=True)
+
+
+def check_ends_solved(ctx, solve, nc):
+    """Two drones flying apart from rest (closest at t = 0) and two flying towards their last waypoints (closest at
+    the window's end, which is no binary fraction here: t_min has to come out as the window itself)."""
+    wp = np.zeros((4, 4, 4))
+    wp[0, :, 0] = [-0.3, -1.1, -2.7, -4.1]
+    wp[1, :, 0] = [0.3, 1.3, 2.2, 4.9]
+    wp[2, :, 1] = [7.3, 4.1, 2.2, 0.4]
+    wp[3, :, 1] = [-6.9, -3.7, -1.9, -0.3]
+    wp[2:, :, 2] = 3.0
+    t = np.array([[0.0, 0.7, 1.9, 3.3], [0.0, 1.1, 2.3, 3.1], [0.0, 0.9, 2.1, 3.7], [0.0, 1.3, 2.2, 3.4]])
+    coef, dur = solve(wp, t, nc)
+    md, tm, lower, _ = CE.check_contract(ctx, coef, dur, [(0, 1), (2, 3), (3, 2)], with_R=True)
+    window = float(min(CE.knots(dur[2])[-1], CE.knots(dur[3])[-1]))
+    assert tm.tolist() == [0.0, window, window]
+
+
+def check_caps(ctx, solve, nc, dz):
+    """lower <= D whether the walk closed or not; no status raised (check_contract asserts both).  Returns the
+    restatement's capped flag."""
+    coef, dur = fast_crossing(solve, nc, dz)
+    st = {}
+    CE.fp64_clearance(coef, dur, np.array([[0, 1]]), stats=st)
+    print("restatement: nodes per lane", st["nodes"].tolist(), "capped", st["capped"].tolist())
+    md, tm, lower, _ = CE.check_contract(ctx, coef, dur, [(0, 1)], with_R=True, closed=False, crossing=True)
+    assert lower[0] <= md[0]
+    return bool(st["capped"].any()), int(st["nodes"].max())
+
+
+# ------------------------------------------------------------------------------------------------ certify_clearance
+AWKWARD_RADIUS = 0.125          # 2 radius = 0.25 m is a binary fraction: "touching" can be exact
+AWKWARD_DT = 0.1
+AWKWARD_SAMPLES = 20            # default_sample_count(2.0, 0.1)
+AWKWARD_HIT = [0, 1, 2, 3]
+
+
+def awkward_swarm(solve, nc=8, offset=5000.0):
+    """12 drones of two segments, the whole swarm at +offset on x, y, z:
+    0, 1    cross at right angles at t = 0.55 s, between the samples at 0.5 and 0.6 s (2 m in 1.1 s each)
+    2, 3    the same 10 m away, crossing at t = 0.65 s (1.3 s each)
+    4, 5    hover 0.25 m = 2 radius apart, coefficients set by hand: they touch exactly, at every sample, and do not hit
+    6       lands after 0.8 s; 7 reaches 6's landing point at t = 2 s, after the pair's window has closed
+    8..11   fly about 20 m away, metres apart.
+    Returns (coef [12, 2, 4, nc], dur [12, 2])."""
+    wp = np.zeros((12, 3, 4))
+    t = np.tile(np.array([0.0, 1.0, 2.0]), (12, 1))
+    wp[0, :, 0] = [-1.0, 0.0, 1.0]
+    wp[1, :, 1] = [-1.0, 0.0, 1.0]
+    t[0:2] = [0.0, 0.55, 1.1]
+    wp[2, :, 0] = [9.0, 10.0, 11.0]
+    wp[3, :, 0] = 10.0
+    wp[3, :, 1] = [-1.0, 0.0, 1.0]
+    t[2:4] = [0.0, 0.65, 1.3]
+    wp[4, :, :3] = [0.0, 10.0, 0.0]
+    wp[5, :, :3] = [0.25, 10.0, 0.0]
+    wp[6, :, 0] = [-0.5, 0.0, 0.5]
+    wp[6, :, 1] = -10.0
+    t[6] = [0.0, 0.4, 0.8]
+    wp[7, :, 0] = [3.0, 1.5, 0.5]
+    wp[7, :, 1] = -10.0
+    rng = np.random.default_rng(7712)
+    wp[8:, :, :3] = np.array([[20.0, 0.0, 0.0], [20.0, 5.0, 1.0], [20.0, 10.0, 0.0], [25.0, 0.0, 2.0]])[:, None, :]
+    wp[8:, :, :3] += rng.uniform(-1.0, 1.0, size=(4, 3, 3))
+    wp[..., :3] += offset
+    coef, dur = solve(wp, t, nc)
+    coef = np.array(coef)
+    for d in (4, 5):                                          # exactly constant, whatever the solve left in c1..
+        coef[d] = 0.0
+        coef[d, :, :3, 0] = wp[d, 0, :3]
+    assert coef[5, 0, 0, 0] - coef[4, 0, 0, 0] == 2 * AWKWARD_RADIUS
+    return coef, np.array(dur)
+
+
+def check_certified(res, coef, dur, radius=AWKWARD_RADIUS):
+    """ClearanceResult fields as numpy arrays in `res` (a dict) against exact_clearance on all 66 pairs."""
+    n = coef.shape[0]
+    pairs = all_pairs(n)
+    exact = exact_of(coef, dur, pairs)
+    Dmin = np.full(n, np.inf)
+    truly_hit = np.zeros(n, dtype=bool)
+    for (a, b), (D, _) in zip(pairs, exact):
+        D = float(D)
+        R = CE.pair_R(coef[a], dur[a], coef[b], dur[b])
+        for i in (a, b):
+            Dmin[i] = min(Dmin[i], D)
+            truly_hit[i] |= D < 2 * radius
+            # certified_lower is below every exact D of the drone, up to the allowance
+            assert res["certified_lower"][i] <= D * (1 + CE.REL_ROUND) + CE.round_terms(R), (i, a, b, D)
+            if res["cleared_by_sampling"][i]:
+                assert D >= 2 * radius, (i, a, b, D)
+    print("smallest exact D per drone:", Dmin.tolist())
+    print("certified_lower:", res["certified_lower"].tolist())
+    print("pairs sent to the kernel:", res["pairs"].tolist())
+    assert np.nonzero(truly_hit)[0].tolist() == AWKWARD_HIT
+    assert np.nonzero(res["hit"])[0].tolist() == AWKWARD_HIT
+    assert not res["undecided"].any()
+    assert Dmin[4] == 2 * radius and Dmin[5] == 2 * radius
+    sent = {tuple(p) for p in res["pairs"].tolist()}
+    assert {(0, 1), (2, 3), (4, 5)} <= sent

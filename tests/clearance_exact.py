@@ -19,8 +19,10 @@ DPS = 60
 # include/msnap.h, "pairwise clearance"
 REL_CLOSE = 1e-9        # lower >= min_dist (1 - REL_CLOSE) - ABS_CLOSE when the walk closes
 ABS_CLOSE = 1e-9
-REL_ROUND = 1e-13       # lower <= D (1 + REL_ROUND) + ABS_ROUND,  D <= min_dist (1 + REL_ROUND) + ABS_ROUND
+REL_ROUND = 1e-13       # lower <= D (1 + REL_ROUND) + ABS_ROUND + C_ROUND 2^-52 R, and the same for D <= min_dist ...
 ABS_ROUND = 1e-13
+C_ROUND = 8.0           # ten times the worst measured, 0.69 (tools/clearance_rounding.py), rounded up
+EPS = 2.0 ** -52
 # csrc/msnap_clearance.hip
 MAX_DEPTH = 40
 MAX_NODES = 4096
@@ -51,6 +53,42 @@ def _mpf(x):
     return mpmath.mpf(x.numerator) / x.denominator
 
 
+def _polyrem(a, b):
+    """Remainder of a by b, ascending exact coefficients, b's leading coefficient non-zero."""
+    a = list(a)
+    while len(a) >= len(b):
+        q = a[-1] / b[-1]
+        if q:
+            for i in range(len(b)):
+                a[len(a) - len(b) + i] -= q * b[i]
+        a.pop()
+        while a and a[-1] == 0:
+            a.pop()
+    return a
+
+
+def _squarefree(p):
+    """p / gcd(p, p') over the rationals: the same roots, each once (mpmath.polyroots converges slowly, or not at
+    all, on the multiple roots that rest-to-rest ends and symmetric paths give g')."""
+    d = [(i + 1) * p[i + 1] for i in range(len(p) - 1)]
+    while d and d[-1] == 0:
+        d.pop()
+    a, b = list(p), d
+    while b:
+        a, b = b, _polyrem(a, b)
+    if len(a) <= 1:
+        return list(p)
+    q, r = [Fraction(0)] * (len(p) - len(a) + 1), list(p)      # exact division p / a
+    while len(r) >= len(a):
+        c = r[-1] / a[-1]
+        q[len(r) - len(a)] = c
+        for i in range(len(a)):
+            r[len(r) - len(a) + i] -= c * a[i]
+        r.pop()
+    assert not any(r)
+    return q
+
+
 def exact_interval_min(ga, t0, t1):
     """min over tau in [0, t1 - t0] of the exact polynomial ga (ascending Fractions): (value, tau) as mpf."""
     with mpmath.workdps(DPS):
@@ -59,12 +97,15 @@ def exact_interval_min(ga, t0, t1):
         gp = [(i + 1) * ga[i + 1] for i in range(len(ga) - 1)]
         while gp and gp[-1] == 0:
             gp.pop()
+        while gp and gp[0] == 0:                          # roots at tau = 0 (a start from rest): a candidate already
+            gp.pop(0)
         if len(gp) >= 2:
             coeffs = [_mpf(x) for x in reversed(gp)]
             try:
                 roots = mpmath.polyroots(coeffs, maxsteps=200, extraprec=DPS)
-            except mpmath.libmp.NoConvergence:
-                roots = mpmath.polyroots(coeffs, maxsteps=4000, extraprec=20 * DPS)
+            except mpmath.libmp.NoConvergence:            # multiple roots: the square-free part has the same ones
+                coeffs = [_mpf(x) for x in reversed(_squarefree([Fraction(x) for x in gp]))]
+                roots = mpmath.polyroots(coeffs, maxsteps=4000, extraprec=20 * DPS) if len(coeffs) >= 2 else []
             for z in roots:
                 z = mpmath.mpc(z)
                 if abs(z.imag) <= mpmath.mpf(10) ** (-DPS // 2) * (1 + abs(z.real)):
@@ -127,17 +168,49 @@ def exact_distance_at(coef_a, dur_a, coef_b, dur_b, t):
         return mpmath.sqrt(s)
 
 
-def contract_violations(min_dist, lower, D, closed=True):
-    """The inequalities of include/msnap.h that (min_dist, lower) break against the exact D (an mpf): a list of text."""
+def pair_R(coef_a, dur_a, coef_b, dur_b):
+    """R of include/msnap.h: the largest sum_k |c_k| T_i^k over x, y, z, both drones and every segment that meets the
+    pair's window (a segment that starts before the window's end; the first one always)."""
+    ka, kb = knots(dur_a), knots(dur_b)
+    W = min(ka[-1], kb[-1])
+    R = 0.0
+    for coef, dur, k in ((coef_a, dur_a, ka), (coef_b, dur_b, kb)):
+        coef = np.asarray(coef, dtype=np.float64)
+        for i, start in enumerate([0.0] + k[:-1]):
+            if i == 0 or start < W:
+                R = max(R, float((np.abs(coef[i, :3]) * float(dur[i]) ** np.arange(coef.shape[2])).sum(axis=1).max()))
+    return R
+
+
+def round_terms(R):
+    """The part of the rounding allowance that does not scale with the distance: ABS_ROUND + C_ROUND 2^-52 R."""
+    return ABS_ROUND + C_ROUND * EPS * R
+
+
+def contract_violations(min_dist, lower, D, closed=True, R=0.0):
+    """The inequalities of include/msnap.h that (min_dist, lower) break against the exact D (an mpf): a list of text.
+    `R`: pair_R of the pair (0: the allowance without its coordinate term, which is stricter)."""
     D = float(D)
     bad = []
-    if not lower <= D * (1 + REL_ROUND) + ABS_ROUND:
+    if not lower <= D * (1 + REL_ROUND) + round_terms(R):
         bad.append(f"lower {lower!r} above D {D!r}")
-    if not D <= min_dist * (1 + REL_ROUND) + ABS_ROUND:
+    if not D <= min_dist * (1 + REL_ROUND) + round_terms(R):
         bad.append(f"min_dist {min_dist!r} below D {D!r}")
-    if closed and not lower >= min_dist * (1 - REL_CLOSE) - ABS_CLOSE - ABS_ROUND:
+    if closed and not lower >= min_dist * (1 - REL_CLOSE) - ABS_CLOSE - round_terms(R):
         bad.append(f"lower {lower!r} not within the closed-walk bound of min_dist {min_dist!r}")
     return bad
+
+
+def round_ratio(min_dist, lower, D, R, attained=None):
+    """What C_ROUND has to cover, in units of 2^-52 R: the larger of lower - D and D - min_dist, less
+    the distance-relative part of the allowance (negative: no coordinate term is needed).  `attained`: the exact
+    distance at t_min -- then also |min_dist - attained|, the rounding of the attained value itself, which does not
+    depend on whether the walk happened to stop right at the infimum."""
+    D = float(D)
+    r = max(lower - D * (1 + REL_ROUND), D - min_dist * (1 + REL_ROUND))
+    if attained is not None:
+        r = max(r, abs(min_dist - float(attained)) - REL_ROUND * float(attained))
+    return r / (EPS * R)
 
 
 # ------------------------------------------------------------------------------------------------ fp64 restatement
@@ -288,3 +361,72 @@ def candidate_intervals(coef, dur, pairs, rel=1e-6):
     for p, t0 in zip(st["lane_pair"][keep], st["lane_start"][keep]):
         out[int(p)].add(float(t0))
     return out
+
+
+# ------------------------------------------------------------------------------------------------ shared test helper
+def check_contract(ctx, coef, dur, pairs, with_R=False, exact=None, closed=True, restated=True, crossing=False):
+    """msnap_pair_clearance through `ctx` (a Context) on `pairs`: no status raised, the header's inequalities against
+    exact_clearance (on the candidate intervals), t_min inside the window, msnap_eval_flat at t_min giving min_dist
+    back.  with_R: the allowance with its coordinate term c 2^-52 R (without it the check is stricter: inputs near the
+    origin).  exact: per pair (D, window) known already.  restated: the kernel also within rtol 1e-9 of fp64_clearance.
+    Returns (min_dist, t_min, lower, worst round_ratio or None)."""
+    pairs = np.asarray(pairs, dtype=np.int32)
+    md, tm, lower, status = ctx.pair_clearance(coef, dur, pairs)
+    assert (status == 0).all()
+    cands = candidate_intervals(coef, dur, pairs) if exact is None else None
+    worst = None
+    Rs = np.zeros(len(pairs))
+    for k, (a, b) in enumerate(pairs):
+        if exact is None:
+            D, _, W = exact_clearance(coef[a], dur[a], coef[b], dur[b], cands[k])
+        else:
+            D, W = exact[k]
+        R = pair_R(coef[a], dur[a], coef[b], dur[b]) if with_R else 0.0
+        Rs[k] = R
+        line = f"pair ({a}, {b}): lower {lower[k]!r} D {float(D)!r} min_dist {md[k]!r} t_min {tm[k]!r}"
+        if with_R:
+            ratio = round_ratio(md[k], lower[k], D, R, exact_distance_at(coef[a], dur[a], coef[b], dur[b], tm[k]))
+            worst = ratio if worst is None else max(worst, ratio)
+            line += f" R {R:.4g} rounding / (2^-52 R) {ratio:.3f}"
+        print(line)
+        assert not contract_violations(md[k], lower[k], D, closed=closed, R=R), (a, b)
+        assert 0.0 <= tm[k] <= float(W)
+        # attained: eval_flat of the two drones at t_min gives min_dist back
+        out = ctx.eval_flat(coef[[a, b]], dur[[a, b]], tm[k:k + 1])
+        d = float(np.linalg.norm(out[0, 0, :3] - out[1, 0, :3]))
+        assert abs(d - md[k]) <= 1e-12 * md[k] + round_terms(R), (a, b, d, md[k])
+    if with_R:
+        print(f"worst rounding / (2^-52 R): {worst:.3f} (C_ROUND {C_ROUND})")
+        assert worst < C_ROUND
+    if restated:
+        # test_large_list_against_the_fp64_restatement's tolerances, with the coordinate term on min_dist where the
+        # allowance has it.  crossing: D is (next to) zero, so both walks stop inside the absolute closing slack A and
+        # their attained values are any two numbers in [D, D + A] -- there, and only there, min_dist gets A as well.
+        rmd, rtm, rlower = fp64_clearance(coef, dur, pairs)
+        print("kernel - restatement: min_dist", np.abs(md - rmd).max(), "lower", np.abs(lower - rlower).max())
+        slack = ABS_CLOSE if crossing else 0.0
+        assert (np.abs(md - rmd) <= 1e-9 * np.abs(rmd) + ABS_ROUND + C_ROUND * EPS * Rs + slack).all(), (md, rmd)
+        assert (np.abs(lower - rlower) <= 1e-9 * np.abs(rlower) + ABS_CLOSE).all(), (lower, rlower)
+    return md, tm, lower, worst
+
+
+class RestatedContext:
+    """fp64_clearance and the restated msnap_eval_flat positions behind Context's two methods that check_contract
+    uses: the CPU twins of the GPU tests run the same checks on the restatement.  (eval_flat here is the routine
+    fp64_clearance forms min_dist with, so the twins' "eval_flat at t_min gives min_dist back" holds by construction;
+    that check says something only on the GPU, where msnap_eval_flat is a kernel of its own.)"""
+
+    def __init__(self, order, max_segments=4096):
+        self.order, self.ncoef, self.max_segments = order, order + 1, max_segments
+
+    def pair_clearance(self, coef, dur, pairs):
+        pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+        md, tm, lower = fp64_clearance(coef, dur, pairs)
+        return md, tm, lower, np.zeros(len(pairs), dtype=np.int32)
+
+    def eval_flat(self, coef, dur, ts):
+        coef, dur, ts = np.asarray(coef, dtype=np.float64), np.asarray(dur, dtype=np.float64), np.asarray(ts, dtype=np.float64)
+        out = np.zeros((coef.shape[0], len(ts), 13))
+        for d in range(coef.shape[0]):
+            out[d, :, :3] = _positions(coef, dur, np.full(len(ts), d), ts)
+        return out

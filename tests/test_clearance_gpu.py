@@ -1,7 +1,7 @@
 """Pairwise clearance on the GPU (include/msnap.h, "pairwise clearance"): the contract against the exact reference
 (tests/clearance_exact.py), a shared grid, unequal totals, the crossing pair the sampled pass misses, attained values,
 bit identity, per-pair status, a large list against the fp64 restatement, the certify_clearance pipeline on the
-formation fixture's swarm, and stream capture."""
+formation fixture's swarm and on an awkward swarm of 12 (every pair), and stream capture."""
 import itertools
 import os
 import sys
@@ -12,6 +12,7 @@ import pytest
 from conftest import GOLDEN_DIR
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import clearance_cases as CC  # noqa: E402
 import clearance_exact as CE  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -30,20 +31,9 @@ def _solved(ctx, cfg, n, m, shared=False):
     return _solve(ctx, *swarm(cfg, n, m, shared_times=shared))
 
 
-def _check_contract(ctx, coef, dur, pairs, exact_equal=False):
-    md, tm, lower, status = ctx.pair_clearance(coef, dur, pairs)
-    assert (status == 0).all()
-    cands = CE.candidate_intervals(coef, dur, pairs)
-    for k, (a, b) in enumerate(pairs):
-        D, _, W = CE.exact_clearance(coef[a], dur[a], coef[b], dur[b], cands[k])
-        print(f"pair ({a}, {b}): lower {lower[k]!r} D {float(D)!r} min_dist {md[k]!r} t_min {tm[k]!r}")
-        assert not CE.contract_violations(md[k], lower[k], D), (a, b)
-        assert 0.0 <= tm[k] <= float(W)
-        # attained: eval_flat of the two drones at t_min gives min_dist back
-        out = ctx.eval_flat(coef[[a, b]], dur[[a, b]], tm[k:k + 1])
-        d = float(np.linalg.norm(out[0, 0, :3] - out[1, 0, :3]))
-        assert abs(d - md[k]) <= 1e-12 * md[k] + CE.ABS_ROUND, (a, b, d, md[k])
-    return md, tm, lower
+def _check_contract(ctx, coef, dur, pairs):
+    """The shared helper (tests/clearance_exact.py) with the allowance of inputs near the origin: no coordinate term."""
+    return CE.check_contract(ctx, coef, dur, pairs, with_R=False, restated=False)[:3]
 
 
 @pytest.mark.parametrize("m", [1, 2, 10])
@@ -122,6 +112,7 @@ def test_large_list_against_the_fp64_restatement(big):
     st = {}
     rmd, rtm, rlower = CE.fp64_clearance(coef, dur, pairs, stats=st)
     print("nodes per lane: mean", st["nodes"].mean(), "max", st["nodes"].max(), "capped", int(st["capped"].sum()))
+    assert st["nodes"].max() < CE.MAX_NODES and int(st["capped"].sum()) == 0       # every walk of this list closes
     np.testing.assert_allclose(md, rmd, rtol=1e-9, atol=CE.ABS_ROUND)
     np.testing.assert_allclose(lower, rlower, rtol=1e-9, atol=CE.ABS_CLOSE)
     assert (lower <= md).all() and (lower >= md * (1 - CE.REL_CLOSE) - CE.ABS_CLOSE - CE.ABS_ROUND).all()
@@ -252,6 +243,24 @@ def test_certify_clearance_on_the_formation_swarm(ctx7):
             assert cl[a] <= D * (1 + CE.REL_ROUND) + CE.ABS_ROUND, (a, b, cl[a], D)
         if cleared[a]:
             assert D >= 2 * radius, (a, b, D)
+
+
+def test_certify_clearance_on_an_awkward_swarm_every_pair(ctx7):
+    """clearance_cases.awkward_swarm: 12 drones at +5000 m, two pairs crossing between samples, one pair touching at
+    exactly 2 radius, one drone that lands early.  All 66 pairs against the exact reference."""
+    import torch
+    from drone_path_planning_python_amd import Context
+    from drone_path_planning_python_amd.swarm import DeviceCompute, certify_clearance
+    coef, dur = CC.awkward_swarm(lambda wp, t, nc: _solve(ctx7, wp, t))
+    with Context(device_id=0, order=7, max_segments=16) as ctx:
+        comp = DeviceCompute(ctx, torch)
+        dev = torch.device("cuda", 0)
+        res = certify_clearance(comp, torch.from_numpy(coef).to(dev), torch.from_numpy(dur).to(dev), CC.AWKWARD_RADIUS,
+                                CC.AWKWARD_DT, CC.AWKWARD_SAMPLES)
+        torch.cuda.synchronize()
+        got = {k: getattr(res, k).cpu().numpy() for k in ("certified_lower", "hit", "undecided", "cleared_by_sampling",
+                                                          "pairs")}
+    CC.check_certified(got, coef, dur)
 
 
 def test_a_captured_call_replays_to_the_eager_result():
