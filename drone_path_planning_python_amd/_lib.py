@@ -22,6 +22,7 @@ c_void_pp = ctypes.POINTER(ctypes.c_void_p)
 _VP = ctypes.c_void_p
 _I = ctypes.c_int
 _D = ctypes.c_double
+_LL = ctypes.c_longlong
 SIGNATURES = {
     "msnap_version": (_I, []),
     "msnap_strerror": (ctypes.c_char_p, [_I]),
@@ -70,6 +71,8 @@ SIGNATURES = {
     "msnap_retime_to_limits_device": (_I, [_VP, _I, _I, _VP, _VP, _VP, _I, _VP, _VP, _VP]),
     "msnap_pair_clearance": (_I, [_VP, _I, _I, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP]),
     "msnap_pair_clearance_device": (_I, [_VP, _I, _I, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP]),
+    "msnap_formation_near_pairs": (_I, [_VP, _I, _I, _VP, _D, _VP, _D, _D, _LL, _VP, _VP, _VP]),
+    "msnap_formation_near_pairs_device": (_I, [_VP, _I, _I, _VP, _D, _VP, _D, _D, _LL, _VP, _VP, _VP]),
     "msnap_formation_collide": (_I, [_VP, _I, _I, _I, _I, _VP, _VP, _D, _VP, _VP, _VP]),
     "msnap_formation_collide_device": (_I, [_VP, _I, _I, _I, _I, _VP, _VP, _D, _VP, _VP, _VP]),
     "msnap_collide_rows_t_doubles": (ctypes.c_size_t, [_I, _I]),

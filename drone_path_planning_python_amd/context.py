@@ -506,6 +506,54 @@ class Context:
                                                            int(n_pairs), _ptr(pairs), _ptr(min_dist), _ptr(t_min),
                                                            _ptr(lower), _ptr(status)))
 
+    # ---- near pairs (include/msnap.h) ---------------------------------------------
+    def near_pairs(self, pos, base: float, speed=None, gap: float = 0.0, margin: float = 0.0, max_pairs=None):
+        """(pairs int32 [P, 2], dist [P]): every pair i < j of the swarm `pos` [N, S, 3] whose sampled distance is below
+        (base + (speed[i] + speed[j]) gap) (1 + margin), in ascending (i, j) order, with that distance
+        (msnap_formation_near_pairs).  `max_pairs=None` counts first and then fetches the whole list; with a number at
+        most that many pairs are returned (the first of the order)."""
+        p, pp = _host(pos, np.float64)
+        if p.ndim != 3 or p.shape[2] != 3:
+            raise ValueError("pos must be [N, S, 3]")
+        N, S, _ = p.shape
+        ps = None
+        if speed is not None:
+            sp, ps = _host(speed, np.float64)
+            if sp.shape != (N,):
+                raise ValueError("speed must be [N]")
+        found = ctypes.c_longlong(0)
+
+        def call(cap, pairs, dist):
+            vp = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None      # noqa: E731
+            with self._lock:
+                self._ck(self._lib.msnap_formation_near_pairs(self._h, N, S, pp, float(base), ps, float(gap),
+                                                              float(margin), cap, vp(pairs), vp(dist),
+                                                              ctypes.byref(found)))
+        if max_pairs is None:
+            call(0, None, None)
+            cap = int(found.value)
+        else:
+            cap = int(max_pairs)
+            if cap < 0:
+                raise ValueError("max_pairs >= 0")
+        pairs = np.empty((cap, 2), dtype=np.int32)
+        dist = np.empty((cap,), dtype=np.float64)
+        if cap:
+            call(cap, pairs, dist)
+        elif max_pairs is not None:
+            call(0, None, None)
+        n = min(cap, int(found.value))
+        return pairs[:n], dist[:n]
+
+    def near_pairs_device(self, n_drones, n_samples, pos, base, speed, gap, margin, max_pairs, pairs, pair_dist, n_found):
+        """Device pointers (speed, pairs with max_pairs == 0, and pair_dist may be None; n_found an int64 [1]),
+        asynchronous on the context's stream."""
+        with self._lock:
+            self._ck(self._lib.msnap_formation_near_pairs_device(self._h, int(n_drones), int(n_samples), _ptr(pos),
+                                                                 float(base), _ptr(speed), float(gap), float(margin),
+                                                                 int(max_pairs), _ptr(pairs), _ptr(pair_dist),
+                                                                 _ptr(n_found)))
+
     # ---- collision passes --------------------------------------------------------
     def formation_collide(self, pos_rows, pos_cols, radius: float, row_offset: int = 0):
         pr, ppr = _host(pos_rows, np.float64)

@@ -209,6 +209,35 @@ class DeviceCompute:
             self.ctx.pair_clearance_device(n, M, coef, dur, P, pairs.contiguous(), md, tm, lower, status)
         return md, tm, lower, status
 
+    # ---- near pairs (include/msnap.h) -------------------------------------------------------------------------------
+    _near_pairs_first_capacity = None      # (tests force a tiny first capacity through this)
+
+    def near_pairs(self, pos, base, speed=None, gap=0.0, margin=0.0):
+        """(pairs int32 [P, 2], dist [P]): the pairs i < j of `pos` [n, S, 3] whose sampled distance is below
+        (base + (speed[i] + speed[j]) gap) (1 + margin), ascending, with that distance (msnap_formation_near_pairs_device).
+        The count is read back once; a list that outgrew the first capacity max(4096, 8 n) is fetched by a second call."""
+        torch = self.torch
+        n, S = pos.shape[0], pos.shape[1]
+        if pos.dim() != 3 or pos.shape[2] != 3 or pos.dtype != torch.float64:
+            raise ValueError("near_pairs: pos must be a float64 tensor [n, S, 3]")
+        if speed is not None and (tuple(speed.shape) != (n,) or speed.dtype != torch.float64):
+            raise ValueError("near_pairs: speed must be a float64 tensor [n]")
+        if n < 2:
+            return (torch.zeros((0, 2), dtype=torch.int32, device=pos.device),
+                    torch.zeros((0,), dtype=torch.float64, device=pos.device))
+        pos = pos.contiguous()
+        speed = None if speed is None else speed.contiguous()
+        cap = self._near_pairs_first_capacity or max(4096, 8 * n)
+        found = self._out("near_pairs.found", (1,), torch.int64)
+        while True:
+            pairs = torch.empty((cap, 2), dtype=torch.int32, device=self.device)
+            dist = torch.empty((cap,), dtype=torch.float64, device=self.device)
+            self.ctx.near_pairs_device(n, S, pos, base, speed, gap, margin, cap, pairs, dist, found)
+            P = int(found.item())
+            if P <= cap:
+                return pairs[:P], dist[:P]
+            cap = P
+
     def collide(self, pos_rows, row_offset, pos_all, radius, rows_t=None):
         torch = self.torch
         r = pos_rows.shape[0]
@@ -607,7 +636,7 @@ def uncertain_pairs(pos_u, idx_u, v_u, radius: float, gap: float, torch, budget:
 
 
 def certify_clearance(compute, coef, dur, radius: float, dt: float, n_samples: int, status=None, world: int = 1,
-                      rank: int = 0) -> ClearanceResult:
+                      rank: int = 0, pair_filter: str = "auto") -> ClearanceResult:
     """Certify the drone-vs-drone clearance of a swarm in continuous time.
 
     1. the sampled pass as `formation_pass` runs it, and the certified speed peaks V_i = peak (1 + 2e-9);
@@ -615,7 +644,9 @@ def certify_clearance(compute, coef, dur, radius: float, dt: float, n_samples: i
     3. a drone whose sampled minimum distance d_i is at least 2 radius + (V_i + V_max) gap is cleared by sampling: a
        pair that truly comes within 2 radius has a sample within gap of that moment, at which both of its drones fail
        this test;
-    4. among the other drones U, the pairs whose sampled distance is below 2 radius + (V_i + V_j) gap
+    4. among the other drones U, the pairs whose sampled distance is below 2 radius + (V_i + V_j) gap -- listed by
+       `compute.near_pairs` (msnap_formation_near_pairs_device) where the compute object has it, by `uncertain_pairs`
+       (torch) where it has not or with `pair_filter="torch"`: the same list, in the same order --
     5. go through `compute.pair_clearance` (msnap_pair_clearance_device).
 
     One rank only: several ranks would need a gather of the uncertain drones' coefficients, which is not built --
@@ -626,6 +657,8 @@ def certify_clearance(compute, coef, dur, radius: float, dt: float, n_samples: i
                                   "coefficients over several ranks is not built")
     if not (radius >= 0.0):
         raise ValueError("certify_clearance: radius >= 0")
+    if pair_filter not in ("auto", "torch"):
+        raise ValueError('certify_clearance: pair_filter is "auto" or "torch"')
     n = dur.shape[0]
     res = formation_pass(compute, coef, dur, n, 1, 0, dt, n_samples, radius, status_local=status)
     peak, _, pst = compute.dynamic_peaks(coef, dur)
@@ -638,7 +671,11 @@ def certify_clearance(compute, coef, dur, radius: float, dt: float, n_samples: i
     reach = (v + v_max) * gap
     cleared = d >= (2.0 * radius + reach) * (1.0 + COMPARE_MARGIN)
     idx_u = torch.nonzero(~cleared, as_tuple=True)[0]
-    pairs = uncertain_pairs(res.positions_all[idx_u], idx_u, v[idx_u], radius, gap, torch)
+    if pair_filter == "auto" and hasattr(compute, "near_pairs"):
+        local, _ = compute.near_pairs(res.positions_all[idx_u], 2.0 * radius, v[idx_u], gap, COMPARE_MARGIN)
+        pairs = idx_u[local.to(torch.int64)].to(torch.int32).reshape(-1, 2).contiguous()
+    else:
+        pairs = uncertain_pairs(res.positions_all[idx_u], idx_u, v[idx_u], radius, gap, torch)
     # everything that is not a kept pair is at least 2 radius apart: a cleared drone by its own bound d_i - reach_i
     # (which covers all of its pairs), a pair of U that was not kept by d_ij - (V_i + V_j) gap >= 2 radius
     lip = torch.where(cleared, (d - reach) * (1.0 - COMPARE_MARGIN), torch.full_like(d, 2.0 * radius))

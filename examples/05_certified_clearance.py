@@ -5,12 +5,14 @@
    On the 0.1 s sampling grid they are never closer than 0.28 m: the formation pass reports no hit at radius 0.1.
    msnap_pair_clearance finds the collision in continuous time.
 2. swarm.certify_clearance on a 512-drone formation swarm: the samples and the certified speed peaks clear most drones,
-   the exact kernel sees the pairs that are left.
+   the exact kernel sees the pairs that are left -- listed on the GPU by msnap_formation_near_pairs, which the example
+   then calls directly for the same pairs and times.
 
     python examples/05_certified_clearance.py        (needs an MI355X)
 """
 import os
 import sys
+import time
 
 import numpy as np
 import torch
@@ -45,4 +47,18 @@ with Context(device_id=0, order=7, max_segments=16) as ctx:
           f"{res.n_uncertain} uncertain, {res.pairs.shape[0]} pairs certified exactly;  sampled hits "
           f"{int(res.sampled_hit.sum())}, certified hits {int(res.hit.sum())}, undecided {int(res.undecided.sum())};  "
           f"smallest certified lower bound {float(res.certified_lower.min()):.4f} m")
+    # the filter of step 4 on its own: the pairs of the uncertain drones closer than 2 radius + (V_i + V_j) gap
+    from drone_path_planning_python_amd.swarm import COMPARE_MARGIN, PEAK_MARGIN  # noqa: E402
+    idx = torch.nonzero(~res.cleared_by_sampling, as_tuple=True)[0]
+    pos = comp.sample(coef, dur, synthetic.SAMPLE_DT, synthetic.formation_sample_count(t))[idx].contiguous()
+    v = (comp.dynamic_peaks(coef, dur)[0][:, 0] * (1.0 + PEAK_MARGIN))[idx].contiguous()
+    comp.near_pairs(pos, 2.0 * synthetic.DRONE_RADIUS, v, res.gap, COMPARE_MARGIN)      # (sizes the scratch)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    pairs, dist = comp.near_pairs(pos, 2.0 * synthetic.DRONE_RADIUS, v, res.gap, COMPARE_MARGIN)
+    torch.cuda.synchronize()
+    ms = (time.perf_counter() - t0) * 1e3
+    assert torch.equal(idx[pairs.to(torch.int64)].to(torch.int32), res.pairs)
+    print(f"near pairs among the {idx.numel()} uncertain drones: {pairs.shape[0]} pairs in {ms:.2f} ms "
+          f"(closest {float(dist.min()) if pairs.shape[0] else float('nan'):.4f} m)")
     ctx.use_own_stream()

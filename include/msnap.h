@@ -349,6 +349,36 @@ int msnap_pair_clearance_device(msnap_ctx *ctx, int n_drones, int n_seg, const d
                                 int n_pairs, const int32_t *pairs, double *min_dist, double *t_min, double *lower,
                                 int32_t *status);
 
+/* ---- near pairs: every pair of a swarm whose sampled distance is below a per-pair limit ----
+ * msnap_formation_collide names one partner per drone; msnap_formation_near_pairs lists every close pair, e.g. the
+ * pairs msnap_pair_clearance has to see.  pos [n_drones][n_samples][3] as the sampler writes it; speed [n_drones] or
+ * NULL (zeros); pairs [max_pairs][2]; pair_dist [max_pairs] or NULL; n_found [1].
+ *   distance  for i < j: d2_ij = min over the samples of fma(dz, dz, fma(dy, dy, dx * dx)) -- the expression and the
+ *             minNum rule of msnap_formation_collide: a non-finite sample never wins, and a drone without a finite
+ *             sample is in no pair;
+ *   limit     lim_ij = (base + (speed[i] + speed[j]) * gap) * (1 + margin), every operation rounded once, in this
+ *             order, none fused (what the same expression gives in NumPy or torch);
+ *   kept      iff sqrt(d2_ij) < lim_ij: strict, so a NaN limit (a NaN speed) keeps nothing of that drone.
+ * Output: the kept pairs as (i, j), i < j, in ascending lexicographic order; pair_dist[p] = sqrt(d2) of pair p;
+ * *n_found = the number of kept pairs whether or not they fit.  Only the first max_pairs pairs of that order are
+ * written and nothing at or beyond max_pairs (nor, when fewer are kept, at or beyond *n_found): a caller that
+ * overflowed calls again with max_pairs >= *n_found and gets the same list.  max_pairs == 0 with pairs == NULL is a
+ * pure count.  The list, its order and pair_dist are bit-identical from run to run, host versus device entry and for
+ * any max_pairs (no atomic decides a position).  n_drones 0 or 1: *n_found = 0, nothing else is touched.
+ * MSNAP_EINVAL: a null context, pos or n_found; negative sizes; n_samples < 1; max_pairs < 0; pairs == NULL with
+ * max_pairs > 0; base, gap or margin NaN; n_drones > 16384, the largest swarm the formation pipeline is sized for.
+ * The device version only launches (n_found is a device long long[1]); its scratch is a buffer of the context under
+ * the capture rules above (MSNAP_ECAPTURE: run the call once outside the capture first).
+ * (Method: the pairwise pass's register tiling over the upper triangle writes keep bits, one byte per 8 columns and
+ * row, each with one writer; popcount per row and a scan give every row its list offset; a wave per row emits.)
+ */
+int msnap_formation_near_pairs(msnap_ctx *ctx, int n_drones, int n_samples, const double *pos, double base,
+                               const double *speed, double gap, double margin, long long max_pairs, int32_t *pairs,
+                               double *pair_dist, long long *n_found);
+int msnap_formation_near_pairs_device(msnap_ctx *ctx, int n_drones, int n_samples, const double *pos, double base,
+                                      const double *speed, double gap, double margin, long long max_pairs,
+                                      int32_t *pairs, double *pair_dist, long long *n_found);
+
 /* ---- time allocation: segment times optimised per drone (new capability) ----
  * Everything above takes the waypoint times as given (the reference's grid t_i = i*10/n,
  * scripts/drones_pols_generator.py:44-46,56).  msnap_optimize_times moves the interior knot times of each drone,

@@ -1,0 +1,374 @@
+"""msnap_formation_near_pairs on the GPU (include/msnap.h, "near pairs") against the NumPy reference
+(tests/near_pairs_ref.py): shapes around every tile boundary, extremes, the strict compare on exact data, capacity,
+non-finite input, bitwise ties to msnap_formation_collide, determinism and stream capture, and certify_clearance with
+both pair filters."""
+import ctypes
+import os
+import sys
+
+import numpy as np
+import pytest
+
+from conftest import GOLDEN_DIR
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import clearance_cases as CC  # noqa: E402
+import near_pairs_ref as NP  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+MARGIN = 1e-9
+DRONES = [2, 7, 8, 9, 127, 128, 129, 137, 300]
+SAMPLES = [1, 5, 6, 7, 13, 91]
+PAIR_CANARY, DIST_CANARY = -77, -7.5
+
+
+def raw_host(ctx, pos, base, speed, gap, margin, cap, pairs, dist):
+    """The host entry on caller arrays (canaries stay visible); returns n_found."""
+    pos = np.ascontiguousarray(pos, dtype=np.float64)
+    vp = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)      # noqa: E731
+    found = ctypes.c_longlong(-1)
+    rc = ctx._lib.msnap_formation_near_pairs(ctx._h, pos.shape[0], pos.shape[1], vp(pos), float(base), vp(speed),
+                                             float(gap), float(margin), int(cap), vp(pairs), vp(dist),
+                                             ctypes.byref(found))
+    assert rc == 0, rc
+    return int(found.value)
+
+
+def host_with_canaries(ctx, pos, base, speed, gap, margin, cap, want_dist=True, extra=3):
+    pairs = np.full((cap + extra, 2), PAIR_CANARY, dtype=np.int32)
+    dist = np.full((cap + extra,), DIST_CANARY) if want_dist else None
+    found = raw_host(ctx, pos, base, speed, gap, margin, cap, pairs if cap else None, dist if cap else None)
+    n = min(found, cap)
+    assert (pairs[n:] == PAIR_CANARY).all()
+    if want_dist:
+        assert (dist[n:] == DIST_CANARY).all()
+    return found, pairs[:n], (dist[:n] if want_dist else None)
+
+
+def device_with_canaries(ctx, pos, base, speed, gap, margin, cap, want_dist=True, extra=3):
+    import torch
+    dev = torch.device("cuda", ctx.device_id)
+    tpos = torch.from_numpy(np.ascontiguousarray(pos)).to(dev)
+    tspeed = None if speed is None else torch.from_numpy(speed).to(dev)
+    pairs = torch.full((cap + extra, 2), PAIR_CANARY, dtype=torch.int32, device=dev)
+    dist = torch.full((cap + extra,), DIST_CANARY, dtype=torch.float64, device=dev)
+    found = torch.full((1,), -1, dtype=torch.int64, device=dev)
+    torch.cuda.synchronize()
+    ctx.near_pairs_device(pos.shape[0], pos.shape[1], tpos, base, tspeed, gap, margin, cap, pairs if cap else None,
+                          dist if (cap and want_dist) else None, found)
+    ctx.sync()
+    torch.cuda.synchronize()
+    n_found = int(found.item())
+    n = min(n_found, cap)
+    pairs, dist = pairs.cpu().numpy(), dist.cpu().numpy()
+    assert (pairs[n:] == PAIR_CANARY).all() and (dist[n:] == DIST_CANARY).all()
+    if not want_dist:
+        assert (dist == DIST_CANARY).all()
+    return n_found, pairs[:n], (dist[:n] if want_dist else None)
+
+
+# ------------------------------------------------------------------------------------------ shapes against the reference
+@pytest.mark.parametrize("s", SAMPLES)
+@pytest.mark.parametrize("n", DRONES)
+def test_shapes_against_the_reference(ctx7, n, s):
+    """Row block 128, column block 8, 64-bit mask words, the plain loop below 6 samples, whole chunks and a remainder
+    of one sample."""
+    pos, speed = NP.box_swarm(1000 * n + s, n, s)
+    base = NP.base_for(pos, speed)
+    pairs, dist = ctx7.near_pairs(pos, base, speed, NP.GAP, MARGIN)
+    rp, _ = NP.assert_matches(pairs, dist, pos, base, speed, NP.GAP, MARGIN)
+    total = n * (n - 1) // 2
+    assert len(rp) >= 1
+    if n >= 127:
+        assert 0.01 <= len(rp) / total <= 0.05
+
+
+@pytest.mark.parametrize("s", [8, 9, 10, 11, 12])
+def test_every_other_chunk_remainder(ctx7, s):
+    """A remainder of two samples (plain loop) and of three to five (a last chunk moved back over its predecessor)."""
+    pos, speed = NP.box_swarm(137000 + s, 137, s)
+    base = NP.base_for(pos, speed)
+    pairs, dist = ctx7.near_pairs(pos, base, speed, NP.GAP, MARGIN)
+    NP.assert_matches(pairs, dist, pos, base, speed, NP.GAP, MARGIN)
+
+
+@pytest.mark.parametrize("n", DRONES)
+def test_null_speed_is_zero_speed(ctx7, n):
+    pos, _ = NP.box_swarm(77 * n, n, 7)
+    base = NP.base_for(pos, None)
+    pairs, dist = ctx7.near_pairs(pos, base, None, NP.GAP, MARGIN)
+    NP.assert_matches(pairs, dist, pos, base, None, NP.GAP, MARGIN)
+    p0, d0 = ctx7.near_pairs(pos, base, np.zeros(n), NP.GAP, MARGIN)
+    assert np.array_equal(p0, pairs) and np.array_equal(d0, dist)
+
+
+# --------------------------------------------------------------------------------------------------------- extremes
+def test_no_drones_and_one_drone_touch_nothing(ctx7):
+    import torch
+    dev = torch.device("cuda", 0)
+    pos = np.zeros((1, 4, 3))                                          # (a valid address for n = 0 as well)
+    tpos = torch.zeros((1, 4, 3), dtype=torch.float64, device=dev)
+    vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)                   # noqa: E731
+    for n in (0, 1):
+        arr = np.full((5, 2), PAIR_CANARY, dtype=np.int32)
+        dist = np.full((5,), DIST_CANARY)
+        found = ctypes.c_longlong(-1)
+        rc = ctx7._lib.msnap_formation_near_pairs(ctx7._h, n, 4, vp(pos), 10.0, None, 0.0, 0.0, 5, vp(arr), vp(dist),
+                                                  ctypes.byref(found))
+        assert rc == 0 and found.value == 0
+        assert (arr == PAIR_CANARY).all() and (dist == DIST_CANARY).all()
+        tarr = torch.full((5, 2), PAIR_CANARY, dtype=torch.int32, device=dev)
+        tdist = torch.full((5,), DIST_CANARY, dtype=torch.float64, device=dev)
+        tfound = torch.full((1,), -1, dtype=torch.int64, device=dev)
+        torch.cuda.synchronize()
+        ctx7.near_pairs_device(n, 4, tpos, 10.0, None, 0.0, 0.0, 5, tarr, tdist, tfound)
+        ctx7.sync()
+        assert int(tfound.item()) == 0
+        assert bool((tarr == PAIR_CANARY).all()) and bool((tdist == DIST_CANARY).all())
+        pairs, d = ctx7.near_pairs(pos[:n], 10.0)
+        assert pairs.shape == (0, 2) and d.shape == (0,)
+
+
+def test_nothing_kept_and_everything_kept(ctx7):
+    pos, speed = NP.box_swarm(137, 137, 13)
+    found, pairs, dist = host_with_canaries(ctx7, pos, 0.0, None, 0.0, 0.0, 16)
+    assert found == 0 and len(pairs) == 0
+    # everything: 9316 pairs, rows whose lists cross wave and word boundaries
+    found, pairs, dist = host_with_canaries(ctx7, pos, 100.0, speed, NP.GAP, MARGIN, 9316 + 4)
+    assert found == 9316
+    NP.assert_matches(pairs, dist, pos, 100.0, speed, NP.GAP, MARGIN)
+    f2, p2, d2 = device_with_canaries(ctx7, pos, 100.0, speed, NP.GAP, MARGIN, 9316)
+    assert f2 == 9316 and np.array_equal(p2, pairs) and np.array_equal(d2, dist)
+
+
+def test_one_dense_row_among_empty_ones(ctx7):
+    n, s = 300, 7
+    rng = np.random.default_rng(300)
+    pos = np.zeros((n, s, 3))
+    pos[:, :, 0] = 10.0 * np.arange(n)[:, None]                       # a line, 10 m apart: no pair within 1 m
+    pos += 0.01 * rng.random((n, s, 3))
+    speed = np.zeros(n)
+    speed[41] = 1e5                                                   # ... but drone 41's limit reaches everybody
+    pairs, dist = ctx7.near_pairs(pos, 1.0, speed, 1.0, 0.0)
+    rp, _ = NP.assert_matches(pairs, dist, pos, 1.0, speed, 1.0, 0.0)
+    assert len(rp) == n - 1 and ((rp == 41).sum(axis=1) == 1).all()
+
+
+# ------------------------------------------------------------------------------------------- strict compare, exact data
+def test_strict_compare_on_an_integer_lattice(ctx7):
+    """Every difference, square and sum is exact in either arithmetic: the 3-4-5 pair is at distance 5 exactly."""
+    n, s = 9, 7
+    pos = np.zeros((n, s, 3))
+    pos[:, :, 0] = 1000.0 * np.arange(n)[:, None]                     # far apart
+    pos[3, :, :] = [3000.0, 0.0, 0.0]
+    pos[6, :, :] = [3000.0, 3.0, 4.0]                                 # (3, 6): 0-3-4 apart in every sample but one, where
+    pos[6, 4, :] = [3000.0, 3.0, 40.0]                                #  it is further
+    pos[8, :, :] = pos[1, :, :]                                       # (1, 8): two drones on one path
+    for call in (host_with_canaries, device_with_canaries):
+        found, pairs, dist = call(ctx7, pos, 5.0, None, 0.0, 0.0, 8)
+        assert pairs.tolist() == [[1, 8]] and dist.tolist() == [0.0]                     # 5 < 5 is false
+        found, pairs, dist = call(ctx7, pos, np.nextafter(5.0, 6.0), None, 0.0, 0.0, 8)
+        assert pairs.tolist() == [[1, 8], [3, 6]] and dist.tolist() == [0.0, 5.0]
+        found, pairs, dist = call(ctx7, pos, 1e-300, None, 0.0, 0.0, 8)                   # any positive base
+        assert pairs.tolist() == [[1, 8]]
+        found, pairs, dist = call(ctx7, pos, 0.0, None, 0.0, 0.0, 8)                      # 0 < 0 is false
+        assert found == 0
+
+
+# --------------------------------------------------------------------------------------------------------- capacity
+def test_capacity_prefix_count_and_canaries(ctx7):
+    n, s = 129, 13
+    pos, speed = NP.box_swarm(4242, n, s)
+    base = NP.base_for(pos, speed, frac=0.04)
+    rp, rd, band = NP.near_pairs(pos, base, speed, NP.GAP, MARGIN)
+    assert band == [] and len(rp) > 64
+    P = len(rp)
+    for call in (host_with_canaries, device_with_canaries):
+        full = None
+        for cap in (P + 5, P, P - 1, 1, 0):
+            found, pairs, dist = call(ctx7, pos, base, speed, NP.GAP, MARGIN, cap)       # (asserts the canaries)
+            assert found == P and len(pairs) == min(cap, P)
+            if full is None:
+                full = (pairs, dist)
+                NP.assert_matches(pairs, dist, pos, base, speed, NP.GAP, MARGIN)
+            assert np.array_equal(pairs, full[0][:cap]) and np.array_equal(dist, full[1][:cap])
+        found, pairs, dist = call(ctx7, pos, base, speed, NP.GAP, MARGIN, P, want_dist=False)      # pair_dist = NULL
+        assert found == P and np.array_equal(pairs, full[0]) and dist is None
+
+
+# ------------------------------------------------------------------------------------------------- non-finite input
+def test_non_finite_positions_and_speeds(ctx7):
+    n, s = 137, 13
+    pos, speed = NP.box_swarm(909, n, s)
+    base = NP.base_for(pos, speed, frac=0.05)
+    clean, _, band = NP.near_pairs(pos, base, speed, NP.GAP, MARGIN)
+    assert band == []
+    bad = pos.copy()
+    bad[70] = np.nan                                                  # no finite sample: in no pair
+    bad[5, 3:9] = np.nan                                              # judged on its finite samples
+    bad[130, 0, 1] = np.inf
+    pairs, dist = ctx7.near_pairs(bad, base, speed, NP.GAP, MARGIN)
+    rp, _ = NP.assert_matches(pairs, dist, bad, base, speed, NP.GAP, MARGIN)
+    assert (clean == 70).any() and not (rp == 70).any() and np.isfinite(dist).all()
+    others = lambda p: p[~np.isin(p, (5, 70, 130)).any(axis=1)]      # noqa: E731
+    assert np.array_equal(others(rp), others(clean))                  # the neighbours are unaffected
+    # a NaN speed removes that drone's pairs only
+    sp = speed.copy()
+    sp[20] = np.nan
+    pairs, dist = ctx7.near_pairs(pos, base, sp, NP.GAP, MARGIN)
+    assert (clean == 20).any()
+    assert np.array_equal(pairs, clean[~(clean == 20).any(axis=1)])
+
+
+# ------------------------------------------------------------------------------------- bitwise ties to the pairwise pass
+def test_bitwise_ties_to_formation_collide(ctx7):
+    n, s = 300, 91
+    pos, _ = NP.box_swarm(300091, n, s)
+    B = NP.base_for(pos, None, frac=0.03)
+    md, partner, hit = ctx7.formation_collide(pos, pos, 0.5 * B)
+    pairs, dist = ctx7.near_pairs(pos, B, None, 0.0, 0.0)
+    assert len(pairs) > 100
+    listed = np.zeros(n, dtype=bool)
+    listed[pairs.reshape(-1)] = True
+    assert np.array_equal(listed, md < B)
+    for i in np.nonzero(listed)[0]:
+        mine = (pairs == i).any(axis=1)
+        other = np.where(pairs[mine, 0] == i, pairs[mine, 1], pairs[mine, 0])
+        d = dist[mine]
+        assert d.min() == md[i]                                        # bit for bit
+        assert other[d == d.min()].min() == partner[i]
+
+
+# ------------------------------------------------------------------------------------- determinism, capture, the limit
+def test_two_calls_and_both_entries_give_identical_bytes(ctx7):
+    pos, speed = NP.box_swarm(5150, 300, 13)
+    base = NP.base_for(pos, speed, frac=0.02)
+    a = host_with_canaries(ctx7, pos, base, speed, NP.GAP, MARGIN, 2000)
+    b = host_with_canaries(ctx7, pos, base, speed, NP.GAP, MARGIN, 2000)
+    c = device_with_canaries(ctx7, pos, base, speed, NP.GAP, MARGIN, 2000)
+    d = device_with_canaries(ctx7, pos, base, speed, NP.GAP, MARGIN, 2000)
+    for x in (b, c, d):
+        assert x[0] == a[0] and x[1].tobytes() == a[1].tobytes() and x[2].tobytes() == a[2].tobytes()
+    assert 0 < a[0] <= 2000
+
+
+def test_capture_replays_and_growth_inside_a_capture_is_refused():
+    import torch
+    from drone_path_planning_python_amd import Context, MsnapError
+    dev = torch.device("cuda", 0)
+    pos, speed = NP.box_swarm(64013, 64, 13)
+    base = NP.base_for(pos, speed, frac=0.05)
+    big, _ = NP.box_swarm(200013, 200, 13)
+    side = torch.cuda.Stream()
+    with Context(device_id=0, order=7, max_segments=16) as ctx:
+        eager_pairs, eager_dist = ctx.near_pairs(pos, base, speed, NP.GAP, MARGIN)
+        P = len(eager_pairs)
+        assert P > 10
+        with torch.cuda.stream(side):
+            ctx.set_stream(side.cuda_stream)
+            tpos, tspeed, tbig = (torch.from_numpy(x).to(dev) for x in (pos, speed, big))
+            pairs = torch.empty((P, 2), dtype=torch.int32, device=dev)
+            dist = torch.empty((P,), dtype=torch.float64, device=dev)
+            found = torch.zeros((1,), dtype=torch.int64, device=dev)
+            ctx.near_pairs_device(64, 13, tpos, base, tspeed, NP.GAP, MARGIN, P, pairs, dist, found)   # sizes the scratch
+            side.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, stream=side, capture_error_mode="thread_local"):
+                ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+                ctx.near_pairs_device(64, 13, tpos, base, tspeed, NP.GAP, MARGIN, P, pairs, dist, found)
+            ctx.set_stream(side.cuda_stream)
+            for _ in range(2):
+                for x in (pairs, dist, found):
+                    x.zero_()
+                g.replay()
+                side.synchronize()
+                assert int(found.item()) == P
+                assert np.array_equal(pairs.cpu().numpy(), eager_pairs) and np.array_equal(dist.cpu().numpy(), eager_dist)
+            # the first call of a larger shape inside a capture: the scratch would have to grow
+            g2 = torch.cuda.CUDAGraph()
+            with pytest.raises(MsnapError) as e:
+                with torch.cuda.graph(g2, stream=side, capture_error_mode="thread_local"):
+                    ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+                    ctx.near_pairs_device(200, 13, tbig, base, None, 0.0, 0.0, P, pairs, dist, found)
+            assert e.value.code == -8
+            ctx.set_stream(side.cuda_stream)
+        ctx.use_own_stream()
+
+
+def test_more_than_16384_drones_are_refused(ctx7):
+    from drone_path_planning_python_amd import MsnapError
+    with pytest.raises(MsnapError) as e:
+        ctx7.near_pairs(np.zeros((16385, 1, 3)), 1.0, max_pairs=4)
+    assert e.value.code == -1
+
+
+# --------------------------------------------------------------------------------------------------------- pipeline
+def _both_filters(coef, dur, radius, dt, S):
+    import torch
+    from drone_path_planning_python_amd import Context
+    from drone_path_planning_python_amd.swarm import COMPARE_MARGIN, DeviceCompute, certify_clearance
+    dev = torch.device("cuda", 0)
+    with Context(device_id=0, order=7, max_segments=16) as ctx:
+        comp = DeviceCompute(ctx, torch)
+        tc, td = torch.from_numpy(coef).to(dev), torch.from_numpy(dur).to(dev)
+        new = certify_clearance(comp, tc, td, radius, dt, S, pair_filter="auto")
+        old = certify_clearance(comp, tc, td, radius, dt, S, pair_filter="torch")
+        torch.cuda.synchronize()
+        assert new.pairs.dtype == old.pairs.dtype == torch.int32 and new.pairs.is_contiguous()
+        assert torch.equal(new.pairs, old.pairs) and new.pairs.shape[0] > 0
+        for k in ("hit", "undecided", "certified_lower", "cleared_by_sampling"):
+            assert torch.equal(getattr(new, k), getattr(old, k)), k
+        # the band of the filter's own input is empty: the agreement is no accident of rounding
+        pos = comp.sample(tc, td, dt, S).cpu().numpy()
+        peak, _, _ = comp.dynamic_peaks(tc, td)
+        from drone_path_planning_python_amd.swarm import PEAK_MARGIN
+        v = (peak[:, 0] * (1.0 + PEAK_MARGIN)).cpu().numpy()
+        idx = np.nonzero(~new.cleared_by_sampling.cpu().numpy())[0]
+        rp, _, band = NP.near_pairs(pos[idx], 2.0 * radius, v[idx], new.gap, COMPARE_MARGIN)
+        assert band == [] and np.array_equal(idx[rp].astype(np.int32), new.pairs.cpu().numpy())
+    return new
+
+
+def test_certify_clearance_with_both_filters_on_the_formation_swarm(ctx7):
+    from drone_path_planning_python_amd import synthetic
+    assert os.path.exists(os.path.join(GOLDEN_DIR, "formation_golden.npz"))
+    rb, off, t = synthetic.formation_config(2)
+    G, m, _ = rb.shape
+    poses = ctx7.formation_transform(rb.reshape(G * m, 7), off)
+    wp = synthetic.formation_waypoints(poses, G)[:512]
+    coef, dur, status = ctx7.solve_batch(wp, t)
+    assert (status == 0).all()
+    res = _both_filters(coef, dur, synthetic.DRONE_RADIUS, synthetic.SAMPLE_DT, synthetic.formation_sample_count(t))
+    assert bool(res.hit.any())
+
+
+def test_certify_clearance_with_both_filters_on_the_awkward_swarm(ctx7):
+    def solve(wp, t, nc):
+        coef, dur, status = ctx7.solve_batch(wp, t)
+        assert (status == 0).all()
+        return coef, dur
+    coef, dur = CC.awkward_swarm(solve)
+    res = _both_filters(coef, dur, CC.AWKWARD_RADIUS, CC.AWKWARD_DT, CC.AWKWARD_SAMPLES)
+    CC.check_certified({k: getattr(res, k).cpu().numpy() for k in ("certified_lower", "hit", "undecided",
+                                                                    "cleared_by_sampling", "pairs")}, coef, dur)
+
+
+def test_device_compute_retries_once_the_list_outgrows_its_first_capacity():
+    import torch
+    from drone_path_planning_python_amd import Context
+    from drone_path_planning_python_amd.swarm import DeviceCompute
+    dev = torch.device("cuda", 0)
+    pos, speed = NP.box_swarm(129007, 129, 7)
+    base = NP.base_for(pos, speed, frac=0.05)
+    with Context(device_id=0, order=7, max_segments=16) as ctx:
+        comp = DeviceCompute(ctx, torch)
+        tpos, tspeed = torch.from_numpy(pos).to(dev), torch.from_numpy(speed).to(dev)
+        pairs, dist = comp.near_pairs(tpos, base, tspeed, NP.GAP, MARGIN)
+        rp, _ = NP.assert_matches(pairs.cpu().numpy(), dist.cpu().numpy(), pos, base, speed, NP.GAP, MARGIN)
+        assert len(rp) > 16
+        comp._near_pairs_first_capacity = 16                           # forces the second call
+        p2, d2 = comp.near_pairs(tpos, base, tspeed, NP.GAP, MARGIN)
+        assert torch.equal(p2, pairs) and torch.equal(d2, dist)
+        e0, e1 = comp.near_pairs(tpos[:1], base, tspeed[:1], NP.GAP, MARGIN)
+        assert e0.shape == (0, 2) and e0.dtype == torch.int32 and e1.shape == (0,)
