@@ -506,6 +506,33 @@ class Context:
                                                            int(n_pairs), _ptr(pairs), _ptr(min_dist), _ptr(t_min),
                                                            _ptr(lower), _ptr(status)))
 
+    # ---- mesh clearance in continuous time (include/msnap.h) ------------------------------
+    def mesh_clearance(self, coef, dur, tris):
+        """Certified distance of each drone's whole path to the mesh `tris` [T, 3, 3]: (min_dist [N], t_min [N],
+        tri_min [N] int32, lower [N], status [N] int32) with lower <= infimum <= min_dist, min_dist attained at t_min
+        against triangle tri_min (msnap_mesh_clearance)."""
+        coef, pc, dur, pd, N, M = self._coef_dur(coef, dur)
+        tr, ptr_ = _host(tris, np.float64)
+        if tr.ndim != 3 or tr.shape[1:] != (3, 3):
+            raise ValueError("tris must be [T, 3, 3]")
+        md = np.empty((N,), dtype=np.float64)
+        tm = np.empty((N,), dtype=np.float64)
+        tri = np.empty((N,), dtype=np.int32)
+        lower = np.empty((N,), dtype=np.float64)
+        status = np.empty((N,), dtype=np.int32)
+        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)      # noqa: E731
+        with self._lock:
+            self._ck(self._lib.msnap_mesh_clearance(self._h, N, M, pc, pd, tr.shape[0], ptr_, vp(md), vp(tm), vp(tri),
+                                                    vp(lower), vp(status)))
+        return md, tm, tri, lower, status
+
+    def mesh_clearance_device(self, n_drones, n_seg, coef, dur, n_tris, tris, min_dist, t_min, tri_min, lower, status):
+        """Device pointers (tri_min, status int32), asynchronous on the context's stream."""
+        with self._lock:
+            self._ck(self._lib.msnap_mesh_clearance_device(self._h, int(n_drones), int(n_seg), _ptr(coef), _ptr(dur),
+                                                           int(n_tris), _ptr(tris), _ptr(min_dist), _ptr(t_min),
+                                                           _ptr(tri_min), _ptr(lower), _ptr(status)))
+
     # ---- near pairs (include/msnap.h) ---------------------------------------------
     def near_pairs(self, pos, base: float, speed=None, gap: float = 0.0, margin: float = 0.0, max_pairs=None):
         """(pairs int32 [P, 2], dist [P]): every pair i < j of the swarm `pos` [N, S, 3] whose sampled distance is below

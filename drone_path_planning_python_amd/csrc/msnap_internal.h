@@ -73,6 +73,7 @@ struct msnap_ctx {
   msnap::DevBuf collide_work;  // the pairwise pass's working set (msnap_collide.hip, launch_formation_collide[_part])
   msnap::DevBuf limits_work;   // msnap_limits.hip: per-(drone, segment, quantity) peaks, then the retiming's per-drone peaks
   msnap::DevBuf clearance_work;   // msnap_clearance.hip: per-(pair, slot) results, then the per-(drone, segment) flags
+  msnap::DevBuf mesh_clearance_work;   // msnap_mesh_clearance.hip: per-(drone, segment) results, then the per-(drone, segment) flags
   msnap::DevBuf pairs_work;       // msnap_pairs.hip: the row image, the keep-bit matrix, the rows' counts and list offsets
   // chunked host-pointer solves: two streams alternate H2D -> kernel -> D2H over chunks of drones,
   // each with its own staging set (wp, t, coef, dur, status)
@@ -218,6 +219,11 @@ inline size_t clearance_lanes(int n_pairs, int M) { return (size_t)n_pairs * (si
 // ctx->clearance_work: per-lane results [lanes][3] doubles, then the flags [N M] int32
 inline size_t clearance_work_bytes(int N, int M, int n_pairs) {
   return clearance_lanes(n_pairs, M) * 3 * sizeof(double) + (size_t)N * M * sizeof(int32_t);
+}
+// mesh clearance (msnap_mesh_clearance.hip): one lane per (drone, segment).  ctx->mesh_clearance_work: per-lane results
+// [N M][3] doubles, then the flags [N M] int32
+inline size_t mesh_clearance_work_bytes(int N, int M) {
+  return (size_t)N * M * (3 * sizeof(double) + sizeof(int32_t));
 }
 // near pairs (msnap_pairs.hip).  ctx->pairs_work: the row image [n_samples][3][rows rounded up to whole blocks of 128]
 // doubles, the keep bits [N][words] of 64-bit words, the rows' list offsets [N] long long, the rows' counts [N] int32

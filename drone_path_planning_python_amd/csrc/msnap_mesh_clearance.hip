@@ -1,0 +1,419 @@
+// Mesh clearance in continuous time: the certified minimum distance of each drone's whole path to a triangle mesh
+// (include/msnap.h, "mesh clearance").  The distance function is the mesh sweep's (msnap_tri.h).
+//
+// Bound.  For any vector n with |n| <= 1 and any point x, dist(x, triangle) >= n.x - max_j n.v_j (the triangle's
+// support function).  On a sub-interval of a segment the Bernstein control points b_k of the three position
+// polynomials enclose the path, so min_k n.b_k - max_j n.v_j bounds the distance from below on the whole sub-interval,
+// whatever n is.  Candidates: +N and -N (the face's unit normal: near the wall the direction below is rounding noise,
+// and the support function charges a tilt eps with eps times the triangle's extent) and the unit direction from the
+// triangle's closest point to whichever of the node's start, middle and end lies farthest from it (the tangent plane
+// of a convex function: the bound converges quadratically with the node's width).  The largest of the three counts.
+// A triangle the sweep takes as the union of its edges (tri_degenerate) is bounded by its hull, which that union lies
+// in: exact for a zero-area triangle, below the edge-union distance inside a sliver of non-zero area.
+//
+// Lane.  One per (drone, segment): the segment's x, y, z scaled to u in [0, 1], then the stackless, wave-uniform walk of
+// clearance_lane_kernel (msnap_clearance.hip) over dyadic sub-intervals: Taylor shift, exact scaling by 2^-lvl, control
+// points; per node a loop over the triangles (wave-uniform: scalar loads), each first tried with box_tri_lb2 of the
+// control points' box against the prune threshold, which leaves few.  A node's bound is the smallest over the
+// triangles; the distances at its start, middle and end are attained values (smaller, then earlier).  A node is
+// pruned when bound >= L (1 - kPruneRel) - kPruneAbs, L the smallest attained distance; the lane carries the smallest
+// bound of every node it pruned or stopped at, and the root's if the node guard ends the walk: what the walk proved.
+//
+// Fold.  One thread per drone over its segments: smallest attained value, then earliest absolute time; smallest bound.
+// The distance is taken again at t_min -- msnap_eval_flat's lookup and Horner, every triangle in index order through
+// the sweep's functions, strict `<` -- so that msnap_mesh_sweep of that one position returns min_dist bit for bit and
+// tri_min is the lowest index that attains it.  Nothing crosses lanes but the trip count.
+#include <math.h>
+
+#include "msnap_api_util.h"
+#include "msnap_tri.h"
+#include "msnap_walk.h"
+#include "msnap_wave.h"
+
+namespace msnap {
+namespace {
+
+constexpr int kMaxDepth = 40;            // sub-intervals of 2^-40 (msnap_clearance.hip)
+constexpr int kMaxNodes = 4096;          // nodes per lane: a guard on the loop
+constexpr double kPruneRel = 1e-9;       // on the distance (msnap_clearance.hip's 2e-9 on the square)
+constexpr double kPruneAbs = 1e-9;       // [m]: what lets a crossing (D = 0) close
+
+// every vertex coordinate finite (wave-uniform: a triangle that is not never wins and is skipped)
+__device__ __forceinline__ bool tri_finite(const double *__restrict__ t) {
+  bool f = true;
+#pragma unroll
+  for (int j = 0; j < 9; ++j) f = f && isfinite(t[j]);
+  return f;
+}
+
+// closest point of the closed segment ab to p (pt_seg_d2's parameter)
+__device__ __forceinline__ void closest_on_seg(double px, double py, double pz, const double *__restrict__ a,
+                                               const double *__restrict__ b, double &qx, double &qy, double &qz) {
+#pragma clang fp contract(off)
+  const double ux = b[0] - a[0], uy = b[1] - a[1], uz = b[2] - a[2];
+  const double wx = px - a[0], wy = py - a[1], wz = pz - a[2];
+  const double l2 = ux * ux + uy * uy + uz * uz;
+  double u = 0.0;
+  if (l2 > 0.0) {
+    u = (wx * ux + wy * uy + wz * uz) / l2;
+    u = (u > 0.0) ? u : 0.0;
+    u = (u < 1.0) ? u : 1.0;
+  }
+  qx = a[0] + u * ux;
+  qy = a[1] + u * uy;
+  qz = a[2] + u * uz;
+}
+
+// The direction from the triangle's closest point to p, as a vector of length <= 1 (up to an ulp; zero when p lies on
+// the triangle).  Only the QUALITY of the bound depends on it, not its validity: the closest point is found by
+// projecting on the plane and, outside the face, on the three edges -- not by the sweep's region walk.
+__device__ __forceinline__ void away_direction(double px, double py, double pz, const double *__restrict__ t,
+                                               bool degenerate, double Nx, double Ny, double Nz, double &nx, double &ny,
+                                               double &nz) {
+#pragma clang fp contract(off)
+  double qx, qy, qz, best;
+  closest_on_seg(px, py, pz, t, t + 3, qx, qy, qz);
+  best = (px - qx) * (px - qx) + (py - qy) * (py - qy) + (pz - qz) * (pz - qz);
+  {
+    double rx, ry, rz;
+    closest_on_seg(px, py, pz, t + 3, t + 6, rx, ry, rz);
+    const double d = (px - rx) * (px - rx) + (py - ry) * (py - ry) + (pz - rz) * (pz - rz);
+    if (d < best) { best = d; qx = rx; qy = ry; qz = rz; }
+    closest_on_seg(px, py, pz, t + 6, t, rx, ry, rz);
+    const double e = (px - rx) * (px - rx) + (py - ry) * (py - ry) + (pz - rz) * (pz - rz);
+    if (e < best) { best = e; qx = rx; qy = ry; qz = rz; }
+  }
+  if (!degenerate) {
+    // the foot of the perpendicular, if it falls inside the face (same side of all three edges)
+    const double h = (px - t[0]) * Nx + (py - t[1]) * Ny + (pz - t[2]) * Nz;
+    const double fx = px - h * Nx, fy = py - h * Ny, fz = pz - h * Nz;
+    bool inside = true;
+#pragma unroll
+    for (int e = 0; e < 3; ++e) {
+      const double *a = t + 3 * e, *b = t + 3 * ((e + 1) % 3);
+      const double ux = b[0] - a[0], uy = b[1] - a[1], uz = b[2] - a[2];
+      const double wx = fx - a[0], wy = fy - a[1], wz = fz - a[2];
+      const double cx = uy * wz - uz * wy, cy = uz * wx - ux * wz, cz = ux * wy - uy * wx;
+      inside = inside && (cx * Nx + cy * Ny + cz * Nz >= 0.0);
+    }
+    if (inside && h * h < best) { qx = fx; qy = fy; qz = fz; }
+  }
+  const double dx = px - qx, dy = py - qy, dz = pz - qz;
+  const double len = sqrt(dx * dx + dy * dy + dz * dz);
+  const double inv = len > 0.0 ? 1.0 / len : 0.0;
+  nx = dx * inv;
+  ny = dy * inv;
+  nz = dz * inv;
+}
+
+// one lane per (drone, segment): work[3 item] = smallest attained SQUARED distance of the segment (+inf: no triangle,
+// or a failed drone), [3 item + 1] = its absolute time, [3 item + 2] = the proven lower bound of the distance there
+template <int NC>
+__global__ void __launch_bounds__(kThreads)
+mesh_clearance_lane_kernel(const double *__restrict__ coef, const double *__restrict__ dur,
+                           const int32_t *__restrict__ flags, int N, int M, int n_tris,
+                           const double *__restrict__ tris, double *__restrict__ work) {
+  constexpr int D = NC - 1;       // degree of the positions
+  constexpr BernsteinWeights<D> W{};
+  const double inf = __builtin_inf();
+  const size_t total = (size_t)N * M;
+  const size_t item = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool in_range = item < total;
+  const size_t d = in_range ? item / (size_t)M : 0;
+  const int k = in_range ? (int)(item - d * (size_t)M) : 0;
+
+  // one pass over the drone's durations: its flags, the lane's segment and where it starts (the running sums of
+  // msnap_eval_flat); every lane makes M trips
+  double acc = 0.0, start = 0.0, T = 1.0;
+  int bad = 0;
+  for (int i = 0; i < M; ++i) {
+    const double Ti = in_range ? dur[d * M + i] : 1.0;
+    bad |= in_range ? flags[d * M + i] : 0;
+    if (i == k) { start = acc; T = Ti; }
+    acc = acc + Ti;
+  }
+  const double E = start + T;
+  const bool ok = in_range && bad == 0;
+
+  // e[s][j]: axis s of the segment in u = t / T
+  double e[3][D + 1];
+  {
+    const double *c = coef + (d * M + k) * 4 * NC;
+    double hp = 1.0;
+#pragma unroll
+    for (int j = 0; j <= D; ++j) {
+#pragma unroll
+      for (int s = 0; s < 3; ++s) e[s][j] = ok ? c[s * NC + j] * hp : 0.0;
+      hp *= T;
+    }
+  }
+
+  // branch and bound over the dyadic sub-intervals; every lane runs the body while any lane is active
+  double best = inf, best_u = 0.0, low = inf, root = inf;      // best: a squared distance; low, root: distances
+  unsigned long long idx = 0;
+  int lvl = 0, nodes = 0;
+  bool active = ok;
+  while (__ballot(active) != 0) {
+    const double hh = ldexp(1.0, -lvl);
+    const double a = (double)idx * hh;
+    // control points b[s][i] of axis s on the node, its three points p[.][s] (x = 0, 1/2, 1) and the points' box
+    double b[3][D + 1], p[3][3], lo[3], hi[3];
+#pragma unroll
+    for (int s = 0; s < 3; ++s) {
+      double f[D + 1];
+#pragma unroll
+      for (int j = 0; j <= D; ++j) f[j] = e[s][j];
+#pragma unroll
+      for (int kk = 0; kk < D; ++kk)
+#pragma unroll
+        for (int j = D - 1; j >= kk; --j) f[j] = fma(a, f[j + 1], f[j]);
+      double hp = hh;
+#pragma unroll
+      for (int j = 1; j <= D; ++j) {
+        f[j] *= hp;
+        hp *= hh;
+      }
+      double vm = 0.0, v1 = 0.0;
+#pragma unroll
+      for (int j = D; j >= 0; --j) {
+        vm = fma(vm, 0.5, f[j]);
+        v1 = v1 + f[j];
+      }
+      p[0][s] = f[0];
+      p[1][s] = vm;
+      p[2][s] = v1;
+      b[s][0] = f[0];
+      lo[s] = hi[s] = f[0];
+#pragma unroll
+      for (int i = 1; i <= D; ++i) {
+        double v = 0.0;
+#pragma unroll
+        for (int j = 0; j <= i; ++j) v = fma(W.w[i][j], f[j], v);
+        b[s][i] = v;
+        lo[s] = fmin(lo[s], v);
+        hi[s] = fmax(hi[s], v);
+      }
+    }
+    // the threshold a triangle's box has to beat to be left out: the one the node is pruned against, from the attained
+    // values so far (NaN while there is none: nothing is left out)
+    const double sb0 = sqrt(best);
+    const double thr0 = fma(-kPruneRel, sb0, sb0) - kPruneAbs;
+    const double thr0sq = thr0 * thr0;
+    const double um = fma(0.5, hh, a), u1 = a + hh;
+    double nb = best, nu = best_u;
+    double bound = inf, skipped = inf;      // bound: a distance; skipped: the smallest squared box distance left out
+    for (int t = 0; t < n_tris; ++t) {
+      const double *tri = tris + (size_t)t * 9;
+      if (!tri_finite(tri)) continue;
+      const double lb2 = box_tri_lb2(lo, hi, tri);
+      const bool need = active && !(thr0 > 0.0 && lb2 >= thr0sq);
+      skipped = need ? skipped : fmin(skipped, lb2);
+      if (__ballot(need) == 0) continue;
+      const bool degenerate = tri_degenerate(tri);      // wave-uniform: a scalar branch
+      double d2[3];
+#pragma unroll
+      for (int q = 0; q < 3; ++q)
+        d2[q] = degenerate ? pt_degenerate_tri_d2(p[q][0], p[q][1], p[q][2], tri)
+                           : pt_tri_d2(p[q][0], p[q][1], p[q][2], tri);
+      // attained values, earlier first: a tie keeps the earlier time (and, in the fold, the lower triangle)
+      if (need) {
+        if (d2[0] < nb || (d2[0] == nb && a < nu)) { nb = d2[0]; nu = a; }
+        if (d2[1] < nb || (d2[1] == nb && um < nu)) { nb = d2[1]; nu = um; }
+        if (d2[2] < nb || (d2[2] == nb && u1 < nu)) { nb = d2[2]; nu = u1; }
+      }
+      // the face's unit normal (zero for a triangle without area)
+      const double abx = tri[3] - tri[0], aby = tri[4] - tri[1], abz = tri[5] - tri[2];
+      const double acx = tri[6] - tri[0], acy = tri[7] - tri[1], acz = tri[8] - tri[2];
+      double Nx = aby * acz - abz * acy, Ny = abz * acx - abx * acz, Nz = abx * acy - aby * acx;
+      const double nn = sqrt(Nx * Nx + Ny * Ny + Nz * Nz);
+      const double ninv = nn > 0.0 ? 1.0 / nn : 0.0;
+      Nx *= ninv;
+      Ny *= ninv;
+      Nz *= ninv;
+      // the node's point farthest from the triangle, and the direction away from the triangle there
+      const int fi = (d2[1] > d2[0]) ? ((d2[2] > d2[1]) ? 2 : 1) : ((d2[2] > d2[0]) ? 2 : 0);
+      const double fx = fi == 0 ? p[0][0] : (fi == 1 ? p[1][0] : p[2][0]);
+      const double fy = fi == 0 ? p[0][1] : (fi == 1 ? p[1][1] : p[2][1]);
+      const double fz = fi == 0 ? p[0][2] : (fi == 1 ? p[1][2] : p[2][2]);
+      double ax, ay, az;
+      away_direction(fx, fy, fz, tri, degenerate, Nx, Ny, Nz, ax, ay, az);
+      // support-plane bounds of the three candidates
+      double pn_min = inf, pn_max = -inf, pa_min = inf;
+#pragma unroll
+      for (int i = 0; i <= D; ++i) {
+        const double pn = fma(Nz, b[2][i], fma(Ny, b[1][i], Nx * b[0][i]));
+        const double pa = fma(az, b[2][i], fma(ay, b[1][i], ax * b[0][i]));
+        pn_min = fmin(pn_min, pn);
+        pn_max = fmax(pn_max, pn);
+        pa_min = fmin(pa_min, pa);
+      }
+      double sn_min = inf, sn_max = -inf, sa_max = -inf;
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        const double sn = fma(Nz, tri[3 * j + 2], fma(Ny, tri[3 * j + 1], Nx * tri[3 * j]));
+        const double sa = fma(az, tri[3 * j + 2], fma(ay, tri[3 * j + 1], ax * tri[3 * j]));
+        sn_min = fmin(sn_min, sn);
+        sn_max = fmax(sn_max, sn);
+        sa_max = fmax(sa_max, sa);
+      }
+      const double tb = fmax(fmax(pn_min - sn_max, sn_min - pn_max), pa_min - sa_max);
+      bound = need ? fmin(bound, tb) : bound;
+    }
+    // (what was left out lies at least thr0 away: said again, so that a last-bit difference between the squared compare
+    // above and this square root cannot split the node for it)
+    bound = fmin(bound, fmax(sqrt(skipped), thr0));
+    if (active) { best = nb; best_u = nu; }
+    // next node: a child, or (pruned / at the depth cap) the next sibling of the deepest ancestor that has one
+    const double sb = sqrt(best);
+    const bool split = bound < fma(-kPruneRel, sb, sb) - kPruneAbs && lvl < kMaxDepth;
+    const int up = __builtin_ctzll(~idx);           // trailing ones of idx: levels to climb (idx < 2^lvl: up <= lvl)
+    const unsigned long long idx_next = split ? idx << 1 : (idx >> up) + 1;
+    const int lvl_next = split ? lvl + 1 : lvl - up;
+    const bool first = nodes == 0;
+    ++nodes;
+    const bool finished = !split && up == lvl;
+    const bool guard = !finished && nodes >= kMaxNodes;      // nodes are left unvisited: only the root's bound holds
+    if (active) {
+      root = first ? bound : root;
+      low = split ? low : fmin(low, bound);
+      low = guard ? fmin(low, root) : low;
+      idx = idx_next;
+      lvl = lvl_next;
+    }
+    active = active && !(finished || guard);
+  }
+
+  if (!in_range) return;
+  const double tm = fmin(fma(T, best_u, start), E);
+  work[3 * item] = ok ? best : inf;
+  work[3 * item + 1] = ok ? tm : 0.0;
+  work[3 * item + 2] = ok ? low : inf;
+}
+
+// one thread per drone: fold the segments (smaller value, then earlier time; smallest bound), status, and the distance
+// again at t_min through the sweep's functions, every triangle in index order
+template <int NC>
+__global__ void __launch_bounds__(kThreads)
+mesh_clearance_fold_kernel(const double *__restrict__ coef, const double *__restrict__ dur,
+                           const int32_t *__restrict__ flags, const double *__restrict__ work, int N, int M, int n_tris,
+                           const double *__restrict__ tris, double *__restrict__ min_dist, double *__restrict__ t_min,
+                           int32_t *__restrict__ tri_min, double *__restrict__ lower, int32_t *__restrict__ status) {
+  const int d = blockIdx.x * blockDim.x + threadIdx.x;
+  if (d >= N) return;
+  const double nan = __builtin_nan("");
+  int bad = 0;
+  for (int i = 0; i < M; ++i) bad |= flags[(size_t)d * M + i];
+  const int st = (bad & 2) ? MSNAP_ST_NONFINITE : ((bad & 1) ? MSNAP_ST_TIMES : MSNAP_ST_OK);
+  double md = nan, tm = nan, lo = nan;
+  int tw = -1;
+  if (st == MSNAP_ST_OK) {
+    const double *w = work + (size_t)d * M * 3;
+    double best = __builtin_inf(), bt = 0.0, low = __builtin_inf();
+    for (int k = 0; k < M; ++k) {
+      const double g = w[3 * k], t = w[3 * k + 1];
+      if (g < best || (g == best && t < bt)) {
+        best = g;
+        bt = t;
+      }
+      low = fmin(low, w[3 * k + 2]);
+    }
+    double x, y, z;
+    position_at<NC>(coef, dur, (size_t)d * M, M, bt, x, y, z);
+    double d2 = __builtin_inf();
+    for (int t = 0; t < n_tris; ++t) {
+      const double *tri = tris + (size_t)t * 9;
+      if (!tri_finite(tri)) continue;
+      const double v = tri_degenerate(tri) ? pt_degenerate_tri_d2(x, y, z, tri) : pt_tri_d2(x, y, z, tri);
+      if (v < d2) {
+        d2 = v;
+        tw = t;
+      }
+    }
+    md = sqrt(d2);
+    tm = bt;
+    lo = fmin(fmax(low, 0.0), md);      // (a distance is not negative, and an attained value bounds the infimum too)
+  }
+  min_dist[d] = md;
+  t_min[d] = tm;
+  tri_min[d] = tw;
+  lower[d] = lo;
+  status[d] = st;
+}
+
+unsigned blocks_of(size_t items, int threads) { return (unsigned)((items + threads - 1) / threads); }
+
+template <int NC>
+int launch(msnap_ctx *ctx, int N, int M, const double *coef, const double *dur, int n_tris, const double *tris,
+           void *scratch, double *min_dist, double *t_min, int32_t *tri_min, double *lower, int32_t *status) {
+  const size_t segs = (size_t)N * M;
+  double *work = (double *)scratch;
+  int32_t *flags = (int32_t *)(work + 3 * segs);
+  hipLaunchKernelGGL((clearance_flags_kernel<NC>), dim3(blocks_of(segs, kThreads)), dim3(kThreads), 0, ctx->stream,
+                     coef, dur, segs, flags);
+  MSNAP_HIP(ctx, hipGetLastError());
+  hipLaunchKernelGGL((mesh_clearance_lane_kernel<NC>), dim3(blocks_of(segs, kThreads)), dim3(kThreads), 0, ctx->stream,
+                     coef, dur, (const int32_t *)flags, N, M, n_tris, tris, work);
+  MSNAP_HIP(ctx, hipGetLastError());
+  hipLaunchKernelGGL((mesh_clearance_fold_kernel<NC>), dim3(blocks_of(N, kThreads)), dim3(kThreads), 0, ctx->stream,
+                     coef, dur, (const int32_t *)flags, (const double *)work, N, M, n_tris, tris, min_dist, t_min,
+                     tri_min, lower, status);
+  MSNAP_HIP(ctx, hipGetLastError());
+  return MSNAP_OK;
+}
+
+int launch_mesh_clearance(msnap_ctx *ctx, int N, int M, const double *coef, const double *dur, int n_tris,
+                          const double *tris, double *min_dist, double *t_min, int32_t *tri_min, double *lower,
+                          int32_t *status) {
+  const int rc = ensure(ctx, ctx->mesh_clearance_work, mesh_clearance_work_bytes(N, M));
+  if (rc) return rc;
+  void *scratch = ctx->mesh_clearance_work.p;
+  return ctx->order == 7
+             ? launch<8>(ctx, N, M, coef, dur, n_tris, tris, scratch, min_dist, t_min, tri_min, lower, status)
+             : launch<10>(ctx, N, M, coef, dur, n_tris, tris, scratch, min_dist, t_min, tri_min, lower, status);
+}
+
+}  // namespace
+}  // namespace msnap
+
+using namespace msnap;
+
+extern "C" {
+
+// the entry points live beside their launcher, as msnap_clearance.hip's do
+static int mesh_clearance_args(const msnap_ctx *ctx, int n_drones, int n_seg, int n_tris, const void *tris,
+                               std::initializer_list<const void *> ptrs) {
+  if (!ctx || n_drones < 0 || n_tris < 0) return MSNAP_EINVAL;
+  if (int rc = check_seg(ctx, n_seg)) return rc;
+  if (((size_t)n_drones * n_seg + kClearanceThreads - 1) / kClearanceThreads > 0x7fffffffu) return MSNAP_EINVAL;   // grid size
+  if (n_drones == 0) return kNoWork;
+  if (n_tris > 0 && !tris) return MSNAP_EINVAL;
+  for (const void *p : ptrs)
+    if (!p) return MSNAP_EINVAL;
+  return MSNAP_OK;
+}
+
+int msnap_mesh_clearance_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,
+                                int n_tris, const double *tris, double *min_dist, double *t_min, int32_t *tri_min,
+                                double *lower, int32_t *status) {
+  MSNAP_ENTER(ctx, mesh_clearance_args(ctx, n_drones, n_seg, n_tris, tris,
+                                       {coef, dur, min_dist, t_min, tri_min, lower, status}));
+  return launch_mesh_clearance(ctx, n_drones, n_seg, coef, dur, n_tris, tris, min_dist, t_min, tri_min, lower, status);
+}
+
+int msnap_mesh_clearance(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur, int n_tris,
+                         const double *tris, double *min_dist, double *t_min, int32_t *tri_min, double *lower,
+                         int32_t *status) {
+  MSNAP_ENTER(ctx, mesh_clearance_args(ctx, n_drones, n_seg, n_tris, tris,
+                                       {coef, dur, min_dist, t_min, tri_min, lower, status}));
+  const size_t b_out = (size_t)n_drones * 8;
+  return staged(ctx, {upload(coef, coef_bytes(ctx, n_drones, n_seg)), upload(dur, dur_bytes(n_drones, n_seg)),
+                      upload(tris, (size_t)n_tris * 9 * 8), download(min_dist, b_out), download(t_min, b_out),
+                      download(tri_min, (size_t)n_drones * 4), download(lower, b_out),
+                      download(status, (size_t)n_drones * 4)},
+                [&](const DevPtr *d) {
+                  return launch_mesh_clearance(ctx, n_drones, n_seg, d[0], d[1], n_tris, d[2], d[3], d[4], d[5], d[6],
+                                               d[7]);
+                });
+}
+
+}  // extern "C"

@@ -209,6 +209,23 @@ class DeviceCompute:
             self.ctx.pair_clearance_device(n, M, coef, dur, P, pairs.contiguous(), md, tm, lower, status)
         return md, tm, lower, status
 
+    # ---- mesh clearance in continuous time (include/msnap.h) --------------------------------------------------------
+    def mesh_clearance(self, coef, dur, tris):
+        """(min_dist [n], t_min [n], tri_min [n] int32, lower [n], status [n] int32): the certified distance of each
+        drone's whole path to the mesh `tris` [T, 3, 3], lower <= infimum <= min_dist."""
+        torch = self.torch
+        n, M = dur.shape
+        if tris.dim() != 3 or tuple(tris.shape[1:]) != (3, 3) or tris.dtype != torch.float64:
+            raise ValueError("mesh_clearance: tris must be a float64 tensor [T, 3, 3]")
+        md = self._out("mesh_clearance.md", (n,), torch.float64)
+        tm = self._out("mesh_clearance.tm", (n,), torch.float64)
+        tri = self._out("mesh_clearance.tri", (n,), torch.int32)
+        lower = self._out("mesh_clearance.lower", (n,), torch.float64)
+        status = self._out("mesh_clearance.status", (n,), torch.int32)
+        if n:
+            self.ctx.mesh_clearance_device(n, M, coef, dur, tris.shape[0], tris.contiguous(), md, tm, tri, lower, status)
+        return md, tm, tri, lower, status
+
     # ---- near pairs (include/msnap.h) -------------------------------------------------------------------------------
     _near_pairs_first_capacity = None      # (tests force a tiny first capacity through this)
 
@@ -699,3 +716,68 @@ def certify_clearance(compute, coef, dur, radius: float, dt: float, n_samples: i
         md = tm = lower = torch.zeros((0,), dtype=torch.float64, device=d.device)
     return ClearanceResult(certified, hit, undecided, cleared, d, res.partner, res.hit, pairs, md, tm, lower, gap,
                            int(idx_u.numel()))
+
+
+# ---- certified clearance of a swarm against a mesh: the sampled sweep decides what it can, the kernel sees the rest --
+@dataclass
+class MeshClearanceResult:
+    min_dist: object          # [N] a distance the drone attains to the mesh (a cleared drone: its sampled minimum)
+    t_min: object             # [N] the absolute time of min_dist (NaN for a drone cleared by sampling)
+    triangle: object          # [N] int32: the triangle of min_dist (-1 for a drone cleared by sampling)
+    # [N] a proven lower bound of the drone's distance to the mesh over its whole path, up to the rounding allowance of
+    # msnap_mesh_clearance (include/msnap.h); for a drone cleared by sampling (d_i - V_i gap) (1 - COMPARE_MARGIN)
+    certified_lower: object
+    hit: object               # [N] bool: min_dist < radius, the sweep's rule (definite: the distance is attained)
+    undecided: object         # [N] bool: no hit, but certified_lower < radius (a search that met its caps)
+    cleared_by_sampling: object   # [N] bool: the sampled sweep and the speed peak alone prove >= radius
+    sampled_min_dist: object  # [N] the sampled sweep, for comparison
+    sampled_hit: object
+    gap: float
+    n_uncertain: int          # drones that went through msnap_mesh_clearance
+
+
+def certify_mesh_clearance(compute, coef, dur, tris, radius: float, dt: float, n_samples: int,
+                           status=None) -> MeshClearanceResult:
+    """Certify the drone-vs-mesh clearance of a swarm in continuous time.
+
+    1. the sampled sweep as `formation_pass` runs it (`compute.sample`, `compute.mesh`), and the certified speed peaks
+       V_i = peak (1 + 2e-9);
+    2. gap = `sample_gap`;
+    3. a drone whose sampled minimum distance d_i is at least (radius + V_i gap) (1 + COMPARE_MARGIN) is cleared by
+       sampling: every moment of its flight is within gap of a sample, and the distance to the mesh changes by at most
+       V_i gap in between;
+    4. the other drones go through `compute.mesh_clearance` (msnap_mesh_clearance_device).
+
+    One rank: every drone is checked on its own, so a sharded swarm calls this per shard.  Drones whose solve failed
+    (`status` != 0) are refused, as `formation_pass` does."""
+    import torch
+    if not (radius >= 0.0):
+        raise ValueError("certify_mesh_clearance: radius >= 0")
+    if status is not None and int(abs(status).sum()) != 0:
+        raise ValueError("certify_mesh_clearance: the solve reported failed drones (status != 0); their samples are "
+                         "NaN and cannot be checked")
+    n = dur.shape[0]
+    pos = compute.sample(coef, dur, dt, n_samples)
+    d, shit = compute.mesh(pos, tris, radius)
+    d, shit = d.clone(), shit.clone().to(torch.bool)
+    peak, _, pst = compute.dynamic_peaks(coef, dur)
+    if int(pst.abs().sum()) != 0:
+        raise ValueError("certify_mesh_clearance: drones with non-finite coefficients or durations <= 0 cannot be certified")
+    v = peak[:, 0] * (1.0 + PEAK_MARGIN)
+    gap = sample_gap(dt, n_samples, dur.sum(dim=1).cpu().numpy())
+    reach = v * gap
+    cleared = d >= (radius + reach) * (1.0 + COMPARE_MARGIN)
+    idx_u = torch.nonzero(~cleared, as_tuple=True)[0]
+    min_dist = d.clone()
+    t_min = torch.full_like(d, float("nan"))
+    triangle = torch.full((n,), -1, dtype=torch.int32, device=d.device)
+    certified = (d - reach) * (1.0 - COMPARE_MARGIN)
+    if idx_u.numel():
+        md, tm, tri, lower, mst = compute.mesh_clearance(coef[idx_u].contiguous(), dur[idx_u].contiguous(), tris)
+        if int(mst.abs().sum()) != 0:
+            raise ValueError("certify_mesh_clearance: msnap_mesh_clearance reported failed drones")
+        min_dist[idx_u], t_min[idx_u], triangle[idx_u], certified[idx_u] = md, tm, tri, lower
+    hit = min_dist < radius
+    undecided = (~hit) & (certified < radius)
+    return MeshClearanceResult(min_dist, t_min, triangle, certified, hit, undecided, cleared, d, shit, gap,
+                               int(idx_u.numel()))

@@ -349,6 +349,47 @@ int msnap_pair_clearance_device(msnap_ctx *ctx, int n_drones, int n_seg, const d
                                 int n_pairs, const int32_t *pairs, double *min_dist, double *t_min, double *lower,
                                 int32_t *status);
 
+/* ---- mesh clearance in continuous time (new capability) ----
+ * msnap_mesh_sweep takes the point-triangle distance on the sampling grid only, and an STL wall has no thickness: a
+ * drone that passes it at 4 m/s has its 0.1 s samples 0.2 m either side of it.  msnap_mesh_clearance certifies the
+ * distance of each drone's whole path to the mesh.  coef, dur as everywhere else; tris [n_tris][3][3] as for
+ * msnap_mesh_sweep; every output is [n_drones].  Per drone, D is the infimum of the sweep's distance function over t in
+ * [0, sum dur] (each segment on its closed [0, T_i]) and over all triangles, for the exact real polynomials of the fp64
+ * coefficients.  A triangle the sweep takes as degenerate counts as the union of its three edges, as there; a triangle
+ * with a non-finite vertex never wins and is skipped.
+ *   min_dist  a distance the drone ATTAINS, at
+ *   t_min     absolute time, against triangle
+ *   tri_min   (smaller value, then the earlier time, then the lowest triangle index): msnap_mesh_sweep of the single
+ *             position msnap_eval_flat gives at t_min, over the whole mesh, returns min_dist bit for bit;
+ *   lower     a proven lower bound:  lower <= D <= min_dist, each up to rounding (ten times the worst deviation
+ *             measured against an exact reference):
+ *               lower <= D (1 + 1e-13) + r   and   D <= min_dist (1 + 1e-13) + r,
+ *               r = 1e-13 + C_ROUND_MESH * 2^-52 * R   [m],   C_ROUND_MESH = 3
+ *             R = the largest value of sum_k |c_k| T_i^k over x, y, z and the drone's segments (msnap_pair_clearance's
+ *             R for one drone) plus the largest |vertex coordinate| of the mesh's finite triangles.
+ *             When the search closes (short of its caps: 40 bisections of a segment, 4096 nodes per segment):
+ *               lower >= min_dist (1 - 1e-9) - 1e-9 - r.
+ *             A drone that meets a cap still gets a valid lower, only further from min_dist; no status is raised.  The
+ *             closing inequality is not promised against a degenerate triangle of non-zero area (the bound is the
+ *             hull's, which is below the edge-union distance inside the sliver); it is for zero-area triangles.
+ *   status    msnap_status: MSNAP_ST_NONFINITE for a NaN / Inf coefficient or duration of the drone, else
+ *             MSNAP_ST_TIMES for a duration <= 0.  min_dist, t_min and lower of a failed drone are NaN, tri_min -1.
+ * n_tris == 0 (or no triangle with finite vertices): min_dist = lower = +inf, t_min = 0, tri_min = -1, status as
+ * above.  n_drones == 0 is a no-op.  MSNAP_EINVAL: a null context, a null array, negative sizes, tris == NULL with
+ * n_tris > 0.  A drone's outputs are bit-identical whatever its place in the batch, the batch size, and host versus
+ * device entry.  The device version only launches; its scratch is a buffer of the context under the capture rules above
+ * (MSNAP_ECAPTURE: run the call once outside the capture first).
+ * (Method: per segment, branch and bound over dyadic sub-intervals; a sub-interval's Bernstein control points enclose
+ * the path, and for any |n| <= 1 the distance to a triangle is at least min_k n.b_k - max_j n.v_j; n is tried as the
+ * two face normals and the direction away from the triangle at the sub-interval's farthest point.)
+ */
+int msnap_mesh_clearance(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur, int n_tris,
+                         const double *tris, double *min_dist, double *t_min, int32_t *tri_min, double *lower,
+                         int32_t *status);
+int msnap_mesh_clearance_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,
+                                int n_tris, const double *tris, double *min_dist, double *t_min, int32_t *tri_min,
+                                double *lower, int32_t *status);
+
 /* ---- near pairs: every pair of a swarm whose sampled distance is below a per-pair limit ----
  * msnap_formation_collide names one partner per drone; msnap_formation_near_pairs lists every close pair, e.g. the
  * pairs msnap_pair_clearance has to see.  pos [n_drones][n_samples][3] as the sampler writes it; speed [n_drones] or
