@@ -15,12 +15,8 @@
 // Lane.  Per axis x, y, z: Taylor shift of each drone's polynomial to its local offset at the interval's start, the
 // DIFFERENCE of the two (before any square: near a minimum the distance carries the rounding of the difference, not
 // of the positions), scaled by h^j to u in [0, 1].  g(u) = sum of the three squares, degree 2 order.  Then the walk of
-// peaks_lane_kernel (msnap_limits.hip) turned to a minimum: dyadic sub-intervals, Taylor shift and exact scaling by
-// 2^-lvl, the smallest Bernstein coefficient of g as a lower bound, g at both ends and the middle as attained values
-// (smaller value, then earlier time), a node pruned when bound >= L (1 - kPruneRel) - kPruneAbs.  The lane carries the
-// minimum of the bounds of every node it pruned or stopped at (depth cap), and of the root's bound if the node guard
-// ends the walk early: exactly what the walk proved.  Stackless and wave-uniform: the loop runs while any lane of the
-// wave is active, every per-lane decision is a select.
+// msnap_walk.h for a minimum: the smallest Bernstein coefficient of g as a lower bound, a node pruned when
+// bound >= L (1 - kPruneRel) - kPruneAbs, L the smallest attained value; the lane carries what the walk proved.
 //
 // Fold.  One thread per pair over its slots: smallest attained value, then earliest absolute time; smallest bound.
 // The attained value is evaluated again at t_min in the t domain -- msnap_eval_flat's segment lookup and Horner, the
@@ -36,8 +32,7 @@
 namespace msnap {
 namespace {
 
-constexpr int kMaxDepth = 40;            // sub-intervals of 2^-40 (msnap_limits.hip)
-constexpr int kMaxNodes = 4096;          // nodes per lane: a guard on the loop
+constexpr int kThreads = kClearanceThreads;
 constexpr double kPruneRel = 2e-9;       // on g = |.|^2: 1e-9 on the distance
 constexpr double kPruneAbs = 1e-18;      // on g: A^2 with A = 1e-9 m (DESIGN.md §5 K9 has the depth arithmetic)
 
@@ -53,8 +48,6 @@ clearance_lane_kernel(const double *__restrict__ coef, const double *__restrict_
                       const int32_t *__restrict__ flags, int N, int M, int n_pairs, const int32_t *__restrict__ pairs,
                       double *__restrict__ work) {
   constexpr int D = NC - 1;       // degree of the positions
-  constexpr int n = 2 * D;        // degree of g
-  constexpr BernsteinWeights<n> W{};
   const double inf = __builtin_inf();
   const int slots = 2 * M - 1;
   const size_t total = (size_t)n_pairs * slots;
@@ -136,93 +129,30 @@ clearance_lane_kernel(const double *__restrict__ coef, const double *__restrict_
     }
   }
 
-  // branch and bound over the dyadic sub-intervals; every lane runs the body while any lane is active
-  double best = inf, best_u = 0.0, low = inf, root = inf;
-  unsigned long long idx = 0;
-  int lvl = 0, nodes = 0;
+  // branch and bound over the dyadic sub-intervals (msnap_walk.h); every lane runs the body while any lane is active
+  double best = inf, best_u = 0.0;
+  WalkNode node;
+  ProvenBound proven;
   bool active = ok;
   while (__ballot(active) != 0) {
-    const double hh = ldexp(1.0, -lvl);
-    const double a = (double)idx * hh;
-    // f_s(x) = e_s(a + hh x): Taylor shift to a, then the exact scaling by hh = 2^-lvl
+    const double hh = node.h(), a = node.a();
     double f[3][D + 1];
 #pragma unroll
-    for (int s = 0; s < 3; ++s) {
-#pragma unroll
-      for (int j = 0; j <= D; ++j) f[s][j] = e[s][j];
-#pragma unroll
-      for (int kk = 0; kk < D; ++kk)
-#pragma unroll
-        for (int j = D - 1; j >= kk; --j) f[s][j] = fma(a, f[s][j + 1], f[s][j]);
-      double hp = hh;
-#pragma unroll
-      for (int j = 1; j <= D; ++j) {
-        f[s][j] *= hp;
-        hp *= hh;
-      }
-    }
-    // g on the sub-interval (power basis in x), then its Bernstein bound
-    double G[n + 1];
-#pragma unroll
-    for (int j = 0; j <= n; ++j) G[j] = 0.0;
-#pragma unroll
-    for (int s = 0; s < 3; ++s)
-#pragma unroll
-      for (int i = 0; i <= D; ++i)
-#pragma unroll
-        for (int j = 0; j <= D; ++j) G[i + j] = fma(f[s][i], f[s][j], G[i + j]);
-    double bound = G[0];
-#pragma unroll
-    for (int i = 1; i <= n; ++i) {
-      double b = 0.0;
-#pragma unroll
-      for (int j = 0; j <= i; ++j) b = fma(W.w[i][j], G[j], b);
-      bound = fmin(bound, b);
-    }
-    // attained values at x = 0, 1/2, 1 (earlier first: a tie keeps the earlier time)
-    double g0 = 0.0, gm = 0.0, g1 = 0.0;
-#pragma unroll
-    for (int s = 0; s < 3; ++s) {
-      double vm = 0.0, v1 = 0.0;
-#pragma unroll
-      for (int j = D; j >= 0; --j) {
-        vm = fma(vm, 0.5, f[s][j]);
-        v1 = v1 + f[s][j];
-      }
-      g0 = fma(f[s][0], f[s][0], g0);
-      gm = fma(vm, vm, gm);
-      g1 = fma(v1, v1, g1);
-    }
+    for (int s = 0; s < 3; ++s) shift_scale<D>(e[s], a, hh, f[s]);
+    const double bound = squares_bound<true, D>(f);
+    double g[3];
+    squares_at_ends_and_middle<D>(f, g);
     double nb = best, nu = best_u;
-    if (g0 < nb || (g0 == nb && a < nu)) { nb = g0; nu = a; }
-    const double um = fma(0.5, hh, a), u1 = a + hh;
-    if (gm < nb || (gm == nb && um < nu)) { nb = gm; nu = um; }
-    if (g1 < nb || (g1 == nb && u1 < nu)) { nb = g1; nu = u1; }
+    take_attained<true>(g, a, hh, nb, nu);
     if (active) { best = nb; best_u = nu; }
-    // next node: a child, or (pruned / at the depth cap) the next sibling of the deepest ancestor that has one
-    const bool split = bound < fma(-kPruneRel, best, best) - kPruneAbs && lvl < kMaxDepth;
-    const int up = __builtin_ctzll(~idx);           // trailing ones of idx: levels to climb (idx < 2^lvl: up <= lvl)
-    const unsigned long long idx_next = split ? idx << 1 : (idx >> up) + 1;
-    const int lvl_next = split ? lvl + 1 : lvl - up;
-    const bool first = nodes == 0;
-    ++nodes;
-    const bool finished = !split && up == lvl;
-    const bool guard = !finished && nodes >= kMaxNodes;      // nodes are left unvisited: only the root's bound holds
-    if (active) {
-      root = first ? bound : root;
-      low = split ? low : fmin(low, bound);
-      low = guard ? fmin(low, root) : low;
-      idx = idx_next;
-      lvl = lvl_next;
-    }
+    const bool split = bound < fma(-kPruneRel, best, best) - kPruneAbs && node.lvl < kMaxDepth;
+    const bool finished = node.advance(split, active);
+    const bool guard = proven.note(node, bound, split, finished, active);
     active = active && !(finished || guard);
   }
 
   if (!in_range) return;
-  const double tm = fmin(fma(h, best_u, start), E);
-  work[3 * item] = ok ? best : inf;
-  work[3 * item + 1] = ok ? tm : 0.0;
-  work[3 * item + 2] = ok ? low : inf;
+  store_lane(work, item, ok, best, best_u, proven.low, h, start, E);
 }
 
 // one thread per pair: fold the slots (smaller value, then earlier time; smallest bound), status, the attained value
@@ -249,15 +179,8 @@ clearance_fold_kernel(const double *__restrict__ coef, const double *__restrict_
   if (st == MSNAP_ST_OK) {
     const int slots = 2 * M - 1;
     const double *w = work + (size_t)p * slots * 3;
-    double best = __builtin_inf(), bt = 0.0, low = __builtin_inf();
-    for (int k = 0; k < slots; ++k) {
-      const double g = w[3 * k], t = w[3 * k + 1];
-      if (g < best || (g == best && t < bt)) {
-        best = g;
-        bt = t;
-      }
-      low = fmin(low, w[3 * k + 2]);
-    }
+    double best, bt, low;
+    fold_slots(w, slots, best, bt, low);
     double xa, ya, za, xb, yb, zb;
     position_at<NC>(coef, dur, (size_t)a * M, M, bt, xa, ya, za);
     position_at<NC>(coef, dur, (size_t)b * M, M, bt, xb, yb, zb);
@@ -271,8 +194,6 @@ clearance_fold_kernel(const double *__restrict__ coef, const double *__restrict_
   lower[p] = lo;
   status[p] = st;
 }
-
-unsigned blocks_of(size_t items, int threads) { return (unsigned)((items + threads - 1) / threads); }
 
 template <int NC>
 int launch(msnap_ctx *ctx, int N, int M, const double *coef, const double *dur, int n_pairs, const int32_t *pairs,

@@ -148,6 +148,9 @@ int handover_form(const msnap_ctx *ctx, const void *ptr, const void *pos, int n,
 // records the kernel instance a solve launcher chose (msnap_last_kernel; bench.py labels its rooflines with it)
 void note_kernel(msnap_ctx *ctx, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 
+// blocks of `threads` that cover `items`
+inline unsigned blocks_of(size_t items, int threads) { return (unsigned)((items + threads - 1) / threads); }
+
 #define MSNAP_HIP(ctx, call)                                         \
   do {                                                               \
     hipError_t e__ = (call);                                         \
@@ -233,11 +236,14 @@ inline size_t near_pairs_work_bytes(int N, int S) {
   return near_pairs_pitch(N) * (size_t)S * 3 * sizeof(double) + (size_t)N * near_pairs_words(N) * 8 +
          (size_t)N * sizeof(long long) + (size_t)N * sizeof(int32_t);
 }
+// the grid of a launch with one thread per (drone, segment) (K9's and K11's flags, K11's lanes) fits a dim3
+inline int check_walk_grid(int n_drones, int n_seg) {
+  return ((size_t)n_drones * n_seg + kClearanceThreads - 1) / kClearanceThreads > 0x7fffffffu ? MSNAP_EINVAL : MSNAP_OK;
+}
 inline int check_clearance_args(const msnap_ctx *ctx, int n_drones, int n_seg, int n_pairs) {
   if (!ctx || n_drones < 0 || n_pairs < 0) return MSNAP_EINVAL;
   if (n_seg < 1 || n_seg > ctx->max_segments) return MSNAP_ESEGMENTS;
   if ((clearance_lanes(n_pairs, n_seg) + kClearanceThreads - 1) / kClearanceThreads > 0x7fffffffu) return MSNAP_EINVAL;   // grid size
-  if (((size_t)n_drones * n_seg + kClearanceThreads - 1) / kClearanceThreads > 0x7fffffffu) return MSNAP_EINVAL;
-  return MSNAP_OK;
+  return check_walk_grid(n_drones, n_seg);
 }
 }  // namespace msnap

@@ -3,49 +3,27 @@
 //
 // Peaks.  One lane per (drone, segment, quantity).  Quantity q differentiates r = q + 1 times (yaw rate: r = 1 on the
 // yaw axis) and forms g(u) = |p^(r)(T u)|^2 on u in [0, 1], a polynomial of degree 2 (order - r) -- the lanes all carry
-// degree 2 (order - 1) so that the code is the same in every lane.  The sup of g is found by branch and bound over the
-// dyadic sub-intervals [idx 2^-lvl, (idx + 1) 2^-lvl]: on each, the Taylor shift of the component polynomials to the
-// sub-interval (the scaling by 2^-lvl is exact), their squares summed, and the Bernstein coefficients of the result --
-// whose maximum bounds g there.  Values at the ends and the middle of every visited sub-interval are attained values
-// (the lower bound L and its time).  A sub-interval is pruned when its bound is <= L (1 + kPruneRel) + kPruneAbs,
-// split otherwise, down to kMaxDepth.  The walk is stackless -- (lvl, idx) integers, the next node after a pruned one
-// is found with one count of trailing ones -- and wave-uniform: every lane runs the same predicated body while any
-// lane of the wave still has nodes, so no lane leaves the loop alone.  The lane's best time is then
-// evaluated in the t domain with the derivative Horner of msnap_eval_flat (so that eval_flat at t_peak reproduces the
-// peak), and a second launch folds the segments of each drone: larger value, then earlier absolute time.
+// degree 2 (order - 1) so that the code is the same in every lane.  The sup of g is found by the walk of msnap_walk.h
+// for a maximum: the largest Bernstein coefficient of g bounds it on a sub-interval, which is pruned when that bound is
+// <= L (1 + kPruneRel) + kPruneAbs, L the largest attained value.  (This walk carries no proven bound: a lane that
+// meets kMaxNodes just ends.)  The lane's best time is then evaluated in the t domain with the derivative Horner of
+// msnap_eval_flat (so that eval_flat at t_peak reproduces the peak), and a second launch folds the segments of each
+// drone: larger value, then earlier absolute time.
 //
 // Retiming.  Both orders impose homogeneous conditions (derivatives 1..khalf-1 zero at both ends, continuity inside),
 // so the minimiser for the times k t is the same path run k times slower: c_j -> c_j k^-j, T -> k T.  The per-drone
 // k comes from the four peaks; one workgroup folds the swarm's maximum for a common k.
 #include <math.h>
 
-#include "msnap_internal.h"
+#include "msnap_walk.h"
 #include "msnap_wave.h"
 
 namespace msnap {
 namespace {
 
-constexpr int kMaxDepth = 40;            // sub-intervals of 2^-40: below that the bound is rounding noise
-constexpr int kMaxNodes = 4096;          // nodes per lane: a guard on the loop, never met by a smooth g
 constexpr double kPruneRel = 1e-9;       // on g = |.|^2: 5e-10 on the norm (contract: 1e-9)
 constexpr double kPruneAbs = 1e-26;      // on g: 1e-13 on the norm (contract: 1e-12)
 constexpr int kThreads = kLimitsThreads;
-
-constexpr double binom(int n, int k) {
-  double r = 1.0;
-  for (int j = 1; j <= k; ++j) r = r * (double)(n - k + j) / (double)j;
-  return r;
-}
-
-// power basis -> Bernstein basis of degree n on [0, 1]: b_i = sum_{k <= i} C(i, k) / C(n, k) a_k
-template <int n>
-struct BernsteinWeights {
-  double w[n + 1][n + 1];
-  constexpr BernsteinWeights() : w() {
-    for (int i = 0; i <= n; ++i)
-      for (int k = 0; k <= i; ++k) w[i][k] = binom(i, k) / binom(n, k);
-  }
-};
 
 // d[0..NC-2] = coefficients of the first, second or third derivative (r) of c, in the order of msnap_eval_flat's
 // horner_derivs ((i + 1) * previous[i + 1]); the tail beyond the derivative's degree is zero
@@ -73,8 +51,6 @@ __global__ void __launch_bounds__(kThreads)
 peaks_lane_kernel(const double *__restrict__ coef, const double *__restrict__ dur, int N, int M,
                   double *__restrict__ work) {
   constexpr int D = NC - 2;       // degree of the first derivative: every lane's component polynomials
-  constexpr int n = 2 * D;        // degree of g
-  constexpr BernsteinWeights<n> W{};
   const size_t total = (size_t)N * M * 4;
   const size_t item = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const bool in_range = item < total;
@@ -113,80 +89,23 @@ peaks_lane_kernel(const double *__restrict__ coef, const double *__restrict__ du
       for (int j = 0; j <= D; ++j) e[s][j] = 0.0;
   }
 
-  // branch and bound over the dyadic sub-intervals; every lane runs the body while any lane is active
+  // branch and bound over the dyadic sub-intervals (msnap_walk.h); every lane runs the body while any lane is active
   double best = -1.0, best_u = 0.0;
-  unsigned long long idx = 0;
-  int lvl = 0, nodes = 0;
+  WalkNode node;
   bool active = ok;
   while (__ballot(active) != 0) {
-    const double h = ldexp(1.0, -lvl);
-    const double a = (double)idx * h;
-    // f_s(x) = e_s(a + h x): Taylor shift to a, then the exact scaling by h = 2^-lvl
+    const double h = node.h(), a = node.a();
     double f[3][D + 1];
 #pragma unroll
-    for (int s = 0; s < 3; ++s) {
-#pragma unroll
-      for (int j = 0; j <= D; ++j) f[s][j] = e[s][j];
-#pragma unroll
-      for (int k = 0; k < D; ++k)
-#pragma unroll
-        for (int j = D - 1; j >= k; --j) f[s][j] = fma(a, f[s][j + 1], f[s][j]);
-      double hp = h;
-#pragma unroll
-      for (int j = 1; j <= D; ++j) {
-        f[s][j] *= hp;
-        hp *= h;
-      }
-    }
-    // g on the sub-interval (power basis in x), then its Bernstein bound
-    double G[n + 1];
-#pragma unroll
-    for (int k = 0; k <= n; ++k) G[k] = 0.0;
-#pragma unroll
-    for (int s = 0; s < 3; ++s)
-#pragma unroll
-      for (int i = 0; i <= D; ++i)
-#pragma unroll
-        for (int j = 0; j <= D; ++j) G[i + j] = fma(f[s][i], f[s][j], G[i + j]);
-    double bound = G[0];
-#pragma unroll
-    for (int i = 1; i <= n; ++i) {
-      double b = 0.0;
-#pragma unroll
-      for (int k = 0; k <= i; ++k) b = fma(W.w[i][k], G[k], b);
-      bound = fmax(bound, b);
-    }
-    // attained values at x = 0, 1/2, 1 (earlier first: a tie keeps the earlier time)
-    double g0 = 0.0, gm = 0.0, g1 = 0.0;
-#pragma unroll
-    for (int s = 0; s < 3; ++s) {
-      double vm = 0.0, v1 = 0.0;
-#pragma unroll
-      for (int j = D; j >= 0; --j) {
-        vm = fma(vm, 0.5, f[s][j]);
-        v1 = v1 + f[s][j];
-      }
-      g0 = fma(f[s][0], f[s][0], g0);
-      gm = fma(vm, vm, gm);
-      g1 = fma(v1, v1, g1);
-    }
+    for (int s = 0; s < 3; ++s) shift_scale<D>(e[s], a, h, f[s]);
+    const double bound = squares_bound<false, D>(f);
+    double g[3];
+    squares_at_ends_and_middle<D>(f, g);
     double nb = best, nu = best_u;
-    if (g0 > nb || (g0 == nb && a < nu)) { nb = g0; nu = a; }
-    const double um = fma(0.5, h, a), u1 = a + h;
-    if (gm > nb || (gm == nb && um < nu)) { nb = gm; nu = um; }
-    if (g1 > nb || (g1 == nb && u1 < nu)) { nb = g1; nu = u1; }
+    take_attained<false>(g, a, h, nb, nu);
     if (active) { best = nb; best_u = nu; }
-    // next node: a child, or (pruned / at the depth cap) the next sibling of the deepest ancestor that has one
-    const bool split = bound > fma(best, kPruneRel, best) + kPruneAbs && lvl < kMaxDepth;
-    const int up = __builtin_ctzll(~idx);           // trailing ones of idx: levels to climb (idx < 2^lvl: up <= lvl)
-    const unsigned long long idx_next = split ? idx << 1 : (idx >> up) + 1;
-    const int lvl_next = split ? lvl + 1 : lvl - up;
-    ++nodes;
-    const bool done = (!split && up == lvl) || nodes >= kMaxNodes;
-    if (active) {
-      idx = idx_next;
-      lvl = lvl_next;
-    }
+    const bool split = bound > fma(best, kPruneRel, best) + kPruneAbs && node.lvl < kMaxDepth;
+    const bool done = node.advance(split, active) || node.nodes >= kMaxNodes;
     active = active && !done;
   }
 
@@ -317,8 +236,6 @@ time_scale_kernel(const double *coef, const double *dur, const double *__restric
     dur_out[seg] = use ? T * k : T;
   }
 }
-
-unsigned blocks_of(size_t items, int threads) { return (unsigned)((items + threads - 1) / threads); }
 
 }  // namespace
 

@@ -11,13 +11,11 @@
 // A triangle the sweep takes as the union of its edges (tri_degenerate) is bounded by its hull, which that union lies
 // in: exact for a zero-area triangle, below the edge-union distance inside a sliver of non-zero area.
 //
-// Lane.  One per (drone, segment): the segment's x, y, z scaled to u in [0, 1], then the stackless, wave-uniform walk of
-// clearance_lane_kernel (msnap_clearance.hip) over dyadic sub-intervals: Taylor shift, exact scaling by 2^-lvl, control
-// points; per node a loop over the triangles (wave-uniform: scalar loads), each first tried with box_tri_lb2 of the
-// control points' box against the prune threshold, which leaves few.  A node's bound is the smallest over the
-// triangles; the distances at its start, middle and end are attained values (smaller, then earlier).  A node is
-// pruned when bound >= L (1 - kPruneRel) - kPruneAbs, L the smallest attained distance; the lane carries the smallest
-// bound of every node it pruned or stopped at, and the root's if the node guard ends the walk: what the walk proved.
+// Lane.  One per (drone, segment): the segment's x, y, z scaled to u in [0, 1], then the walk of msnap_walk.h for a
+// minimum; per node the control points and a loop over the triangles (wave-uniform: scalar loads), each first tried
+// with box_tri_lb2 of the control points' box against the prune threshold, which leaves few.  A node's bound is the
+// smallest over the triangles; the distances at its start, middle and end are attained values.  A node is pruned when
+// bound >= L (1 - kPruneRel) - kPruneAbs, L the smallest attained distance; the lane carries what the walk proved.
 //
 // Fold.  One thread per drone over its segments: smallest attained value, then earliest absolute time; smallest bound.
 // The distance is taken again at t_min -- msnap_eval_flat's lookup and Horner, every triangle in index order through
@@ -33,8 +31,7 @@
 namespace msnap {
 namespace {
 
-constexpr int kMaxDepth = 40;            // sub-intervals of 2^-40 (msnap_clearance.hip)
-constexpr int kMaxNodes = 4096;          // nodes per lane: a guard on the loop
+constexpr int kThreads = kClearanceThreads;
 constexpr double kPruneRel = 1e-9;       // on the distance (msnap_clearance.hip's 2e-9 on the square)
 constexpr double kPruneAbs = 1e-9;       // [m]: what lets a crossing (D = 0) close
 
@@ -148,40 +145,22 @@ mesh_clearance_lane_kernel(const double *__restrict__ coef, const double *__rest
     }
   }
 
-  // branch and bound over the dyadic sub-intervals; every lane runs the body while any lane is active
-  double best = inf, best_u = 0.0, low = inf, root = inf;      // best: a squared distance; low, root: distances
-  unsigned long long idx = 0;
-  int lvl = 0, nodes = 0;
+  // branch and bound over the dyadic sub-intervals (msnap_walk.h); every lane runs the body while any lane is active
+  double best = inf, best_u = 0.0;      // best: a squared distance; the proven bound: a distance
+  WalkNode node;
+  ProvenBound proven;
   bool active = ok;
   while (__ballot(active) != 0) {
-    const double hh = ldexp(1.0, -lvl);
-    const double a = (double)idx * hh;
+    const double hh = node.h(), a = node.a();
     // control points b[s][i] of axis s on the node, its three points p[.][s] (x = 0, 1/2, 1) and the points' box
     double b[3][D + 1], p[3][3], lo[3], hi[3];
 #pragma unroll
     for (int s = 0; s < 3; ++s) {
-      double f[D + 1];
+      double f[D + 1], at[3];
+      shift_scale<D>(e[s], a, hh, f);
+      values_at_ends_and_middle<D>(f, at);
 #pragma unroll
-      for (int j = 0; j <= D; ++j) f[j] = e[s][j];
-#pragma unroll
-      for (int kk = 0; kk < D; ++kk)
-#pragma unroll
-        for (int j = D - 1; j >= kk; --j) f[j] = fma(a, f[j + 1], f[j]);
-      double hp = hh;
-#pragma unroll
-      for (int j = 1; j <= D; ++j) {
-        f[j] *= hp;
-        hp *= hh;
-      }
-      double vm = 0.0, v1 = 0.0;
-#pragma unroll
-      for (int j = D; j >= 0; --j) {
-        vm = fma(vm, 0.5, f[j]);
-        v1 = v1 + f[j];
-      }
-      p[0][s] = f[0];
-      p[1][s] = vm;
-      p[2][s] = v1;
+      for (int q = 0; q < 3; ++q) p[q][s] = at[q];
       b[s][0] = f[0];
       lo[s] = hi[s] = f[0];
 #pragma unroll
@@ -199,7 +178,6 @@ mesh_clearance_lane_kernel(const double *__restrict__ coef, const double *__rest
     const double sb0 = sqrt(best);
     const double thr0 = fma(-kPruneRel, sb0, sb0) - kPruneAbs;
     const double thr0sq = thr0 * thr0;
-    const double um = fma(0.5, hh, a), u1 = a + hh;
     double nb = best, nu = best_u;
     double bound = inf, skipped = inf;      // bound: a distance; skipped: the smallest squared box distance left out
     for (int t = 0; t < n_tris; ++t) {
@@ -216,11 +194,7 @@ mesh_clearance_lane_kernel(const double *__restrict__ coef, const double *__rest
         d2[q] = degenerate ? pt_degenerate_tri_d2(p[q][0], p[q][1], p[q][2], tri)
                            : pt_tri_d2(p[q][0], p[q][1], p[q][2], tri);
       // attained values, earlier first: a tie keeps the earlier time (and, in the fold, the lower triangle)
-      if (need) {
-        if (d2[0] < nb || (d2[0] == nb && a < nu)) { nb = d2[0]; nu = a; }
-        if (d2[1] < nb || (d2[1] == nb && um < nu)) { nb = d2[1]; nu = um; }
-        if (d2[2] < nb || (d2[2] == nb && u1 < nu)) { nb = d2[2]; nu = u1; }
-      }
+      if (need) take_attained<true>(d2, a, hh, nb, nu);
       // the face's unit normal (zero for a triangle without area)
       const double abx = tri[3] - tri[0], aby = tri[4] - tri[1], abz = tri[5] - tri[2];
       const double acx = tri[6] - tri[0], acy = tri[7] - tri[1], acz = tri[8] - tri[2];
@@ -263,31 +237,15 @@ mesh_clearance_lane_kernel(const double *__restrict__ coef, const double *__rest
     // above and this square root cannot split the node for it)
     bound = fmin(bound, fmax(sqrt(skipped), thr0));
     if (active) { best = nb; best_u = nu; }
-    // next node: a child, or (pruned / at the depth cap) the next sibling of the deepest ancestor that has one
     const double sb = sqrt(best);
-    const bool split = bound < fma(-kPruneRel, sb, sb) - kPruneAbs && lvl < kMaxDepth;
-    const int up = __builtin_ctzll(~idx);           // trailing ones of idx: levels to climb (idx < 2^lvl: up <= lvl)
-    const unsigned long long idx_next = split ? idx << 1 : (idx >> up) + 1;
-    const int lvl_next = split ? lvl + 1 : lvl - up;
-    const bool first = nodes == 0;
-    ++nodes;
-    const bool finished = !split && up == lvl;
-    const bool guard = !finished && nodes >= kMaxNodes;      // nodes are left unvisited: only the root's bound holds
-    if (active) {
-      root = first ? bound : root;
-      low = split ? low : fmin(low, bound);
-      low = guard ? fmin(low, root) : low;
-      idx = idx_next;
-      lvl = lvl_next;
-    }
+    const bool split = bound < fma(-kPruneRel, sb, sb) - kPruneAbs && node.lvl < kMaxDepth;
+    const bool finished = node.advance(split, active);
+    const bool guard = proven.note(node, bound, split, finished, active);
     active = active && !(finished || guard);
   }
 
   if (!in_range) return;
-  const double tm = fmin(fma(T, best_u, start), E);
-  work[3 * item] = ok ? best : inf;
-  work[3 * item + 1] = ok ? tm : 0.0;
-  work[3 * item + 2] = ok ? low : inf;
+  store_lane(work, item, ok, best, best_u, proven.low, T, start, E);
 }
 
 // one thread per drone: fold the segments (smaller value, then earlier time; smallest bound), status, and the distance
@@ -308,15 +266,8 @@ mesh_clearance_fold_kernel(const double *__restrict__ coef, const double *__rest
   int tw = -1;
   if (st == MSNAP_ST_OK) {
     const double *w = work + (size_t)d * M * 3;
-    double best = __builtin_inf(), bt = 0.0, low = __builtin_inf();
-    for (int k = 0; k < M; ++k) {
-      const double g = w[3 * k], t = w[3 * k + 1];
-      if (g < best || (g == best && t < bt)) {
-        best = g;
-        bt = t;
-      }
-      low = fmin(low, w[3 * k + 2]);
-    }
+    double best, bt, low;
+    fold_slots(w, M, best, bt, low);
     double x, y, z;
     position_at<NC>(coef, dur, (size_t)d * M, M, bt, x, y, z);
     double d2 = __builtin_inf();
@@ -339,8 +290,6 @@ mesh_clearance_fold_kernel(const double *__restrict__ coef, const double *__rest
   lower[d] = lo;
   status[d] = st;
 }
-
-unsigned blocks_of(size_t items, int threads) { return (unsigned)((items + threads - 1) / threads); }
 
 template <int NC>
 int launch(msnap_ctx *ctx, int N, int M, const double *coef, const double *dur, int n_tris, const double *tris,
@@ -384,7 +333,7 @@ static int mesh_clearance_args(const msnap_ctx *ctx, int n_drones, int n_seg, in
                                std::initializer_list<const void *> ptrs) {
   if (!ctx || n_drones < 0 || n_tris < 0) return MSNAP_EINVAL;
   if (int rc = check_seg(ctx, n_seg)) return rc;
-  if (((size_t)n_drones * n_seg + kClearanceThreads - 1) / kClearanceThreads > 0x7fffffffu) return MSNAP_EINVAL;   // grid size
+  if (int rc = check_walk_grid(n_drones, n_seg)) return rc;
   if (n_drones == 0) return kNoWork;
   if (n_tris > 0 && !tris) return MSNAP_EINVAL;
   for (const void *p : ptrs)

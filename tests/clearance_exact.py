@@ -10,19 +10,18 @@ against exact_clearance.  Not bit-exact with the kernel (no f
 from __future__ import annotations
 
 from fractions import Fraction
-from math import comb
 
 import mpmath
 import numpy as np
 
+import dyadic_walk as DW
+# (re-exported: the contract's constants that the mesh clearance shares, and the restatements' common pieces)
+from dyadic_walk import ABS_CLOSE, ABS_ROUND, EPS, REL_CLOSE, REL_ROUND, _bernstein_weights, _positions, _taylor  # noqa: F401
+
 DPS = 60
-# include/msnap.h, "pairwise clearance"
-REL_CLOSE = 1e-9        # lower >= min_dist (1 - REL_CLOSE) - ABS_CLOSE when the walk closes
-ABS_CLOSE = 1e-9
-REL_ROUND = 1e-13       # lower <= D (1 + REL_ROUND) + ABS_ROUND + C_ROUND 2^-52 R, and the same for D <= min_dist ...
-ABS_ROUND = 1e-13
+# include/msnap.h, "pairwise clearance": lower <= D (1 + REL_ROUND) + ABS_ROUND + C_ROUND 2^-52 R, the same for
+# D <= min_dist, and lower >= min_dist (1 - REL_CLOSE) - ABS_CLOSE when the walk closes
 C_ROUND = 8.0           # ten times the worst measured, 0.69 (tools/clearance_rounding.py), rounded up
-EPS = 2.0 ** -52
 # csrc/msnap_clearance.hip
 MAX_DEPTH = 40
 MAX_NODES = 4096
@@ -184,67 +183,21 @@ def pair_R(coef_a, dur_a, coef_b, dur_b):
 
 def round_terms(R):
     """The part of the rounding allowance that does not scale with the distance: ABS_ROUND + C_ROUND 2^-52 R."""
-    return ABS_ROUND + C_ROUND * EPS * R
+    return DW.round_terms(R, C_ROUND)
 
 
 def contract_violations(min_dist, lower, D, closed=True, R=0.0):
     """The inequalities of include/msnap.h that (min_dist, lower) break against the exact D (an mpf): a list of text.
     `R`: pair_R of the pair (0: the allowance without its coordinate term, which is stricter)."""
-    D = float(D)
-    bad = []
-    if not lower <= D * (1 + REL_ROUND) + round_terms(R):
-        bad.append(f"lower {lower!r} above D {D!r}")
-    if not D <= min_dist * (1 + REL_ROUND) + round_terms(R):
-        bad.append(f"min_dist {min_dist!r} below D {D!r}")
-    if closed and not lower >= min_dist * (1 - REL_CLOSE) - ABS_CLOSE - round_terms(R):
-        bad.append(f"lower {lower!r} not within the closed-walk bound of min_dist {min_dist!r}")
-    return bad
+    return DW.contract_violations(min_dist, lower, D, closed, R, C_ROUND, lower_le_min_dist=False)
 
 
 def round_ratio(min_dist, lower, D, R, attained=None):
-    """What C_ROUND has to cover, in units of 2^-52 R: the larger of lower - D and D - min_dist, less
-    the distance-relative part of the allowance (negative: no coordinate term is needed).  `attained`: the exact
-    distance at t_min -- then also |min_dist - attained|, the rounding of the attained value itself, which does not
-    depend on whether the walk happened to stop right at the infimum."""
-    D = float(D)
-    r = max(lower - D * (1 + REL_ROUND), D - min_dist * (1 + REL_ROUND))
-    if attained is not None:
-        r = max(r, abs(min_dist - float(attained)) - REL_ROUND * float(attained))
-    return r / (EPS * R)
+    """What C_ROUND has to cover, in units of 2^-52 R: dyadic_walk.round_ratio."""
+    return DW.round_ratio(min_dist, lower, D, R, attained)
 
 
 # ------------------------------------------------------------------------------------------------ fp64 restatement
-def _bernstein_weights(n):
-    w = np.zeros((n + 1, n + 1))
-    for i in range(n + 1):
-        for k in range(i + 1):
-            w[i, k] = comb(i, k) / comb(n, k)
-    return w
-
-
-def _taylor(c, a):
-    """c [L, D + 1] (ascending) -> coefficients of c(x + a), a [L]; in place on a copy."""
-    c = c.copy()
-    D = c.shape[1] - 1
-    for k in range(D):
-        for j in range(D - 1, k - 1, -1):
-            c[:, j] = a * c[:, j + 1] + c[:, j]
-    return c
-
-
-def _positions(coef, dur, d, t):
-    """msnap_eval_flat's lookup and Horner: positions [P, 3] of drones d [P] at absolute times t [P]."""
-    K = np.add.accumulate(dur[d], axis=1)
-    seg = np.minimum((t[:, None] > K).sum(axis=1), dur.shape[1] - 1)
-    off = np.concatenate([np.zeros((len(d), 1)), K], axis=1)[np.arange(len(d)), seg]
-    tl = t - off
-    c = coef[d, seg, :3, :]                       # [P, 3, nc]
-    v = np.zeros((len(d), 3))
-    for j in range(c.shape[2] - 1, -1, -1):
-        v = v * tl[:, None] + c[:, :, j]
-    return v
-
-
 def fp64_clearance(coef, dur, pairs, stats=None):
     """coef [N, M, 4, nc], dur [N, M], pairs [P, 2] (valid, finite) -> (min_dist [P], t_min [P], lower [P]) by the
     kernel's method in NumPy fp64.  `stats` (a dict) receives the nodes per live lane ("nodes") and the lanes that met
@@ -274,18 +227,7 @@ def fp64_clearance(coef, dur, pairs, stats=None):
             e[:, ax, :] += sign * _taylor(coef[drone, seg, ax, :], t0 - off)
     e *= (h[:, None] ** np.arange(D + 1))[:, None, :]
 
-    best = np.full(L, np.inf)
-    best_u = np.zeros(L)
-    low = np.full(L, np.inf)
-    root = np.full(L, np.inf)
-    idx = np.zeros(L, dtype=np.uint64)
-    lvl = np.zeros(L, dtype=np.int64)
-    nodes = np.zeros(L, dtype=np.int64)
-    capped = np.zeros(L, dtype=bool)
-    act = np.arange(L)
-    while len(act):
-        hh = np.ldexp(1.0, -lvl[act])
-        a = idx[act].astype(np.float64) * hh
+    def node(act, a, hh, best, best_u):
         G = np.zeros((len(act), n + 1))
         g0 = np.zeros(len(act))
         gm = np.zeros(len(act))
@@ -303,34 +245,10 @@ def fp64_clearance(coef, dur, pairs, stats=None):
             gm += vm ** 2
             g1 += v1 ** 2
         bound = (G @ Wt.T).min(axis=1)
-        nb, nu = best[act].copy(), best_u[act].copy()
-        for gv, uv in ((g0, a), (gm, a + 0.5 * hh), (g1, a + hh)):
-            take = (gv < nb) | ((gv == nb) & (uv < nu))
-            nb = np.where(take, gv, nb)
-            nu = np.where(take, uv, nu)
-        best[act], best_u[act] = nb, nu
-        at_cap = lvl[act] >= MAX_DEPTH
-        split = (bound < nb - PRUNE_REL * nb - PRUNE_ABS) & ~at_cap
-        ix = idx[act]
-        up = np.zeros(len(act), dtype=np.int64)
-        tmp = ix.copy()
-        while True:                                   # trailing ones of idx
-            m = (tmp & np.uint64(1)) == 1
-            if not m.any():
-                break
-            up += m
-            tmp = np.where(m, tmp >> np.uint64(1), tmp)
-        first = nodes[act] == 0
-        root[act] = np.where(first, bound, root[act])
-        nodes[act] += 1
-        finished = ~split & (up == lvl[act])
-        guard = ~finished & (nodes[act] >= MAX_NODES)
-        lw = np.where(split, low[act], np.minimum(low[act], bound))
-        low[act] = np.where(guard, np.minimum(lw, root[act]), lw)
-        capped[act] |= guard | (~split & at_cap & (bound < nb - PRUNE_REL * nb - PRUNE_ABS))
-        idx[act] = np.where(split, ix << np.uint64(1), (ix >> up.astype(np.uint64)) + np.uint64(1))
-        lvl[act] = np.where(split, lvl[act] + 1, lvl[act] - up)
-        act = act[~(finished | guard)]
+        nb, nu = DW.take_attained(((g0, a), (gm, a + 0.5 * hh), (g1, a + hh)), best, best_u)
+        return bound, nb, nu, bound < nb - PRUNE_REL * nb - PRUNE_ABS
+
+    best, best_u, low, nodes, capped = DW.walk(L, node, MAX_DEPTH, MAX_NODES)
 
     tm = np.minimum(h * best_u + t0, E)
     g_pair = np.full(P, np.inf)

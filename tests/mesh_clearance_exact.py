@@ -16,14 +16,13 @@ from fractions import Fraction
 import mpmath
 import numpy as np
 
-import clearance_exact as CE
-from clearance_exact import DPS, EPS, _mpf, _shift, _squarefree, knots
+import clearance_exact as CE  # noqa: F401 (ME.CE: the pairwise module, for the tests that use both)
+import dyadic_walk as DW
+from clearance_exact import DPS, _mpf, _shift, _squarefree, knots
+from dyadic_walk import ABS_CLOSE, ABS_ROUND, EPS, REL_CLOSE, REL_ROUND  # noqa: F401 (re-exported)
 
-# include/msnap.h, "mesh clearance"
-REL_CLOSE = 1e-9        # lower >= min_dist (1 - REL_CLOSE) - ABS_CLOSE - r when the walk closes
-ABS_CLOSE = 1e-9
-REL_ROUND = 1e-13       # lower <= D (1 + REL_ROUND) + r and D <= min_dist (1 + REL_ROUND) + r,
-ABS_ROUND = 1e-13       # r = ABS_ROUND + C_ROUND_MESH 2^-52 R
+# include/msnap.h, "mesh clearance": lower <= D (1 + REL_ROUND) + r, D <= min_dist (1 + REL_ROUND) + r, lower <= min_dist,
+# and lower >= min_dist (1 - REL_CLOSE) - ABS_CLOSE - r when the walk closes; r = ABS_ROUND + C_ROUND_MESH 2^-52 R
 C_ROUND_MESH = 3.0      # ten times the worst measured, 0.271 (tools/mesh_clearance_rounding.py), rounded up
 # csrc/msnap_mesh_clearance.hip
 MAX_DEPTH = 40
@@ -105,33 +104,18 @@ def mesh_R(coef_d, dur_d, tris):
 
 
 def round_terms(R):
-    return ABS_ROUND + C_ROUND_MESH * EPS * R
+    return DW.round_terms(R, C_ROUND_MESH)
 
 
 def contract_violations(min_dist, lower, D, closed=True, R=0.0):
     """The inequalities of include/msnap.h that (min_dist, lower) break against the exact D: a list of text.  `R`:
     mesh_R (0: the allowance without its coordinate term, which is stricter)."""
-    D = float(D)
-    bad = []
-    if not lower <= D * (1 + REL_ROUND) + round_terms(R):
-        bad.append(f"lower {lower!r} above D {D!r}")
-    if not D <= min_dist * (1 + REL_ROUND) + round_terms(R):
-        bad.append(f"min_dist {min_dist!r} below D {D!r}")
-    if not lower <= min_dist:
-        bad.append(f"lower {lower!r} above min_dist {min_dist!r}")
-    if closed and not lower >= min_dist * (1 - REL_CLOSE) - ABS_CLOSE - round_terms(R):
-        bad.append(f"lower {lower!r} not within the closed-walk bound of min_dist {min_dist!r}")
-    return bad
+    return DW.contract_violations(min_dist, lower, D, closed, R, C_ROUND_MESH, lower_le_min_dist=True)
 
 
 def round_ratio(min_dist, lower, D, R, attained=None):
-    """What C_ROUND_MESH has to cover, in units of 2^-52 R: the largest of lower - D, D - min_dist and (attained: the
-    exact distance at t_min) |min_dist - attained|, each less the distance-relative part of the allowance."""
-    D = float(D)
-    r = max(lower - D * (1 + REL_ROUND), D - min_dist * (1 + REL_ROUND))
-    if attained is not None:
-        r = max(r, abs(min_dist - float(attained)) - REL_ROUND * float(attained))
-    return r / (EPS * R)
+    """What C_ROUND_MESH has to cover, in units of 2^-52 R: dyadic_walk.round_ratio."""
+    return DW.round_ratio(min_dist, lower, D, R, attained)
 
 
 # ------------------------------------------------------------------------------------------------ exact reference
@@ -350,7 +334,7 @@ def fp64_mesh_clearance(coef, dur, tris, stats=None):
     degen, normals = tri_degenerate(tris), unit_normals(tris)
     N, M, nc = dur.shape[0], dur.shape[1], coef.shape[3]
     D = nc - 1
-    Wt = CE._bernstein_weights(D)
+    Wt = DW._bernstein_weights(D)
     K = np.add.accumulate(dur, axis=1)
     start = np.concatenate([np.zeros((N, 1)), K[:, :-1]], axis=1).reshape(-1)
     T = dur.reshape(-1)
@@ -359,86 +343,49 @@ def fp64_mesh_clearance(coef, dur, tris, stats=None):
     e = coef[:, :, :3, :].reshape(L, 3, nc) * (T[:, None] ** np.arange(nc))[:, None, :]
     tmin_box, tmax_box = tris.min(axis=1), tris.max(axis=1)               # [T, 3]
 
-    best = np.full(L, np.inf)
-    best_u = np.zeros(L)
-    low = np.full(L, np.inf)
-    root = np.full(L, np.inf)
-    idx = np.zeros(L, dtype=np.uint64)
-    lvl = np.zeros(L, dtype=np.int64)
-    nodes = np.zeros(L, dtype=np.int64)
-    capped = np.zeros(L, dtype=bool)
-    act = np.arange(L)
+    def node(act, a, hh, best, best_u):
+        A = len(act)
+        scale = hh[:, None] ** np.arange(nc)
+        B = np.zeros((A, 3, nc))
+        P = np.zeros((A, 3, 3))                                       # [lane, point, axis]
+        for s in range(3):
+            f = DW._taylor(e[act, s, :], a) * scale
+            vm = np.zeros(A)
+            for j in range(D, -1, -1):
+                vm = vm * 0.5 + f[:, j]
+            P[:, 0, s], P[:, 1, s], P[:, 2, s] = f[:, 0], vm, f[:, ::-1].cumsum(axis=1)[:, -1]
+            B[:, s, :] = f @ Wt.T
+        lo, hi = B.min(axis=2), B.max(axis=2)                         # [A, 3]
+        sb0 = np.sqrt(best)
+        thr0 = sb0 - PRUNE_REL * sb0 - PRUNE_ABS
+        nb, nu = best, best_u
+        bound = np.full(A, np.inf)
+        if Tn:
+            gap = np.maximum(0.0, np.maximum(lo[:, None, :] - tmax_box[None], tmin_box[None] - hi[:, None, :]))
+            lb2 = (gap * gap).sum(axis=2)                             # [A, T]
+            need = ~((thr0 > 0.0)[:, None] & (lb2 >= (thr0 * thr0)[:, None]))
+            q, d2 = closest_np(P, tris, degen, normals)               # [A, 3, T, 3], [A, 3, T]
+            d2n = np.where(need[:, None, :], d2, np.inf).min(axis=2)
+            nb, nu = DW.take_attained(((d2n[:, 0], a), (d2n[:, 1], a + 0.5 * hh), (d2n[:, 2], a + hh)), best, best_u)
+            fi = np.where(d2[:, 1] > d2[:, 0], np.where(d2[:, 2] > d2[:, 1], 2, 1), np.where(d2[:, 2] > d2[:, 0], 2, 0))
+            ai, ti = np.arange(A)[:, None], np.arange(Tn)[None, :]
+            dirv = P[ai, fi, :] - q[ai, fi, ti, :]                    # [A, T, 3]
+            ln = np.sqrt((dirv * dirv).sum(axis=2))
+            dirv = dirv * np.where(ln > 0, 1.0 / np.where(ln > 0, ln, 1.0), 0.0)[..., None]
+            pn = np.einsum("tk,akd->atd", normals, B)
+            pa = np.einsum("atk,akd->atd", dirv, B)
+            sn = np.einsum("tk,tjk->tj", normals, tris)               # [T, 3]
+            sa = np.einsum("atk,tjk->atj", dirv, tris)
+            tb = np.fmax(np.fmax(pn.min(axis=2) - sn.max(axis=1)[None], sn.min(axis=1)[None] - pn.max(axis=2)),
+                         pa.min(axis=2) - sa.max(axis=2))
+            bound = np.where(need, tb, np.inf).min(axis=1)
+            skipped = np.where(need, np.inf, lb2).min(axis=1)
+            bound = np.fmin(bound, np.fmax(np.sqrt(skipped), thr0))
+        sb = np.sqrt(nb)
+        return bound, nb, nu, bound < sb - PRUNE_REL * sb - PRUNE_ABS
+
     with np.errstate(all="ignore"):
-        while len(act):
-            A = len(act)
-            hh = np.ldexp(1.0, -lvl[act])
-            a = idx[act].astype(np.float64) * hh
-            scale = hh[:, None] ** np.arange(nc)
-            B = np.zeros((A, 3, nc))
-            P = np.zeros((A, 3, 3))                                       # [lane, point, axis]
-            for s in range(3):
-                f = CE._taylor(e[act, s, :], a) * scale
-                vm = np.zeros(A)
-                for j in range(D, -1, -1):
-                    vm = vm * 0.5 + f[:, j]
-                P[:, 0, s], P[:, 1, s], P[:, 2, s] = f[:, 0], vm, f[:, ::-1].cumsum(axis=1)[:, -1]
-                B[:, s, :] = f @ Wt.T
-            lo, hi = B.min(axis=2), B.max(axis=2)                         # [A, 3]
-            sb0 = np.sqrt(best[act])
-            thr0 = sb0 - PRUNE_REL * sb0 - PRUNE_ABS
-            nb, nu = best[act].copy(), best_u[act].copy()
-            bound = np.full(A, np.inf)
-            if Tn:
-                gap = np.maximum(0.0, np.maximum(lo[:, None, :] - tmax_box[None], tmin_box[None] - hi[:, None, :]))
-                lb2 = (gap * gap).sum(axis=2)                             # [A, T]
-                need = ~((thr0 > 0.0)[:, None] & (lb2 >= (thr0 * thr0)[:, None]))
-                q, d2 = closest_np(P, tris, degen, normals)               # [A, 3, T, 3], [A, 3, T]
-                d2n = np.where(need[:, None, :], d2, np.inf)
-                for k, uv in enumerate((a, a + 0.5 * hh, a + hh)):
-                    gv = d2n[:, k, :].min(axis=1)
-                    take = (gv < nb) | ((gv == nb) & (uv < nu))
-                    nb = np.where(take, gv, nb)
-                    nu = np.where(take, uv, nu)
-                fi = np.where(d2[:, 1] > d2[:, 0], np.where(d2[:, 2] > d2[:, 1], 2, 1), np.where(d2[:, 2] > d2[:, 0], 2, 0))
-                ai, ti = np.arange(A)[:, None], np.arange(Tn)[None, :]
-                dirv = P[ai, fi, :] - q[ai, fi, ti, :]                    # [A, T, 3]
-                ln = np.sqrt((dirv * dirv).sum(axis=2))
-                dirv = dirv * np.where(ln > 0, 1.0 / np.where(ln > 0, ln, 1.0), 0.0)[..., None]
-                pn = np.einsum("tk,akd->atd", normals, B)
-                pa = np.einsum("atk,akd->atd", dirv, B)
-                sn = np.einsum("tk,tjk->tj", normals, tris)               # [T, 3]
-                sa = np.einsum("atk,tjk->atj", dirv, tris)
-                tb = np.fmax(np.fmax(pn.min(axis=2) - sn.max(axis=1)[None], sn.min(axis=1)[None] - pn.max(axis=2)),
-                             pa.min(axis=2) - sa.max(axis=2))
-                bound = np.where(need, tb, np.inf).min(axis=1)
-                skipped = np.where(need, np.inf, lb2).min(axis=1)
-                bound = np.fmin(bound, np.fmax(np.sqrt(skipped), thr0))
-            best[act], best_u[act] = nb, nu
-            sb = np.sqrt(nb)
-            thr = sb - PRUNE_REL * sb - PRUNE_ABS
-            at_cap = lvl[act] >= MAX_DEPTH
-            wants = bound < thr
-            split = wants & ~at_cap
-            ix = idx[act]
-            up = np.zeros(A, dtype=np.int64)
-            tmp = ix.copy()
-            while True:
-                m = (tmp & np.uint64(1)) == 1
-                if not m.any():
-                    break
-                up += m
-                tmp = np.where(m, tmp >> np.uint64(1), tmp)
-            first = nodes[act] == 0
-            root[act] = np.where(first, bound, root[act])
-            nodes[act] += 1
-            finished = ~split & (up == lvl[act])
-            guard = ~finished & (nodes[act] >= MAX_NODES)
-            lw = np.where(split, low[act], np.fmin(low[act], bound))
-            low[act] = np.where(guard, np.fmin(lw, root[act]), lw)
-            capped[act] |= guard | (wants & at_cap)
-            idx[act] = np.where(split, ix << np.uint64(1), (ix >> up.astype(np.uint64)) + np.uint64(1))
-            lvl[act] = np.where(split, lvl[act] + 1, lvl[act] - up)
-            act = act[~(finished | guard)]
+        best, best_u, low, nodes, capped = DW.walk(L, node, MAX_DEPTH, MAX_NODES)
 
         tm = np.minimum(T * best_u + start, E)
         best, tm, low = best.reshape(N, M), tm.reshape(N, M), low.reshape(N, M)
@@ -446,7 +393,7 @@ def fp64_mesh_clearance(coef, dur, tris, stats=None):
         t_d = np.where(best == g[:, None], tm, np.inf).min(axis=1)
         t_d = np.where(np.isfinite(t_d), t_d, 0.0)
         low_d = low.min(axis=1)
-        pos = CE._positions(coef, dur, np.arange(N), t_d)
+        pos = DW._positions(coef, dur, np.arange(N), t_d)
         if Tn:
             _, d2 = closest_np(pos, tris, degen, normals)                 # [N, T]
             tri = d2.argmin(axis=1)
