@@ -588,7 +588,11 @@ def default_sample_count(total_duration: float, dt: float) -> int:
 
 
 # ---- certified clearance of a swarm: the sampled pass decides what it can, the exact kernel sees the rest ------------
-PEAK_MARGIN = 2e-9       # V_i = peak (1 + 2e-9): the peaks' contract (include/msnap.h), so that V_i bounds the true speed
+# V_i = peak (1 + 2e-9) exceeds the true speed S by the peaks' contract (include/msnap.h: S (1 - 1e-9) <= peak + 1e-12
+# + r_0) wherever 1e-12 + r_0 <= 9e-10 peak: then S <= peak (1 + 9e-10) / (1 - 1e-9) < peak (1 + 2e-9).  That is a speed
+# of at least 2e-3 m/s (1e-12 <= 5e-10 peak) with r_0 <= 4e-10 peak.  A solved path has r_0 around 1e-14 of its peak;
+# hand-made coefficients that cancel to 1e-5 of their size do not qualify.
+PEAK_MARGIN = 2e-9
 COMPARE_MARGIN = 1e-9    # relative margin of the fp64 compares against 2 radius + (V_i + V_j) gap
 
 

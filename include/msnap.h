@@ -263,10 +263,42 @@ int msnap_snap_cost_device(msnap_ctx *ctx, int n_drones, int n_seg, const double
  *   q = 1  acceleration  max |p''(t)|
  *   q = 2  jerk          max |p'''(t)|
  *   q = 3  yaw rate      max |psi'(t)|
- *   peak   [n_drones][4]  a value the trajectory ATTAINS (SI units), at
- *   t_peak [n_drones][4]  absolute time.  If S is the supremum for the exact real polynomials of the fp64
- *                         coefficients: S (1 - 1e-9) - 1e-12 <= peak <= S (1 + 1e-12) + 1e-12.  Ties and near-ties:
- *                         the larger value, then the earlier time.  A stationary drone reports peaks <= 1e-12.
+ *   peak   [n_drones][4]  a value the trajectory ATTAINS (SI units), up to rounding (below), at
+ *   t_peak [n_drones][4]  absolute time, 0 <= t_peak <= sum(dur) as msnap_eval_flat accumulates it (both ends
+ *                         included: msnap_eval_flat at t_peak is finite).  If S is the supremum for the exact real
+ *                         polynomials of the fp64 coefficients:
+ *                           S (1 - 1e-9) - 1e-12 - r_q  <=  peak  <=  S (1 + 1e-12) + 1e-12 + r_q
+ *                           r_q = C_ROUND_PEAKS * 2^-52 * R_q,   C_ROUND_PEAKS = 17
+ *                         R_q is the size of what the value is summed from: the largest value, over the quantity's
+ *                         axes and the drone's segments i, of sum_j |d_j| T_i^j, d the coefficients of the r-th
+ *                         derivative of that axis (r = q + 1; yaw rate: r = 1) and T_i the segment's duration.  peak is
+ *                         the segment's polynomial at its local time T_i u, recomputed by msnap_eval_flat's Horner,
+ *                         which is good to an ulp of that sum, not of the value: for a solved path r_q is some 1e-14
+ *                         of the peak, for a segment whose speed oscillates between equal extrema (R_q 2e4 to 7e5
+ *                         times the value) 1e-10 to 3e-9 of it.  (C_ROUND_PEAKS: ten times the worst
+ *                         |peak - exact value at T_i u| / (2^-52 R_q) measured, 1.64 -- DESIGN.md §5 K7.)
+ *                         t_peak = (start of the segment, the running fp64 sum of dur) + T_i u is rounded once more,
+ *                         by up to half an ulp of t_peak, and r_q does NOT cover what that does to the value: on a
+ *                         steep flank 1500 segments into a path the exact polynomial at t_peak differs from peak
+ *                         by 7 times r_q, and by more further on.  What holds is
+ *                           | peak - |p^(r)(t_peak)| |  <=  r_q + 2^-52 * t_peak * R'_q
+ *                         with R'_q the size of the NEXT derivative, the largest sum_j j |d_j| T_i^(j-1) over the same
+ *                         axes and segments (proven: half an ulp of t_peak times that sum per axis, sqrt(3) for the
+ *                         norm), the polynomial being that of the segment msnap_eval_flat's lookup selects at t_peak.
+ *                         The second term is zero at t_peak = 0 and negligible where the peak is a stationary point
+ *                         of the quantity -- every interior peak of a solved path.  The inequality against S does not
+ *                         involve t_peak.  A caller computes R_q and R'_q from coef and dur alone.
+ *                         Ties and near-ties: the larger value, then the earlier time.  A stationary drone reports
+ *                         peaks <= 1e-12.
+ *                         Coefficient sets whose derivative of order r jumps at a knot (no solve produces one): the
+ *                         peak may sit on either side of the jump; t_peak names the knot, and the value is that of
+ *                         the segment that holds it.  msnap_eval_flat at the same time evaluates the EARLIER segment, so
+ *                         it gives the peak back only when that one holds it.
+ *                         The search ends a lane at 40 bisections of a segment or 4096 nodes with the best value seen;
+ *                         no status is raised for it, and the inequality above is not proven for such a lane (the
+ *                         clearances carry a proven bound for theirs; the peaks do not).  No input is known that gets
+ *                         there: the most found is 183 nodes, on the order-9 equioscillating speed, and none of the
+ *                         families of tools/limits_rounding.py meets a cap.
  *   status [n_drones]     msnap_status: MSNAP_ST_NONFINITE for a NaN / Inf coefficient or duration (what a failed
  *                         solve leaves), else MSNAP_ST_TIMES for a duration <= 0; peak and t_peak are NaN then.
  * A drone's results are bit-identical whatever its position in the batch, the batch size, or host versus device entry.

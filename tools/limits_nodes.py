@@ -7,47 +7,15 @@ prune rule and stackless walk; no GPU needed): mean per (drone, segment, quantit
 """
 import os
 import sys
-from math import comb
 
 import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle"))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")):
+    sys.path.insert(0, p)
+import limits_exact as LE  # noqa: E402  (fp64_walk_peaks: the restated walk)
 import msnap_oracle as O  # noqa: E402  (the CPU solve, tools only)
 from drone_path_planning_python_amd.synthetic import swarm  # noqa: E402
-
-PRUNE_REL, PRUNE_ABS, MAX_DEPTH, MAX_NODES = 1e-9, 1e-26, 40, 4096
-
-
-def lane_nodes(e):
-    """e [3, D+1]: the lane's component polynomials in u.  Returns the nodes its walk visits."""
-    D = e.shape[1] - 1
-    n = 2 * D
-    W = np.array([[comb(i, k) / comb(n, k) if k <= i else 0.0 for k in range(n + 1)] for i in range(n + 1)])
-    best, idx, lvl, nodes = -1.0, 0, 0, 0
-    while True:
-        h = 2.0 ** -lvl
-        a = idx * h
-        f = e.copy()
-        for k in range(D):
-            for j in range(D - 1, k - 1, -1):
-                f[:, j] += a * f[:, j + 1]
-        f *= h ** np.arange(D + 1)
-        G = np.zeros(n + 1)
-        for s in range(3):
-            G += np.convolve(f[s], f[s])
-        bound = (W @ G).max()
-        vals = [np.sum(f[:, 0] ** 2), np.sum(np.polynomial.polynomial.polyval(0.5, f.T) ** 2), np.sum(f.sum(axis=1) ** 2)]
-        best = max(best, *vals)
-        nodes += 1
-        split = bound > best * (1 + PRUNE_REL) + PRUNE_ABS and lvl < MAX_DEPTH
-        if split:
-            idx, lvl = idx << 1, lvl + 1
-            continue
-        up = ((~idx) & (idx + 1)).bit_length() - 1
-        if up == lvl or nodes >= MAX_NODES:
-            return nodes
-        idx, lvl = (idx >> up) + 1, lvl - up
 
 
 def main():
@@ -57,19 +25,8 @@ def main():
     nc = order + 1
     wp, t = swarm(40 + order, N, M)
     coef, dur = O.solve_batch_fast(wp, t, ncoef=nc)
-    counts = []
-    for d in range(N):
-        for i in range(M):
-            for q in range(4):
-                r, axes = (q + 1, (0, 1, 2)) if q < 3 else (1, (3,))
-                e = np.zeros((3, nc - 1))
-                for s, a in enumerate(axes):
-                    c = coef[d, i, a]
-                    for _ in range(r):
-                        c = c[1:] * np.arange(1, len(c))
-                    e[s, :len(c)] = c * dur[d, i] ** np.arange(len(c))
-                counts.append(lane_nodes(e))
-    c = np.array(counts)
+    _, _, nodes, _ = LE.fp64_walk_peaks(coef, dur)
+    c = nodes.reshape(-1)
     waves = c[: len(c) // 64 * 64].reshape(-1, 64).max(axis=1)
     print(f"order {order}, {N} x {M}: nodes per item mean {c.mean():.1f} (q: "
           + ", ".join(f"{c.reshape(-1, 4)[:, q].mean():.1f}" for q in range(4))
