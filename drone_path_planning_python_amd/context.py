@@ -533,6 +533,33 @@ class Context:
                                                            int(n_tris), _ptr(tris), _ptr(min_dist), _ptr(t_min),
                                                            _ptr(tri_min), _ptr(lower), _ptr(status)))
 
+    # ---- path extent in continuous time (include/msnap.h) --------------------------------
+    def path_extent(self, coef, dur, dirs):
+        """Certified reach of each drone's whole path in the directions `dirs` [K, 3]: (ext [N, K], t_ext [N, K],
+        upper [N, K], status [N] int32) with ext <= sup_t n.p(t) <= upper, ext attained at t_ext (msnap_path_extent).
+        The six signed axes give a path's certified bounding box."""
+        coef, pc, dur, pd, N, M = self._coef_dur(coef, dur)
+        dr, pdr = _host(dirs, np.float64)
+        if dr.ndim != 2 or dr.shape[1] != 3:
+            raise ValueError("dirs must be [K, 3]")
+        K = dr.shape[0]
+        ext = np.empty((N, K), dtype=np.float64)
+        t_ext = np.empty((N, K), dtype=np.float64)
+        upper = np.empty((N, K), dtype=np.float64)
+        status = np.empty((N,), dtype=np.int32)
+        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)      # noqa: E731
+        with self._lock:
+            self._ck(self._lib.msnap_path_extent(self._h, N, M, pc, pd, K, pdr, vp(ext), vp(t_ext), vp(upper),
+                                                 vp(status)))
+        return ext, t_ext, upper, status
+
+    def path_extent_device(self, n_drones, n_seg, coef, dur, n_dirs, dirs, ext, t_ext, upper, status):
+        """Device pointers (dirs float64 [n_dirs, 3], status int32), asynchronous on the context's stream."""
+        with self._lock:
+            self._ck(self._lib.msnap_path_extent_device(self._h, int(n_drones), int(n_seg), _ptr(coef), _ptr(dur),
+                                                        int(n_dirs), _ptr(dirs), _ptr(ext), _ptr(t_ext), _ptr(upper),
+                                                        _ptr(status)))
+
     # ---- near pairs (include/msnap.h) ---------------------------------------------
     def near_pairs(self, pos, base: float, speed=None, gap: float = 0.0, margin: float = 0.0, max_pairs=None):
         """(pairs int32 [P, 2], dist [P]): every pair i < j of the swarm `pos` [N, S, 3] whose sampled distance is below

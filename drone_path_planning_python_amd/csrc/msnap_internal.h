@@ -72,6 +72,7 @@ struct msnap_ctx {
                                // side of solve_host's bounce buffer and its shared time grid when chunked
   msnap::DevBuf collide_work;  // the pairwise pass's working set (msnap_collide.hip, launch_formation_collide[_part])
   msnap::DevBuf limits_work;   // msnap_limits.hip: per-(drone, segment, quantity) peaks, then the retiming's per-drone peaks
+  msnap::DevBuf extent_work;   // msnap_extent.hip: per-(drone, direction, segment) results, then the per-(drone, segment) flags
   msnap::DevBuf clearance_work;   // msnap_clearance.hip: per-(pair, slot) results, then the per-(drone, segment) flags
   msnap::DevBuf mesh_clearance_work;   // msnap_mesh_clearance.hip: per-(drone, segment) results, then the per-(drone, segment) flags
   msnap::DevBuf pairs_work;       // msnap_pairs.hip: the row image, the keep-bit matrix, the rows' counts and list offsets
@@ -240,6 +241,18 @@ inline size_t near_pairs_work_bytes(int N, int S) {
 inline int check_walk_grid(int n_drones, int n_seg) {
   return ((size_t)n_drones * n_seg + kClearanceThreads - 1) / kClearanceThreads > 0x7fffffffu ? MSNAP_EINVAL : MSNAP_OK;
 }
+// path extent (msnap_extent.hip): one lane per (drone, segment, direction), one fold thread per (drone, direction).
+// ctx->extent_work: per-lane results [N][K][M][3] doubles, then the flags [N M] int32
+inline size_t extent_lanes(int N, int M, int K) { return (size_t)N * M * K; }
+inline size_t extent_work_bytes(int N, int M, int K) {
+  return extent_lanes(N, M, K) * 3 * sizeof(double) + (size_t)N * M * sizeof(int32_t);
+}
+inline int check_extent_grid(int n_drones, int n_seg, int n_dirs) {
+  if ((extent_lanes(n_drones, n_seg, n_dirs) + kClearanceThreads - 1) / kClearanceThreads > 0x7fffffffu) return MSNAP_EINVAL;   // grid size
+  return check_walk_grid(n_drones, n_seg);
+}
+int launch_path_extent(msnap_ctx *ctx, int N, int M, const double *coef, const double *dur, int K, const double *dirs,
+                       double *ext, double *t_ext, double *upper, int32_t *status);
 inline int check_clearance_args(const msnap_ctx *ctx, int n_drones, int n_seg, int n_pairs) {
   if (!ctx || n_drones < 0 || n_pairs < 0) return MSNAP_EINVAL;
   if (n_seg < 1 || n_seg > ctx->max_segments) return MSNAP_ESEGMENTS;

@@ -1,11 +1,13 @@
-// The certified walk over a path, and what its three instances share: peaks_lane_kernel (msnap_limits.hip, K7: a
-// supremum), clearance_lane_kernel (msnap_clearance.hip, K9: a minimum between two drones) and
-// mesh_clearance_lane_kernel (msnap_mesh_clearance.hip, K11: a minimum against a mesh).  DESIGN.md §5 K7 has the method.
+// The certified walk over a path, and what its four instances share: peaks_lane_kernel (msnap_limits.hip, K7: a
+// supremum), clearance_lane_kernel (msnap_clearance.hip, K9: a minimum between two drones),
+// mesh_clearance_lane_kernel (msnap_mesh_clearance.hip, K11: a minimum against a mesh) and extent_lane_kernel
+// (msnap_extent.hip, K12: a supremum in a direction, walked as the minimum of the negated polynomial).  DESIGN.md §5 K7
+// has the method.
 //
 // Walk.  Branch and bound over the dyadic sub-intervals [idx 2^-lvl, (idx + 1) 2^-lvl] of u in [0, 1].  Per node:
 //   1. shift_scale: the Taylor shift of each component polynomial to the node's start, then the scaling by 2^-lvl
 //      (exact), so that the node is x in [0, 1];
-//   2. a bound of the quantity over the node (K7, K9: squares_bound; K11: its own, from the control points);
+//   2. a bound of the quantity over the node (K7, K9: squares_bound; K11, K12: their own, from the control points);
 //   3. attained values at x = 0, 1/2, 1 (values_at_ends_and_middle, squares_at_ends_and_middle), kept by take_attained:
 //      the better value, then the earlier time;
 //   4. split, or prune against the best attained value (the kernel's own kPruneRel, kPruneAbs), down to kMaxDepth;
@@ -13,10 +15,10 @@
 //      one, found with one count of trailing ones.
 // The loop is wave-uniform: `while (__ballot(active) != 0)`, every lane runs the same body while any lane
 // of the wave has nodes, every per-lane commit is a select under `if (active)`.  A lane must never leave it alone.
-// K9 and K11 also carry what the walk has proven (ProvenBound), write one (value, time, bound) triple per lane
-// (store_lane) and fold a row of them (fold_slots).
+// K9, K11 and K12 also carry what the walk has proven (ProvenBound) and write one (value, time, bound) triple per lane
+// (store_lane); K9 and K11 fold a row of them with fold_slots.
 //
-// Also here: the per-(drone, segment) flags launch and the position of a drone at an absolute time (K9, K11).
+// Also here: the per-(drone, segment) flags launch and the position of a drone at an absolute time (K9, K11, K12).
 // Internal linkage: each translation unit instantiates its own kernels, and names its own kThreads.
 #pragma once
 

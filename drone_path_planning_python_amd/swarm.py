@@ -226,6 +226,23 @@ class DeviceCompute:
             self.ctx.mesh_clearance_device(n, M, coef, dur, tris.shape[0], tris.contiguous(), md, tm, tri, lower, status)
         return md, tm, tri, lower, status
 
+    # ---- path extent in continuous time (include/msnap.h) ------------------------------------------------------------
+    def path_extent(self, coef, dur, dirs):
+        """(ext [n, K], t_ext [n, K], upper [n, K], status [n] int32): the certified reach of each drone's whole path in
+        the directions `dirs` [K, 3], ext <= sup_t n.p(t) <= upper.  With K == 0 the call does nothing (status too)."""
+        torch = self.torch
+        n, M = dur.shape
+        if dirs.dim() != 2 or dirs.shape[1] != 3 or dirs.dtype != torch.float64:
+            raise ValueError("path_extent: dirs must be a float64 tensor [K, 3]")
+        K = dirs.shape[0]
+        ext = self._out("path_extent.ext", (n, K), torch.float64)
+        t_ext = self._out("path_extent.t_ext", (n, K), torch.float64)
+        upper = self._out("path_extent.upper", (n, K), torch.float64)
+        status = self._out("path_extent.status", (n,), torch.int32)
+        if n and K:
+            self.ctx.path_extent_device(n, M, coef, dur, K, dirs.contiguous(), ext, t_ext, upper, status)
+        return ext, t_ext, upper, status
+
     # ---- near pairs (include/msnap.h) -------------------------------------------------------------------------------
     _near_pairs_first_capacity = None      # (tests force a tiny first capacity through this)
 
@@ -785,3 +802,100 @@ def certify_mesh_clearance(compute, coef, dur, tris, radius: float, dt: float, n
     undecided = (~hit) & (certified < radius)
     return MeshClearanceResult(min_dist, t_min, triangle, certified, hit, undecided, cleared, d, shit, gap,
                                int(idx_u.numel()))
+
+
+# ---- certified geofence: a box and / or half-spaces against the support function of every path ----------------------
+GEOFENCE_INSIDE, GEOFENCE_OUTSIDE, GEOFENCE_UNDECIDED, GEOFENCE_FAILED = 0, 1, 2, 3
+
+
+@dataclass
+class GeofenceResult:
+    verdict: object           # [N] int8: GEOFENCE_INSIDE / _OUTSIDE / _UNDECIDED / _FAILED
+    inside: object            # [N] bool: every upper is below its limit (certified)
+    outside: object           # [N] bool: some ext exceeds its limit (definite: the value is attained)
+    undecided: object         # [N] bool: neither -- only possible within the closing gap of msnap_path_extent
+    failed: object            # [N] bool: status != 0, the solve's or msnap_path_extent's: nothing is certified
+    worst: object             # [N] int64: the constraint with the largest ext - limit (index into `normals`; -1: failed)
+    t_worst: object           # [N] the absolute time of that constraint's ext (NaN: failed)
+    excess: object            # [N] ext - limit of that constraint: > 0 for an `outside` drone (NaN: failed)
+    normals: object           # [C, 3] the constraints' directions: the box's finite sides (+x, -x, +y, -y, +z, -z order), then the planes
+    limits: object            # [C] their limits, the drone's radius taken off: n.p <= limit
+    ext: object               # [N, C] msnap_path_extent's outputs for `normals`
+    t_ext: object
+    upper: object
+    box_lo: object            # [N, 3] the certified box of each path, [-upper(-e_a), upper(+e_a)] (None: no box given)
+    box_hi: object
+
+
+def certify_geofence(compute, coef, dur, lo=None, hi=None, planes=None, radius: float = 0.0,
+                     status=None) -> GeofenceResult:
+    """Certify in continuous time that every drone of `coef`, `dur` stays inside a convex geofence.
+
+    The fence is a box `lo` / `hi` (each [3]; -inf / +inf: that side is unconstrained) and / or half-spaces `planes`
+    [P, 4] = (n, b) meaning n.x <= b; a drone is a sphere of `radius`, which moves each limit by radius |n|.  The
+    directions go through `compute.path_extent` (msnap_path_extent_device).  Per drone, the first that applies:
+      failed     status != 0 (`status`: the solve's; or this call's): such a drone is refused, nothing is certified;
+      outside    some ext exceeds its limit: an attained violation -- `worst`, `t_worst`, `excess` name it;
+      inside     every upper is below its limit (strictly: a path that only touches a limit is not certified);
+      undecided  neither: a limit inside the closing gap between ext and upper.
+    When a box is given the certified box of every path comes back as well (all six axes are evaluated then).
+
+    One rank: every drone is checked on its own, so a sharded swarm calls this per shard."""
+    import torch
+    if not (radius >= 0.0):
+        raise ValueError("certify_geofence: radius >= 0")
+    dev = dur.device
+    n = dur.shape[0]
+    f64 = dict(dtype=torch.float64, device=dev)
+    axes = torch.tensor([[1, 0, 0], [-1, 0, 0], [0, 1, 0], [0, -1, 0], [0, 0, 1], [0, 0, -1]], **f64)
+    have_box = lo is not None or hi is not None
+    box_lim = torch.full((6,), float("inf"), **f64)
+    if have_box:
+        lo_t = torch.full((3,), -float("inf"), **f64) if lo is None else torch.as_tensor(lo, dtype=torch.float64).to(dev)
+        hi_t = torch.full((3,), float("inf"), **f64) if hi is None else torch.as_tensor(hi, dtype=torch.float64).to(dev)
+        if tuple(lo_t.shape) != (3,) or tuple(hi_t.shape) != (3,) or bool(torch.isnan(lo_t).any() | torch.isnan(hi_t).any()):
+            raise ValueError("certify_geofence: lo and hi are [3], without NaN")
+        box_lim[0::2], box_lim[1::2] = hi_t, -lo_t
+    if planes is not None:
+        pl = torch.as_tensor(planes, dtype=torch.float64).to(dev).reshape(-1, 4)
+        if not bool(torch.isfinite(pl).all()):
+            raise ValueError("certify_geofence: planes must be finite")
+    else:
+        pl = torch.zeros((0, 4), **f64)
+    # what is sent: all six axes when a box is given (the certified box), then the planes; what is judged: the finite ones
+    dirs = torch.cat([axes if have_box else axes[:0], pl[:, :3]]).contiguous()
+    lim_all = torch.cat([box_lim if have_box else box_lim[:0], pl[:, 3]])
+    lim_all = lim_all - radius * torch.linalg.vector_norm(dirs, dim=1)
+    bad = torch.zeros((n,), dtype=torch.bool, device=dev)
+    if status is not None:
+        bad |= torch.as_tensor(status).to(dev) != 0
+    ext, t_ext, upper, st = compute.path_extent(coef, dur, dirs)
+    if dirs.shape[0]:
+        bad |= st != 0
+    ext, t_ext, upper = ext.clone(), t_ext.clone(), upper.clone()
+    box_lo = box_hi = None
+    if have_box:
+        box_hi, box_lo = upper[:, 0:6:2].clone(), -upper[:, 1:6:2]
+    keep = torch.isfinite(lim_all)
+    normals, limits = dirs[keep], lim_all[keep]
+    ext, t_ext, upper = ext[:, keep], t_ext[:, keep], upper[:, keep]
+    C = int(keep.sum())
+    nan = torch.full((n,), float("nan"), **f64)
+    if C:
+        over = ext - limits[None, :]
+        over = torch.where(torch.isnan(over), torch.full_like(over, -float("inf")), over)
+        excess, worst = over.max(dim=1)
+        t_worst = t_ext.gather(1, worst[:, None])[:, 0]
+        outside = ~bad & (ext > limits[None, :]).any(dim=1)
+        inside = ~bad & ~outside & (upper < limits[None, :]).all(dim=1)
+    else:
+        excess, worst, t_worst = nan.clone(), torch.full((n,), -1, dtype=torch.int64, device=dev), nan.clone()
+        outside = torch.zeros_like(bad)
+        inside = ~bad
+    undecided = ~bad & ~outside & ~inside
+    worst = torch.where(bad, torch.full_like(worst, -1), worst)
+    t_worst, excess = torch.where(bad, nan, t_worst), torch.where(bad, nan, excess)
+    verdict = torch.full((n,), GEOFENCE_UNDECIDED, dtype=torch.int8, device=dev)
+    verdict[inside], verdict[outside], verdict[bad] = GEOFENCE_INSIDE, GEOFENCE_OUTSIDE, GEOFENCE_FAILED
+    return GeofenceResult(verdict, inside, outside, undecided, bad, worst, t_worst, excess, normals, limits, ext, t_ext,
+                          upper, box_lo, box_hi)

@@ -422,6 +422,49 @@ int msnap_mesh_clearance_device(msnap_ctx *ctx, int n_drones, int n_seg, const d
                                 int n_tris, const double *tris, double *min_dist, double *t_min, int32_t *tri_min,
                                 double *lower, int32_t *status);
 
+/* ---- path extent in continuous time: the support function of a path (new capability) ----
+ * The peaks, the pairwise clearance and the mesh clearance say nothing about WHERE a path goes, and a minimum-snap fit
+ * through waypoints inside a workspace overshoots it between them.  msnap_path_extent certifies, per drone and per given
+ * direction, how far the whole path reaches in that direction.  coef, dur as everywhere else; dirs [n_dirs][3]
+ * (directions need not have unit length); ext, t_ext and upper are [n_drones][n_dirs], status is [n_drones].  For
+ * direction n_k and one drone, S is the supremum of n_k.p(t) over t in [0, sum dur] (each segment on its closed
+ * [0, T_i]), for the exact real polynomials of the fp64 coefficients and the fp64 direction.  The six signed axes give
+ * the certified bounding box of a path; the normals of half-spaces n.x <= b a convex geofence or corridor.
+ *   ext      a value the path ATTAINS, at
+ *   t_ext    absolute time, 0 <= t_ext <= sum dur (larger value, then the earlier time): for the position (x, y, z)
+ *            msnap_eval_flat gives at t_ext, (n_x * x + n_y * y) + n_z * z -- every operation rounded once, in this
+ *            order, none fused -- is ext bit for bit;
+ *   upper    a proven upper bound:  ext <= upper always, and ext <= S <= upper, each up to rounding (ten times the worst
+ *            deviation measured against an exact reference):
+ *              ext <= S + r   and   S <= upper + r,
+ *              r = 1e-13 + C_ROUND_EXTENT * 2^-52 * R_k,   C_ROUND_EXTENT = 9
+ *            R_k = the largest value, over the drone's segments i, of sum_a |n_a| sum_j |c_{a,j}| T_i^j (a over x, y, z;
+ *            c_{a,j} the segment's coefficients, T_i its duration): the size of what n_k.p is computed from.  A caller
+ *            computes R_k from coef, dur and dirs alone.
+ *            When the search closes (short of its caps: 40 bisections of a segment, 4096 nodes per segment):
+ *              upper <= ext + 1e-9 |ext| + 1e-9 + r.
+ *            A lane that meets a cap still gets a valid upper, only further from ext; no status is raised.
+ *            No solve produces coefficient sets whose position jumps at a knot.  For such a set t_ext may name the
+ *            knot, and ext is the value of the segment that msnap_eval_flat's lookup selects there; upper still bounds
+ *            both sides; the closing inequality is not promised.
+ *   status   msnap_status: MSNAP_ST_NONFINITE for a NaN / Inf coefficient or duration of the drone, else
+ *            MSNAP_ST_TIMES for a duration <= 0.  ext, t_ext and upper of a failed drone are NaN.
+ * A direction with a non-finite component has NaN in its column for every drone; status is unaffected.  A zero
+ * direction gives ext = upper = 0 at t_ext = 0.  n_dirs == 0 or n_drones == 0 is a no-op.  MSNAP_EINVAL: a null context,
+ * a null array, negative sizes, dirs == NULL with n_dirs > 0, n_drones * n_seg * n_dirs beyond what one launch covers.
+ * MSNAP_ESEGMENTS as everywhere.  Both orders, n_seg 1 .. max_segments.  An (ext, t_ext, upper) triple is bit-identical
+ * whatever the drone's place in the batch, the batch size, the direction's place in dirs, n_dirs, and host versus
+ * device entry.  The device version takes device pointers, dirs included, and only launches; its scratch is a buffer of
+ * the context under the capture rules above (MSNAP_ECAPTURE: run the call once outside the capture first).
+ * (Method: per segment and direction, branch and bound over dyadic sub-intervals on the scalar polynomial n.p; the
+ * largest Bernstein coefficient on a sub-interval bounds it there.)
+ */
+int msnap_path_extent(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur, int n_dirs,
+                      const double *dirs /* [n_dirs][3] */, double *ext, double *t_ext, double *upper, int32_t *status);
+int msnap_path_extent_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,
+                             int n_dirs, const double *dirs, double *ext, double *t_ext, double *upper,
+                             int32_t *status);
+
 /* ---- near pairs: every pair of a swarm whose sampled distance is below a per-pair limit ----
  * msnap_formation_collide names one partner per drone; msnap_formation_near_pairs lists every close pair, e.g. the
  * pairs msnap_pair_clearance has to see.  pos [n_drones][n_samples][3] as the sampler writes it; speed [n_drones] or
