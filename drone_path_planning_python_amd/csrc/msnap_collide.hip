@@ -4,6 +4,7 @@
 
 #include "msnap_internal.h"
 #include "msnap_collide.h"
+#include "msnap_pair_tile.h"
 #include "msnap_wave.h"
 
 namespace msnap {
@@ -15,9 +16,9 @@ namespace msnap {
 //
 // Arithmetic.  One lane per TWO row drones (row blocks of 128: rows lane and lane + 64); the column
 // drone is wave-uniform, its samples arrive through scalar loads and are SGPR operands of the 7
-// operations per pair and sample: 3 differences, d2 = fma(dz, dz, fma(dy, dy, dx * dx)) -- the
-// definition of include/msnap.h, restated bit for bit by both oracles, which is what decides ties
-// between equidistant formation neighbours -- and the minimum.
+// operations per pair and sample: 3 differences, d2 = pair_d2 (msnap_pair_tile.h) -- the definition
+// of include/msnap.h, restated bit for bit by both oracles, which is what decides ties between
+// equidistant formation neighbours -- and the minimum.
 // The running minima of a block of 8 columns stay in registers over all samples.  A scalar load has
 // only an all-or-nothing wait, so a wave has ONE column fetch (6 samples, 2 x 42 operations) in
 // flight while it computes the previous one; the other waves of the SIMD (4 fit) cover the rest of
@@ -75,41 +76,6 @@ __device__ __host__ __forceinline__ long long collide_share_of(const CollideGeom
   return ul < g.split ? ul / g.upw : g.split / g.upw + (ul - g.split) / g.upw_tail;
 }
 
-// 6 samples of a column drone = 18 contiguous doubles in scalar registers.  The loads are issued by
-// hand: next to LDS fences the compiler can no longer prove that the position arrays are not written
-// and would fall back to vector loads of a uniform address.  SMEM returns out of order, so the only
-// wait is lgkmcnt(0); it carries the registers as operands so that no use is scheduled above it.
-typedef unsigned int u32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4s __attribute__((ext_vector_type(4)));
-struct ColChunk {
-  u32x16 a, b;
-  u32x4s c;
-  __device__ __forceinline__ void fetch(const double *p) {
-    asm volatile("s_load_dwordx16 %0, %3, 0x0\n\ts_load_dwordx16 %1, %3, 0x40\n\ts_load_dwordx4 %2, %3, 0x80"
-                 : "=&s"(a), "=&s"(b), "=&s"(c)
-                 : "s"(p));
-  }
-  // `after` (a value the preceding arithmetic produces) pins the wait behind that arithmetic: without
-  // it the compiler may sink the other register set's VALU work below this wait and lose the overlap
-  __device__ __forceinline__ void wait(double &after) {
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(a), "+s"(b), "+s"(c), "+v"(after));
-  }
-  // element i (a compile-time constant after unrolling) minus v, exactly rounded.  The difference is issued
-  // by hand with the scalar register pair as the first operand: a lane owns two rows, and left to the
-  // compiler a scalar value with two VALU users is first copied into vector registers (36 extra moves per
-  // fetch).
-  __device__ __forceinline__ double minus(int i, double v) const {
-    const unsigned long long x =
-        i < 8 ? ((unsigned long long)a[2 * i + 1] << 32) | a[2 * i]
-              : i < 16 ? ((unsigned long long)b[2 * (i - 8) + 1] << 32) | b[2 * (i - 8)]
-                       : ((unsigned long long)c[2 * (i - 16) + 1] << 32) | c[2 * (i - 16)];
-    double d;
-    asm("v_add_f64 %0, %1, -%2" : "=v"(d) : "s"(x), "v"(v));
-    return d;
-  }
-};
-
-
 // What a lane carries through a share: its kRowsPerLane rows (lane, lane + 64, ...)
 struct RowSet {
   bool live[kRowsPerLane];       // row exists (rows past the batch end replay row R - 1 and must not win)
@@ -117,6 +83,20 @@ struct RowSet {
   double best[kRowsPerLane];     // row-side minimum over the share's columns
   int bestj[kRowsPerLane];
 };
+// the rows of row block I of a call with R rows, the first of them global drone ro.  (The callers value-initialise the
+// set where they declare it, `RowSet rs = {}`: where its first stores arrive only through this inlined helper the
+// compiler carries every row's `best` twice through the column loop, one copy for the compare and one for the value
+// stored -- collide_span_kernel 127 -> 128 VGPRs and 28 bytes of scratch.)
+__device__ __forceinline__ void row_set_init(RowSet &rs, int I, int lane, int R, int ro) {
+#pragma unroll
+  for (int rr = 0; rr < kRowsPerLane; ++rr) {
+    const int raw = I * kRowBlock + rr * kWave + lane;
+    rs.live[rr] = raw < R;
+    rs.grow[rr] = ro + (rs.live[rr] ? raw : R - 1);
+    rs.best[rr] = INFINITY;
+    rs.bestj[rr] = -1;
+  }
+}
 
 // The exact broad phase of a whole-swarm pass (launch_formation_collide, "cull" path).  Rows and columns are walked in
 // a spatially sorted order (Morton order of the drones' path boxes); every aligned group of 8 drones of that order has
@@ -131,6 +111,8 @@ struct CollideCull {
   const double *colbox;    // [ceil(N / 8)][6] lo x,y,z / hi x,y,z per aligned group of 8 sorted drones
 };
 
+// (clamped gaps, not differences, through pair_d2's own formula: the value must never exceed pair_d2 of any pair of
+// points of the two boxes)
 __device__ __forceinline__ double box_box_lb2(const double *__restrict__ a, const double *__restrict__ b) {
 #pragma clang fp contract(off)
   double gp[3];
@@ -143,106 +125,18 @@ __device__ __forceinline__ double box_box_lb2(const double *__restrict__ a, cons
 }
 
 // One block of NC (even, <= kColBlock) consecutive columns [cj, cj + ncols) against the wave's
-// kRowBlock rows: straight-line code over the columns -- with a branch inside the column loop the
-// scalar register sets cross basic blocks and the compiler copies every fetched value into vector
-// registers (36 extra VALU moves per fetch) -- so a short block takes the next instance up and
-// re-reads its last column instead of branching.
+// kRowBlock rows: the minima of the register tile (pair_tile_minima, msnap_pair_tile.h: straight-line
+// code over the columns, so a short block takes the next instance up), folded into the row side and,
+// for a two-sided block, the column side.
 template <int NC, bool CULL = false>
 __device__ __forceinline__ void collide_block(const CollideGeom &g, const double *__restrict__ prowT,
                                               const double *__restrict__ pcol, int cj, int ncols, bool two_sided,
                                               RowSet &rs, int I, int h, int crow, int lane, double *sFold, int *sFoldI,
                                               double *__restrict__ cpart_d2, int32_t *__restrict__ cpart_i,
                                               const int32_t *__restrict__ oid = nullptr) {
-#pragma clang fp contract(off)
-  constexpr int CH = kSampleChunk, RPL = kRowsPerLane;
-  const int S = g.S;
-  const int stride = S * 3;
+  constexpr int RPL = kRowsPerLane;
   double acc[RPL][NC];
-#pragma unroll
-  for (int rr = 0; rr < RPL; ++rr)
-#pragma unroll
-    for (int jj = 0; jj < NC; ++jj) acc[rr][jj] = INFINITY;
-  // One or two samples behind the last whole chunk (91 = 15 x 6 + 1) go through a plain loop at the end;
-  // a longer remainder is a last chunk moved back to overlap its predecessor (a minimum does not mind seeing
-  // a sample twice), so that every chunk takes the wide scalar loads.
-  const int rem = S % CH;
-  const int Sw = (rem == 1 || rem == 2) ? S - rem : S;
-  // sample part h of g.sparts takes its range of whole chunks (the last part also the plain remainder)
-  const int nch = (Sw + CH - 1) / CH;
-  const int sc_begin = (int)((long long)nch * h / g.sparts) * CH, sc_end = (int)((long long)nch * (h + 1) / g.sparts) * CH;
-  for (int sc = sc_begin; sc < sc_end; sc += CH) {
-    const int s0 = (Sw - sc < CH) ? Sw - CH : sc;
-    double row[RPL][CH][3];
-    // the rows come from the transposed image [sample][xyz][row]: the 64 lanes of a load read 512
-    // contiguous bytes (from the drone-major layout every lane would touch its own cache line, and with
-    // several rows per lane the texture addresser, not the VALU, would set the pace: TA_BUSY 79 %)
-    // (uniform base per load, lane offset in one register: no per-lane 64-bit address arithmetic)
-    const double *pt = prowT + (size_t)s0 * 3 * g.Rp;
-#pragma unroll
-    for (int q = 0; q < CH; ++q)
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        const double *pk = pt + (size_t)(3 * q + k) * g.Rp;
-#pragma unroll
-        for (int rr = 0; rr < RPL; ++rr) row[rr][q][k] = pk[lane + rr * kWave];
-      }
-    // one running pointer walks the block's columns; `nvalid` is made opaque per chunk so that the
-    // per-column strides are not hoisted out of the sample loop into spilled scalar registers
-    int nvalid = ncols;
-    asm volatile("" : "+s"(nvalid));
-    const double *pc = pcol + ((size_t)cj * S + s0) * 3;
-    auto consume = [&](int jj, const ColChunk &k) {
-#pragma unroll
-      for (int q = 0; q < CH; ++q)
-#pragma unroll
-        for (int rr = 0; rr < RPL; ++rr) {
-          const double dx = k.minus(3 * q + 0, row[rr][q][0]), dy = k.minus(3 * q + 1, row[rr][q][1]),
-                       dz = k.minus(3 * q + 2, row[rr][q][2]);
-          const double d2 = __builtin_fma(dz, dz, __builtin_fma(dy, dy, dx * dx));
-          // the minimum by hand: behind the wait's register tie the compiler no longer knows the accumulator
-          // to be canonical and would put a v_max in front of every fmin.  Neither operand can be a signalling
-          // NaN (d2 comes out of arithmetic, the accumulator out of earlier minima), and a quiet NaN loses, as
-          // fmin's would.
-          asm("v_min_f64 %0, %1, %0" : "+v"(acc[rr][jj]) : "v"(d2));
-        }
-    };
-    // two register sets alternate: the loads of column j+1 are issued right after the wait for
-    // column j and fly during its RPL x 6 x 7 VALU operations
-    ColChunk ca, cb2;
-    ca.fetch(pc);
-#pragma unroll
-    for (int jj = 0; jj < NC; jj += 2) {
-      pc += (jj + 1 < nvalid) ? stride : 0;
-      ca.wait(acc[RPL - 1][jj > 0 ? jj - 1 : 0]);
-      cb2.fetch(pc);
-      consume(jj, ca);
-      pc += (jj + 2 < nvalid) ? stride : 0;
-      cb2.wait(acc[RPL - 1][jj]);
-      if (jj + 2 < NC) ca.fetch(pc);
-      consume(jj + 1, cb2);
-    }
-  }
-  for (int s1 = (h == g.sparts - 1) ? Sw : S; s1 < S; ++s1) {
-    const double *pt = prowT + (size_t)s1 * 3 * g.Rp;
-    const double *px = pt, *py = pt + g.Rp, *pz = pt + 2 * (size_t)g.Rp;
-    double rx[RPL], ry[RPL], rz[RPL];
-#pragma unroll
-    for (int rr = 0; rr < RPL; ++rr) {
-      rx[rr] = px[lane + rr * kWave];
-      ry[rr] = py[lane + rr * kWave];
-      rz[rr] = pz[lane + rr * kWave];
-    }
-#pragma unroll
-    for (int jj = 0; jj < NC; ++jj) {
-      const double *pcs = pcol + ((size_t)(cj + (jj < ncols ? jj : ncols - 1)) * S + s1) * 3;
-      const double cx = pcs[0], cy = pcs[1], cz = pcs[2];
-#pragma unroll
-      for (int rr = 0; rr < RPL; ++rr) {
-        const double dx = cx - rx[rr], dy = cy - ry[rr], dz = cz - rz[rr];
-        acc[rr][jj] = __builtin_fmin(__builtin_fma(dz, dz, __builtin_fma(dy, dy, dx * dx)), acc[rr][jj]);
-      }
-    }
-  }
+  pair_tile_minima<NC>(prowT, g.Rp, pcol, g.S, cj, ncols, lane, h, g.sparts, acc);
   // row side: columns ascend, so the lowest index wins a tie (cull path: sorted order, ties by the ORIGINAL index)
 #pragma unroll
   for (int jj = 0; jj < NC; ++jj) {
@@ -322,6 +216,23 @@ __device__ __forceinline__ void collide_block(const CollideGeom &g, const double
   }
 }
 
+// the narrowest instance (2, kColBlock / 2 or kColBlock columns) that holds the block's ncols columns
+template <bool CULL>
+__device__ __forceinline__ void collide_block_by_width(int ncols, const CollideGeom &g, const double *__restrict__ prowT,
+                                                       const double *__restrict__ pcol, int cj, bool two_sided,
+                                                       RowSet &rs, int I, int h, int crow, int lane, double *sFold,
+                                                       int *sFoldI, double *__restrict__ cpart_d2,
+                                                       int32_t *__restrict__ cpart_i, const int32_t *__restrict__ oid) {
+  if (ncols <= 2)
+    collide_block<2, CULL>(g, prowT, pcol, cj, ncols, two_sided, rs, I, h, crow, lane, sFold, sFoldI, cpart_d2, cpart_i, oid);
+  else if (ncols <= kColBlock / 2)
+    collide_block<kColBlock / 2, CULL>(g, prowT, pcol, cj, ncols, two_sided, rs, I, h, crow, lane, sFold, sFoldI, cpart_d2,
+                                       cpart_i, oid);
+  else
+    collide_block<kColBlock, CULL>(g, prowT, pcol, cj, ncols, two_sided, rs, I, h, crow, lane, sFold, sFoldI, cpart_d2,
+                                   cpart_i, oid);
+}
+
 // The rows of a call as [sample][xyz][row] (row pitch Rp; the rows behind R replay row R - 1): 64 x 64
 // tiles through LDS, read along a drone's samples and written along the rows.
 // Rows of workgroups behind the `ny` of the transposition mark the column-side partner slots of a part launch
@@ -383,15 +294,8 @@ __device__ __forceinline__ void collide_span_body(const double *__restrict__ pro
     // unit -> column: the columns left of the own range, then from the row block's own first column on
     const int diag0 = g.os + I * kRowBlock;                               // only meaningful with g.sym
     const int skip = g.sym ? I * kRowBlock : 0;                           // own-range columns not met
-    RowSet rs;
-#pragma unroll
-    for (int rr = 0; rr < kRowsPerLane; ++rr) {
-      const int raw = I * kRowBlock + rr * kWave + lane;
-      rs.live[rr] = raw < g.R;
-      rs.grow[rr] = g.ro + (rs.live[rr] ? raw : g.R - 1);
-      rs.best[rr] = INFINITY;
-      rs.bestj[rr] = -1;
-    }
+    RowSet rs = {};
+    row_set_init(rs, I, lane, g.R, g.ro);
     const double *prowT = prow_t + (size_t)(I - g.I_lo) * kRowBlock;
     const int crow = (I - g.I_lo) * g.sparts + h;
     for (int ux = ua; ux < ue;) {
@@ -409,12 +313,8 @@ __device__ __forceinline__ void collide_span_body(const double *__restrict__ pro
       }
       const int ncols = lim < CB ? lim : CB;
       ux += ncols;
-      if (ncols <= 2)
-        collide_block<2>(g, prowT, pcol, cj, ncols, two_sided, rs, I, h, crow, lane, sFold, sFoldI, cpart_d2, cpart_i);
-      else if (ncols <= kColBlock / 2)
-        collide_block<kColBlock / 2>(g, prowT, pcol, cj, ncols, two_sided, rs, I, h, crow, lane, sFold, sFoldI, cpart_d2, cpart_i);
-      else
-        collide_block<kColBlock>(g, prowT, pcol, cj, ncols, two_sided, rs, I, h, crow, lane, sFold, sFoldI, cpart_d2, cpart_i);
+      collide_block_by_width<false>(ncols, g, prowT, pcol, cj, two_sided, rs, I, h, crow, lane, sFold, sFoldI, cpart_d2,
+                                    cpart_i, nullptr);
     }
     // one partial entry per (wave, row block): w + I is unique (a later wave starts in a later or the same
     // row block) and the entries of row block I are the contiguous ids of the waves that meet it
@@ -482,12 +382,6 @@ __device__ __host__ __forceinline__ CullSplit cull_split(int tot, int slots, int
   c.lo = c.hi = best;
   return c;
 }
-__device__ __host__ __forceinline__ int cull_nch(int S) {
-  const int rem = S % kSampleChunk;
-  const int Sw = (rem == 1 || rem == 2) ? S - rem : S;
-  return (Sw + kSampleChunk - 1) / kSampleChunk;
-}
-
 
 // The second granularity of the broad phase: pairs of GROUPS (8 x 8 drones of the sorted order).  Of a surviving share
 // (128 rows x 8 columns) usually one or two of its 16 row groups are what kept it; the group pairs that pass the same
@@ -744,7 +638,7 @@ collide_span_list_body(const double *__restrict__ prow_t, const double *__restri
   __shared__ int sFoldI[CB * kWave];
   const int lane = threadIdx.x;
   const int tot = meta[kMetaTotal];
-  const CullSplit sp = cull_split(tot, slots, cull_nch(g.S), sp_force);
+  const CullSplit sp = cull_split(tot, slots, pair_tile_chunks(g.S), sp_force);
   if (blockIdx.x == 0 && lane == 0) {
     meta[kMetaParts] = sp.lo;
     meta[kMetaParts + 1] = sp.hi;
@@ -766,22 +660,11 @@ collide_span_list_body(const double *__restrict__ prow_t, const double *__restri
     const int cj = I * kRowBlock + k * CB;
     const int ncols = g.Cn - cj < CB ? g.Cn - cj : CB;
     const bool two_sided = k >= kRowBlock / CB;
-    RowSet rs;
-#pragma unroll
-    for (int rr = 0; rr < kRowsPerLane; ++rr) {
-      const int raw = I * kRowBlock + rr * kWave + lane;
-      rs.live[rr] = raw < g.R;
-      rs.grow[rr] = rs.live[rr] ? raw : g.R - 1;
-      rs.best[rr] = INFINITY;
-      rs.bestj[rr] = -1;
-    }
+    RowSet rs = {};
+    row_set_init(rs, I, lane, g.R, 0);      // (sorted order: rows are numbered from 0)
     const double *prowT = prow_t + (size_t)I * kRowBlock;
-    if (ncols <= 2)
-      collide_block<2, true>(g, prowT, pcol, cj, ncols, two_sided, rs, I, h, crow, lane, sFold, sFoldI, cpart_d2, cpart_i, oid);
-    else if (ncols <= CB / 2)
-      collide_block<CB / 2, true>(g, prowT, pcol, cj, ncols, two_sided, rs, I, h, crow, lane, sFold, sFoldI, cpart_d2, cpart_i, oid);
-    else
-      collide_block<CB, true>(g, prowT, pcol, cj, ncols, two_sided, rs, I, h, crow, lane, sFold, sFoldI, cpart_d2, cpart_i, oid);
+    collide_block_by_width<true>(ncols, g, prowT, pcol, cj, two_sided, rs, I, h, crow, lane, sFold, sFoldI, cpart_d2,
+                                 cpart_i, oid);
 #pragma unroll
     for (int rr = 0; rr < kRowsPerLane; ++rr) {
       part_d2[(size_t)it * kRowBlock + rr * kWave + lane] = rs.best[rr];
@@ -975,10 +858,7 @@ collide_eval_groups_kernel(const double *__restrict__ pcol, int N, int S, const 
 #pragma unroll
         for (int c = 0; c < kGroupHalf; ++c) {
           const double dx = cx[c] - x, dy = cy[c] - y, dz = cz[c] - z;
-          const double d2 = __builtin_fma(dz, dz, __builtin_fma(dy, dy, dx * dx));
-          // (the minimum by hand, as in collide_block: fmin would canonicalise the accumulator with a v_max first --
-          // an eighth instruction per pair and sample; a quiet NaN loses either way)
-          asm("v_min_f64 %0, %1, %0" : "+v"(acc[r * kGroupHalf + c]) : "v"(d2));
+          min_quiet(acc[r * kGroupHalf + c], pair_d2(dx, dy, dz));      // (behind the opaque lane copy: by hand)
         }
       }
     }
@@ -1072,8 +952,7 @@ collide_short_kernel(const double *__restrict__ prow, const double *__restrict__
       const double dx = pc[(size_t)sq * 3 + 0] - pr[(size_t)sq * 3 + 0];
       const double dy = pc[(size_t)sq * 3 + 1] - pr[(size_t)sq * 3 + 1];
       const double dz = pc[(size_t)sq * 3 + 2] - pr[(size_t)sq * 3 + 2];
-      const double d2 = __builtin_fma(dz, dz, __builtin_fma(dy, dy, dx * dx));
-      m = __builtin_fmin(d2, m);
+      m = __builtin_fmin(pair_d2(dx, dy, dz), m);
     }
     if (j == grow) m = INFINITY;
     if (m < best) {
@@ -1349,7 +1228,7 @@ collide_rank_kernel(const unsigned *__restrict__ key, int N, int32_t *__restrict
 //  * TILES (64 sorted rows x 5 samples, through LDS, as collide_transpose_kernel): the sorted row image
 //    [sample][xyz][row] and the sorted drone-major copy from one read of pos through the permutation -- and, while the
 //    tile (with the 4 rows behind it) sits in LDS, the drones' BOUNDS: for sorted drone r the minimum over its sorted
-//    neighbours r +- 1..4 and the tile's samples of the pass's own squared distance (fma(dz, dz, fma(dy, dy, dx dx));
+//    neighbours r +- 1..4 and the tile's samples of the pass's own squared distance (pair_d2;
 //    non-finite samples never win), folded into bound[r] with an atomic minimum on the bit pattern (squared distances
 //    are non-negative doubles: ordered like their patterns).  ANY subset of a drone's pair-samples bounds its final
 //    minimum from above; with every tile contributing, all samples and the pairs across tile boundaries count.
@@ -1436,7 +1315,7 @@ collide_gather_kernel(const double *__restrict__ pos, int N, int Rp, int E, doub
     double f = INFINITY;
     for (int q = 0; q < ne; q += 3) {
       const double dx = pb[q] - pa[q], dy = pb[q + 1] - pa[q + 1], dz = pb[q + 2] - pa[q + 2];
-      f = __builtin_fmin(__builtin_fma(dz, dz, __builtin_fma(dy, dy, dx * dx)), f);
+      f = __builtin_fmin(pair_d2(dx, dy, dz), f);
     }
     sF[k - 1][row] = r0 + row + k < N ? f : INFINITY;      // (rows past the end replay row N - 1)
   }
@@ -1667,7 +1546,7 @@ static WholePlan plan_whole_pass(const msnap_ctx *ctx, int n_rows, int row_offse
   if (ctx->collide_sample_parts > 0) {
     g.sparts = ctx->collide_sample_parts < 8 ? ctx->collide_sample_parts : 8;
   } else if (ctx->collide_waves_per_cu == 0) {
-    const int nch = (n_samples + kSampleChunk - 1) / kSampleChunk;
+    const int nch = (n_samples + kSampleChunk - 1) / kSampleChunk;      // (the unrounded count, on purpose: not pair_tile_chunks)
     while (g.sparts < 8 && p.waves * g.sparts < slots / 4 && nch / (g.sparts * 2) >= 2) g.sparts *= 2;
   }
   return p;
@@ -1859,7 +1738,7 @@ static long long plan_part_pass(const msnap_ctx *ctx, int N, int n_samples, int 
     //  * a few shares more than whole rounds of the slots: the excess goes out as 2-column shares (the whole-pass
     //    rule above)
     const long long slots = (long long)ctx->n_cu * 4 * 4;
-    const int nch = (n_samples + kSampleChunk - 1) / kSampleChunk;
+    const int nch = (n_samples + kSampleChunk - 1) / kSampleChunk;      // (the unrounded count, on purpose: not pair_tile_chunks)
     if (ctx->collide_sample_parts > 0) {
       g.sparts = ctx->collide_sample_parts < 8 ? ctx->collide_sample_parts : 8;
     } else if (shares * 2 <= slots) {

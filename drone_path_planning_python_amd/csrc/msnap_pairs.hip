@@ -1,15 +1,16 @@
 // Near pairs of a swarm: the sorted list of every unordered pair of drones whose sampled distance is below a per-pair
 // limit (include/msnap.h, "near pairs").  gfx950, wave64.
 //
-// Distance.  d2_ij = min over the samples of fma(dz, dz, fma(dy, dy, dx dx)), the pairwise pass's expression
-// (msnap_collide.hip) with its minNum rule: a non-finite sample never wins, a drone without a finite sample keeps
-// d2 = +inf and is in no pair.  Limit: lim_ij = (base + (speed_i + speed_j) gap) (1 + margin), every operation rounded
-// once (__dadd_rn / __dmul_rn: the library builds with -ffp-contract=on).  Kept iff sqrt(d2_ij) < lim_ij.
+// Distance.  d2_ij = min over the samples of pair_d2, the pairwise pass's expression (msnap_pair_tile.h) with its
+// minNum rule: a non-finite sample never wins, a drone without a finite sample keeps d2 = +inf and is in no pair.
+// Limit: lim_ij = (base + (speed_i + speed_j) gap) (1 + margin), every operation rounded once (__dadd_rn / __dmul_rn:
+// the library builds with -ffp-contract=on).  Kept iff sqrt(d2_ij) < lim_ij.
 //
-// Mask pass.  The pairwise pass's register tiling (msnap_collide.h): a wave owns a row block of 128 drones (two rows
-// per lane) and 8 column drones, whose samples arrive through scalar loads in chunks of 6 and are scalar operands of
-// the 7 operations per pair and sample; the rows come from a transposed image [sample][xyz][row].  Only the upper
-// triangle is walked: row block I meets the column blocks from its own first one on.  At the end of a tile nothing is
+// Mask pass.  The pairwise pass's register tile itself (pair_tile_minima, msnap_pair_tile.h): a wave owns a row block
+// of 128 drones (two rows per lane) and 8 column drones, whose samples arrive through scalar loads in chunks of 6 and
+// are scalar operands of the 7 operations per pair and sample; the rows come from a transposed image
+// [sample][xyz][row].  Only the upper triangle is walked: row block I meets the column blocks from its own first one
+// on.  At the end of a tile nothing is
 // folded: each of the 2 x 8 minima is compared with its pair's limit and the lane stores, per row, ONE BYTE of the
 // keep-bit matrix [N][ceil(N / 64)] of 64-bit words -- byte c of a row holds the columns 8 c .. 8 c + 7, so every byte
 // has exactly one writer, and every byte of a row from its own diagonal word on is written (bits of columns <= row or
@@ -25,6 +26,7 @@
 
 #include "msnap_api_util.h"
 #include "msnap_collide.h"
+#include "msnap_pair_tile.h"
 #include "msnap_wave.h"
 
 namespace msnap {
@@ -35,32 +37,6 @@ constexpr int kRowWaves = 4;                                       // rows (wave
 constexpr int kScanThreads = 1024;
 static_assert(kCullMaxDrones <= kScanThreads * 16, "the scan walks at most 16 rows per thread");
 static_assert(kColBlock == 8, "one byte of the keep-bit matrix per column block");
-
-// 6 samples of a column drone = 18 contiguous doubles in scalar registers (the pairwise pass's ColChunk: loads issued
-// by hand, one all-or-nothing wait that carries the registers, the difference with the scalar pair as first operand)
-typedef unsigned int u32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4s __attribute__((ext_vector_type(4)));
-struct ColChunk {
-  u32x16 a, b;
-  u32x4s c;
-  __device__ __forceinline__ void fetch(const double *p) {
-    asm volatile("s_load_dwordx16 %0, %3, 0x0\n\ts_load_dwordx16 %1, %3, 0x40\n\ts_load_dwordx4 %2, %3, 0x80"
-                 : "=&s"(a), "=&s"(b), "=&s"(c)
-                 : "s"(p));
-  }
-  __device__ __forceinline__ void wait(double &after) {
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(a), "+s"(b), "+s"(c), "+v"(after));
-  }
-  __device__ __forceinline__ double minus(int i, double v) const {
-    const unsigned long long x =
-        i < 8 ? ((unsigned long long)a[2 * i + 1] << 32) | a[2 * i]
-              : i < 16 ? ((unsigned long long)b[2 * (i - 8) + 1] << 32) | b[2 * (i - 8)]
-                       : ((unsigned long long)c[2 * (i - 16) + 1] << 32) | c[2 * (i - 16)];
-    double d;
-    asm("v_add_f64 %0, %1, -%2" : "=v"(d) : "s"(x), "v"(v));
-    return d;
-  }
-};
 
 struct PairLimit {
   const double *speed;      // [N] or null (zeros)
@@ -95,91 +71,22 @@ __device__ __forceinline__ void store_keep_bits(const double (&acc)[kRowsPerLane
 __global__ void __launch_bounds__(kWave, 4)
 pairs_mask_kernel(const double *__restrict__ prowT, const double *__restrict__ pcol, int N, int S, int Rp, PairLimit pl,
                   size_t pitch_bytes, unsigned char *__restrict__ mask) {
-#pragma clang fp contract(off)
-  constexpr int CH = kSampleChunk, RPL = kRowsPerLane, NC = kColBlock;
+  constexpr int RPL = kRowsPerLane, NC = kColBlock;
   const int I = blockIdx.y, c = blockIdx.x;
   if (c < I * kColBlocksPerRowBlock) return;      // left of the diagonal block: the pair belongs to the other row
   const int lane = threadIdx.x;
   const int cj = c * NC;
   const int ncols = min(N - cj, NC);
   double acc[RPL][NC];
-#pragma unroll
-  for (int rr = 0; rr < RPL; ++rr)
-#pragma unroll
-    for (int jj = 0; jj < NC; ++jj) acc[rr][jj] = INFINITY;
   if (ncols <= 0) {      // the last word's bytes behind the last drone
+#pragma unroll
+    for (int rr = 0; rr < RPL; ++rr)
+#pragma unroll
+      for (int jj = 0; jj < NC; ++jj) acc[rr][jj] = INFINITY;
     store_keep_bits(acc, pl, N, I, c, 0, lane, pitch_bytes, mask);
     return;
   }
-  const double *pt0 = prowT + (size_t)I * kRowBlock;
-  const int stride = S * 3;
-  // one or two samples behind the last whole chunk go through the plain loop; a longer remainder is a last chunk
-  // moved back to overlap its predecessor (a minimum does not mind seeing a sample twice)
-  const int rem = S % CH;
-  const int Sw = (rem == 1 || rem == 2) ? S - rem : S;
-  for (int sc = 0; sc < Sw; sc += CH) {
-    const int s0 = (Sw - sc < CH) ? Sw - CH : sc;
-    double row[RPL][CH][3];
-    const double *pt = pt0 + (size_t)s0 * 3 * Rp;
-#pragma unroll
-    for (int q = 0; q < CH; ++q)
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        const double *pk = pt + (size_t)(3 * q + k) * Rp;
-#pragma unroll
-        for (int rr = 0; rr < RPL; ++rr) row[rr][q][k] = pk[lane + rr * kWave];
-      }
-    // (opaque per chunk: the per-column strides are not to be hoisted out of the sample loop)
-    int nvalid = ncols;
-    asm volatile("" : "+s"(nvalid));
-    const double *pc = pcol + ((size_t)cj * S + s0) * 3;
-    auto consume = [&](int jj, const ColChunk &k) {
-#pragma unroll
-      for (int q = 0; q < CH; ++q)
-#pragma unroll
-        for (int rr = 0; rr < RPL; ++rr) {
-          const double dx = k.minus(3 * q + 0, row[rr][q][0]), dy = k.minus(3 * q + 1, row[rr][q][1]),
-                       dz = k.minus(3 * q + 2, row[rr][q][2]);
-          const double d2 = __builtin_fma(dz, dz, __builtin_fma(dy, dy, dx * dx));
-          // (by hand, as in the pairwise pass: no canonicalising v_max in front of the minimum; a quiet NaN loses)
-          asm("v_min_f64 %0, %1, %0" : "+v"(acc[rr][jj]) : "v"(d2));
-        }
-    };
-    // two register sets alternate; a short block re-reads its last column instead of branching
-    ColChunk ca, cb;
-    ca.fetch(pc);
-#pragma unroll
-    for (int jj = 0; jj < NC; jj += 2) {
-      pc += (jj + 1 < nvalid) ? stride : 0;
-      ca.wait(acc[RPL - 1][jj > 0 ? jj - 1 : 0]);
-      cb.fetch(pc);
-      consume(jj, ca);
-      pc += (jj + 2 < nvalid) ? stride : 0;
-      cb.wait(acc[RPL - 1][jj]);
-      if (jj + 2 < NC) ca.fetch(pc);
-      consume(jj + 1, cb);
-    }
-  }
-  for (int s1 = Sw; s1 < S; ++s1) {
-    const double *pt = pt0 + (size_t)s1 * 3 * Rp;
-    double rx[RPL], ry[RPL], rz[RPL];
-#pragma unroll
-    for (int rr = 0; rr < RPL; ++rr) {
-      rx[rr] = pt[lane + rr * kWave];
-      ry[rr] = pt[(size_t)Rp + lane + rr * kWave];
-      rz[rr] = pt[2 * (size_t)Rp + lane + rr * kWave];
-    }
-#pragma unroll
-    for (int jj = 0; jj < NC; ++jj) {
-      const double *pcs = pcol + ((size_t)(cj + (jj < ncols ? jj : ncols - 1)) * S + s1) * 3;
-      const double cx = pcs[0], cy = pcs[1], cz = pcs[2];
-#pragma unroll
-      for (int rr = 0; rr < RPL; ++rr) {
-        const double dx = cx - rx[rr], dy = cy - ry[rr], dz = cz - rz[rr];
-        acc[rr][jj] = __builtin_fmin(__builtin_fma(dz, dz, __builtin_fma(dy, dy, dx * dx)), acc[rr][jj]);
-      }
-    }
-  }
+  pair_tile_minima<NC>(prowT + (size_t)I * kRowBlock, Rp, pcol, S, cj, ncols, lane, 0, 1, acc);
   store_keep_bits(acc, pl, N, I, c, ncols, lane, pitch_bytes, mask);
 }
 
@@ -215,7 +122,7 @@ pairs_mask_short_kernel(const double *__restrict__ pos, int N, int S, PairLimit 
 #pragma unroll
       for (int rr = 0; rr < RPL; ++rr) {
         const double dx = cx - rx[rr], dy = cy - ry[rr], dz = cz - rz[rr];
-        acc[rr][jj] = __builtin_fmin(__builtin_fma(dz, dz, __builtin_fma(dy, dy, dx * dx)), acc[rr][jj]);
+        acc[rr][jj] = __builtin_fmin(pair_d2(dx, dy, dz), acc[rr][jj]);
       }
     }
   }
@@ -299,7 +206,7 @@ pairs_emit_kernel(const unsigned long long *__restrict__ mask, const int32_t *__
         double d2 = INFINITY;
         for (int s = 0; s < S; ++s) {
           const double dx = pb[3 * s] - pa[3 * s], dy = pb[3 * s + 1] - pa[3 * s + 1], dz = pb[3 * s + 2] - pa[3 * s + 2];
-          d2 = __builtin_fmin(__builtin_fma(dz, dz, __builtin_fma(dy, dy, dx * dx)), d2);
+          d2 = __builtin_fmin(pair_d2(dx, dy, dz), d2);
         }
         if (put) pair_dist[p] = sqrt(d2);
       }

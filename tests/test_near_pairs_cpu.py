@@ -21,6 +21,7 @@ import near_pairs_ref as NP  # noqa: E402
 from drone_path_planning_python_amd import swarm  # noqa: E402
 
 OBJ = os.path.join(ROOT, "drone_path_planning_python_amd", "csrc", "msnap_pairs.o")
+COLLIDE_OBJ = os.path.join(ROOT, "drone_path_planning_python_amd", "csrc", "msnap_collide.o")
 LLVM = "/opt/rocm/lib/llvm/bin"
 
 
@@ -233,10 +234,10 @@ def test_exec_check_and_latch_census_cover_the_new_object():
     assert chk.lane_latches(OBJ) == {}       # every loop of the file is wave-uniform
 
 
-def test_new_kernels_use_no_scratch_and_no_agprs(tmp_path):
-    _need_tools(OBJ)
-    fat, co = str(tmp_path / "fat.bin"), str(tmp_path / "pairs.co")
-    subprocess.run([f"{LLVM}/llvm-objcopy", f"--dump-section=.hip_fatbin={fat}", OBJ, str(tmp_path / "copy.o")], check=True)
+def _kernel_registers(obj, tmp_path):
+    """(names, scratch bytes, VGPRs, AGPRs) of the kernels of one object file, from the code object's metadata"""
+    fat, co = str(tmp_path / "fat.bin"), str(tmp_path / "kernels.co")
+    subprocess.run([f"{LLVM}/llvm-objcopy", f"--dump-section=.hip_fatbin={fat}", obj, str(tmp_path / "copy.o")], check=True)
     subprocess.run([f"{LLVM}/clang-offload-bundler", "--unbundle", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
                     f"--input={fat}", f"--output={co}"], check=True)
     notes = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", co], capture_output=True, text=True, check=True).stdout
@@ -244,8 +245,27 @@ def test_new_kernels_use_no_scratch_and_no_agprs(tmp_path):
     scratch = [int(x) for x in re.findall(r"\.private_segment_fixed_size:\s+(\d+)", notes)]
     vgpr = [int(x) for x in re.findall(r"\.vgpr_count:\s+(\d+)", notes)]
     agpr = [int(x) for x in re.findall(r"\.agpr_count:\s+(\d+)", notes)]
-    assert len(names) == len(scratch) == len(vgpr) == len(agpr) and len(names) >= 3
+    assert len(names) == len(scratch) == len(vgpr) == len(agpr)
+    return names, scratch, vgpr, agpr
+
+
+def test_new_kernels_use_no_scratch_and_no_agprs(tmp_path):
+    _need_tools(OBJ)
+    names, scratch, vgpr, agpr = _kernel_registers(OBJ, tmp_path)
+    assert len(names) >= 3
     assert any("pairs_mask_kernel" in n for n in names)
     assert scratch == [0] * len(names) and agpr == [0] * len(names)
-    # the mask pass at no worse than the pairwise evaluator's 3 waves per SIMD: 512 / 3 -> 168 registers
-    assert vgpr[[i for i, n in enumerate(names) if "pairs_mask_kernel" in n][0]] <= 168
+    # the mask pass at the pairwise evaluator's 4 waves per SIMD (its __launch_bounds__): 512 / 4 -> 128 registers
+    assert vgpr[[i for i, n in enumerate(names) if "pairs_mask_kernel" in n][0]] <= 128
+
+
+def test_tile_kernels_of_the_pairwise_pass_keep_their_register_budget(tmp_path):
+    """The kernels built on the shared register tile (csrc/msnap_pair_tile.h) and the group evaluator run at 4 waves per
+    SIMD: 512 / 4 = 128 VGPRs, nothing in scratch or in AGPRs -- in any kernel of the object."""
+    _need_tools(COLLIDE_OBJ)
+    names, scratch, vgpr, agpr = _kernel_registers(COLLIDE_OBJ, tmp_path)
+    assert scratch == [0] * len(names) and agpr == [0] * len(names), list(zip(names, scratch, agpr))
+    for kernel in ("collide_span_kernel", "collide_eval_shares_kernel", "collide_eval_groups_kernel"):
+        at = [i for i, n in enumerate(names) if kernel in n]
+        assert len(at) == 1, (kernel, names)
+        assert vgpr[at[0]] <= 128, (kernel, vgpr[at[0]])

@@ -240,6 +240,31 @@ def test_bitwise_ties_to_formation_collide(ctx7):
         assert other[d == d.min()].min() == partner[i]
 
 
+@pytest.mark.parametrize("s", [6, 7, 8, 9, 11, 13])
+def test_one_chunk_rule_for_the_pairwise_pass_and_the_mask(ctx7, s):
+    """Both callers of the register tile (csrc/msnap_pair_tile.h) on one swarm, with every pair kept: one chunk, the
+    plain remainders of one and two samples, a last chunk moved back, and the pairwise pass's shares cut into three sample
+    parts (more parts than chunks).  The option reaches the pairwise pass only."""
+    n = 137
+    pos, _ = NP.box_swarm(137100 + s, n, s)
+    base = 100.0                                                       # (the walks start in a unit box)
+    runs = []
+    try:
+        for parts in (0, 3):
+            ctx7.set_option("collide_sample_parts", parts)
+            md, _, _ = ctx7.formation_collide(pos, pos, 0.5)
+            pairs, dist = ctx7.near_pairs(pos, base, None, 0.0, 0.0)
+            assert len(pairs) == n * (n - 1) // 2
+            per_drone = np.full(n, np.inf)
+            np.minimum.at(per_drone, pairs[:, 0], dist)
+            np.minimum.at(per_drone, pairs[:, 1], dist)
+            assert per_drone.tobytes() == md.tobytes()                 # bit for bit
+            runs.append((pairs, dist))
+    finally:
+        ctx7.set_option("collide_sample_parts", 0)
+    assert runs[0][0].tobytes() == runs[1][0].tobytes() and runs[0][1].tobytes() == runs[1][1].tobytes()
+
+
 # ------------------------------------------------------------------------------------- determinism, capture, the limit
 def test_two_calls_and_both_entries_give_identical_bytes(ctx7):
     pos, speed = NP.box_swarm(5150, 300, 13)
