@@ -560,6 +560,69 @@ class Context:
                                                         int(n_dirs), _ptr(dirs), _ptr(ext), _ptr(t_ext), _ptr(upper),
                                                         _ptr(status)))
 
+    # ---- replanning in flight (include/msnap.h) -------------------------------------
+    def solve_states_max_segments(self) -> int:
+        """Largest segment count solve_states takes at this context's order (and at most max_segments)."""
+        return min(int(self._lib.msnap_solve_states_max_segments(self.order)), self.max_segments)
+
+    def _state_block(self, x, N, name):
+        if x is None:
+            return None, None
+        x, px = _host(x, np.float64)
+        if x.shape != (N, 4, self.ncoef // 2 - 1):
+            raise ValueError(f"{name} must be [N, 4, {self.ncoef // 2 - 1}] for this order-{self.order} context, "
+                             f"got {x.shape}")
+        return x, px
+
+    def solve_states(self, wp, t, start=None, end=None):
+        """solve_batch from and to given end states (msnap_solve_states): wp [N, m, 4], t [N, m] or shared [m] with
+        t[0] == 0, start / end [N, 4, K-1] -- entry q-1 the q-th derivative at the first / last waypoint -- or None for
+        rest -> coef [N, M, 4, ncoef], dur [N, M], status [N] int32."""
+        wp, pwp = _host(wp, np.float64)
+        t, pt = _host(t, np.float64)
+        if wp.ndim != 3 or wp.shape[2] != 4:
+            raise ValueError("wp must be [N, m, 4]")
+        N, m, _ = wp.shape
+        shared = int(t.ndim == 1)
+        if (shared and t.shape != (m,)) or (not shared and t.shape != (N, m)):
+            raise ValueError("t must be [N, m] or [m]")
+        M = m - 1
+        start, ps = self._state_block(start, N, "start")
+        end, pe = self._state_block(end, N, "end")
+        coef, dur, status = _out_arrays(None, ((N, max(M, 0), 4, self.ncoef), (N, max(M, 0)), (N,)))
+        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)      # noqa: E731
+        with self._lock:
+            self._ck(self._lib.msnap_solve_states(self._h, N, M, pwp, pt, shared, ps, pe, vp(coef), vp(dur),
+                                                  vp(status)))
+        return coef, dur, status
+
+    def solve_states_device(self, n_drones, n_seg, wp, t, shared_times, start, end, coef, dur, status):
+        """Device pointers (start / end may be None: rest), asynchronous on the context's stream."""
+        with self._lock:
+            self._ck(self._lib.msnap_solve_states_device(self._h, int(n_drones), int(n_seg), _ptr(wp), _ptr(t),
+                                                         int(bool(shared_times)), _ptr(start), _ptr(end), _ptr(coef),
+                                                         _ptr(dur), _ptr(status)))
+
+    def eval_state(self, coef, dur, tq):
+        """Full state of each drone at its own time tq [N] (msnap_eval_state): pos [N, 4], deriv [N, 4, K-1] with
+        entry q-1 the q-th derivative -- the layout solve_states takes as `start`.  NaN where tq is outside the path."""
+        coef, pc, dur, pd, N, M = self._coef_dur(coef, dur)
+        tq, ptq = _host(tq, np.float64)
+        if tq.shape != (N,):
+            raise ValueError("tq must be [N]")
+        pos = np.empty((N, 4), dtype=np.float64)
+        deriv = np.empty((N, 4, self.ncoef // 2 - 1), dtype=np.float64)
+        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)      # noqa: E731
+        with self._lock:
+            self._ck(self._lib.msnap_eval_state(self._h, N, M, pc, pd, ptq, vp(pos), vp(deriv)))
+        return pos, deriv
+
+    def eval_state_device(self, n_drones, n_seg, coef, dur, tq, pos, deriv):
+        """Device pointers, asynchronous on the context's stream."""
+        with self._lock:
+            self._ck(self._lib.msnap_eval_state_device(self._h, int(n_drones), int(n_seg), _ptr(coef), _ptr(dur),
+                                                       _ptr(tq), _ptr(pos), _ptr(deriv)))
+
     # ---- near pairs (include/msnap.h) ---------------------------------------------
     def near_pairs(self, pos, base: float, speed=None, gap: float = 0.0, margin: float = 0.0, max_pairs=None):
         """(pairs int32 [P, 2], dist [P]): every pair i < j of the swarm `pos` [N, S, 3] whose sampled distance is below

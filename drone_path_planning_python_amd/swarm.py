@@ -243,6 +243,38 @@ class DeviceCompute:
             self.ctx.path_extent_device(n, M, coef, dur, K, dirs.contiguous(), ext, t_ext, upper, status)
         return ext, t_ext, upper, status
 
+    # ---- replanning in flight (include/msnap.h) ----------------------------------------------------------------------
+    def solve_states(self, wp, t, start=None, end=None):
+        """(coef, dur, status) of the solve from and to given end states: `start` / `end` [n, 4, K-1] float64 -- entry
+        q-1 the q-th derivative at the first / last waypoint -- or None for rest; t[0] must be 0."""
+        torch = self.torch
+        n, m, _ = wp.shape
+        M = m - 1
+        nd = self.ctx.ncoef // 2 - 1
+        for name, x in (("start", start), ("end", end)):
+            if x is not None and (tuple(x.shape) != (n, 4, nd) or x.dtype != torch.float64):
+                raise ValueError(f"solve_states: {name} must be a float64 tensor [n, 4, {nd}]")
+        coef = self._out("solve_states.coef", (n, M, 4, self.ctx.ncoef), torch.float64)
+        dur = self._out("solve_states.dur", (n, M), torch.float64)
+        status = self._out("solve_states.status", (n,), torch.int32)
+        if n:
+            self.ctx.solve_states_device(n, M, wp.contiguous(), t.contiguous(), t.dim() == 1,
+                                         None if start is None else start.contiguous(),
+                                         None if end is None else end.contiguous(), coef, dur, status)
+        return coef, dur, status
+
+    def eval_state(self, coef, dur, tq):
+        """(pos [n, 4], deriv [n, 4, K-1]) of each drone at its own time tq [n]: NaN outside its path."""
+        torch = self.torch
+        n, M = dur.shape
+        if tuple(tq.shape) != (n,) or tq.dtype != torch.float64:
+            raise ValueError("eval_state: tq must be a float64 tensor [n]")
+        pos = self._out("eval_state.pos", (n, 4), torch.float64)
+        deriv = self._out("eval_state.deriv", (n, 4, self.ctx.ncoef // 2 - 1), torch.float64)
+        if n:
+            self.ctx.eval_state_device(n, M, coef, dur, tq.contiguous(), pos, deriv)
+        return pos, deriv
+
     # ---- near pairs (include/msnap.h) -------------------------------------------------------------------------------
     _near_pairs_first_capacity = None      # (tests force a tiny first capacity through this)
 
@@ -899,3 +931,31 @@ def certify_geofence(compute, coef, dur, lo=None, hi=None, planes=None, radius: 
     verdict[inside], verdict[outside], verdict[bad] = GEOFENCE_INSIDE, GEOFENCE_OUTSIDE, GEOFENCE_FAILED
     return GeofenceResult(verdict, inside, outside, undecided, bad, worst, t_worst, excess, normals, limits, ext, t_ext,
                           upper, box_lo, box_hi)
+
+
+def replan(compute, coef, dur, t_r, wp_new, t_new, end=None):
+    """Replan a flying swarm: leave the paths `coef`, `dur` at time `t_r` and fly through new waypoints.
+
+    `t_r` is a number or a tensor [N] (per drone, on the current paths' clock); `wp_new` [N, M', 4] are the waypoints
+    after the current position, `t_new` [N, M'] or [M'] their times counted from `t_r`, strictly positive and
+    increasing; `end` [N, 4, K-1] the state to arrive in (None: rest).  The state at `t_r` comes from
+    `compute.eval_state`, its position becomes the waypoint at time 0, its derivatives the start state of
+    `compute.solve_states`.  Returns (coef, dur, status, (pos, deriv)) -- the new paths on a clock that starts at `t_r`,
+    and the state they start from.  A drone whose `t_r` lies outside its path has a NaN state and comes back with
+    status 3 and NaN coefficients, as does one with bad times (status 2): nothing raises per drone."""
+    import torch
+    n = dur.shape[0]
+    dev = dur.device
+    if wp_new.dim() != 3 or wp_new.shape[0] != n or wp_new.shape[2] != 4 or wp_new.shape[1] < 1:
+        raise ValueError("replan: wp_new must be [N, M', 4] with M' >= 1")
+    mp_ = wp_new.shape[1]
+    if tuple(t_new.shape) not in ((mp_,), (n, mp_)):
+        raise ValueError("replan: t_new must be [N, M'] or [M']")
+    tq = torch.as_tensor(t_r, dtype=torch.float64).to(dev)
+    tq = tq.expand(n).contiguous() if tq.dim() == 0 else tq.contiguous()
+    pos, deriv = compute.eval_state(coef, dur, tq)
+    wp = torch.cat([pos[:, None, :], wp_new.to(torch.float64)], dim=1).contiguous()
+    t = torch.cat([torch.zeros(t_new.shape[:-1] + (1,), dtype=torch.float64, device=dev), t_new.to(torch.float64)],
+                  dim=-1).contiguous()
+    new_coef, new_dur, status = compute.solve_states(wp, t, start=deriv, end=end)
+    return new_coef, new_dur, status, (pos, deriv)

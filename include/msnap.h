@@ -465,6 +465,57 @@ int msnap_path_extent_device(msnap_ctx *ctx, int n_drones, int n_seg, const doub
                              int n_dirs, const double *dirs, double *ext, double *t_ext, double *upper,
                              int32_t *status);
 
+/* ---- replanning in flight: solve from and to given end states (new capability) ----
+ * Every other solve starts and ends at rest.  msnap_eval_state reads the full state of each drone on its current path
+ * at a time of its own; msnap_solve_states solves a new path from such a state, through new waypoints, to a given end
+ * state.  With K = (order + 1) / 2:
+ *
+ * msnap_solve_states.  wp, t, shared_times, coef, dur, status as for msnap_solve_batch.  start and end are
+ * [n_drones][4][K-1], axis-major (x, y, z, yaw): entry q-1 is the q-th time derivative at the first / last waypoint, in
+ * SI units (velocity, acceleration, jerk; snap too at order 9).  Either may be NULL: rest.  The result minimises the same
+ * cost as msnap_solve_batch -- the integral of (p^(K))^2 per axis -- interpolates the waypoints and has derivatives
+ * 1 .. K-1 at both ends equal to the given values; coef[0][a][0] is wp[0][a] bit for bit.  msnap_eval_state returns
+ * the given start derivatives at tq = 0 within 4 * 2^-52 relative, and the given end derivatives at the sum of the
+ * durations (as msnap_eval_flat accumulates it) within 4 * 2^-52 of max(|value|, sum_j |d_j| T^j), d the coefficients
+ * of the derivative being evaluated on the last segment: that segment takes one refinement step on its end conditions.
+ *   status   MSNAP_ST_NONFINITE for a NaN / Inf waypoint, time or state entry of that drone; MSNAP_ST_TIMES for times
+ *            not strictly increasing or t[0] != 0 (as msnap_optimize_times: the reference's quirk of taking segment 0's
+ *            start rows at local time t[0] has no meaning for a path that starts from a moving state, so it is not
+ *            reproduced here); MSNAP_ST_SINGULAR as in msnap_solve_batch.  A failed drone gets NaN coefficients;
+ *            dur[i] = t[i+1] - t[i] is written for every drone.
+ *   n_seg    1 .. msnap_solve_states_max_segments(order) -- 47 at order 7, 32 at order 9: what a 16-drone tile's state
+ *            leaves of 160 KiB of LDS; a replanning horizon is short -- and at most max_segments; MSNAP_ESEGMENTS above,
+ *            and nothing is written.  msnap_solve_states_max_segments returns MSNAP_EORDER for any other order.
+ * MSNAP_EINVAL: a null context, a null wp, t, coef, dur or status, negative n_drones.  n_drones == 0 is a no-op.  A
+ * drone's outputs are bit-identical whatever its place in the batch, the batch size, and host versus device entry;
+ * NULL and an array of zeros give the same bits.  The device version only launches (no synchronisation, no context
+ * buffer, so no capture rules).
+ *
+ * msnap_eval_state.  coef, dur as everywhere else; tq [n_drones]: drone d is evaluated at its own time tq[d].
+ *   pos   [n_drones][4]       the value of each axis;
+ *   deriv [n_drones][4][K-1]  entry q-1 its q-th derivative: the layout of msnap_solve_states' start, so a replan hands
+ *                             deriv over unchanged and copies pos into wp[d][0].
+ * The piece lookup is msnap_eval_flat's (the first segment with t <= acc + T_i: a knot belongs to the earlier segment),
+ * the arithmetic its Horner carried to derivative K-1: each derivative's coefficients are (double)(i + 1) * d[i + 1] of
+ * the previous one's, Horner uses a separate multiply and add, nothing is fused -- reproducible bit for bit in NumPy,
+ * and position, first and second derivative are bit for bit msnap_eval_flat's out[0..2], [3..5], [6..8] and yaw out[12]
+ * at the same time.  tq[d] outside [0, sum dur], or NaN, gives NaN in that drone's pos and deriv.  Both orders, n_seg
+ * 1 .. max_segments.  MSNAP_EINVAL / MSNAP_ESEGMENTS as everywhere; n_drones == 0 is a no-op; the device version only
+ * launches.
+ */
+int msnap_solve_states(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, const double *t, int shared_times,
+                       const double *start /* [n_drones][4][K-1] or NULL */,
+                       const double *end /* [n_drones][4][K-1] or NULL */, double *coef, double *dur, int32_t *status);
+int msnap_solve_states_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, const double *t,
+                              int shared_times, const double *start, const double *end, double *coef, double *dur,
+                              int32_t *status);
+int msnap_solve_states_max_segments(int order);     /* largest n_seg the entry takes; < 0: MSNAP_EORDER */
+int msnap_eval_state(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,
+                     const double *tq /* [n_drones] */, double *pos /* [n_drones][4] */,
+                     double *deriv /* [n_drones][4][K-1] */);
+int msnap_eval_state_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,
+                            const double *tq, double *pos, double *deriv);
+
 /* ---- near pairs: every pair of a swarm whose sampled distance is below a per-pair limit ----
  * msnap_formation_collide names one partner per drone; msnap_formation_near_pairs lists every close pair, e.g. the
  * pairs msnap_pair_clearance has to see.  pos [n_drones][n_samples][3] as the sampler writes it; speed [n_drones] or
