@@ -71,6 +71,8 @@ SIGNATURES = {
     "msnap_retime_to_limits_device": (_I, [_VP, _I, _I, _VP, _VP, _VP, _I, _VP, _VP, _VP]),
     "msnap_pair_clearance": (_I, [_VP, _I, _I, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP]),
     "msnap_pair_clearance_device": (_I, [_VP, _I, _I, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP]),
+    "msnap_cross_clearance": (_I, [_VP, _I, _I, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP]),
+    "msnap_cross_clearance_device": (_I, [_VP, _I, _I, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP]),
     "msnap_mesh_clearance": (_I, [_VP, _I, _I, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
     "msnap_mesh_clearance_device": (_I, [_VP, _I, _I, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
     "msnap_path_extent": (_I, [_VP, _I, _I, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP]),

@@ -506,6 +506,47 @@ class Context:
                                                            int(n_pairs), _ptr(pairs), _ptr(min_dist), _ptr(t_min),
                                                            _ptr(lower), _ptr(status)))
 
+    # ---- cross clearance: two path sets on shifted clocks (include/msnap.h) ----------------
+    def cross_clearance(self, coef_a, dur_a, coef_b, dur_b, pairs, t0_a=None, t0_b=None):
+        """Certified distance of drone a of set A and drone b of set B for the listed pairs [P, 2] = (index in A, index
+        in B), drone a flying P_a(t - t0_a[a]) on the common clock: (min_dist [P], t_min [P], lower [P], status [P]
+        int32) as pair_clearance, t_min on the common clock (msnap_cross_clearance).  The sets have their own segment
+        counts; t0_a [Na] / t0_b [Nb] default to zeros."""
+        coef_a, pca, dur_a, pda, Na, Ma = self._coef_dur(coef_a, dur_a)
+        coef_b, pcb, dur_b, pdb, Nb, Mb = self._coef_dur(coef_b, dur_b)
+        pr, ppr = _host(pairs, np.int32)
+        if pr.ndim != 2 or pr.shape[1] != 2:
+            raise ValueError("pairs must be [P, 2]")
+        t0 = []
+        for name, x, n in (("t0_a", t0_a, Na), ("t0_b", t0_b, Nb)):
+            if x is None:
+                t0.append((None, None))
+                continue
+            x, px = _host(x, np.float64)
+            if x.shape != (n,):
+                raise ValueError(f"{name} must be [{n}]")
+            t0.append((x, px))
+        P = pr.shape[0]
+        md = np.empty((P,), dtype=np.float64)
+        tm = np.empty((P,), dtype=np.float64)
+        lower = np.empty((P,), dtype=np.float64)
+        status = np.empty((P,), dtype=np.int32)
+        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)      # noqa: E731
+        with self._lock:
+            self._ck(self._lib.msnap_cross_clearance(self._h, Na, Ma, pca, pda, t0[0][1], Nb, Mb, pcb, pdb, t0[1][1], P,
+                                                     ppr, vp(md), vp(tm), vp(lower), vp(status)))
+        return md, tm, lower, status
+
+    def cross_clearance_device(self, n_a, n_seg_a, coef_a, dur_a, t0_a, n_b, n_seg_b, coef_b, dur_b, t0_b, n_pairs,
+                               pairs, min_dist, t_min, lower, status):
+        """Device pointers (t0_a / t0_b may be None: zeros; pairs int32 [n_pairs, 2]), asynchronous on the context's
+        stream."""
+        with self._lock:
+            self._ck(self._lib.msnap_cross_clearance_device(self._h, int(n_a), int(n_seg_a), _ptr(coef_a), _ptr(dur_a),
+                                                            _ptr(t0_a), int(n_b), int(n_seg_b), _ptr(coef_b),
+                                                            _ptr(dur_b), _ptr(t0_b), int(n_pairs), _ptr(pairs),
+                                                            _ptr(min_dist), _ptr(t_min), _ptr(lower), _ptr(status)))
+
     # ---- mesh clearance in continuous time (include/msnap.h) ------------------------------
     def mesh_clearance(self, coef, dur, tris):
         """Certified distance of each drone's whole path to the mesh `tris` [T, 3, 3]: (min_dist [N], t_min [N],

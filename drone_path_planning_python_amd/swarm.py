@@ -209,6 +209,30 @@ class DeviceCompute:
             self.ctx.pair_clearance_device(n, M, coef, dur, P, pairs.contiguous(), md, tm, lower, status)
         return md, tm, lower, status
 
+    # ---- cross clearance: two path sets on shifted clocks (include/msnap.h) ------------------------------------------
+    def cross_clearance(self, coef_a, dur_a, coef_b, dur_b, pairs, t0_a=None, t0_b=None):
+        """(min_dist [P], t_min [P], lower [P], status [P] int32) of the listed pairs (int32 [P, 2]: index in set A,
+        index in set B), drone a flying P_a(t - t0_a[a]) on the common clock; t0_a [Na] / t0_b [Nb] float64 or None
+        (zeros).  The sets have their own segment counts."""
+        torch = self.torch
+        (na, Ma), (nb, Mb) = dur_a.shape, dur_b.shape
+        if pairs.dim() != 2 or pairs.shape[1] != 2 or pairs.dtype != torch.int32:
+            raise ValueError("cross_clearance: pairs must be an int32 tensor [P, 2]")
+        for name, x, n in (("t0_a", t0_a, na), ("t0_b", t0_b, nb)):
+            if x is not None and (tuple(x.shape) != (n,) or x.dtype != torch.float64):
+                raise ValueError(f"cross_clearance: {name} must be a float64 tensor [{n}]")
+        P = pairs.shape[0]
+        md = self._out("cross_clearance.md", (P,), torch.float64)
+        tm = self._out("cross_clearance.tm", (P,), torch.float64)
+        lower = self._out("cross_clearance.lower", (P,), torch.float64)
+        status = self._out("cross_clearance.status", (P,), torch.int32)
+        if P:
+            self.ctx.cross_clearance_device(na, Ma, coef_a.contiguous(), dur_a.contiguous(),
+                                            None if t0_a is None else t0_a.contiguous(), nb, Mb, coef_b.contiguous(),
+                                            dur_b.contiguous(), None if t0_b is None else t0_b.contiguous(), P,
+                                            pairs.contiguous(), md, tm, lower, status)
+        return md, tm, lower, status
+
     # ---- mesh clearance in continuous time (include/msnap.h) --------------------------------------------------------
     def mesh_clearance(self, coef, dur, tris):
         """(min_dist [n], t_min [n], tri_min [n] int32, lower [n], status [n] int32): the certified distance of each
@@ -959,3 +983,87 @@ def replan(compute, coef, dur, t_r, wp_new, t_new, end=None):
                   dim=-1).contiguous()
     new_coef, new_dur, status = compute.solve_states(wp, t, start=deriv, end=end)
     return new_coef, new_dur, status, (pos, deriv)
+
+
+# ---- certified clearance of replanned paths against the paths that stay, and against each other ---------------------
+@dataclass
+class ReplanClearanceResult:
+    # per replanned drone [K], in the order of `idx`: a proven lower bound of its distance, on the new path, to every
+    # drone that keeps its path and to every other replanned drone while both fly, up to the rounding allowance of
+    # msnap_cross_clearance (include/msnap.h): certified_lower <= D (1 + 1e-13) + r for the exact infimum D of each pair
+    certified_lower: object
+    hit: object               # [K] bool: some pair of the drone ATTAINS a distance below 2 radius (definite)
+    undecided: object         # [K] bool: no hit, but a pair with lower < 2 radius <= min_dist (a search that met its caps)
+    pairs: object             # [P, 2] int32, swarm indices: (replanned drone, the other drone); new-old pairs first
+    pair_new_new: object      # [P] bool: the other drone is replanned too (both on their new paths)
+    pair_min_dist: object     # [P]
+    pair_t_min: object        # [P] on the swarm's clock
+    pair_lower: object        # [P]
+
+
+def certify_replan(compute, coef, dur, idx, t_r, new_coef, new_dur, radius: float, new_status=None) -> ReplanClearanceResult:
+    """Certify replanned paths next to the paths that stay, in continuous time.
+
+    The drones `idx` [K] (distinct swarm indices) leave the swarm's paths `coef`, `dur` at `t_r` -- a number, or one
+    value per replanned drone [K], on the swarm's clock -- for `new_coef` [K, M', 4, nc], `new_dur` [K, M'], whose clock
+    starts at `t_r` (what `replan` returns for those drones).  Every (new i, old j) pair with j not in `idx` and every
+    (new i, new j) pair with i < j goes through `compute.cross_clearance` (msnap_cross_clearance_device) with the
+    offsets `t_r`: the window of a pair is the time both fly, from the later start.  A drone that keeps its path is
+    certified against the new path only; its own pairs with other such drones are `certify_clearance`'s.
+
+    There is no sampled pre-filter: the pair count is K x N (K (N - K) + K (K - 1) / 2), which is small for the few
+    drones a replan touches and grows with the swarm.  One rank only.  Raises on failed drones (`new_status` != 0,
+    non-finite coefficients, durations <= 0), as `certify_clearance` does."""
+    import torch
+    if not (radius >= 0.0):
+        raise ValueError("certify_replan: radius >= 0")
+    n, dev = dur.shape[0], dur.device
+    idx = torch.as_tensor(idx, dtype=torch.int64).to(dev).reshape(-1)
+    K = int(idx.numel())
+    if new_dur.shape[0] != K or new_coef.shape[0] != K:
+        raise ValueError("certify_replan: new_coef, new_dur hold one path per entry of idx")
+    if K and (int(idx.min()) < 0 or int(idx.max()) >= n or int(torch.unique(idx).numel()) != K):
+        raise ValueError("certify_replan: idx holds distinct drone indices of the swarm")
+    if new_status is not None and int(new_status.abs().sum()) != 0:
+        raise ValueError("certify_replan: the replan reported failed drones (status != 0)")
+    t0 = torch.as_tensor(t_r, dtype=torch.float64).to(dev)
+    t0 = t0.expand(K).contiguous() if t0.dim() == 0 else t0.contiguous()
+    if tuple(t0.shape) != (K,):
+        raise ValueError("certify_replan: t_r is a number or one value per replanned drone")
+    stays = torch.ones((n,), dtype=torch.bool, device=dev)
+    stays[idx] = False
+    old = torch.nonzero(stays, as_tuple=True)[0]
+    loc = torch.arange(K, device=dev)
+    no = torch.stack([loc.repeat_interleave(old.numel()), old.repeat(K)], dim=1).to(torch.int32).contiguous()
+    ii, jj = torch.triu_indices(K, K, offset=1, device=dev)
+    nn = torch.stack([ii, jj], dim=1).to(torch.int32).contiguous()
+    outs = []
+    if no.shape[0]:
+        outs.append(tuple(x.clone() for x in compute.cross_clearance(new_coef, new_dur, coef, dur, no, t0_a=t0)))
+    if nn.shape[0]:
+        outs.append(tuple(x.clone() for x in compute.cross_clearance(new_coef, new_dur, new_coef, new_dur, nn, t0_a=t0,
+                                                                     t0_b=t0)))
+    certified = torch.full((K,), float("inf"), dtype=torch.float64, device=dev)
+    hit = torch.zeros((K,), dtype=torch.bool, device=dev)
+    undecided = torch.zeros((K,), dtype=torch.bool, device=dev)
+    if not outs:
+        empty = torch.zeros((0,), dtype=torch.float64, device=dev)
+        return ReplanClearanceResult(certified, hit, undecided, torch.zeros((0, 2), dtype=torch.int32, device=dev),
+                                     torch.zeros((0,), dtype=torch.bool, device=dev), empty, empty, empty)
+    md, tm, lower, pstat = (torch.cat([o[k] for o in outs]) for k in range(4))
+    if int(pstat.abs().sum()) != 0:
+        raise ValueError("certify_replan: msnap_cross_clearance reported failed pairs")
+    p_hit = md < 2.0 * radius
+    p_und = (~p_hit) & (lower < 2.0 * radius)
+    # the replanned drones a pair counts for: its first member, and its second where that one is replanned too
+    who = torch.cat([no[:, 0], nn[:, 0], nn[:, 1]]).to(torch.int64)
+    P0 = no.shape[0]
+    take = lambda x: torch.cat([x, x[P0:]])      # noqa: E731
+    certified.scatter_reduce_(0, who, take(lower), reduce="amin", include_self=True)
+    hit[who[take(p_hit)]] = True
+    undecided[who[take(p_und)]] = True
+    undecided &= ~hit
+    pairs = torch.cat([torch.stack([idx[no[:, 0].to(torch.int64)], no[:, 1].to(torch.int64)], dim=1),
+                       idx[nn.to(torch.int64)].reshape(-1, 2)]).to(torch.int32)
+    new_new = torch.arange(pairs.shape[0], device=dev) >= P0
+    return ReplanClearanceResult(certified, hit, undecided, pairs, new_new, md, tm, lower)

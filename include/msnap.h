@@ -70,7 +70,8 @@ enum msnap_status {       /* per-drone, written to status[]                   */
   MSNAP_ST_SINGULAR = 1,  /* a pivot of the block LDL^T was <= 0 or not finite */
   MSNAP_ST_TIMES = 2,     /* times not strictly increasing (or t[1] <= 2 t[0]) */
   MSNAP_ST_NONFINITE = 3, /* NaN / Inf in the waypoints or times               */
-  MSNAP_ST_PAIR = 4       /* msnap_pair_clearance: a drone index outside [0, n_drones), or a == b */
+  MSNAP_ST_PAIR = 4       /* msnap_pair_clearance: a drone index outside [0, n_drones), or a == b; msnap_cross_clearance:
+                             an index outside its set */
 };
 
 int msnap_version(void);                       /* 10000*major + 100*minor + patch */
@@ -380,6 +381,60 @@ int msnap_pair_clearance(msnap_ctx *ctx, int n_drones, int n_seg, const double *
 int msnap_pair_clearance_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,
                                 int n_pairs, const int32_t *pairs, double *min_dist, double *t_min, double *lower,
                                 int32_t *status);
+
+/* ---- cross clearance: two path sets on shifted clocks (new capability) ----
+ * msnap_pair_clearance takes both drones from one batch on one clock.  A replanned path (msnap_solve_states) starts at
+ * its own time, with its own segment count.  msnap_cross_clearance certifies the distance of drone a of set A and drone
+ * b of set B for the listed pairs p = (a, b) = pairs[p][0..1] (index in A, index in B).  Both sets have the context's
+ * order; n_seg_a and n_seg_b are independent, each 1 .. max_segments; the two sets may be the same arrays.
+ * Clock.  Drone a of set A is at P_a(t - t0_a[a]) at common-clock time t, P_a its piecewise polynomial with knots at
+ * the fp64 running sums of dur_a, as everywhere else; set B likewise.  t0_a [n_a] and t0_b [n_b] may each be NULL:
+ * zeros.
+ * Window.  [S, W] with S = max(t0_a[a], t0_b[b]) and W = min(fl(t0_a[a] + total_a), fl(t0_b[b] + total_b)), total the
+ * running sum of the drone's durations: while both fly.  A drone that has landed is NOT held at its end point, as for
+ * msnap_pair_clearance.  D is the infimum of the distance over the window for the exact real polynomials of the fp64
+ * coefficients, with the exact sums t0 + knot as knots.
+ *   min_dist [n_pairs]  a distance the pair ATTAINS, at
+ *   t_min    [n_pairs]  common-clock time, S <= t_min <= W (smaller value, then the earlier time).  Attained bit for
+ *                       bit: with tau_x = min(max(fl(t_min - t0_x), 0), total_x) for each of the two drones,
+ *                       msnap_eval_flat of drone a at tau_a and of drone b at tau_b gives positions whose
+ *                       sqrt(fma(dz, dz, fma(dy, dy, dx * dx))) is min_dist;
+ *   lower    [n_pairs]  a proven lower bound.  The inequalities are msnap_pair_clearance's,
+ *                         lower <= D (1 + 1e-13) + r   and   D <= min_dist (1 + 1e-13) + r,
+ *                         lower >= min_dist (1 - 1e-9) - 1e-9 - r   when the search closes (same caps: 40 bisections
+ *                         of an interval between knots, 4096 nodes per interval),
+ *                       with
+ *                         r = 1e-13 + C_ROUND_CROSS * 2^-52 * R + C_CLOCK * 2^-52 * T_c * R'   [m],
+ *                         C_ROUND_CROSS = 7,   C_CLOCK = 1
+ *                       R is msnap_pair_clearance's R over the segments of either drone that meet the window (the
+ *                       largest sum_k |c_k| T_i^k over x, y, z); T_c = max(|S|, |W|); R' is the largest
+ *                       sum_j j |c_j| T_i^(j-1) over the same axes, drones and segments -- the size of the velocity, as
+ *                       R'_q of msnap_dynamic_peaks.  The clock term is there because a local time fl(t - t0) is off by
+ *                       up to an ulp of t: at t0 = 1e4 s a drone at 10 m/s carries 2e-11 m of it.  Both constants are
+ *                       ten times the worst deviation measured against an exact reference.
+ *   status   [n_pairs]  msnap_status, first condition wins: MSNAP_ST_PAIR for an index outside [0, n_a) or [0, n_b)
+ *                       (nothing is read for such a pair; a == b is legal here), else MSNAP_ST_NONFINITE for a NaN /
+ *                       Inf coefficient, duration or t0 of either drone, else MSNAP_ST_TIMES for a duration <= 0.
+ *                       min_dist, t_min and lower of a failed pair are NaN.
+ * W < S (the drones never fly at the same time): min_dist = lower = +inf, t_min = NaN, status 0.  W == S: the distance
+ * at that one instant, t_min = S, lower = min_dist.
+ * Bit identities.  A pair's outputs do not depend on its place in the list or on the list's length; host entry and
+ * device entry give the same bits; NULL and an array of zeros give the same bits; exchanging the two sets, with the
+ * pairs flipped, gives the same bits; and with A == B, equal segment counts and zero offsets the outputs are bit for
+ * bit those of msnap_pair_clearance (a != b).
+ * n_pairs == 0 is a no-op.  MSNAP_EINVAL: a null context, a null array other than t0_a / t0_b, negative sizes, a launch
+ * grid beyond 2^31 blocks; MSNAP_ESEGMENTS per set as everywhere.  The device version only launches; its scratch is a
+ * buffer of the context under the capture rules above (MSNAP_ECAPTURE: run the call once outside the capture first).
+ * (Method: msnap_pair_clearance's, on the merged knots of the two drones on the common clock.)
+ */
+int msnap_cross_clearance(msnap_ctx *ctx, int n_a, int n_seg_a, const double *coef_a, const double *dur_a,
+                          const double *t0_a, int n_b, int n_seg_b, const double *coef_b, const double *dur_b,
+                          const double *t0_b, int n_pairs, const int32_t *pairs, double *min_dist, double *t_min,
+                          double *lower, int32_t *status);
+int msnap_cross_clearance_device(msnap_ctx *ctx, int n_a, int n_seg_a, const double *coef_a, const double *dur_a,
+                                 const double *t0_a, int n_b, int n_seg_b, const double *coef_b, const double *dur_b,
+                                 const double *t0_b, int n_pairs, const int32_t *pairs, double *min_dist, double *t_min,
+                                 double *lower, int32_t *status);
 
 /* ---- mesh clearance in continuous time (new capability) ----
  * msnap_mesh_sweep takes the point-triangle distance on the sampling grid only, and an STL wall has no thickness: a

@@ -1,0 +1,236 @@
+"""Cross clearance on the GPU (include/msnap.h, "cross clearance"): bit identity with msnap_pair_clearance, unequal
+segment counts and offsets against the exact reference (tests/cross_clearance_exact.py), a replanned drone against the
+path it left, the shifted crossing, the windows, the bit identities, per-pair status, a far clock and a far origin with
+the measured ratios, stream capture, and swarm.certify_replan on 12 drones."""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import cross_clearance_cases as XC  # noqa: E402
+import cross_clearance_exact as XE  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+ALL15 = XC.ALL15
+
+
+def _solver(ctx):
+    def solve(wp, t, nc):
+        assert nc == ctx.ncoef
+        coef, dur, status = ctx.solve_batch(wp, t)
+        assert (status == 0).all()
+        return coef, dur
+    return solve
+
+
+def _same(x, y):
+    return all(np.array_equal(p, q, equal_nan=True) for p, q in zip(x, y))
+
+
+def _identity(ctx, m):
+    coef, dur = _solver(ctx)(*XC.swarm(7000 + m, 6, m), ctx.ncoef)
+    want = ctx.pair_clearance(coef, dur, ALL15)
+    assert (want[3] == 0).all()
+    for t0 in (None, np.zeros(6)):
+        got = ctx.cross_clearance(coef, dur, coef, dur, ALL15, t0_a=t0, t0_b=t0)
+        assert _same(got, want), (got, want)
+
+
+@pytest.mark.parametrize("m", [1, 2, 10])
+def test_one_set_against_itself_is_pair_clearance_bit_for_bit_order7(ctx7, m):
+    _identity(ctx7, m)
+
+
+def test_one_set_against_itself_is_pair_clearance_bit_for_bit_order9(ctx9):
+    _identity(ctx9, 4)
+
+
+@pytest.mark.parametrize("ma, mb", [(3, 10), (1, 1)])
+def test_unequal_segment_counts_and_offsets_against_the_exact_reference_order7(ctx7, ma, mb):
+    XC.check_near(ctx7, _solver(ctx7), 8, ma, mb, attained_bits=True)
+
+
+def test_unequal_segment_counts_and_offsets_against_the_exact_reference_order9(ctx9):
+    XC.check_near(ctx9, _solver(ctx9), 10, 2, 5, attained_bits=True)
+
+
+def test_a_replanned_drone_against_the_path_it_left(ctx7):
+    """Example 08's replan of 3 of 8 drones at 40 % of the flight: the new path starts on the old one, so the pair's
+    minimum is at the window's start, t_min == t_r, and is zero up to the allowance."""
+    wp, t = XC.swarm(8, 8, 6)
+    coef, dur = _solver(ctx7)(wp, t, 8)
+    idx = [1, 4, 6]
+    t_r = 0.4 * np.add.accumulate(dur, axis=1)[idx, -1]
+    pos, deriv = ctx7.eval_state(coef[idx], dur[idx], t_r)
+    rng = np.random.default_rng(8)
+    wp_new = np.concatenate([pos[:, None, :], pos[:, None, :] + np.cumsum(rng.uniform(-2.0, 2.0, (3, 3, 4)), axis=1)], axis=1)
+    new_coef, new_dur, status = ctx7.solve_states(wp_new, np.array([0.0, 1.5, 3.0, 4.5]), start=deriv)
+    assert (status == 0).all()
+    pairs = np.array([[k, k] for k in range(3)], dtype=np.int32)
+    md, tm, lower, st = ctx7.cross_clearance(new_coef, new_dur, coef[idx], dur[idx], pairs, t0_a=t_r)
+    print("min_dist", md, "t_min", tm, "t_r", t_r, "lower", lower)
+    assert (st == 0).all()
+    for k in range(3):
+        args = (new_coef[k], new_dur[k], t_r[k], coef[idx[k]], dur[idx[k]], 0.0)
+        r = XE.allowance(XE.pair_R(*args), XE.T_c(new_dur[k], t_r[k], dur[idx[k]], 0.0), XE.pair_Rprime(*args))
+        assert tm[k] == t_r[k] and md[k] <= r and lower[k] <= r, (k, md[k], lower[k], r)
+
+
+def test_the_crossing_the_samples_miss_shifted(ctx7):
+    XC.check_crossing(ctx7, _solver(ctx7), attained_bits=True)
+
+
+def test_windows_disjoint_touching_and_inside_a_segment(ctx7):
+    XC.check_windows(ctx7, _solver(ctx7), attained_bits=True)
+
+
+def test_identities_sets_exchanged_list_position_null_offsets_and_entries(ctx7):
+    import torch
+    from drone_path_planning_python_amd import Context
+    from drone_path_planning_python_amd.swarm import DeviceCompute
+    ref = XC.check_identities_in_one_entry(ctx7, _solver(ctx7))
+    (ca, da, ta), (cb, db, _), pairs = XC.unequal(_solver(ctx7), 8, 3, 10)
+    with Context(device_id=0, order=7, max_segments=16) as ctx:
+        comp = DeviceCompute(ctx, torch)
+        dev = torch.device("cuda", 0)
+        tt = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)      # noqa: E731
+        out = comp.cross_clearance(tt(ca), tt(da), tt(cb), tt(db), tt(pairs), t0_a=tt(ta))
+        torch.cuda.synchronize()
+        assert _same([x.cpu().numpy() for x in out], ref)
+        out = comp.cross_clearance(tt(ca), tt(da), tt(cb), tt(db), torch.zeros((0, 2), dtype=torch.int32, device=dev))
+        assert all(x.shape == (0,) for x in out)                  # an empty list is a no-op
+
+
+def test_per_pair_status_precedence_and_guarded_buffers(ctx7):
+    import torch
+    from drone_path_planning_python_amd import Context
+    from drone_path_planning_python_amd._lib import MsnapError
+    from drone_path_planning_python_amd.swarm import DeviceCompute
+    (ca, da, ta), (cb, db, _), _ = XC.unequal(_solver(ctx7), 8, 3, 10)
+    good = ctx7.cross_clearance(ca, da, cb, db, ALL15, t0_a=ta)
+    ca, da, ta, cb, db, tb = ca.copy(), da.copy(), ta.copy(), cb.copy(), db.copy(), np.zeros(6)
+    ca[4, 1, 3, 2] = np.nan           # (the yaw axis: any coefficient of the drone counts)
+    db[5, 7] = 0.0
+    tb[4] = np.nan
+    da[5, 0] = -1.0
+    pairs = np.array([(0, 1), (-1, 2), (0, 2), (3, 6), (6, 3), (2, 2), (1, 5), (4, 5), (4, -1), (0, 4), (5, 4), (5, 5), (5, 3)],
+                     dtype=np.int32)
+    #       ok      PAIR     ok      PAIR    PAIR    ok      TIMES   NONFIN  PAIR     NONFIN  NONFIN  TIMES   TIMES
+    want = [0, 4, 0, 4, 4, 0, 2, 3, 4, 3, 3, 2, 2]
+    G = 1024                          # guard margins around every input on the device
+    with Context(device_id=0, order=7, max_segments=16) as ctx:
+        comp = DeviceCompute(ctx, torch)
+        dev = torch.device("cuda", 0)
+        arrs, bufs = (ca, da, ta, cb, db, tb), []
+        for arr in arrs:
+            g = torch.full((arr.size + 2 * G,), -7.25e300, dtype=torch.float64, device=dev)
+            g[G:G + arr.size] = torch.from_numpy(arr.reshape(-1)).to(dev)
+            bufs.append(g)
+        v = [b[G:G + a.size].view(a.shape) for b, a in zip(bufs, arrs)]
+        out = comp.cross_clearance(v[0], v[1], v[3], v[4], torch.from_numpy(pairs).to(dev), t0_a=v[2], t0_b=v[5])
+        torch.cuda.synchronize()
+        md, tm, lower, status = (x.cpu().numpy() for x in out)
+        for g, arr in zip(bufs, arrs):
+            g = g.cpu().numpy()
+            assert (g[:G] == -7.25e300).all() and (g[G + arr.size:] == -7.25e300).all()
+            assert np.array_equal(g[G:G + arr.size], arr.reshape(-1), equal_nan=True)
+    assert status.tolist() == want
+    lookup = {tuple(p): k for k, p in enumerate(ALL15.tolist())}
+    for k, (p, st) in enumerate(zip(pairs.tolist(), want)):
+        if st:
+            assert np.isnan(md[k]) and np.isnan(tm[k]) and np.isnan(lower[k])
+        elif tuple(p) in lookup:
+            j = lookup[tuple(p)]
+            assert (md[k], tm[k], lower[k]) == (good[0][j], good[1][j], good[2][j])
+        else:
+            assert np.isfinite(md[k]) and lower[k] <= md[k]       # (2, 2): the same index in both sets is legal
+    # the host entry gives the same; shape errors are refused
+    h = ctx7.cross_clearance(ca, da, cb, db, pairs, t0_a=ta, t0_b=tb)
+    assert np.array_equal(h[3], status) and _same(h[:3], (md, tm, lower))
+    big = ctx7.max_segments + 1
+    with pytest.raises(MsnapError):
+        ctx7.cross_clearance(ca, da, np.zeros((2, big, 4, 8)), np.ones((2, big)), pairs[:1])
+    with pytest.raises(MsnapError):
+        ctx7.cross_clearance(np.zeros((2, big, 4, 8)), np.ones((2, big)), cb, db, pairs[:1])
+    out = ctx7.cross_clearance(ca, da, cb, db, np.zeros((0, 2), dtype=np.int32))
+    assert all(x.shape == (0,) for x in out)
+
+
+def test_far_origin_ratio_below_c_round_cross(ctx7):
+    XC.check_far_origin(ctx7, _solver(ctx7), attained_bits=True)
+
+
+def test_far_clock_and_far_origin_ratios_below_the_constants(ctx7):
+    """t0 around 1e4 s, positions at +5000 m, the full allowance.  check_contract prints both ratios per pair; the
+    whole deviation is counted against the clock term and asserted below C_CLOCK, and the contract with both terms
+    holds."""
+    XC.check_far_clock(ctx7, _solver(ctx7), attained_bits=True)
+
+
+def test_a_captured_call_replays_and_a_capture_that_would_grow_the_scratch_is_refused():
+    import torch
+    from drone_path_planning_python_amd import Context
+    from drone_path_planning_python_amd._lib import MsnapError
+    dev = torch.device("cuda", 0)
+    with Context(device_id=0, order=7, max_segments=16) as ctx:
+        solve = _solver(ctx)
+        ca, da = solve(*XC.swarm(7501, 32, 3), 8)
+        cb, db = solve(*XC.swarm(7502, 64, 5), 8)
+        rng = np.random.default_rng(5)
+        pairs = np.stack([rng.integers(0, 32, size=300), rng.integers(0, 64, size=300)], axis=1).astype(np.int32)
+        ta = rng.uniform(0.0, 2.0, size=32)
+        eager = ctx.cross_clearance(ca, da, cb, db, pairs, t0_a=ta)
+        assert (eager[3] == 0).all()
+        side = torch.cuda.Stream()
+        P = pairs.shape[0]
+        with torch.cuda.stream(side):
+            ctx.set_stream(side.cuda_stream)
+            tca, tda, tta, tcb, tdb, tp = (torch.from_numpy(x).to(dev) for x in (ca, da, ta, cb, db, pairs))
+            md = torch.empty((P,), dtype=torch.float64, device=dev)
+            tm, lower = torch.empty_like(md), torch.empty_like(md)
+            st = torch.empty((P,), dtype=torch.int32, device=dev)
+            args = (32, 3, tca, tda, tta, 64, 5, tcb, tdb, None, P, tp, md, tm, lower, st)
+            ctx.cross_clearance_device(*args)                         # once eagerly: the scratch has its size
+            side.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, stream=side, capture_error_mode="thread_local"):
+                ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+                ctx.cross_clearance_device(*args)
+            ctx.set_stream(side.cuda_stream)
+            for _ in range(2):
+                for x in (md, tm, lower, st):
+                    x.zero_()
+                g.replay()
+                side.synchronize()
+                for got, want in zip((md, tm, lower, st), eager):
+                    assert np.array_equal(got.cpu().numpy(), want)
+            # the first call of a longer list inside a capture: the scratch would have to grow
+            tp2 = tp.repeat(4, 1).contiguous()
+            out2 = [torch.empty((4 * P,), dtype=torch.float64, device=dev) for _ in range(3)]
+            st2 = torch.empty((4 * P,), dtype=torch.int32, device=dev)
+            g2 = torch.cuda.CUDAGraph()
+            with pytest.raises(MsnapError) as err:
+                with torch.cuda.graph(g2, stream=side, capture_error_mode="thread_local"):
+                    ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+                    ctx.cross_clearance_device(32, 3, tca, tda, tta, 64, 5, tcb, tdb, None, 4 * P, tp2, *out2, st2)
+            assert err.value.code == -8                              # MSNAP_ECAPTURE
+            ctx.set_stream(side.cuda_stream)
+        ctx.use_own_stream()
+
+
+def test_certify_replan_on_12_drones_3_replanned(ctx7):
+    import torch
+    from drone_path_planning_python_amd import Context
+    from drone_path_planning_python_amd.swarm import DeviceCompute, certify_replan
+    coef, dur, new_coef, new_dur = XC.replan_swarm(_solver(ctx7))
+    with Context(device_id=0, order=7, max_segments=16) as ctx:
+        comp = DeviceCompute(ctx, torch)
+        dev = torch.device("cuda", 0)
+        tt = lambda x: torch.from_numpy(x).to(dev)      # noqa: E731
+        res = certify_replan(comp, tt(coef), tt(dur), XC.REPLAN_IDX, tt(np.array(XC.REPLAN_T_R)), tt(new_coef),
+                             tt(new_dur), XC.REPLAN_RADIUS, new_status=torch.zeros(3, dtype=torch.int32, device=dev))
+        torch.cuda.synchronize()
+        XC.check_replan(res, coef, dur, new_coef, new_dur)
