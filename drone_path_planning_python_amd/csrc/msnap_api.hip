@@ -189,7 +189,7 @@ void msnap_destroy(msnap_ctx *ctx) {
   if (ctx->own_stream) (void)hipStreamSynchronize(ctx->own_stream);
   (void)msnap_release_graph_buffers(ctx, nullptr);
   if (ctx->mesh_tests) (void)hipFree(ctx->mesh_tests);
-  for (msnap::DevBuf *b : {&ctx->scratch, &ctx->limits_work, &ctx->extent_work, &ctx->clearance_work, &ctx->cross_clearance_work, &ctx->mesh_clearance_work, &ctx->pairs_work, &ctx->host_stage, &ctx->collide_work, &ctx->grid_t,
+  for (msnap::DevBuf *b : {&ctx->scratch, &ctx->limits_work, &ctx->extent_work, &ctx->clearance_work,&ctx->mesh_clearance_work, &ctx->pairs_work, &ctx->host_stage, &ctx->collide_work, &ctx->grid_t,
                            &ctx->grid_wp, &ctx->grid_op, &ctx->grid_dur, &ctx->grid_status, &ctx->grid_frag})
     if (b->p) (void)hipFree(b->p);
   for (int k = 0; k < 2; ++k) {

@@ -1,28 +1,39 @@
-// Pairwise clearance in continuous time: the certified minimum distance of two drones of one batch while both fly
-// (include/msnap.h, "pairwise clearance").
+// Clearance of two drones in continuous time: the certified minimum distance of drone a and drone b while both fly.
+// One method, two entries (include/msnap.h), told apart by the template flag CROSS:
+//   CROSS = false  msnap_pair_clearance (K9): both drones from ONE batch on ONE clock.  Set B is set A, every offset is
+//                  the literal zero (no t0 is read, no 0.0 + x is formed), the window starts at 0, a == b is no pair.
+//   CROSS = true   msnap_cross_clearance (K14): drone a of set A against drone b of set B, each set with its own
+//                  segment count, each drone with its own start time t0 on a common clock (NULL: zeros).
+// With A == B and zero offsets the CROSS instance performs K9's operations (an offset of 0.0 added to or subtracted from
+// a time changes no bit of it).
 //
-// Window.  Knot times are the running sums acc = acc + T of each drone (as peaks_fold_kernel and msnap_eval_flat form
-// them); the window of a pair is [0, W], W = min of the two totals.  A drone that has landed is NOT held at its end
-// point: what happens after the shorter path ends is out of scope here.
+// Clock.  Drone a is at P_a(t - t0_a[a]) at common time t.  Its knots on the common clock are fl(t0_a + acc_i), acc_i
+// the running sums acc = acc + T of its durations (as peaks_fold_kernel and msnap_eval_flat form them); set B likewise.
+// The window is [S, W], S = max(t0_a, t0_b), W = min(fl(t0_a + total_a), fl(t0_b + total_b)).  A drone that has landed
+// is NOT held at its end point: what happens after the shorter path ends is out of scope here.
 //
-// Intervals.  Between consecutive knots of the two drones |p_a(t) - p_b(t)|^2 is one polynomial.  The end points
-// inside the window are the M - 1 interior knots of a, the M - 1 interior knots of b and W itself: 2 M - 1 slots, one
-// lane per (pair, slot).  The lane's interval ends at its end point and starts at the largest end point below it, ties
-// ordered a's knots < b's knots < W -- so coincident knots (a shared grid) leave the later slot empty, a slot whose end
-// point lies beyond W is dead, and every live interval is found exactly once whichever drone is called a.  Both are
-// found with uniform loops over the M durations (every lane of a pair loads the same addresses).
+// Intervals.  Between consecutive knots of the two drones |p_a - p_b|^2 is one polynomial.  The end points inside the
+// window are the Ma - 1 interior knots of a, the Mb - 1 interior knots of b and W itself: Ma + Mb - 1 slots, one lane
+// per (pair, slot).  The lane's interval ends at its end point and starts at the largest end point below it or at S,
+// ties ordered a's knots < b's knots < W -- so coincident knots (a shared grid) leave the later slot empty, a slot whose
+// end point lies at or below S, or beyond W, is dead, and every live interval is found exactly once whichever drone is
+// called a.  Both are found with two uniform loops over the durations of the two drones (every lane of a pair loads
+// the same addresses).
 //
-// Lane.  Per axis x, y, z: Taylor shift of each drone's polynomial to its local offset at the interval's start, the
-// DIFFERENCE of the two (before any square: near a minimum the distance carries the rounding of the difference, not
-// of the positions), scaled by h^j to u in [0, 1].  g(u) = sum of the three squares, degree 2 order.  Then the walk of
-// msnap_walk.h for a minimum: the smallest Bernstein coefficient of g as a lower bound, a node pruned when
+// Lane.  Per axis x, y, z: Taylor shift of each drone's polynomial to ITS local time at the interval's start,
+// fl(fl(start - t0) - knot) -- what msnap_eval_flat forms for the local time fl(start - t0) --, the DIFFERENCE of the
+// two (before any square: near a minimum the distance carries the rounding of the difference, not of the positions),
+// scaled by h^j to u in [0, 1].  g(u) = sum of the three squares, degree 2 order.  Then the walk of msnap_walk.h for a
+// minimum: the smallest Bernstein coefficient of g as a lower bound, a node pruned when
 // bound >= L (1 - kPruneRel) - kPruneAbs, L the smallest attained value; the lane carries what the walk proved.
 //
-// Fold.  One thread per pair over its slots: smallest attained value, then earliest absolute time; smallest bound.
-// The attained value is evaluated again at t_min in the t domain -- msnap_eval_flat's segment lookup and Horner, the
-// formation pass's fma(dz, dz, fma(dy, dy, dx dx)) -- so that eval_flat at t_min reproduces min_dist.  Nothing crosses
-// lanes but the trip count: a pair's outputs do not depend on its place in the list, and (b, a) gives the bits of
-// (a, b) (the difference changes sign exactly, every later quantity is even in it).
+// Fold.  One thread per pair over its slots: smallest attained value, then earliest time; smallest bound.  The attained
+// value is evaluated again at t_min in the t domain -- msnap_eval_flat's segment lookup and Horner at the local times
+// (CROSS: clamped, tau_x = min(max(fl(t_min - t0_x), 0), total_x)), the formation pass's
+// fma(dz, dz, fma(dy, dy, dx dx)) -- so that eval_flat at t_min reproduces min_dist.  CROSS, W < S: +inf, NaN, +inf;
+// W == S: no slot is live, the distance at S.  Nothing crosses lanes but the trip count: a pair's outputs do not depend
+// on its place in the list, and (b, a) gives the bits of (a, b) (the difference changes sign exactly, every later
+// quantity is even in it).
 #include <math.h>
 
 #include "msnap_api_util.h"
@@ -36,66 +47,86 @@ constexpr int kThreads = kClearanceThreads;
 constexpr double kPruneRel = 2e-9;       // on g = |.|^2: 1e-9 on the distance
 constexpr double kPruneAbs = 1e-18;      // on g: A^2 with A = 1e-9 m (DESIGN.md §5 K9 has the depth arithmetic)
 
-__device__ __forceinline__ bool pair_in_range(int a, int b, int N) {
-  return a >= 0 && b >= 0 && a < N && b < N && a != b;
-}
+// n drones of m segments; t0 [n]: the drones' start times on the common clock (NULL: zeros; CROSS only); flags [n m]:
+// clearance_flags_kernel's, filled in by the launcher
+struct PathSet {
+  int n, m;
+  const double *coef, *dur, *t0;
+  const int32_t *flags;
+};
 
-// one lane per (pair, slot): work[3 item] = smallest attained g of the slot's interval (+inf: an empty or dead slot, or
-// a failed pair), [3 item + 1] = its absolute time, [3 item + 2] = the proven lower bound of g there (+inf likewise)
-template <int NC>
+template <bool CROSS>
+__device__ __forceinline__ bool pair_in_range(int a, int b, int Na, int Nb) {
+  return a >= 0 && b >= 0 && a < Na && b < Nb && (CROSS || a != b);
+}
+// a drone's local time on the common clock, and back
+template <bool CROSS>
+__device__ __forceinline__ double on_clock(double t0, double local) { return CROSS ? t0 + local : local; }
+template <bool CROSS>
+__device__ __forceinline__ double local_time(double t, double t0) { return CROSS ? t - t0 : t; }
+
+// one lane per (pair, slot): the triple of store_lane (msnap_walk.h)
+template <int NC, bool CROSS>
 __global__ void __launch_bounds__(kThreads)
-clearance_lane_kernel(const double *__restrict__ coef, const double *__restrict__ dur,
-                      const int32_t *__restrict__ flags, int N, int M, int n_pairs, const int32_t *__restrict__ pairs,
-                      double *__restrict__ work) {
+pair_lane_kernel(const PathSet A, const PathSet B_, int n_pairs, const int32_t *__restrict__ pairs,
+                 double *__restrict__ work) {
   constexpr int D = NC - 1;       // degree of the positions
+  const PathSet &B = CROSS ? B_ : A;
   const double inf = __builtin_inf();
-  const int slots = 2 * M - 1;
+  const int slots = A.m + B.m - 1;
   const size_t total = (size_t)n_pairs * slots;
   const size_t item = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const bool in_range = item < total;
   const size_t p = in_range ? item / (size_t)slots : 0;
   const int k = (int)(item - p * (size_t)slots);
   const int a0 = in_range ? pairs[2 * p] : 0, b0 = in_range ? pairs[2 * p + 1] : 0;
-  const bool pair_ok = in_range && pair_in_range(a0, b0, N);
-  const size_t da = pair_ok ? (size_t)a0 * M : 0, db = pair_ok ? (size_t)b0 * M : 0;
+  const bool pair_ok = in_range && pair_in_range<CROSS>(a0, b0, A.n, B.n);
+  const size_t da = pair_ok ? (size_t)a0 * A.m : 0, db = pair_ok ? (size_t)b0 * B.m : 0;
+  const double ta = (CROSS && pair_ok && A.t0) ? A.t0[a0] : 0.0, tb = (CROSS && pair_ok && B.t0) ? B.t0[b0] : 0.0;
   // the slot's end point: an interior knot of a (kind 0), of b (kind 1), or the window's end (kind 2)
-  const int kind = k < M - 1 ? 0 : (k < 2 * M - 2 ? 1 : 2);
-  const int own = kind == 0 ? k : k - (M - 1);
+  const int kind = k < A.m - 1 ? 0 : (k < A.m + B.m - 2 ? 1 : 2);
+  const int own = kind == 0 ? k : k - (A.m - 1);
 
-  // first pass over the durations: the totals, the slot's end point, the drones' flags
+  // first pass over the durations, both drones in one loop (their loads are in flight together; a set with fewer
+  // segments sits out the last rounds): the totals, the slot's end point, the drones' flags
+  const int Mmax = max(A.m, B.m);
   double accA = 0.0, accB = 0.0, E = 0.0;
-  int bad = 0;
-  for (int i = 0; i < M; ++i) {
-    const double Ta = pair_ok ? dur[da + i] : 1.0, Tb = pair_ok ? dur[db + i] : 1.0;
-    bad |= pair_ok ? (flags[da + i] | flags[db + i]) : 0;
-    accA = accA + Ta;
-    accB = accB + Tb;
-    if (kind == 0 && i == own) E = accA;
-    if (kind == 1 && i == own) E = accB;
+  int bad = (!CROSS || (isfinite(ta) && isfinite(tb))) ? 0 : 2;
+  for (int i = 0; i < Mmax; ++i) {
+    const bool inA = i < A.m, inB = i < B.m;
+    const double Ta = (pair_ok && inA) ? A.dur[da + i] : 1.0, Tb = (pair_ok && inB) ? B.dur[db + i] : 1.0;
+    bad |= (pair_ok && inA) ? A.flags[da + i] : 0;
+    bad |= (pair_ok && inB) ? B.flags[db + i] : 0;
+    accA = inA ? accA + Ta : accA;
+    accB = inB ? accB + Tb : accB;
+    if (kind == 0 && i == own) E = on_clock<CROSS>(ta, accA);
+    if (kind == 1 && i == own) E = on_clock<CROSS>(tb, accB);
   }
-  const double Wend = fmin(accA, accB);
+  const double S = CROSS ? fmax(ta, tb) : 0.0;
+  const double Wend = fmin(on_clock<CROSS>(ta, accA), on_clock<CROSS>(tb, accB));
   if (kind == 2) E = Wend;
   const bool valid = pair_ok && bad == 0;
 
-  // second pass: the interval's start (the largest end point below E; ties: a's knots < b's knots < the window's
-  // end) and the segment of each drone that holds it, by msnap_eval_flat's lookup (first i with E <= acc_i)
-  double start = 0.0, offA = 0.0, offB = 0.0;
-  int segA = M - 1, segB = M - 1;
+  // second pass: the interval's start (the largest end point below E, or S; ties: a's knots < b's knots < the
+  // window's end) and the segment of each drone that holds it, by msnap_eval_flat's lookup (first i with E <= knot_i)
+  double start = S, offA = 0.0, offB = 0.0;
+  int segA = A.m - 1, segB = B.m - 1;
   bool foundA = false, foundB = false;
   accA = 0.0;
   accB = 0.0;
-  for (int i = 0; i < M; ++i) {
-    const double Ta = valid ? dur[da + i] : 1.0, Tb = valid ? dur[db + i] : 1.0;
+  for (int i = 0; i < Mmax; ++i) {
+    const bool inA = i < A.m, inB = i < B.m;
+    const double Ta = (valid && inA) ? A.dur[da + i] : 1.0, Tb = (valid && inB) ? B.dur[db + i] : 1.0;
     const double prevA = accA, prevB = accB;
-    accA = accA + Ta;
-    accB = accB + Tb;
-    const bool interior = i < M - 1;
-    const bool belowA = kind == 0 ? accA < E : accA <= E;
-    const bool belowB = kind == 2 ? accB <= E : accB < E;
-    if (interior && belowA) start = fmax(start, accA);
-    if (interior && belowB) start = fmax(start, accB);
-    if (!foundA && E <= accA) { segA = i; offA = prevA; foundA = true; }
-    if (!foundB && E <= accB) { segB = i; offB = prevB; foundB = true; }
+    accA = inA ? accA + Ta : accA;
+    accB = inB ? accB + Tb : accB;
+    const double kA = on_clock<CROSS>(ta, accA), kB = on_clock<CROSS>(tb, accB);
+    const bool belowA = kind == 0 ? kA < E : kA <= E;
+    const bool belowB = kind == 2 ? kB <= E : kB < E;
+    if (i < A.m - 1 && belowA) start = fmax(start, kA);
+    if (i < B.m - 1 && belowB) start = fmax(start, kB);
+    if (inA && !foundA && E <= kA) { segA = i; offA = prevA; foundA = true; }
+    if (inB && !foundB && E <= kB) { segB = i; offB = prevB; foundB = true; }
   }
   const double h = E - start;
   const bool ok = valid && E <= Wend && h > 0.0;
@@ -103,8 +134,8 @@ clearance_lane_kernel(const double *__restrict__ coef, const double *__restrict_
   // e[s][j]: the difference polynomial of axis s on the interval, in u
   double e[3][D + 1];
   {
-    const double la = start - offA, lb = start - offB;
-    const double *ca = coef + (da + segA) * 4 * NC, *cb = coef + (db + segB) * 4 * NC;
+    const double la = local_time<CROSS>(start, ta) - offA, lb = local_time<CROSS>(start, tb) - offB;
+    const double *ca = A.coef + (da + segA) * 4 * NC, *cb = B.coef + (db + segB) * 4 * NC;
 #pragma unroll
     for (int s = 0; s < 3; ++s) {
       double pa[NC], pb[NC];
@@ -155,35 +186,51 @@ clearance_lane_kernel(const double *__restrict__ coef, const double *__restrict_
   store_lane(work, item, ok, best, best_u, proven.low, h, start, E);
 }
 
-// one thread per pair: fold the slots (smaller value, then earlier time; smallest bound), status, the attained value
-// again in the t domain
-template <int NC>
+// one thread per pair: status, the window, the fold of the slots (smaller value, then earlier time; smallest bound),
+// the attained value again in the t domain
+template <int NC, bool CROSS>
 __global__ void __launch_bounds__(kThreads)
-clearance_fold_kernel(const double *__restrict__ coef, const double *__restrict__ dur,
-                      const int32_t *__restrict__ flags, const double *__restrict__ work, int N, int M, int n_pairs,
-                      const int32_t *__restrict__ pairs, double *__restrict__ min_dist, double *__restrict__ t_min,
-                      double *__restrict__ lower, int32_t *__restrict__ status) {
+pair_fold_kernel(const PathSet A, const PathSet B_, const double *__restrict__ work, int n_pairs,
+                 const int32_t *__restrict__ pairs, double *__restrict__ min_dist, double *__restrict__ t_min,
+                 double *__restrict__ lower, int32_t *__restrict__ status) {
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= n_pairs) return;
-  const double nan = __builtin_nan("");
+  const PathSet &B = CROSS ? B_ : A;
+  const double nan = __builtin_nan(""), inf = __builtin_inf();
   const int a = pairs[2 * (size_t)p], b = pairs[2 * (size_t)p + 1];
-  int st = MSNAP_ST_OK;
-  if (!pair_in_range(a, b, N)) {
-    st = MSNAP_ST_PAIR;
-  } else {
-    int bad = 0;
-    for (int i = 0; i < M; ++i) bad |= flags[(size_t)a * M + i] | flags[(size_t)b * M + i];
-    st = (bad & 2) ? MSNAP_ST_NONFINITE : ((bad & 1) ? MSNAP_ST_TIMES : MSNAP_ST_OK);
+  const size_t da = (size_t)a * A.m, db = (size_t)b * B.m;
+  int st = MSNAP_ST_PAIR;
+  double ta = 0.0, tb = 0.0, totA = 0.0, totB = 0.0;      // (CROSS only: the clamp's)
+  if (pair_in_range<CROSS>(a, b, A.n, B.n)) {
+    if (CROSS) {
+      ta = A.t0 ? A.t0[a] : 0.0;
+      tb = B.t0 ? B.t0[b] : 0.0;
+    }
+    int bad = (isfinite(ta) && isfinite(tb)) ? 0 : 2;
+    for (int i = 0; i < A.m; ++i) {
+      bad |= A.flags[da + i];
+      if (CROSS) totA = totA + A.dur[da + i];
+    }
+    for (int i = 0; i < B.m; ++i) {
+      bad |= B.flags[db + i];
+      if (CROSS) totB = totB + B.dur[db + i];
+    }
+    st = status_of_flags(bad);
   }
   double md = nan, tm = nan, lo = nan;
-  if (st == MSNAP_ST_OK) {
-    const int slots = 2 * M - 1;
-    const double *w = work + (size_t)p * slots * 3;
+  const double S = fmax(ta, tb);
+  if (st == MSNAP_ST_OK && CROSS && fmin(ta + totA, tb + totB) < S) {      // the drones never fly at the same time
+    md = inf;
+    lo = inf;
+  } else if (st == MSNAP_ST_OK) {
+    const int slots = A.m + B.m - 1;
     double best, bt, low;
-    fold_slots(w, slots, best, bt, low);
+    fold_slots(work + (size_t)p * slots * 3, slots, best, bt, low);
+    if (CROSS && !(best < inf)) bt = S;      // no live slot: W == S, the one instant
+    const double tauA = CROSS ? fmin(fmax(bt - ta, 0.0), totA) : bt, tauB = CROSS ? fmin(fmax(bt - tb, 0.0), totB) : bt;
     double xa, ya, za, xb, yb, zb;
-    position_at<NC>(coef, dur, (size_t)a * M, M, bt, xa, ya, za);
-    position_at<NC>(coef, dur, (size_t)b * M, M, bt, xb, yb, zb);
+    position_at<NC>(A.coef, A.dur, da, A.m, tauA, xa, ya, za);
+    position_at<NC>(B.coef, B.dur, db, B.m, tauB, xb, yb, zb);
     const double dx = xa - xb, dy = ya - yb, dz = za - zb;
     md = sqrt(fma(dz, dz, fma(dy, dy, dx * dx)));
     tm = bt;
@@ -195,35 +242,44 @@ clearance_fold_kernel(const double *__restrict__ coef, const double *__restrict_
   status[p] = st;
 }
 
-template <int NC>
-int launch(msnap_ctx *ctx, int N, int M, const double *coef, const double *dur, int n_pairs, const int32_t *pairs,
-           void *scratch, double *min_dist, double *t_min, double *lower, int32_t *status) {
-  const size_t lanes = clearance_lanes(n_pairs, M), segs = (size_t)N * M;
+template <int NC, bool CROSS>
+int launch(msnap_ctx *ctx, PathSet A, PathSet B, int n_pairs, const int32_t *pairs, void *scratch, double *min_dist,
+           double *t_min, double *lower, int32_t *status) {
+  const size_t lanes = clearance_lanes(n_pairs, A.m, B.m), segs_a = (size_t)A.n * A.m;
   double *work = (double *)scratch;
-  int32_t *flags = (int32_t *)(work + 3 * lanes);
-  if (segs) {
+  int32_t *flags[2] = {(int32_t *)(work + 3 * lanes), nullptr};
+  flags[1] = CROSS ? flags[0] + segs_a : flags[0];
+  PathSet *sets[2] = {&A, &B};
+  for (int s = 0; s < (CROSS ? 2 : 1); ++s) {       // K9's set B is its set A: one flags launch
+    const size_t segs = (size_t)sets[s]->n * sets[s]->m;
+    if (!segs) continue;
     hipLaunchKernelGGL((clearance_flags_kernel<NC>), dim3(blocks_of(segs, kThreads)), dim3(kThreads), 0, ctx->stream,
-                       coef, dur, segs, flags);
+                       sets[s]->coef, sets[s]->dur, segs, flags[s]);
     MSNAP_HIP(ctx, hipGetLastError());
   }
-  hipLaunchKernelGGL((clearance_lane_kernel<NC>), dim3(blocks_of(lanes, kThreads)), dim3(kThreads), 0, ctx->stream,
-                     coef, dur, (const int32_t *)flags, N, M, n_pairs, pairs, work);
+  A.flags = flags[0];
+  B.flags = flags[1];
+  hipLaunchKernelGGL((pair_lane_kernel<NC, CROSS>), dim3(blocks_of(lanes, kThreads)), dim3(kThreads), 0, ctx->stream,
+                     A, B, n_pairs, pairs, work);
   MSNAP_HIP(ctx, hipGetLastError());
-  hipLaunchKernelGGL((clearance_fold_kernel<NC>), dim3(blocks_of(n_pairs, kThreads)), dim3(kThreads), 0, ctx->stream,
-                     coef, dur, (const int32_t *)flags, (const double *)work, N, M, n_pairs, pairs, min_dist, t_min,
-                     lower, status);
+  hipLaunchKernelGGL((pair_fold_kernel<NC, CROSS>), dim3(blocks_of(n_pairs, kThreads)), dim3(kThreads), 0, ctx->stream,
+                     A, B, (const double *)work, n_pairs, pairs, min_dist, t_min, lower, status);
   MSNAP_HIP(ctx, hipGetLastError());
   return MSNAP_OK;
 }
 
-int launch_pair_clearance(msnap_ctx *ctx, int N, int M, const double *coef, const double *dur, int n_pairs,
-                          const int32_t *pairs, double *min_dist, double *t_min, double *lower, int32_t *status) {
-  const int rc = ensure(ctx, ctx->clearance_work, clearance_work_bytes(N, M, n_pairs));
+// cross = false: B is A given again (the K9 instances read only A)
+int launch_clearance(msnap_ctx *ctx, bool cross, const PathSet &A, const PathSet &B, int n_pairs, const int32_t *pairs,
+                     double *min_dist, double *t_min, double *lower, int32_t *status) {
+  const size_t segs = (size_t)A.n * A.m + (cross ? (size_t)B.n * B.m : 0);
+  const int rc = ensure(ctx, ctx->clearance_work, clearance_work_bytes(clearance_lanes(n_pairs, A.m, B.m), segs));
   if (rc) return rc;
   void *scratch = ctx->clearance_work.p;
-  return ctx->order == 7
-             ? launch<8>(ctx, N, M, coef, dur, n_pairs, pairs, scratch, min_dist, t_min, lower, status)
-             : launch<10>(ctx, N, M, coef, dur, n_pairs, pairs, scratch, min_dist, t_min, lower, status);
+  if (ctx->order == 7)
+    return cross ? launch<8, true>(ctx, A, B, n_pairs, pairs, scratch, min_dist, t_min, lower, status)
+                 : launch<8, false>(ctx, A, B, n_pairs, pairs, scratch, min_dist, t_min, lower, status);
+  return cross ? launch<10, true>(ctx, A, B, n_pairs, pairs, scratch, min_dist, t_min, lower, status)
+               : launch<10, false>(ctx, A, B, n_pairs, pairs, scratch, min_dist, t_min, lower, status);
 }
 
 }  // namespace
@@ -234,9 +290,9 @@ using namespace msnap;
 extern "C" {
 
 // the entry points live beside their launcher, as msnap_timeopt.hip's do
-static int clearance_args(const msnap_ctx *ctx, int n_drones, int n_seg, int n_pairs,
+static int clearance_args(const msnap_ctx *ctx, int n_a, int n_seg_a, int n_b, int n_seg_b, int n_pairs,
                           std::initializer_list<const void *> ptrs) {
-  if (int rc = check_clearance_args(ctx, n_drones, n_seg, n_pairs)) return rc;
+  if (int rc = check_clearance_args(ctx, n_a, n_seg_a, n_b, n_seg_b, n_pairs)) return rc;
   if (n_pairs == 0) return kNoWork;
   for (const void *p : ptrs)
     if (!p) return MSNAP_EINVAL;
@@ -246,19 +302,52 @@ static int clearance_args(const msnap_ctx *ctx, int n_drones, int n_seg, int n_p
 int msnap_pair_clearance_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,
                                 int n_pairs, const int32_t *pairs, double *min_dist, double *t_min, double *lower,
                                 int32_t *status) {
-  MSNAP_ENTER(ctx, clearance_args(ctx, n_drones, n_seg, n_pairs, {coef, dur, pairs, min_dist, t_min, lower, status}));
-  return launch_pair_clearance(ctx, n_drones, n_seg, coef, dur, n_pairs, pairs, min_dist, t_min, lower, status);
+  MSNAP_ENTER(ctx, clearance_args(ctx, n_drones, n_seg, n_drones, n_seg, n_pairs,
+                                  {coef, dur, pairs, min_dist, t_min, lower, status}));
+  const PathSet A = {n_drones, n_seg, coef, dur, nullptr, nullptr};
+  return launch_clearance(ctx, false, A, A, n_pairs, pairs, min_dist, t_min, lower, status);
 }
 
 int msnap_pair_clearance(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur, int n_pairs,
                          const int32_t *pairs, double *min_dist, double *t_min, double *lower, int32_t *status) {
-  MSNAP_ENTER(ctx, clearance_args(ctx, n_drones, n_seg, n_pairs, {coef, dur, pairs, min_dist, t_min, lower, status}));
+  MSNAP_ENTER(ctx, clearance_args(ctx, n_drones, n_seg, n_drones, n_seg, n_pairs,
+                                  {coef, dur, pairs, min_dist, t_min, lower, status}));
   const size_t b_out = (size_t)n_pairs * 8;
   return staged(ctx, {upload(coef, coef_bytes(ctx, n_drones, n_seg)), upload(dur, dur_bytes(n_drones, n_seg)),
                       upload(pairs, (size_t)n_pairs * 2 * 4), download(min_dist, b_out), download(t_min, b_out),
                       download(lower, b_out), download(status, (size_t)n_pairs * 4)},
                 [&](const DevPtr *d) {
-                  return launch_pair_clearance(ctx, n_drones, n_seg, d[0], d[1], n_pairs, d[2], d[3], d[4], d[5], d[6]);
+                  const PathSet A = {n_drones, n_seg, d[0], d[1], nullptr, nullptr};
+                  return launch_clearance(ctx, false, A, A, n_pairs, d[2], d[3], d[4], d[5], d[6]);
+                });
+}
+
+int msnap_cross_clearance_device(msnap_ctx *ctx, int n_a, int n_seg_a, const double *coef_a, const double *dur_a,
+                                 const double *t0_a, int n_b, int n_seg_b, const double *coef_b, const double *dur_b,
+                                 const double *t0_b, int n_pairs, const int32_t *pairs, double *min_dist, double *t_min,
+                                 double *lower, int32_t *status) {
+  MSNAP_ENTER(ctx, clearance_args(ctx, n_a, n_seg_a, n_b, n_seg_b, n_pairs,
+                                  {coef_a, dur_a, coef_b, dur_b, pairs, min_dist, t_min, lower, status}));
+  return launch_clearance(ctx, true, {n_a, n_seg_a, coef_a, dur_a, t0_a, nullptr},
+                          {n_b, n_seg_b, coef_b, dur_b, t0_b, nullptr}, n_pairs, pairs, min_dist, t_min, lower, status);
+}
+
+int msnap_cross_clearance(msnap_ctx *ctx, int n_a, int n_seg_a, const double *coef_a, const double *dur_a,
+                          const double *t0_a, int n_b, int n_seg_b, const double *coef_b, const double *dur_b,
+                          const double *t0_b, int n_pairs, const int32_t *pairs, double *min_dist, double *t_min,
+                          double *lower, int32_t *status) {
+  MSNAP_ENTER(ctx, clearance_args(ctx, n_a, n_seg_a, n_b, n_seg_b, n_pairs,
+                                  {coef_a, dur_a, coef_b, dur_b, pairs, min_dist, t_min, lower, status}));
+  const size_t b_out = (size_t)n_pairs * 8;
+  return staged(ctx, {upload(coef_a, coef_bytes(ctx, n_a, n_seg_a)), upload(dur_a, dur_bytes(n_a, n_seg_a)),
+                      upload(t0_a, t0_a ? (size_t)n_a * 8 : 0), upload(coef_b, coef_bytes(ctx, n_b, n_seg_b)),
+                      upload(dur_b, dur_bytes(n_b, n_seg_b)), upload(t0_b, t0_b ? (size_t)n_b * 8 : 0),
+                      upload(pairs, (size_t)n_pairs * 2 * 4), download(min_dist, b_out), download(t_min, b_out),
+                      download(lower, b_out), download(status, (size_t)n_pairs * 4)},
+                [&](const DevPtr *d) {
+                  const double *da = t0_a ? (const double *)d[2] : nullptr, *db = t0_b ? (const double *)d[5] : nullptr;
+                  return launch_clearance(ctx, true, {n_a, n_seg_a, d[0], d[1], da, nullptr},
+                                          {n_b, n_seg_b, d[3], d[4], db, nullptr}, n_pairs, d[6], d[7], d[8], d[9], d[10]);
                 });
 }
 

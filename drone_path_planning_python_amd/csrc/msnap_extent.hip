@@ -128,7 +128,7 @@ extent_fold_kernel(const double *__restrict__ coef, const double *__restrict__ d
   const double nan = __builtin_nan("");
   int bad = 0;
   for (int i = 0; i < M; ++i) bad |= flags[d * M + i];
-  const int st = (bad & 2) ? MSNAP_ST_NONFINITE : ((bad & 1) ? MSNAP_ST_TIMES : MSNAP_ST_OK);
+  const int st = status_of_flags(bad);
   double ev = nan, et = nan, up = nan;
   const double *n = dirs + 3 * dir;
   if (st == MSNAP_ST_OK && dir_finite(n)) {

@@ -73,8 +73,7 @@ struct msnap_ctx {
   msnap::DevBuf collide_work;  // the pairwise pass's working set (msnap_collide.hip, launch_formation_collide[_part])
   msnap::DevBuf limits_work;   // msnap_limits.hip: per-(drone, segment, quantity) peaks, then the retiming's per-drone peaks
   msnap::DevBuf extent_work;   // msnap_extent.hip: per-(drone, direction, segment) results, then the per-(drone, segment) flags
-  msnap::DevBuf clearance_work;   // msnap_clearance.hip: per-(pair, slot) results, then the per-(drone, segment) flags
-  msnap::DevBuf cross_clearance_work;   // msnap_cross_clearance.hip: per-(pair, slot) results, then the flags of set A and of set B
+  msnap::DevBuf clearance_work;   // msnap_clearance.hip (pairwise and cross): per-(pair, slot) results, then the per-(drone, segment) flags of each set
   msnap::DevBuf mesh_clearance_work;   // msnap_mesh_clearance.hip: per-(drone, segment) results, then the per-(drone, segment) flags
   msnap::DevBuf pairs_work;       // msnap_pairs.hip: the row image, the keep-bit matrix, the rows' counts and list offsets
   // chunked host-pointer solves: two streams alternate H2D -> kernel -> D2H over chunks of drones,
@@ -218,18 +217,14 @@ int launch_time_scale(msnap_ctx *ctx, int N, int M, const double *coef, const do
 int launch_retime(msnap_ctx *ctx, int N, int M, const double *coef, const double *dur, const double *limits, int flags,
                   double *coef_out, double *dur_out, double *scale);
 
-// pairwise clearance (msnap_clearance.hip): one lane per (pair, slot), 2 n_seg - 1 slots per pair
+// pairwise and cross clearance (msnap_clearance.hip): one lane per (pair, slot), n_seg_a + n_seg_b - 1 slots per pair
+// (pairwise: both are n_seg)
 constexpr int kClearanceThreads = 256;
-inline size_t clearance_lanes(int n_pairs, int M) { return (size_t)n_pairs * (size_t)(2 * M - 1); }
-// ctx->clearance_work: per-lane results [lanes][3] doubles, then the flags [N M] int32
-inline size_t clearance_work_bytes(int N, int M, int n_pairs) {
-  return clearance_lanes(n_pairs, M) * 3 * sizeof(double) + (size_t)N * M * sizeof(int32_t);
-}
-// cross clearance (msnap_cross_clearance.hip): one lane per (pair, slot), n_seg_a + n_seg_b - 1 slots per pair.
-// ctx->cross_clearance_work: per-lane results [lanes][3] doubles, then the flags [n_a Ma] and [n_b Mb] int32
-inline size_t cross_clearance_lanes(int n_pairs, int Ma, int Mb) { return (size_t)n_pairs * (size_t)(Ma + Mb - 1); }
-inline size_t cross_clearance_work_bytes(int Na, int Ma, int Nb, int Mb, int n_pairs) {
-  return cross_clearance_lanes(n_pairs, Ma, Mb) * 3 * sizeof(double) + ((size_t)Na * Ma + (size_t)Nb * Mb) * sizeof(int32_t);
+inline size_t clearance_lanes(int n_pairs, int Ma, int Mb) { return (size_t)n_pairs * (size_t)(Ma + Mb - 1); }
+// ctx->clearance_work: per-lane results [lanes][3] doubles, then the flags [segs] int32 (pairwise: [N M]; cross: those
+// of set A [n_a Ma], then of set B [n_b Mb])
+inline size_t clearance_work_bytes(size_t lanes, size_t segs) {
+  return lanes * 3 * sizeof(double) + segs * sizeof(int32_t);
 }
 // mesh clearance (msnap_mesh_clearance.hip): one lane per (drone, segment).  ctx->mesh_clearance_work: per-lane results
 // [N M][3] doubles, then the flags [N M] int32
@@ -260,17 +255,11 @@ inline int check_extent_grid(int n_drones, int n_seg, int n_dirs) {
 }
 int launch_path_extent(msnap_ctx *ctx, int N, int M, const double *coef, const double *dur, int K, const double *dirs,
                        double *ext, double *t_ext, double *upper, int32_t *status);
-inline int check_clearance_args(const msnap_ctx *ctx, int n_drones, int n_seg, int n_pairs) {
-  if (!ctx || n_drones < 0 || n_pairs < 0) return MSNAP_EINVAL;
-  if (n_seg < 1 || n_seg > ctx->max_segments) return MSNAP_ESEGMENTS;
-  if ((clearance_lanes(n_pairs, n_seg) + kClearanceThreads - 1) / kClearanceThreads > 0x7fffffffu) return MSNAP_EINVAL;   // grid size
-  return check_walk_grid(n_drones, n_seg);
-}
-// the same per set, and the lane grid of the two segment counts together
-inline int check_cross_clearance_args(const msnap_ctx *ctx, int n_a, int n_seg_a, int n_b, int n_seg_b, int n_pairs) {
+// per set, and the lane grid of the two segment counts together (pairwise: the one set given twice)
+inline int check_clearance_args(const msnap_ctx *ctx, int n_a, int n_seg_a, int n_b, int n_seg_b, int n_pairs) {
   if (!ctx || n_a < 0 || n_b < 0 || n_pairs < 0) return MSNAP_EINVAL;
   if (n_seg_a < 1 || n_seg_a > ctx->max_segments || n_seg_b < 1 || n_seg_b > ctx->max_segments) return MSNAP_ESEGMENTS;
-  if ((cross_clearance_lanes(n_pairs, n_seg_a, n_seg_b) + kClearanceThreads - 1) / kClearanceThreads > 0x7fffffffu) return MSNAP_EINVAL;   // grid size
+  if ((clearance_lanes(n_pairs, n_seg_a, n_seg_b) + kClearanceThreads - 1) / kClearanceThreads > 0x7fffffffu) return MSNAP_EINVAL;   // grid size
   if (int rc = check_walk_grid(n_a, n_seg_a)) return rc;
   return check_walk_grid(n_b, n_seg_b);
 }

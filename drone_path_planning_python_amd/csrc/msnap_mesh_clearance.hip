@@ -261,7 +261,7 @@ mesh_clearance_fold_kernel(const double *__restrict__ coef, const double *__rest
   const double nan = __builtin_nan("");
   int bad = 0;
   for (int i = 0; i < M; ++i) bad |= flags[(size_t)d * M + i];
-  const int st = (bad & 2) ? MSNAP_ST_NONFINITE : ((bad & 1) ? MSNAP_ST_TIMES : MSNAP_ST_OK);
+  const int st = status_of_flags(bad);
   double md = nan, tm = nan, lo = nan;
   int tw = -1;
   if (st == MSNAP_ST_OK) {

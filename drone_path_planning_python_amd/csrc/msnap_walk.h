@@ -1,5 +1,5 @@
 // The certified walk over a path, and what its four instances share: peaks_lane_kernel (msnap_limits.hip, K7: a
-// supremum), clearance_lane_kernel (msnap_clearance.hip, K9: a minimum between two drones),
+// supremum), pair_lane_kernel (msnap_clearance.hip, K9 and, with CROSS, K14: a minimum between two drones),
 // mesh_clearance_lane_kernel (msnap_mesh_clearance.hip, K11: a minimum against a mesh) and extent_lane_kernel
 // (msnap_extent.hip, K12: a supremum in a direction, walked as the minimum of the negated polynomial).  DESIGN.md §5 K7
 // has the method.
@@ -211,6 +211,11 @@ clearance_flags_kernel(const double *__restrict__ coef, const double *__restrict
 #pragma unroll
   for (int j = 0; j < 4 * NC; ++j) finite = finite && isfinite(coef[seg * 4 * NC + j]);
   flags[seg] = !finite ? 2 : (T > 0.0 ? 0 : 1);
+}
+
+// the status of a path (or of a pair of them) from the OR of its segments' flags: non-finite goes before the times
+__device__ __forceinline__ int status_of_flags(int bad) {
+  return (bad & 2) ? MSNAP_ST_NONFINITE : ((bad & 1) ? MSNAP_ST_TIMES : MSNAP_ST_OK);
 }
 
 // position of one drone at absolute time t: msnap_eval_flat's lookup (first segment with t <= acc + T) and Horner

@@ -5,6 +5,7 @@ functions are the bodies of the tests: they take `ctx`, a Context of the right o
 from __future__ import annotations
 
 import itertools
+import os
 
 import numpy as np
 
@@ -318,6 +319,28 @@ def check_caps(ctx, solve, nc, dz):
     md, tm, lower, _ = CE.check_contract(ctx, coef, dur, [(0, 1)], with_R=True, closed=False, crossing=True)
     assert lower[0] <= md[0]
     return bool(st["capped"].any()), int(st["nodes"].max())
+
+
+# ------------------------------------------------------------------------------------------------ recorded bits
+# tests/golden/make_clearance_bits_golden.py: inputs and outputs of the pairwise and the cross entry, recorded on a GPU
+BITS_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "clearance_bits_golden.npz")
+BITS_OUT = ("min_dist", "t_min", "lower", "status")
+
+
+def bits_cases(entry):
+    """The recorded cases of `entry` ("pair" or "cross"): [(name, {field: array})], fields as the recorder lists them."""
+    z = np.load(BITS_GOLDEN)
+    keys = [k.split("/") for k in z.files if k.startswith(entry + "/")]
+    return [(name, {f: z[f"{entry}/{name}/{f}"] for _, n, f in keys if n == name}) for name in sorted({n for _, n, _ in keys})]
+
+
+def check_bits(what, got, case):
+    """The four outputs `got` (arrays or tensors) of a recorded case: every bit as stored, NaN where NaN is stored."""
+    for field, g in zip(BITS_OUT, got):
+        g = g.cpu().numpy() if hasattr(g, "cpu") else np.asarray(g)
+        want = case[field]
+        assert g.dtype == want.dtype and g.shape == want.shape, (what, field, g.dtype, g.shape)
+        assert np.array_equal(g, want, equal_nan=field != "status"), (what, field, g.tolist(), want.tolist())
 
 
 # ------------------------------------------------------------------------------------------------ certify_clearance

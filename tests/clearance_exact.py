@@ -4,9 +4,11 @@ exact_clearance: the coefficients and the fp64 knot times (running sums, as the 
 Fractions; the merged knots with the window's end included; on every interval g = |p_a - p_b|^2 as an exact rational
 polynomial in the time since the interval's start, the real roots of g' from mpmath.polyroots at 60 digits, g there and
 at both ends; D = sqrt of the minimum.
-fp64_clearance: a plain NumPy fp64 restatement of the kernel's walk (csrc/msnap_clearance.hip), vectorised over the
-(pair, interval) lanes -- for large lists, for the node counts, and for measuring the rounding of the fp64 method
-against exact_clearance.  Not bit-exact with the kernel (no fused multiply-add here)."""
+fp64_cross_clearance: a plain NumPy fp64 restatement of the kernel's lanes and fold (csrc/msnap_clearance.hip),
+vectorised over the (pair, interval) lanes, in the kernel's general form: two sets, each with its own segment count and
+start times (K14) -- for large lists, for the node counts, and for measuring the rounding of the fp64 method against
+the exact references.  Not bit-exact with the kernel (no fused multiply-add here).
+fp64_clearance: the same with one set given twice and no start times (K9), as the kernel's CROSS = false instance is."""
 from __future__ import annotations
 
 from fractions import Fraction
@@ -198,40 +200,46 @@ def round_ratio(min_dist, lower, D, R, attained=None):
 
 
 # ------------------------------------------------------------------------------------------------ fp64 restatement
-def fp64_clearance(coef, dur, pairs, stats=None):
-    """coef [N, M, 4, nc], dur [N, M], pairs [P, 2] (valid, finite) -> (min_dist [P], t_min [P], lower [P]) by the
-    kernel's method in NumPy fp64.  `stats` (a dict) receives the nodes per live lane ("nodes") and the lanes that met
-    the depth cap or the node guard ("capped")."""
-    coef = np.asarray(coef, dtype=np.float64)
-    dur = np.asarray(dur, dtype=np.float64)
-    pairs = np.asarray(pairs, dtype=np.int64)
-    P, M, nc = len(pairs), dur.shape[1], coef.shape[3]
+def _t0(t0, n):
+    return np.zeros(n) if t0 is None else np.asarray(t0, dtype=np.float64)
+
+
+def fp64_cross_clearance(coef_a, dur_a, t0_a, coef_b, dur_b, t0_b, pairs, stats=None):
+    """coef_x [Nx, Mx, 4, nc], dur_x [Nx, Mx], t0_x [Nx] or None (zeros), pairs [P, 2] (valid, finite) -> (min_dist [P],
+    t_min [P], lower [P]) by the kernel's method in NumPy fp64 (drone a of set A against drone b of set B, include/msnap.h
+    "cross clearance").  `stats` (a dict) receives the nodes per live lane ("nodes") and the lanes that met the depth
+    cap or the node guard ("capped")."""
+    coef_a, coef_b = np.asarray(coef_a, dtype=np.float64), np.asarray(coef_b, dtype=np.float64)
+    dur_a, dur_b = np.asarray(dur_a, dtype=np.float64), np.asarray(dur_b, dtype=np.float64)
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    P, Ma, Mb, nc = len(pairs), dur_a.shape[1], dur_b.shape[1], coef_a.shape[3]
     D, n = nc - 1, 2 * (nc - 1)
     Wt = _bernstein_weights(n)
     a_i, b_i = pairs[:, 0], pairs[:, 1]
-    KA, KB = np.add.accumulate(dur[a_i], axis=1), np.add.accumulate(dur[b_i], axis=1)
-    Wend = np.minimum(KA[:, -1], KB[:, -1])
-    ends = np.concatenate([KA[:, :M - 1], KB[:, :M - 1], Wend[:, None]], axis=1)          # [P, 2M - 1]
-    ends = np.sort(np.minimum(ends, Wend[:, None]), axis=1)
-    starts = np.concatenate([np.zeros((P, 1)), ends[:, :-1]], axis=1)
+    ta, tb = _t0(t0_a, dur_a.shape[0])[a_i], _t0(t0_b, dur_b.shape[0])[b_i]
+    LA, LB = np.add.accumulate(dur_a[a_i], axis=1), np.add.accumulate(dur_b[b_i], axis=1)      # local knots
+    KA, KB = ta[:, None] + LA, tb[:, None] + LB                                                # on the common clock
+    S, Wend = np.maximum(ta, tb), np.minimum(KA[:, -1], KB[:, -1])
+    ends = np.concatenate([KA[:, :Ma - 1], KB[:, :Mb - 1], Wend[:, None]], axis=1)             # [P, Ma + Mb - 1]
+    ends = np.sort(np.maximum(np.minimum(ends, Wend[:, None]), S[:, None]), axis=1)
+    starts = np.concatenate([S[:, None], ends[:, :-1]], axis=1)
     h_all = ends - starts
-    live = h_all > 0
+    live = (h_all > 0) & (Wend >= S)[:, None]
     pi, si = np.nonzero(live)
     E, t0, h = ends[pi, si], starts[pi, si], h_all[pi, si]
     L = len(pi)
     e = np.zeros((L, 3, D + 1))
-    for drone, K, sign in ((a_i[pi], KA[pi], 1.0), (b_i[pi], KB[pi], -1.0)):
+    for coef, drone, K, Lk, tx, M, sign in ((coef_a, a_i[pi], KA[pi], LA[pi], ta[pi], Ma, 1.0),
+                                            (coef_b, b_i[pi], KB[pi], LB[pi], tb[pi], Mb, -1.0)):
         seg = np.minimum((E[:, None] > K).sum(axis=1), M - 1)
-        off = np.concatenate([np.zeros((L, 1)), K], axis=1)[np.arange(L), seg]
+        off = np.concatenate([np.zeros((L, 1)), Lk], axis=1)[np.arange(L), seg]
         for ax in range(3):
-            e[:, ax, :] += sign * _taylor(coef[drone, seg, ax, :], t0 - off)
+            e[:, ax, :] += sign * _taylor(coef[drone, seg, ax, :], (t0 - tx) - off)
     e *= (h[:, None] ** np.arange(D + 1))[:, None, :]
 
     def node(act, a, hh, best, best_u):
         G = np.zeros((len(act), n + 1))
-        g0 = np.zeros(len(act))
-        gm = np.zeros(len(act))
-        g1 = np.zeros(len(act))
+        g0, gm, g1 = np.zeros(len(act)), np.zeros(len(act)), np.zeros(len(act))
         scale = hh[:, None] ** np.arange(D + 1)
         for s in range(3):
             f = _taylor(e[act, s, :], a) * scale
@@ -256,29 +264,43 @@ def fp64_clearance(coef, dur, pairs, stats=None):
     t_pair = np.full(P, np.inf)
     winners = best == g_pair[pi]
     np.minimum.at(t_pair, pi[winners], tm[winners])
+    t_pair = np.where(np.isfinite(t_pair), t_pair, S)                  # no live slot: Wend == S, the one instant
     low_pair = np.full(P, np.inf)
     np.minimum.at(low_pair, pi, low)
-    diff = _positions(coef, dur, a_i, t_pair) - _positions(coef, dur, b_i, t_pair)
+    tau_a = np.minimum(np.maximum(t_pair - ta, 0.0), LA[:, -1])
+    tau_b = np.minimum(np.maximum(t_pair - tb, 0.0), LB[:, -1])
+    diff = _positions(coef_a, dur_a, a_i, tau_a) - _positions(coef_b, dur_b, b_i, tau_b)
     md = np.sqrt(diff[:, 2] ** 2 + (diff[:, 1] ** 2 + diff[:, 0] ** 2))
     lower = np.minimum(np.sqrt(np.maximum(low_pair, 0.0)), md)
+    disjoint = Wend < S
+    md, lower, t_pair = np.where(disjoint, np.inf, md), np.where(disjoint, np.inf, lower), np.where(disjoint, np.nan, t_pair)
     if stats is not None:
         stats["lane_pair"], stats["lane_start"], stats["lane_low"], stats["pair_best"] = pi, t0, low, g_pair
-        stats["nodes"] = nodes
-        stats["capped"] = capped
-        stats["lanes"] = L
+        stats["nodes"], stats["capped"], stats["lanes"] = nodes, capped, L
     return md, t_pair, lower
 
 
-def candidate_intervals(coef, dur, pairs, rel=1e-6):
+def cross_candidate_intervals(coef_a, dur_a, t0_a, coef_b, dur_b, t0_b, pairs, rel=1e-6):
     """Per pair, the start times of the intervals whose fp64 lower bound of g is within `rel` (on the distance) of the
-    pair's smallest attained value: the only ones that can hold the infimum (exact_clearance's `candidates`)."""
+    pair's smallest attained value: the only ones that can hold the infimum (exact_cross_clearance's `candidates`)."""
     st = {}
-    fp64_clearance(coef, dur, pairs, stats=st)
+    fp64_cross_clearance(coef_a, dur_a, t0_a, coef_b, dur_b, t0_b, pairs, stats=st)
     out = [set() for _ in range(len(pairs))]
     keep = st["lane_low"] <= st["pair_best"][st["lane_pair"]] * (1 + rel) ** 2 + 1e-12
     for p, t0 in zip(st["lane_pair"][keep], st["lane_start"][keep]):
         out[int(p)].add(float(t0))
     return out
+
+
+def fp64_clearance(coef, dur, pairs, stats=None):
+    """The pairwise form: coef [N, M, 4, nc], dur [N, M], pairs [P, 2] (valid, finite) -> (min_dist [P], t_min [P],
+    lower [P]): one set against itself on one clock."""
+    return fp64_cross_clearance(coef, dur, None, coef, dur, None, pairs, stats)
+
+
+def candidate_intervals(coef, dur, pairs, rel=1e-6):
+    """cross_candidate_intervals of one set against itself on one clock (exact_clearance's `candidates`)."""
+    return cross_candidate_intervals(coef, dur, None, coef, dur, None, pairs, rel)
 
 
 # ------------------------------------------------------------------------------------------------ shared test helper

@@ -5,8 +5,7 @@ coefficients, the fp64 running sums of the durations and the offsets t0 are take
 the common clock are the EXACT sums t0 + running sum.  The window is the header's: S = max of the two t0, W = min of the
 two fp64 sums fl(t0 + total).  On every interval between consecutive knots inside the window g = |p_a - p_b|^2 is an
 exact rational polynomial; clearance_exact.exact_interval_min gives its minimum at 60 digits.
-fp64_cross_clearance: a NumPy fp64 restatement of the kernel's lanes and fold (csrc/msnap_cross_clearance.hip), as
-clearance_exact.fp64_clearance is of K9's.  Not bit-exact with the kernel (no fused multiply-add here).
+fp64_cross_clearance, candidate_intervals: clearance_exact's (one NumPy restatement of the kernel serves both entries).
 pair_R, pair_Rprime, T_c, contract_violations, the two measured ratios, and RestatedContext: the stand-in through
 which tests/test_cross_clearance_cpu.py runs the test bodies of tests/test_cross_clearance_gpu.py on the restatement."""
 from __future__ import annotations
@@ -18,17 +17,14 @@ import numpy as np
 
 import clearance_exact as CE
 import dyadic_walk as DW
-from clearance_exact import DPS, MAX_DEPTH, MAX_NODES, PRUNE_ABS, PRUNE_REL, _mpf, _shift, exact_interval_min, knots
+from clearance_exact import DPS, MAX_DEPTH, MAX_NODES, PRUNE_ABS, PRUNE_REL, _mpf, _shift, _t0, exact_interval_min, knots  # noqa: F401
+from clearance_exact import cross_candidate_intervals as candidate_intervals, fp64_cross_clearance  # noqa: F401
 from dyadic_walk import ABS_CLOSE, ABS_ROUND, EPS, REL_CLOSE, REL_ROUND, _bernstein_weights, _positions, _taylor  # noqa: F401
 
 # include/msnap.h, "cross clearance": r = ABS_ROUND + C_ROUND_CROSS 2^-52 R + C_CLOCK 2^-52 T_c R'.  Ten times the worst
 # measured ratio, rounded up (tools/cross_clearance_rounding.py)
 C_ROUND_CROSS = 7.0          # worst measured 0.686 (one set against itself at +1e5 m, order 7: K9's own worst case)
 C_CLOCK = 1.0                # worst measured 0.0007 (continued paths against the paths they left)
-
-
-def _t0(t0, n):
-    return np.zeros(n) if t0 is None else np.asarray(t0, dtype=np.float64)
 
 
 def window(dur_a, t0a, dur_b, t0b):
@@ -157,93 +153,6 @@ def deviation(min_dist, lower, D, attained=None):
     """What the two terms have to cover [m]: the larger of lower - D, D - min_dist and |min_dist - exact distance at
     t_min|, less the distance-relative part of the allowance (dyadic_walk.round_ratio's numerator)."""
     return DW.round_ratio(min_dist, lower, D, 1.0 / EPS, attained)
-
-
-# ------------------------------------------------------------------------------------------------ fp64 restatement
-def fp64_cross_clearance(coef_a, dur_a, t0_a, coef_b, dur_b, t0_b, pairs, stats=None):
-    """coef_x [Nx, Mx, 4, nc], dur_x [Nx, Mx], t0_x [Nx] or None, pairs [P, 2] (valid, finite) -> (min_dist [P],
-    t_min [P], lower [P]) by the kernel's method in NumPy fp64.  `stats` as clearance_exact.fp64_clearance's."""
-    coef_a, coef_b = np.asarray(coef_a, dtype=np.float64), np.asarray(coef_b, dtype=np.float64)
-    dur_a, dur_b = np.asarray(dur_a, dtype=np.float64), np.asarray(dur_b, dtype=np.float64)
-    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
-    P, Ma, Mb, nc = len(pairs), dur_a.shape[1], dur_b.shape[1], coef_a.shape[3]
-    D, n = nc - 1, 2 * (nc - 1)
-    Wt = _bernstein_weights(n)
-    a_i, b_i = pairs[:, 0], pairs[:, 1]
-    ta, tb = _t0(t0_a, dur_a.shape[0])[a_i], _t0(t0_b, dur_b.shape[0])[b_i]
-    LA, LB = np.add.accumulate(dur_a[a_i], axis=1), np.add.accumulate(dur_b[b_i], axis=1)      # local knots
-    KA, KB = ta[:, None] + LA, tb[:, None] + LB                                                # on the common clock
-    S, Wend = np.maximum(ta, tb), np.minimum(KA[:, -1], KB[:, -1])
-    ends = np.concatenate([KA[:, :Ma - 1], KB[:, :Mb - 1], Wend[:, None]], axis=1)             # [P, Ma + Mb - 1]
-    ends = np.sort(np.maximum(np.minimum(ends, Wend[:, None]), S[:, None]), axis=1)
-    starts = np.concatenate([S[:, None], ends[:, :-1]], axis=1)
-    h_all = ends - starts
-    live = (h_all > 0) & (Wend >= S)[:, None]
-    pi, si = np.nonzero(live)
-    E, t0, h = ends[pi, si], starts[pi, si], h_all[pi, si]
-    L = len(pi)
-    e = np.zeros((L, 3, D + 1))
-    for coef, drone, K, Lk, tx, M, sign in ((coef_a, a_i[pi], KA[pi], LA[pi], ta[pi], Ma, 1.0),
-                                            (coef_b, b_i[pi], KB[pi], LB[pi], tb[pi], Mb, -1.0)):
-        seg = np.minimum((E[:, None] > K).sum(axis=1), M - 1)
-        off = np.concatenate([np.zeros((L, 1)), Lk], axis=1)[np.arange(L), seg]
-        for ax in range(3):
-            e[:, ax, :] += sign * _taylor(coef[drone, seg, ax, :], (t0 - tx) - off)
-    e *= (h[:, None] ** np.arange(D + 1))[:, None, :]
-
-    def node(act, a, hh, best, best_u):
-        G = np.zeros((len(act), n + 1))
-        g0, gm, g1 = np.zeros(len(act)), np.zeros(len(act)), np.zeros(len(act))
-        scale = hh[:, None] ** np.arange(D + 1)
-        for s in range(3):
-            f = _taylor(e[act, s, :], a) * scale
-            for i in range(D + 1):
-                G[:, i:i + D + 1] += f[:, i:i + 1] * f
-            vm = np.zeros(len(act))
-            for j in range(D, -1, -1):
-                vm = vm * 0.5 + f[:, j]
-            v1 = f[:, ::-1].cumsum(axis=1)[:, -1]
-            g0 += f[:, 0] ** 2
-            gm += vm ** 2
-            g1 += v1 ** 2
-        bound = (G @ Wt.T).min(axis=1)
-        nb, nu = DW.take_attained(((g0, a), (gm, a + 0.5 * hh), (g1, a + hh)), best, best_u)
-        return bound, nb, nu, bound < nb - PRUNE_REL * nb - PRUNE_ABS
-
-    best, best_u, low, nodes, capped = DW.walk(L, node, MAX_DEPTH, MAX_NODES)
-
-    tm = np.minimum(h * best_u + t0, E)
-    g_pair = np.full(P, np.inf)
-    np.minimum.at(g_pair, pi, best)
-    t_pair = np.full(P, np.inf)
-    winners = best == g_pair[pi]
-    np.minimum.at(t_pair, pi[winners], tm[winners])
-    t_pair = np.where(np.isfinite(t_pair), t_pair, S)                  # no live slot: Wend == S, the one instant
-    low_pair = np.full(P, np.inf)
-    np.minimum.at(low_pair, pi, low)
-    tau_a = np.minimum(np.maximum(t_pair - ta, 0.0), LA[:, -1])
-    tau_b = np.minimum(np.maximum(t_pair - tb, 0.0), LB[:, -1])
-    diff = _positions(coef_a, dur_a, a_i, tau_a) - _positions(coef_b, dur_b, b_i, tau_b)
-    md = np.sqrt(diff[:, 2] ** 2 + (diff[:, 1] ** 2 + diff[:, 0] ** 2))
-    lower = np.minimum(np.sqrt(np.maximum(low_pair, 0.0)), md)
-    disjoint = Wend < S
-    md, lower, t_pair = np.where(disjoint, np.inf, md), np.where(disjoint, np.inf, lower), np.where(disjoint, np.nan, t_pair)
-    if stats is not None:
-        stats["lane_pair"], stats["lane_start"], stats["lane_low"], stats["pair_best"] = pi, t0, low, g_pair
-        stats["nodes"], stats["capped"], stats["lanes"] = nodes, capped, L
-    return md, t_pair, lower
-
-
-def candidate_intervals(coef_a, dur_a, t0_a, coef_b, dur_b, t0_b, pairs, rel=1e-6):
-    """Per pair, the start times of the intervals whose fp64 lower bound of g is within `rel` (on the distance) of the
-    pair's smallest attained value: the only ones that can hold the infimum (exact_cross_clearance's `candidates`)."""
-    st = {}
-    fp64_cross_clearance(coef_a, dur_a, t0_a, coef_b, dur_b, t0_b, pairs, stats=st)
-    out = [set() for _ in range(len(pairs))]
-    keep = st["lane_low"] <= st["pair_best"][st["lane_pair"]] * (1 + rel) ** 2 + 1e-12
-    for p, t0 in zip(st["lane_pair"][keep], st["lane_start"][keep]):
-        out[int(p)].add(float(t0))
-    return out
 
 
 # ------------------------------------------------------------------------------------------------ shared test helper

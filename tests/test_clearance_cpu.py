@@ -335,6 +335,11 @@ def test_new_kernels_use_no_scratch_and_fit_the_register_file(tmp_path):
     scratch = [int(x) for x in re.findall(r"\.private_segment_fixed_size:\s+(\d+)", notes)]
     vgpr = [int(x) for x in re.findall(r"\.vgpr_count:\s+(\d+)", notes)]
     agpr = [int(x) for x in re.findall(r"\.agpr_count:\s+(\d+)", notes)]
-    assert len(names) == 6 == len(scratch) == len(vgpr) == len(agpr)
-    assert sum("clearance_lane_kernel" in n for n in names) == 2
-    assert scratch == [0] * 6 and agpr == [0] * 6 and max(vgpr) <= 256, list(zip(names, vgpr, agpr, scratch))
+    # 2 flags kernels, and a lane and a fold kernel per (order, CROSS): the pairwise and the cross entry
+    assert len(names) == 10 == len(scratch) == len(vgpr) == len(agpr)
+    lane = {n: v for n, v in zip(names, vgpr) if "pair_lane_kernel" in n}
+    assert len(lane) == 4 and sum("pair_fold_kernel" in n for n in names) == 4
+    assert scratch == [0] * 10 and agpr == [0] * 10 and max(vgpr) <= 256, list(zip(names, vgpr, agpr, scratch))
+    # the occupancy steps the timings rest on: 3 waves per SIMD at order 7, 2 at order 9
+    assert sum("pair_lane_kernelILi8E" in n for n in lane) == 2 == sum("pair_lane_kernelILi10E" in n for n in lane)
+    assert all(v <= (160 if "ILi8E" in n else 196) for n, v in lane.items()), lane

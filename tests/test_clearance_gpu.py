@@ -204,6 +204,30 @@ def test_per_pair_status_and_guarded_buffers(ctx7):
     assert all(x.shape == (0,) for x in out)
 
 
+def test_outputs_are_the_bits_recorded_before_the_pair_kernels_were_merged(ctx7, ctx9):
+    """tests/golden/clearance_bits_golden.npz holds what msnap_pair_clearance computed when it had a kernel file of its
+    own (tests/golden/make_clearance_bits_golden.py): 1, 2 and 10 segments with every pair both ways round, a shared
+    grid, unequal totals, invalid pairs, a zero duration and a NaN coefficient at order 7, 4 segments at order 9.  The
+    host and the device entry give every stored bit."""
+    import torch
+    from drone_path_planning_python_amd import Context
+    from drone_path_planning_python_amd.swarm import DeviceCompute
+    dev = torch.device("cuda", 0)
+    tt = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)      # noqa: E731
+    cases = CC.bits_cases("pair")
+    assert len(cases) == 7 and sorted(int(c["order"]) for _, c in cases) == [7] * 6 + [9]
+    for order, host in ((7, ctx7), (9, ctx9)):
+        with Context(device_id=0, order=order, max_segments=16) as ctx:
+            comp = DeviceCompute(ctx, torch)
+            for name, c in cases:
+                if int(c["order"]) != order:
+                    continue
+                CC.check_bits(name + ", host entry", host.pair_clearance(c["coef"], c["dur"], c["pairs"]), c)
+                out = comp.pair_clearance(tt(c["coef"]), tt(c["dur"]), tt(c["pairs"]))
+                torch.cuda.synchronize()
+                CC.check_bits(name + ", device entry", out, c)
+
+
 def test_certify_clearance_on_the_formation_swarm(ctx7):
     import torch
     from drone_path_planning_python_amd import Context, synthetic

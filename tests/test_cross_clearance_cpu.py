@@ -1,7 +1,7 @@
 """Cross clearance without a GPU: the NumPy restatement of the new lanes against the exact reference on the cases of
 tests/test_cross_clearance_gpu.py (through cross_clearance_exact.RestatedContext), the measured ratios below the two
 constants, every walk closed, the restatement's own identities, the pair logic of swarm.certify_replan with a stand-in
-compute object, the argument checks of the C entries that need no GPU, and the build checks on the new object."""
+compute object, the argument checks of the C entries that need no GPU, and the build checks on the kernels' object."""
 import ctypes
 import os
 import sys
@@ -17,7 +17,7 @@ import clearance_exact as CE  # noqa: E402
 import cross_clearance_cases as XC  # noqa: E402
 import cross_clearance_exact as XE  # noqa: E402
 
-OBJ = os.path.join(ROOT, "drone_path_planning_python_amd", "csrc", "msnap_cross_clearance.o")
+OBJ = os.path.join(ROOT, "drone_path_planning_python_amd", "csrc", "msnap_clearance.o")
 
 
 def solve(wp, t, nc):
@@ -133,9 +133,9 @@ def test_argument_checks_without_gpu():
 def test_the_new_object_is_in_the_build_checks_and_has_no_lane_retiring_loop():
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import check_exec_isa as chk
-    assert OBJ in chk.K14_OBJS
+    assert OBJ in chk.DEFAULT_OBJS
     if not os.path.exists(OBJ) or not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-objdump"):
         pytest.skip("no object file / ROCm LLVM tools here")
     assert chk.lane_latches(OBJ) == {}
     n_kernels, n_spill, bad = chk.check(OBJ)
-    assert n_kernels == 6 and not bad
+    assert n_kernels == 10 and not bad      # 2 flags kernels, a lane and a fold kernel per (order, CROSS)

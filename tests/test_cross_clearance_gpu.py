@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import clearance_cases as CC  # noqa: E402
 import cross_clearance_cases as XC  # noqa: E402
 import cross_clearance_exact as XE  # noqa: E402
 
@@ -46,6 +47,32 @@ def test_one_set_against_itself_is_pair_clearance_bit_for_bit_order7(ctx7, m):
 
 def test_one_set_against_itself_is_pair_clearance_bit_for_bit_order9(ctx9):
     _identity(ctx9, 4)
+
+
+def test_outputs_are_the_bits_recorded_before_the_pair_kernels_were_merged(ctx7, ctx9):
+    """tests/golden/clearance_bits_golden.npz holds what msnap_cross_clearance computed when it had a kernel file of its
+    own (tests/golden/make_clearance_bits_golden.py): unequal segment counts and offsets at both orders, the windows,
+    the two crossings, non-finite offsets, one set against itself with NULL offsets and with zeros.  The host and the
+    device entry give every stored bit."""
+    import torch
+    from drone_path_planning_python_amd import Context
+    from drone_path_planning_python_amd.swarm import DeviceCompute
+    dev = torch.device("cuda", 0)
+    tt = lambda x: None if x is None else torch.from_numpy(np.ascontiguousarray(x)).to(dev)      # noqa: E731
+    cases = CC.bits_cases("cross")
+    assert len(cases) == 9 and sorted(int(c["order"]) for _, c in cases) == [7] * 8 + [9]
+    for order, host in ((7, ctx7), (9, ctx9)):
+        with Context(device_id=0, order=order, max_segments=16) as ctx:
+            comp = DeviceCompute(ctx, torch)
+            for name, c in cases:
+                if int(c["order"]) != order:
+                    continue
+                sets = [c[k] for k in ("coef_a", "dur_a", "coef_b", "dur_b", "pairs")]
+                ta, tb = c.get("t0_a"), c.get("t0_b")             # (absent: NULL)
+                CC.check_bits(name + ", host entry", host.cross_clearance(*sets, t0_a=ta, t0_b=tb), c)
+                out = comp.cross_clearance(*(tt(x) for x in sets), t0_a=tt(ta), t0_b=tt(tb))
+                torch.cuda.synchronize()
+                CC.check_bits(name + ", device entry", out, c)
 
 
 @pytest.mark.parametrize("ma, mb", [(3, 10), (1, 1)])

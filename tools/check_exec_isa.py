@@ -53,7 +53,6 @@ MORE_OBJS = [os.path.join(CSRC, f) for f in ("msnap_pairs.o",)]
 K11_OBJS = [os.path.join(CSRC, f) for f in ("msnap_mesh_clearance.o",)]      # (tests pin the two lists above)
 K12_OBJS = [os.path.join(CSRC, f) for f in ("msnap_extent.o",)]
 K13_OBJS = [os.path.join(CSRC, f) for f in ("msnap_states.o",)]
-K14_OBJS = [os.path.join(CSRC, f) for f in ("msnap_cross_clearance.o",)]
 
 
 def disassemble(obj):
@@ -226,13 +225,13 @@ def check(obj):
 
 def main():
     if sys.argv[1:2] == ["--latches"]:      # the census: one line per kernel with a lane-retiring loop
-        for obj in sys.argv[2:] or DEFAULT_OBJS + MORE_OBJS + K11_OBJS + K12_OBJS + K13_OBJS + K14_OBJS:
+        for obj in sys.argv[2:] or DEFAULT_OBJS + MORE_OBJS + K11_OBJS + K12_OBJS + K13_OBJS:
             found = lane_latches(obj)
             print(f"check_exec_isa: {os.path.basename(obj)}: {sum(found.values())} lane-retiring loop latches in {len(found)} kernels")
             for k, n in sorted(found.items()):
                 print(f"    {n:3d}  {k}")
         return 0
-    objs = sys.argv[1:] or DEFAULT_OBJS + MORE_OBJS + K11_OBJS + K12_OBJS + K13_OBJS + K14_OBJS
+    objs = sys.argv[1:] or DEFAULT_OBJS + MORE_OBJS + K11_OBJS + K12_OBJS + K13_OBJS
     rc = 0
     for obj in objs:
         n_kernels, n_spill, bad = check(obj)
