@@ -879,6 +879,9 @@ solve_kernel_twin(const double *__restrict__ wp, const double *__restrict__ tt, 
 constexpr int kTwistDrones = 8;
 constexpr int kTwistFenceHalf = 9;   // instances with this many knots per side fence the scheduler per knot
 
+// T > 0 and finite -- !(T > 0) | !finite64(T) exactly -- as one v_cmp_class_f64: positive normal or positive subnormal
+__device__ __forceinline__ bool usable_duration(double T) { return __builtin_amdgcn_class(T, 0x180); }
+
 #ifdef MSNAP_TOOLS_TIMELINE
 // phase timestamps of the twisted kernel (s_memrealtime, 100 MHz, and s_memtime): tools/twist_timeline.py.
 // One row of 32 words per WAVE (row = tile * NW + wave): points 0..4 in words 0..9.
@@ -1024,8 +1027,20 @@ solve_kernel_twist(const double *__restrict__ wp, const double *__restrict__ tt,
     wreg[1] = Wown(1);
     const double T0 = Town(0);
     const double T0q = side ? T0 : T0 - t0;   // Appendix-A quirk lives on the start side only
-    bool nonfinite = !(finite64(t0) & finite64(T0) & finite64(wreg[0]) & finite64(wreg[1]));
-    bool badtime = !(T0 > 0.0) | !(T0q > 0.0) | (t0 < 0.0);
+    // Input flags.  The instances that fit the architectural register file (kLean) carry ONE per-lane flag through
+    // the sweeps, "an input of this lane is not usable" (not finite, or times out of order): which of the two it was
+    // is found again from the staged inputs on the rare path behind the merge.  A duration is usable iff it is
+    // positive and finite, one class test.  The long instances keep the two flags apart and classify in line, as
+    // they always did: a branch behind their merge moves the compiler's accumulation-register copies into the
+    // divergent regions of the recovery (tools/check_exec_isa.py).
+    constexpr bool kLean = MAXH * NU * NU <= 36;   // order 7: up to 10 segments, order 9: up to 6
+    bool inbad = false, nonfinite = false, badtime = false;
+    if constexpr (kLean) {
+      inbad = !(finite64(t0) & finite64(wreg[0]) & finite64(wreg[1]) & usable_duration(T0)) | !(T0q > 0.0) | (t0 < 0.0);
+    } else {
+      nonfinite = !(finite64(t0) & finite64(T0) & finite64(wreg[0]) & finite64(wreg[1]));
+      badtime = !(T0 > 0.0) | !(T0q > 0.0) | (t0 < 0.0);
+    }
     xreg[0] = rcp64(T0q);
     SW sw;
     sw.init(xreg[0], wreg[1] - wreg[0]);
@@ -1039,8 +1054,12 @@ solve_kernel_twist(const double *__restrict__ wp, const double *__restrict__ tt,
     auto ahead = [&](int it, double (&xp)[SW::PM + 1], double &dw) {
       wreg[it + 1] = Wown(it + 1);
       const double Tit = Town(it);
-      nonfinite |= !finite64(Tit) | !finite64(wreg[it + 1]);
-      badtime |= !(Tit > 0.0);
+      if constexpr (kLean) {
+        inbad |= !(usable_duration(Tit) & finite64(wreg[it + 1]));
+      } else {
+        nonfinite |= !finite64(Tit) | !finite64(wreg[it + 1]);
+        badtime |= !(Tit > 0.0);
+      }
       xreg[it] = rcp64(Tit);
       SW::powers(xreg[it], xp);
       dw = wreg[it + 1] - wreg[it];
@@ -1101,11 +1120,11 @@ solve_kernel_twist(const double *__restrict__ wp, const double *__restrict__ tt,
 #pragma unroll
     for (int r = 0; r < NU; ++r) {
       const double q = sw.re[r] + sw.Otz[r];
-      um[r] = -q - dsg[r] * __shfl_xor(q, 4);
+      um[r] = -q - dsg[r] * row_xor4_f64(q);
 #pragma unroll
       for (int c = 0; c <= r; ++c) {
         const double p = sw.E[sidx(r, c)] - sw.OtG[sidx(r, c)];
-        Sm[sidx(r, c)] = p + (dsg[r] * dsg[c]) * __shfl_xor(p, 4);
+        Sm[sidx(r, c)] = p + (dsg[r] * dsg[c]) * row_xor4_f64(p);
       }
     }
     {
@@ -1114,28 +1133,62 @@ solve_kernel_twist(const double *__restrict__ wp, const double *__restrict__ tt,
       SW::ldl_solve(Sm, dinv, um);
     }
 
-    // per-drone status over the 8 lanes (2 sides x 4 axes): wave ballots, no cross-lane round trips
-    const int gsh = lane & ~7;
-    const bool f_nonfinite = ((__ballot(nonfinite) >> gsh) & 0xFFull) != 0;
-    const bool f_time = ((__ballot(badtime) >> gsh) & 0xFFull) != 0;
-    const bool f_sing = ((__ballot(singular) >> gsh) & 0xFFull) != 0;
-    const int st = f_nonfinite ? MSNAP_ST_NONFINITE : f_time ? MSNAP_ST_TIMES : f_sing ? MSNAP_ST_SINGULAR : MSNAP_ST_OK;
-    if (live && (lane & 7) == 0 && wave == NW - 1) status[d] = st;   // (moved to the end with the durations: no gain, 4.30 against 4.28 us)
-    const bool bad = st != 0;
+    // Status: per drone over its 8 lanes (2 sides x 4 axes) from wave ballots, no cross-lane round trips
+    auto classify = [&]() -> int {
+      const int gsh = lane & ~7;
+      const bool f_nonfinite = ((__ballot(nonfinite) >> gsh) & 0xFFull) != 0;
+      const bool f_time = ((__ballot(badtime) >> gsh) & 0xFFull) != 0;
+      const bool f_sing = ((__ballot(singular) >> gsh) & 0xFFull) != 0;
+      return f_nonfinite ? MSNAP_ST_NONFINITE : f_time ? MSNAP_ST_TIMES : f_sing ? MSNAP_ST_SINGULAR : MSNAP_ST_OK;
+    };
+    auto put_status = [&](int st) {
+      if (live && (lane & 7) == 0 && wave == NW - 1) status[d] = st;   // (moved to the end with the durations: no gain, 4.30 against 4.28 us)
+    };
+    // A failed drone's outputs are NaN: poison what every coefficient is computed from once
+    // (waypoints -> c0 and the end-side block, knot states -> c1..) instead of selecting per piece.
+    double zero_or_nan = 0.0;
+    double un[NU];
+    auto poison = [&](bool bad) {
+      const double qnan = __builtin_nan("");
+      zero_or_nan = bad ? qnan : 0.0;
+#pragma unroll
+      for (int i = 0; i < MAXH + 2; ++i) wreg[i] = bad ? qnan : wreg[i];
+#pragma unroll
+      for (int r = 0; r < NU; ++r) un[r] = bad ? qnan : um[r];
+    };
+    if constexpr (kLean) {
+      // The common case -- no lane of the wave has anything to report -- is one wave ballot: status 0, and the
+      // back-substitution starts from the merge's registers as they are.  Only a wave that holds a failed drone
+      // takes the branch (wave-uniform: exec stays whole).
+      int st = MSNAP_ST_OK;
+#pragma unroll
+      for (int r = 0; r < NU; ++r) un[r] = um[r];
+      if (__builtin_expect(__builtin_amdgcn_ballot_w64(inbad | singular) != 0, 0)) {
+        asm volatile("" ::: "memory");   // keep the block a branch: the compiler would flatten it into selects again
+        // which kind of input failure: the sweeps' own tests again, on the inputs still staged in LDS
+        const double T0r = Town(0);
+        nonfinite = !(finite64(t0) & finite64(T0r) & finite64(wreg[0]) & finite64(wreg[1]));
+        badtime = !(T0r > 0.0) | !((side ? T0r : T0r - t0) > 0.0) | (t0 < 0.0);
+#pragma unroll
+        for (int it = 1; it <= MAXH; ++it) {
+          const double Tit = Town(it);
+          nonfinite |= !finite64(Tit) | !finite64(wreg[it + 1]);
+          badtime |= !(Tit > 0.0);
+        }
+        st = classify();
+        poison(st != 0);
+      }
+      put_status(st);
+    } else {
+      const int st = classify();
+      put_status(st);
+      poison(st != 0);
+    }
 
     MSNAP_TL(3);
     // ---- outward back-substitution + recovery: side s owns its segments 0 .. mside; this wave recovers the
     // pieces lo .. hi of each side and back-substitutes out to lo (scalar bounds: wave-uniform branches) ----
     const int lo = twist_chunk_lo<MAXH + 1, NW>(wave), hi = twist_chunk_lo<MAXH + 1, NW>(wave + 1) - 1;
-    // A failed drone's outputs are NaN: poison what every coefficient is computed from once
-    // (waypoints -> c0 and the end-side block, knot states -> c1..) instead of selecting per piece.
-    const double qnan = __builtin_nan("");
-    const double zero_or_nan = bad ? qnan : 0.0;
-#pragma unroll
-    for (int i = 0; i < MAXH + 2; ++i) wreg[i] = bad ? qnan : wreg[i];
-    double un[NU];
-#pragma unroll
-    for (int r = 0; r < NU; ++r) un[r] = bad ? qnan : um[r];
 #pragma unroll
     for (int it = MAXH; it >= 0; --it) {
       if (NW > 1 && (it < lo || hi < lo)) break;     // (no piece of this wave further out)
@@ -1241,7 +1294,8 @@ static int launch_solve_k(msnap_ctx *ctx, int N, int M, const double *wp, const 
     const int nw = ctx->twist_waves > 0 ? ctx->twist_waves : nt8 * 4 <= ctx->n_cu ? 4 : nt8 * 2 <= ctx->n_cu ? 2 : 1;
     // inputs + z stash per wave (64 lanes x NU per knot; used by the long-path instances only, 4 x 16.5 KiB at M = 24)
     const size_t lds_bytes = ((size_t)kTwistDrones * (M + 1) * 5 + (size_t)nw * 64 * (K - 1) * nR) * sizeof(double);
-    // grid == tile count: one workgroup of nw waves per 8-drone tile (the kernel has no tile loop and no tile guard)
+    // grid == tile count: one workgroup of nw waves per 8-drone tile (the kernel has no tile loop and no tile guard,
+    // and no tile-count argument either: its seven arguments are exactly the 12 dwords the build preloads into SGPRs)
 #define MSNAP_TWIST_NW(MM, NWV)                                                                                    \
   hipLaunchKernelGGL((solve_kernel_twist<K, (MM - 2) - (MM - 2) / 2, MM, NWV>), dim3(nt8), dim3(kWave * NWV),      \
                      lds_bytes, ctx->stream, wp, t, shared, N, coef, dur, status)

@@ -13,6 +13,19 @@ __device__ __forceinline__ double shfl_xor_f64(double v, int mask) {
   return __hiloint2double(hi, lo);
 }
 
+// v of lane (lane xor 4) without the LDS crossbar: the partners sit in one row of 16, four lanes apart, so two DPP row
+// shifts under complementary bank masks (a bank = 4 lanes) deliver them -- lanes 0-3 and 8-11 of a row read four lanes
+// up (row_shl:4, banks 0 and 2), lanes 4-7 and 12-15 four lanes down (row_shr:4, banks 1 and 3).  All 64 lanes active.
+__device__ __forceinline__ int row_xor4_b32(int v) {
+  const int up = __builtin_amdgcn_mov_dpp(v, 0x104, 0xF, 0x5, false);
+  return __builtin_amdgcn_update_dpp(up, v, 0x114, 0xF, 0xA, false);
+}
+__device__ __forceinline__ double row_xor4_f64(double v) {
+  const int lo = row_xor4_b32(__double2loint(v));
+  const int hi = row_xor4_b32(__double2hiint(v));
+  return __hiloint2double(hi, lo);
+}
+
 // fp64 min / max over the 64 lanes of a wave (every lane gets the result): four DPP stages inside
 // the rows of 16 (lane xor 1, xor 2, mirror of 8, mirror of 16), two exchanges across the rows
 template <int CTRL>
