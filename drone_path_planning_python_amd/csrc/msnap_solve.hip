@@ -38,27 +38,26 @@
 
 #include "msnap_internal.h"
 #include "msnap_sweep.h"
+#include "msnap_rolled.h"
 
 namespace msnap {
 
 
 // ------------------------------------------------------------------------------------
-// generic variant: rolled loops, G_i / z_i stashed in LDS (GS = false) or on a
-// global slab (GS = true)
+// generic variant: rolled loops, G_i / z_i stashed in LDS (GS = false) or on a global slab (GS = true).  The solve
+// of a tile is rolled_solve_tile (msnap_rolled.h), shared with the boundary-state solve of msnap_states.hip; here
+// are the layout and the tile loop.
 // ------------------------------------------------------------------------------------
 template <int K, bool GS>
 __global__ void __launch_bounds__(kWave)
 solve_kernel(const double *__restrict__ wp, const double *__restrict__ tt, int shared_times,
              int N, int M, double *__restrict__ coef, double *__restrict__ dur,
              int32_t *__restrict__ status, double *__restrict__ gscratch, int ntiles) {
-  using SW = Sweep<K>;
-  constexpr int NU = SW::NU, NC = SW::NC;
+  constexpr int NU = K - 1, NC = 2 * K;
 
   extern __shared__ __attribute__((aligned(16))) double lds[];
 
   const int lane = threadIdx.x;
-  const int dl = lane >> 2;
-  const int a = lane & 3;
   const int knots = M - 1;
   const int wpitch = (M + 1) * 4;
   const int tpitch = M + 1;
@@ -66,154 +65,29 @@ solve_kernel(const double *__restrict__ wp, const double *__restrict__ tt, int s
   // LDS: output transpose image Tr[NC/2][68] (16-B slots) | then, LDS variant only,
   //      inputs Wraw[16][(M+1)*4] | Traw[16][M+1]
   // stash (LDS or global slab): X[M][16] | G[knots][NU*NU][16] | Z[knots][NU][64]
+  RolledTile p;
   double2 *sTr = reinterpret_cast<double2 *>(lds);
-  double *sWraw = lds + (NC / 2) * kTrPitch * 2;
-  double *sTraw = sWraw + 16 * wpitch;
-  double *scr;
+  p.sWraw = lds + (NC / 2) * kTrPitch * 2;
+  p.sTraw = p.sWraw + 16 * wpitch;
   if constexpr (GS) {
-    scr = gscratch + (size_t)blockIdx.x * (size_t)(16 * M + 16 * NU * NU * knots + 64 * NU * knots);
+    p.sX = gscratch + (size_t)blockIdx.x * (size_t)(16 * M + 16 * NU * NU * knots + 64 * NU * knots);
   } else {
-    scr = sTraw + 16 * tpitch;
+    p.sX = p.sTraw + 16 * tpitch;
   }
-  double *sX = scr;
-  double *sG = sX + 16 * M;
-  double *sZ = sG + 16 * NU * NU * knots;
+  p.sG = p.sX + 16 * M;
+  p.sZ = p.sG + 16 * NU * NU * knots;
+  p.sS0 = p.sS1 = nullptr;
 
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    const int d_raw = tile * kDronesPerWave + dl;
-    const bool live = d_raw < N;
-    const int d = live ? d_raw : N - 1;
-    const double *wrow = wp + (size_t)d * (size_t)wpitch + a;
-    const double *trow = shared_times ? tt : tt + (size_t)d * (size_t)tpitch;
-    double *drow = dur + (size_t)d * M;
-
     const int left = N - tile * kDronesPerWave;
     const int nvalid = left < kDronesPerWave ? left : kDronesPerWave;
     if constexpr (!GS) {
       if (tile != (int)blockIdx.x) __syncthreads();  // LDS is reused by this block's next tile
-      stage_inputs(wp, tt, shared_times, tile, nvalid, wpitch, tpitch, sWraw, sTraw, lane);
+      stage_inputs(wp, tt, shared_times, tile, nvalid, wpitch, tpitch, p.sWraw, p.sTraw, lane);
       __syncthreads();
-      store_durations(sTraw, shared_times, tpitch, M, nvalid, lane, dur + (size_t)tile * kDronesPerWave * M);
+      store_durations(p.sTraw, shared_times, tpitch, M, nvalid, lane, dur + (size_t)tile * kDronesPerWave * M);
     }
-    // lanes past the end of the batch replay the last valid drone (and store on top of its results)
-    const int dloc = live ? dl : (N - 1 - tile * kDronesPerWave);
-    const double *lw = sWraw + dloc * wpitch + a;
-    const double *lt = sTraw + (shared_times ? 0 : dloc * tpitch);
-    auto Wv = [&](int i) -> double { if constexpr (GS) return wrow[(size_t)i * 4]; else return lw[i * 4]; };
-    auto Tv = [&](int i) -> double { if constexpr (GS) return trow[i]; else return lt[i]; };
-
-    // ---------------- segment 0 ----------------
-    const double t0 = Tv(0);
-    double tcur = Tv(1);
-    const double w0 = Wv(0);
-    double wcur = Wv(1);
-    bool nonfinite = !(finite64(t0) & finite64(tcur) & finite64(w0) & finite64(wcur));
-    double T = tcur - t0;
-    const double Teff = T - t0;   // Appendix-A quirk, see taylor_shift()
-    bool badtime = !(T > 0.0) | !(Teff > 0.0) | (t0 < 0.0);
-    if constexpr (GS) {
-      if (live && a == 0) drow[0] = T;
-    }
-    double x = rcp64(Teff);
-    sX[0 * 16 + dl] = x;
-    SW sw;
-    sw.init(x, wcur - w0);
-
-    // ---------------- forward block LDL^T sweep over interior knots ----------------
-    // operands of knot i+1 are fetched one iteration ahead (LDS latency off the chain)
-    double tpre = Tv(M >= 2 ? 2 : M);
-    double wpre = Wv(M >= 2 ? 2 : M);
-    for (int i = 1; i < M; ++i) {
-      const double tnext = tpre;
-      const double wnext = wpre;
-      {
-        const int ip = (i + 2 <= M) ? i + 2 : M;
-        tpre = Tv(ip);
-        wpre = Wv(ip);
-      }
-      nonfinite |= !finite64(tnext) | !finite64(wnext);
-      T = tnext - tcur;
-      badtime |= !(T > 0.0);
-      if constexpr (GS) {
-        if (live && a == 0) drow[i] = T;
-      }
-      x = rcp64(T);
-      sX[i * 16 + dl] = x;
-      double G[NU][NU], z[NU];
-      sw.step(x, wnext - wcur, G, z);
-      double *g = sG + (size_t)(i - 1) * (NU * NU * 16) + dl;
-      double *zz = sZ + (size_t)(i - 1) * (NU * 64) + lane;
-#pragma unroll
-      for (int r = 0; r < NU; ++r) {
-#pragma unroll
-        for (int c = 0; c < NU; ++c) g[(r * NU + c) * 16] = G[r][c];
-        zz[r * 64] = z[r];
-      }
-      tcur = tnext;
-      wcur = wnext;
-    }
-
-    const int st = drone_status(nonfinite, badtime, sw.singular);
-    if (live && a == 0) status[d] = st;
-    const bool bad = st != 0;
-
-    // ---------------- backward sweep + coefficient recovery ----------------
-    // operands of segment i-1 are fetched while segment i is being recovered
-    double un[NU], zq[NU], gq[NU][NU];
-#pragma unroll
-    for (int r = 0; r < NU; ++r) un[r] = 0.0;
-    double wn = wcur;   // w_M
-    double wq = Wv(M - 1), xq1 = sX[(M - 1) * 16 + dl];
-    {
-      const int kq = (M >= 2) ? M - 2 : 0;  // stash slot of knot M-1
-      const double *zz = sZ + (size_t)kq * (NU * 64) + lane;
-      const double *g = sG + (size_t)kq * (NU * NU * 16) + dl;
-#pragma unroll
-      for (int r = 0; r < NU; ++r) {
-        zq[r] = (M >= 2) ? zz[r * 64] : 0.0;
-#pragma unroll
-        for (int c = 0; c < NU; ++c) gq[r][c] = (M >= 2) ? g[(r * NU + c) * 16] : 0.0;
-      }
-    }
-    for (int i = M - 1; i >= 0; --i) {
-      double u[NU];
-      const double wi = wq;
-      const double xi = xq1;
-#pragma unroll
-      for (int r = 0; r < NU; ++r) {
-        double v = zq[r];
-        if (i < M - 1) {
-#pragma unroll
-          for (int c = 0; c < NU; ++c) v = __builtin_fma(-gq[r][c], un[c], v);
-        }
-        u[r] = (i >= 1) ? v : 0.0;
-      }
-      if (i >= 1) {
-        wq = Wv(i - 1);
-        xq1 = sX[(i - 1) * 16 + dl];
-        if (i >= 2) {
-          const double *zz = sZ + (size_t)(i - 2) * (NU * 64) + lane;
-          const double *g = sG + (size_t)(i - 2) * (NU * NU * 16) + dl;
-#pragma unroll
-          for (int r = 0; r < NU; ++r) {
-            zq[r] = zz[r * 64];
-#pragma unroll
-            for (int c = 0; c < NU; ++c) gq[r][c] = g[(r * NU + c) * 16];
-          }
-        }
-      }
-      double c[NC];
-      recover_segment<K>(wi, wn - wi, xi, u, un, c);
-      if (i == 0 && t0 != 0.0) taylor_shift<NC>(c, -t0);
-      if constexpr (NC == 8)
-        store_segment_quad8(MSNAP_SEG_BASE(coef, tile, M, i, NC), MSNAP_SEG_STRIDE(M, NC), nvalid, lane, c, bad);
-      else
-        store_segment_coalesced<NC>(sTr, MSNAP_SEG_BASE(coef, tile, M, i, NC), MSNAP_SEG_STRIDE(M, NC), nvalid,
-                                    lane, c, bad);
-#pragma unroll
-      for (int r = 0; r < NU; ++r) un[r] = u[r];
-      wn = wi;
-    }
+    rolled_solve_tile<K, GS, false>(p, sTr, wp, tt, shared_times, false, false, M, tile, nvalid, lane, coef, dur, status);
   }
 }
 

@@ -5,23 +5,26 @@
 // Solve.  In the Hermite form of DESIGN.md §3 the derivative vectors u_0, u_M of the end knots are not unknowns; given
 // as data they only move to the right-hand side of the block tridiagonal system
 //     O_{i-1}^T u_{i-1} + D_i u_i + O_i u_{i+1} = r_i ,   i = 1..M-1 .
-// states_solve_kernel<K> is the generic solve_kernel<K, false> of msnap_solve.hip -- lane = 4 drone + axis, inputs
-// staged in LDS, rolled knot loops over Sweep<K>::step, X / G / Z stash in LDS, recover_segment and full-line stores --
-// with the end states entering in three places:
+// states_solve_kernel<K> carves StatesLayout<K>, stages the inputs and the two state blocks in LDS, and solves its tile
+// with rolled_solve_tile<K, false, true> of msnap_rolled.h -- the body it shares with the generic solve_kernel<K, false>
+// of msnap_solve.hip.  ENDS = true turns on, in that body:
+//   start      u_0 / u_M are read from the state blocks (a missing one is rest) and checked for finiteness;
+//   segment 0  x = 1 / T_0, and the first time must be 0 (MSNAP_ST_TIMES otherwise): the reference's start-row quirk --
+//              segment 0's start rows taken at local time t[0] -- has no meaning for a path that starts from a moving
+//              state, so there is no Taylor shift here;
 //   knot 1     the sweep's carried term starts as Otz = O_0^T u_0 (y_1 = -yb_1 - Otz), not 0;
+//   forward    the durations before the current segment are summed as msnap_eval_flat sums them;
 //   knot M-1   the sweep stores G_{M-1} = S^-1 O_{M-1} for every knot, the last one included, and the backward sweep
 //              starts from un = u_M:  u_{M-1} = z_{M-1} - G_{M-1} u_M, which is S^-1 (y_{M-1} - O_{M-1} u_M).  With two
 //              segments the one knot receives both terms;
 //   recovery   segment M-1 ends in u_M, segment 0 starts from u_0; one segment is recover_segment alone.  The last
 //              segment then takes one refinement step on its end conditions (refine_end), so that msnap_eval_state at
 //              the sum of the durations returns the given end state to the evaluator's own rounding.
-// The first time must be 0 (MSNAP_ST_TIMES otherwise): the reference's start-row quirk -- segment 0's start rows taken
-// at local time t[0] -- has no meaning for a path that starts from a moving state, so there is no Taylor shift here.
 //
 // Evaluator.  One thread per drone: msnap_eval_flat's piece lookup (t <= acc + T_i: a knot belongs to the earlier
 // segment) and horner_derivs' arithmetic of msnap_aux.hip carried to derivative K-1, no contraction.
 #include "msnap_api_util.h"
-#include "msnap_sweep.h"
+#include "msnap_rolled.h"
 
 namespace msnap {
 namespace {
@@ -75,76 +78,31 @@ __device__ __forceinline__ void store_states(double *sS, int nvalid, int lane, c
   }
 }
 
-// One step of iterative refinement of the LAST segment's end conditions.  recover_segment's upper coefficients are
-// cancelling sums (constants of 10^2 .. 10^3) computed with 1/T rounded, so the polynomial it returns has the given
-// end state only to the accuracy of its coefficients.  Here the end values are evaluated with msnap_eval_state's own
-// arithmetic at `tl` -- the local time that evaluator reaches at the sum of the durations -- and their residual
-// against (w_M, u_M) is taken out of the upper coefficients through CE (a_hi = CS e_start + CE e_end is linear in the
-// end vector; the lower coefficients, and with them the continuity at the knot before, do not move).  The change is
-// a few units in the last place; what it buys is that the evaluator returns the given end state to its own rounding.
-template <int K>
-__device__ __forceinline__ void refine_end(double (&c)[2 * K], double tl, double x, double wend,
-                                           const double (&uend)[K - 1]) {
-#pragma clang fp contract(off)
-  using C = HermiteConsts<K>;
-  constexpr int NC = 2 * K;
-  double r[K], dd[NC];
-#pragma unroll
-  for (int i = 0; i < NC; ++i) dd[i] = c[i];
-  double tp = 1.0;
-#pragma unroll
-  for (int q = 0; q < K; ++q) {
-    if (q > 0) {
-#pragma unroll
-      for (int i = 0; i < NC - q; ++i) dd[i] = (double)(i + 1) * dd[i + 1];
-    }
-    double p = 0.0;
-#pragma unroll
-    for (int i = NC - 1 - q; i >= 0; --i) p = p * tl + dd[i];
-    r[q] = (p - (q == 0 ? wend : uend[q > 0 ? q - 1 : 0])) * tp;      // in normalised time: T^q times the q-th derivative
-    tp = tp * tl;
-  }
-  double xq = 1.0;
-#pragma unroll
-  for (int m = 0; m < K; ++m) xq = xq * x;
-#pragma unroll
-  for (int m = 0; m < K; ++m) {
-    double acc = 0.0;
-#pragma unroll
-    for (int n = 0; n < K; ++n) acc = acc + C::CE[m][n] * r[n];
-    c[K + m] = c[K + m] - acc * xq;
-    xq = xq * x;
-  }
-}
-
 template <int K>
 __global__ void __launch_bounds__(kWave)
 states_solve_kernel(const double *__restrict__ wp, const double *__restrict__ tt, int shared_times,
                     const double *__restrict__ start, const double *__restrict__ end, int N, int M,
                     double *__restrict__ coef, double *__restrict__ dur, int32_t *__restrict__ status) {
-  using SW = Sweep<K>;
   using L = StatesLayout<K>;
-  using C = HermiteConsts<K>;
-  constexpr int NU = SW::NU, NC = SW::NC, KK = SW::KK, PM = SW::PM, PITCH = L::kPitch;
+  constexpr int NU = K - 1, PITCH = L::kPitch;
 
   extern __shared__ __attribute__((aligned(16))) double lds[];
 
   const int lane = threadIdx.x;
-  const int dl = lane >> 2;
-  const int a = lane & 3;
   const int knots = M - 1;
   const int wpitch = (M + 1) * 4;
   const int tpitch = M + 1;
   const int tile = blockIdx.x;
 
+  RolledTile p;
   double2 *sTr = reinterpret_cast<double2 *>(lds);
-  double *sWraw = lds + L::kTrWords;
-  double *sTraw = sWraw + 16 * wpitch;
-  double *sS0 = sTraw + 16 * tpitch;
-  double *sS1 = sS0 + L::kStateWords;
-  double *sX = sS1 + L::kStateWords;
-  double *sG = sX + 16 * M;
-  double *sZ = sG + 16 * NU * NU * knots;
+  p.sWraw = lds + L::kTrWords;
+  p.sTraw = p.sWraw + 16 * wpitch;
+  p.sS0 = p.sTraw + 16 * tpitch;
+  p.sS1 = p.sS0 + L::kStateWords;
+  p.sX = p.sS1 + L::kStateWords;
+  p.sG = p.sX + 16 * M;
+  p.sZ = p.sG + 16 * NU * NU * knots;
 
   const int left = N - tile * kDronesPerWave;
   const int nvalid = left < kDronesPerWave ? left : kDronesPerWave;
@@ -156,154 +114,14 @@ states_solve_kernel(const double *__restrict__ wp, const double *__restrict__ tt
   for (int q = 0; q < NU; ++q) v0[q] = v1[q] = 0.0;
   if (has_start) load_states<NU, PITCH>(start, tile, nvalid, lane, v0);
   if (has_end) load_states<NU, PITCH>(end, tile, nvalid, lane, v1);
-  stage_inputs(wp, tt, shared_times, tile, nvalid, wpitch, tpitch, sWraw, sTraw, lane);
-  if (has_start) store_states<NU, PITCH>(sS0, nvalid, lane, v0);
-  if (has_end) store_states<NU, PITCH>(sS1, nvalid, lane, v1);
+  stage_inputs(wp, tt, shared_times, tile, nvalid, wpitch, tpitch, p.sWraw, p.sTraw, lane);
+  if (has_start) store_states<NU, PITCH>(p.sS0, nvalid, lane, v0);
+  if (has_end) store_states<NU, PITCH>(p.sS1, nvalid, lane, v1);
   __syncthreads();
-  store_durations(sTraw, shared_times, tpitch, M, nvalid, lane, dur + (size_t)tile * kDronesPerWave * M);
+  store_durations(p.sTraw, shared_times, tpitch, M, nvalid, lane, dur + (size_t)tile * kDronesPerWave * M);
 
-  // lanes past the end of the batch replay the last valid drone (and store on top of its results)
-  const bool live = dl < nvalid;
-  const int dloc = live ? dl : nvalid - 1;
-  const double *lw = sWraw + dloc * wpitch + a;
-  const double *lt = sTraw + (shared_times ? 0 : dloc * tpitch);
-  const int sl = (dloc * 4 + a) * PITCH;
-
-  double u0[NU], uM[NU];
-  bool nonfinite = false;
-#pragma unroll
-  for (int q = 0; q < NU; ++q) {
-    u0[q] = has_start ? sS0[sl + q] : 0.0;
-    uM[q] = has_end ? sS1[sl + q] : 0.0;
-    nonfinite |= !finite64(u0[q]) | !finite64(uM[q]);
-  }
-
-  // ---------------- segment 0 ----------------
-  const double t0 = lt[0];
-  double tcur = lt[1];
-  const double w0 = lw[0];
-  double wcur = lw[4];
-  nonfinite |= !(finite64(t0) & finite64(tcur) & finite64(w0) & finite64(wcur));
-  double T = tcur - t0;
-  bool badtime = !(T > 0.0) | (t0 != 0.0);
-  double x = rcp64(T);
-  sX[dl] = x;
-  SW sw;
-  sw.init(x, wcur - w0);
-  {
-    // knot 1 sees the start state through the coupling block of segment 0: Otz = O_0^T u_0
-    double xp[PM + 1];
-    SW::powers(x, xp);
-#pragma unroll
-    for (int n = 0; n < NU; ++n) {
-      double w = 0.0;
-#pragma unroll
-      for (int q = 0; q < NU; ++q) w = __builtin_fma(C::HSE[q + 1][n + 1] * xp[KK - (q + 1) - (n + 1)], u0[q], w);
-      sw.Otz[n] = w;
-    }
-  }
-
-  // ---------------- forward block LDL^T sweep over interior knots ----------------
-  // operands of knot i+1 are fetched one iteration ahead (LDS latency off the chain)
-  double tpre = lt[M >= 2 ? 2 : M];
-  double wpre = lw[(M >= 2 ? 2 : M) * 4];
-  double tacc = 0.0;      // the durations before the current segment, summed as msnap_eval_flat sums them
-  for (int i = 1; i < M; ++i) {
-    const double tnext = tpre;
-    const double wnext = wpre;
-    tacc = tacc + T;
-    {
-      const int ip = (i + 2 <= M) ? i + 2 : M;
-      tpre = lt[ip];
-      wpre = lw[ip * 4];
-    }
-    nonfinite |= !finite64(tnext) | !finite64(wnext);
-    T = tnext - tcur;
-    badtime |= !(T > 0.0);
-    x = rcp64(T);
-    sX[i * 16 + dl] = x;
-    double G[NU][NU], z[NU];
-    sw.step(x, wnext - wcur, G, z);
-    double *g = sG + (size_t)(i - 1) * (NU * NU * 16) + dl;
-    double *zz = sZ + (size_t)(i - 1) * (NU * 64) + lane;
-#pragma unroll
-    for (int r = 0; r < NU; ++r) {
-#pragma unroll
-      for (int c = 0; c < NU; ++c) g[(r * NU + c) * 16] = G[r][c];
-      zz[r * 64] = z[r];
-    }
-    tcur = tnext;
-    wcur = wnext;
-  }
-
-  const int st = drone_status(nonfinite, badtime, sw.singular);
-  if (live && a == 0) status[tile * kDronesPerWave + dl] = st;
-  const bool bad = st != 0;
-
-  // ---------------- backward sweep + coefficient recovery ----------------
-  // u_i = z_i - G_i u_{i+1} from u_M, the last knot included; operands of segment i-1 are fetched while segment i is
-  // being recovered
-  double un[NU], zq[NU], gq[NU][NU];
-#pragma unroll
-  for (int r = 0; r < NU; ++r) un[r] = uM[r];
-  double wn = wcur;   // w_M
-  // the local time msnap_eval_state evaluates the last segment at when asked for the sum of the durations
-  const double tl_end = (tacc + T) - tacc;
-  double wq = lw[(M - 1) * 4], xq1 = sX[(M - 1) * 16 + dl];
-  if (M >= 2) {
-    const double *zz = sZ + (size_t)(M - 2) * (NU * 64) + lane;
-    const double *g = sG + (size_t)(M - 2) * (NU * NU * 16) + dl;
-#pragma unroll
-    for (int r = 0; r < NU; ++r) {
-      zq[r] = zz[r * 64];
-#pragma unroll
-      for (int c = 0; c < NU; ++c) gq[r][c] = g[(r * NU + c) * 16];
-    }
-  } else {
-#pragma unroll
-    for (int r = 0; r < NU; ++r) {
-      zq[r] = 0.0;
-#pragma unroll
-      for (int c = 0; c < NU; ++c) gq[r][c] = 0.0;
-    }
-  }
-  for (int i = M - 1; i >= 0; --i) {
-    double u[NU];
-    const double wi = wq;
-    const double xi = xq1;
-#pragma unroll
-    for (int r = 0; r < NU; ++r) {
-      double v = zq[r];
-#pragma unroll
-      for (int c = 0; c < NU; ++c) v = __builtin_fma(-gq[r][c], un[c], v);
-      u[r] = (i >= 1) ? v : u0[r];
-    }
-    if (i >= 1) {
-      wq = lw[(i - 1) * 4];
-      xq1 = sX[(i - 1) * 16 + dl];
-      if (i >= 2) {
-        const double *zz = sZ + (size_t)(i - 2) * (NU * 64) + lane;
-        const double *g = sG + (size_t)(i - 2) * (NU * NU * 16) + dl;
-#pragma unroll
-        for (int r = 0; r < NU; ++r) {
-          zq[r] = zz[r * 64];
-#pragma unroll
-          for (int c = 0; c < NU; ++c) gq[r][c] = g[(r * NU + c) * 16];
-        }
-      }
-    }
-    double c[NC];
-    recover_segment<K>(wi, wn - wi, xi, u, un, c);
-    if (i == M - 1) refine_end<K>(c, tl_end, xi, wn, un);
-    if constexpr (NC == 8)
-      store_segment_quad8(MSNAP_SEG_BASE(coef, tile, M, i, NC), MSNAP_SEG_STRIDE(M, NC), nvalid, lane, c, bad);
-    else
-      store_segment_coalesced<NC>(sTr, MSNAP_SEG_BASE(coef, tile, M, i, NC), MSNAP_SEG_STRIDE(M, NC), nvalid, lane, c,
-                                  bad);
-#pragma unroll
-    for (int r = 0; r < NU; ++r) un[r] = u[r];
-    wn = wi;
-  }
+  rolled_solve_tile<K, false, true>(p, sTr, wp, tt, shared_times, has_start, has_end, M, tile, nvalid, lane, coef,
+                                    dur, status);
 }
 
 // ------------------------------------------------------------------------------------

@@ -248,18 +248,6 @@ __device__ __forceinline__ void taylor_shift(double (&c)[NC], double h) {
     for (int q = NC - 2; q >= j; --q) c[q] = __builtin_fma(h, c[q + 1], c[q]);
 }
 
-template <int NC>
-__device__ __forceinline__ void store_segment(double *__restrict__ o, double (&c)[NC], bool bad, bool live) {
-  if (bad) {
-#pragma unroll
-    for (int m = 0; m < NC; ++m) c[m] = __builtin_nan("");
-  }
-  if (live) {
-#pragma unroll
-    for (int m = 0; m < NC; m += 2) *reinterpret_cast<double2 *>(o + m) = make_double2(c[m], c[m + 1]);
-  }
-}
-
 // Full-line output stores.  A lane owns the NC coefficients of one (drone, axis):
 // stored directly, a wave instruction would scatter 64 x 16 B over 64 different
 // 64-byte segments.  Instead the segment's 64 x NC doubles take a round trip
@@ -463,61 +451,9 @@ __device__ __forceinline__ void stage_inputs(const double *__restrict__ wp, cons
   }
 }
 
-// the same sweep split in two for software pipelining across tiles (n_seg <= 12: one round):
-// the loads of tile k+1 are issued near the end of tile k and land in LDS at the top of k+1
-template <int MAXM>
-struct StageRegs {
-  static constexpr int UW = (MAXM + 2) / 2;   // ceil(16*(MAXM+1)*4/2 / 64) 16-byte loads per lane
-  static constexpr int UT = (MAXM + 4) / 4;   // ceil(16*(MAXM+1) / 64) 8-byte loads per lane
-  double2 vw[UW];
-  double vt[UT];
-};
-
-template <int MAXM>
-__device__ __forceinline__ void stage_load_once(const double *__restrict__ wp, const double *__restrict__ tt,
-                                                int shared_times, int tile, int nvalid, int wpitch, int tpitch,
-                                                int lane, StageRegs<MAXM> &r) {
-  constexpr int kStageUW = StageRegs<MAXM>::UW, kStageUT = StageRegs<MAXM>::UT;
-  const double2 *wsrc = reinterpret_cast<const double2 *>(wp + (size_t)tile * kDronesPerWave * wpitch);
-  const int wcnt = nvalid * wpitch / 2;
-  const double *tsrc = shared_times ? tt : tt + (size_t)tile * kDronesPerWave * tpitch;
-  const int tcnt = shared_times ? tpitch : nvalid * tpitch;
-#pragma unroll
-  for (int u = 0; u < kStageUW; ++u) {
-    const int e = u * kWave + lane;
-    r.vw[u] = wsrc[e < wcnt ? e : wcnt - 1];
-  }
-#pragma unroll
-  for (int u = 0; u < kStageUT; ++u) {
-    const int f = u * kWave + lane;
-    r.vt[u] = tsrc[f < tcnt ? f : tcnt - 1];
-  }
-}
-
-template <int MAXM>
-__device__ __forceinline__ void stage_store_once(int shared_times, int nvalid, int wpitch, int tpitch,
-                                                 double *sWraw, double *sTraw, int lane, StageRegs<MAXM> &r) {
-  constexpr int kStageUW = StageRegs<MAXM>::UW, kStageUT = StageRegs<MAXM>::UT;
-  double2 *wdst = reinterpret_cast<double2 *>(sWraw);
-  const int wcnt = nvalid * wpitch / 2;
-  const int tcnt = shared_times ? tpitch : nvalid * tpitch;
-#pragma unroll
-  for (int u = 0; u < kStageUW; ++u) asm volatile("" : "+v"(r.vw[u].x), "+v"(r.vw[u].y));
-#pragma unroll
-  for (int u = 0; u < kStageUT; ++u) asm volatile("" : "+v"(r.vt[u]));
-#pragma unroll
-  for (int u = 0; u < kStageUW; ++u) {
-    const int e = u * kWave + lane;
-    if (e < wcnt) wdst[e] = r.vw[u];
-  }
-#pragma unroll
-  for (int u = 0; u < kStageUT; ++u) {
-    const int f = u * kWave + lane;
-    if (f < tcnt) sTraw[f] = r.vt[u];
-  }
-}
-
-// Hand-managed variant of the same prefetch for the persistent kernel.  hipcc waits for a
+// The same sweep split in two for software pipelining across tiles in the persistent kernel (one round of
+// (MAXM + 2) / 2 16-byte and (MAXM + 4) / 4 8-byte loads per lane): the loads of tile k+1 are issued near the end of
+// tile k and land in LDS at the top of k+1.  Left to the compiler, hipcc waits for a
 // prefetched load with vmcnt(0) once the wait sits behind the loop back-edge, which also
 // drains the tile's 40 KB of output stores at every tile boundary.  The loads are therefore
 // issued from inline asm (invisible to the compiler's wait-count pass) and retired with an
