@@ -31,14 +31,16 @@ def deriv_row(nc, j, t):
     return row
 
 
-def _assemble(T, K):
+def _assemble(T, K, t_start=None):
     """rows of the collocation matrix as (first column, values) and, per row, where its right-hand side comes from:
-    ("w", i) the waypoint i, ("s", q) / ("e", q) the q-th derivative of the start / end state, None: zero"""
+    ("w", i) the waypoint i, ("s", q) / ("e", q) the q-th derivative of the start / end state, None: zero.
+    t_start: the local time of segment 0 at which its K start rows are taken (None: 0; tests/solve_exact.py passes
+    t[0], the reference's start-row quirk)"""
     NC, M = 2 * K, len(T)
     zero = mp.mpf(0)
     rows, src = [], []
     for j in range(K):
-        rows.append((0, deriv_row(NC, j, zero)))
+        rows.append((0, deriv_row(NC, j, zero if t_start is None else t_start)))
         src.append(("w", 0) if j == 0 else ("s", j))
     for i in range(1, M):
         lo = NC * (i - 1)
@@ -104,13 +106,19 @@ def _banded_lu_solve(rows, rhs, n, NC):
 def exact_solve(times, wp, states, K):
     """times [M+1] and wp [M+1, 4] float64 (taken exactly); states: list of (start, end), each [4, K-1] float64 or
     None (rest).  Returns one float64 array [M, 4, 2K] per entry of `states`: the 60-digit solutions rounded once."""
-    NC = 2 * K
     t = [mp.mpf(float(x)) for x in times]
     assert t[0] == 0
+    return solve_checked(t, wp, states, K, None)
+
+
+def solve_checked(t, wp, states, K, t_start):
+    """exact_solve's body for knot times t given as mpf: assembly (start rows of segment 0 at local time t_start, see
+    _assemble), the banded LU, the residual assertion against the unfactored rows, one rounding to float64"""
+    NC = 2 * K
     M = len(t) - 1
     T = [t[i + 1] - t[i] for i in range(M)]
     n = NC * M
-    rows, src = _assemble(T, K)
+    rows, src = _assemble(T, K, t_start)
     assert len(rows) == n
     rhs = []
     for start, end in states:
@@ -127,7 +135,7 @@ def exact_solve(times, wp, states, K):
             rhs.append(col)
     X = _banded_lu_solve(rows, rhs, n, NC)
     # the solutions against the unfactored rows
-    rows0, _ = _assemble(T, K)
+    rows0, _ = _assemble(T, K, t_start)
     for x, col in zip(X, rhs):
         scale = max(abs(v) for v in x) + 1
         for (lo, vals), want in zip(rows0, col):

@@ -8,13 +8,9 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN_DIR, norm_rel
+from solve_cases import TIGHT, TIGHT9, TOL      # the bars, shared with tests/test_solve_exact_gpu.py
 
 pytestmark = pytest.mark.gpu
-
-TOL = 1e-6        # north-star gate
-TIGHT9 = 1e-9     # order 9: pinned by the 60-digit solves of tests/golden/order9_golden.npz (SURVEY.md 8c iii); the
-                  # fp64 oracles are within 2e-11 of them on every fixture case, the HIP kernels within 1e-10
-TIGHT = 1e-9      # what the algorithm actually delivers (regression tripwire)
 
 SINGLE = ["cfg1", "testdata", "m1", "m2", "t0quirk", "path49"]
 BATCH = ["cfg2", "cfg2s", "m20", "m3"]

@@ -22,33 +22,15 @@ def _inputs(order, m, n, shared):
 
 
 def _solve(ctx, waves, wp, t):
-    """One solve into FRESH device outputs pre-filled with sentinels (coefficients and durations NaN with a payload
-    no kernel writes, status -7), so a piece, a duration or a status word that a form fails to store shows up as the
-    sentinel instead of another run's value left in reused buffers."""
-    import torch
-    n, m1, _ = wp.shape
-    m = m1 - 1
-    ncoef = ctx.order + 1
-    dev = torch.device("cuda", ctx.device_id)
-    dwp = torch.from_numpy(np.ascontiguousarray(wp)).to(dev)
-    dt = torch.from_numpy(np.ascontiguousarray(t)).to(dev)
-    sentinel = np.array([0x7FF8DEADBEEF0001], dtype=np.int64).view(np.float64)[0]
-    coef = torch.full((n, m, 4, ncoef), sentinel, dtype=torch.float64, device=dev)
-    dur = torch.full((n, m), sentinel, dtype=torch.float64, device=dev)
-    status = torch.full((n,), -7, dtype=torch.int32, device=dev)
-    torch.cuda.synchronize(dev)
+    """One solve into FRESH sentinel-filled device outputs (solve_cases.solve_fresh: a piece, a duration or a status
+    word that a form fails to store shows up as the sentinel instead of another run's value left in reused buffers)."""
+    from solve_cases import solve_fresh
     ctx.set_option("twist_waves", waves)
     try:
-        ctx.solve_batch_device(n, m, dwp, dt, t.ndim == 1, coef, dur, status)
-        ctx.sync()
+        out = solve_fresh(ctx, wp, t)
     finally:
         ctx.set_option("twist_waves", 0)
     assert ctx.last_kernel().startswith("msnap::solve_kernel_twist<"), ctx.last_kernel()
-    out = coef.cpu().numpy(), dur.cpu().numpy(), status.cpu().numpy()
-    # every word written: no sentinel survives
-    for x in out[:2]:
-        assert not (x.view(np.int64) == 0x7FF8DEADBEEF0001).any(), "an output the kernel did not store"
-    assert not (out[2] == -7).any(), "a status word the kernel did not store"
     return out
 
 

@@ -16,9 +16,14 @@ import c_oracle  # noqa: E402
 from conftest import norm_rel  # noqa: E402
 from drone_path_planning_python_amd import Context  # noqa: E402
 
-# order 9 on random grids with duration ratios up to 6 and 15-20 segments: the two fp64 solves (the oracle's dense LU, the
-# kernels' block recurrence) differ by up to a few 1e-9 of the largest coefficient; the tests hold 1e-9 on their shapes
-TOL = {7: 1e-9, 9: 2e-8}
+# order 9 on random grids with duration ratios up to 6 and 15-20 segments: kernels and oracle differ by up to a few 1e-9 of
+# the largest coefficient, and the difference is the KERNELS'.  Against 60-digit solutions on this draw the oracle's dense
+# LU is within 1e-12 (8e-12 at worst), the kernels within 8e-10 on nine drones per segment count and, over the millions of
+# drones walked here, 5.5e-9: the reduced block system has a condition number of 1-2e9 on such grids, every kernel family
+# loses the same digits in the same places (DESIGN.md sections 2 and 3, profiles/solve_accuracy.md,
+# profiles/solve_loss_stages.md).  Order 7: oracle 1e-12, kernels 2.5e-12.  The tests hold 1e-9 on the suite's even grids
+# and these bars on this draw (tests/test_solve_exact_gpu.py).
+from solve_cases import STRESS_TOL as TOL  # noqa: E402  ({7: 1e-9, 9: 2e-8})
 
 
 def run(budget=60.0, seed=1, max_cases=None):
