@@ -31,6 +31,7 @@
 #include <cstdlib>
 
 #include "msnap_internal.h"
+#include "msnap_dispatch.h"
 #include "msnap_wave.h"
 
 namespace msnap {
@@ -302,12 +303,24 @@ grid_gemm_stream_kernel(const double *__restrict__ wp, const double *__restrict_
   }
 }
 
-static bool grid_gemm_reg_supported(const msnap_ctx *ctx, int n_seg) {
-  const int nc = ctx->order + 1;
-  const int nct = (n_seg * nc + 15) / 16;
-  const int nks = (n_seg + 1 + 3) / 4;
-  return nct <= kGridMaxCT && nks <= kGridMaxKS;
+// the register variant holds the whole operator: its column tiles and k steps within kGridMaxCT x kGridMaxKS
+constexpr bool grid_reg_fits(int nc, int n_seg) {
+  return (n_seg * nc + 15) / 16 <= kGridMaxCT && (n_seg + 1 + 3) / 4 <= kGridMaxKS;
 }
+// the longest such grid: one grid_gemm_kernel<NC, M> per M up to here (15 segments at order 7, 12 at order 9)
+constexpr int grid_reg_max_seg(int nc) {
+  int m = 1;
+  while (grid_reg_fits(nc, m + 1)) ++m;
+  return m;
+}
+// the streaming variant's instances start where the register variant's k steps end: a grid of fewer k steps fits the
+// registers at both orders
+constexpr int kStreamMinKS = kGridMaxKS;
+static_assert((grid_reg_max_seg(8) + 1 + 1 + 3) / 4 >= kStreamMinKS &&
+                  (grid_reg_max_seg(10) + 1 + 1 + 3) / 4 >= kStreamMinKS,
+              "the shortest streamed grid has fewer k steps than the first instance");
+
+static bool grid_gemm_reg_supported(const msnap_ctx *ctx, int n_seg) { return grid_reg_fits(ctx->order + 1, n_seg); }
 
 bool grid_gemm_supported(const msnap_ctx *ctx, int n_seg) {
   (void)ctx;
@@ -394,14 +407,10 @@ static void launch_stream_nks(msnap_ctx *ctx, int N, int M, const double *wp, do
 template <int NC>
 static int launch_stream_nc(msnap_ctx *ctx, int N, int M, const double *wp, double *coef, double *dur,
                             int32_t *status) {
-  switch ((M + 1 + 3) / 4) {
-#define MSNAP_STREAM_CASE(KS) case KS: launch_stream_nks<NC, KS>(ctx, N, M, wp, coef, dur, status); break;
-    MSNAP_STREAM_CASE(4) MSNAP_STREAM_CASE(5) MSNAP_STREAM_CASE(6) MSNAP_STREAM_CASE(7) MSNAP_STREAM_CASE(8)
-    MSNAP_STREAM_CASE(9) MSNAP_STREAM_CASE(10) MSNAP_STREAM_CASE(11) MSNAP_STREAM_CASE(12) MSNAP_STREAM_CASE(13)
-    MSNAP_STREAM_CASE(14) MSNAP_STREAM_CASE(15) MSNAP_STREAM_CASE(16)
-#undef MSNAP_STREAM_CASE
-    default: return MSNAP_EINVAL;   // unreachable: grid_gemm_supported / grid_gemm_reg_supported
-  }
+  if (!dispatch_range<kStreamMinKS, kStreamMaxKS>((M + 1 + 3) / 4, [&](auto ks) {
+        launch_stream_nks<NC, decltype(ks)::value>(ctx, N, M, wp, coef, dur, status);
+      }))
+    return MSNAP_EINVAL;   // unreachable: grid_gemm_supported / grid_gemm_reg_supported
   MSNAP_HIP(ctx, hipGetLastError());
   return MSNAP_OK;
 }
@@ -429,30 +438,19 @@ int launch_solve_grid(msnap_ctx *ctx, int n_drones, const double *wp, double *co
   int grid = ctx->n_cu * 64;
   if (ctx->gemm_grid_waves > 0) grid = ctx->gemm_grid_waves;   // msnap_set_option
   if (grid > nrt) grid = nrt;
-#define MSNAP_GRID_CASE(NCV, MM)                                                                       \
-  case MM:                                                                                             \
-    note_kernel(ctx, "msnap::grid_gemm_kernel<%d, %d>", NCV, MM);                                      \
-    hipLaunchKernelGGL((grid_gemm_kernel<NCV, MM>), dim3(grid), dim3(kWave), 0, ctx->stream, wp,       \
-                       (const double *)ctx->grid_frag.p, (const double *)ctx->grid_dur.p,              \
-                       (const int32_t *)ctx->grid_status.p, n_drones, coef, dur, status, nrt);         \
-    break;
-  if (nc == 8) {
-    switch (M) {   // grid_gemm_supported: M <= 15
-      MSNAP_GRID_CASE(8, 1) MSNAP_GRID_CASE(8, 2) MSNAP_GRID_CASE(8, 3) MSNAP_GRID_CASE(8, 4)
-      MSNAP_GRID_CASE(8, 5) MSNAP_GRID_CASE(8, 6) MSNAP_GRID_CASE(8, 7) MSNAP_GRID_CASE(8, 8)
-      MSNAP_GRID_CASE(8, 9) MSNAP_GRID_CASE(8, 10) MSNAP_GRID_CASE(8, 11) MSNAP_GRID_CASE(8, 12)
-      MSNAP_GRID_CASE(8, 13) MSNAP_GRID_CASE(8, 14) MSNAP_GRID_CASE(8, 15)
-      default: return MSNAP_EINVAL;
-    }
-  } else {
-    switch (M) {   // grid_gemm_supported: M <= 12
-      MSNAP_GRID_CASE(10, 1) MSNAP_GRID_CASE(10, 2) MSNAP_GRID_CASE(10, 3) MSNAP_GRID_CASE(10, 4)
-      MSNAP_GRID_CASE(10, 5) MSNAP_GRID_CASE(10, 6) MSNAP_GRID_CASE(10, 7) MSNAP_GRID_CASE(10, 8)
-      MSNAP_GRID_CASE(10, 9) MSNAP_GRID_CASE(10, 10) MSNAP_GRID_CASE(10, 11) MSNAP_GRID_CASE(10, 12)
-      default: return MSNAP_EINVAL;
-    }
-  }
-#undef MSNAP_GRID_CASE
+  auto launch = [&](auto ncv, auto seg) {
+    constexpr int NC = decltype(ncv)::value, MM = decltype(seg)::value;
+    note_kernel(ctx, "msnap::grid_gemm_kernel<%d, %d>", NC, MM);
+    hipLaunchKernelGGL((grid_gemm_kernel<NC, MM>), dim3(grid), dim3(kWave), 0, ctx->stream, wp,
+                       (const double *)ctx->grid_frag.p, (const double *)ctx->grid_dur.p,
+                       (const int32_t *)ctx->grid_status.p, n_drones, coef, dur, status, nrt);
+  };
+  // grid_gemm_reg_supported: M <= 15 at order 7, <= 12 at order 9
+  constexpr std::integral_constant<int, 8> nc8{};
+  constexpr std::integral_constant<int, 10> nc10{};
+  const bool found = nc == 8 ? dispatch_range<1, grid_reg_max_seg(8)>(M, [&](auto seg) { launch(nc8, seg); })
+                             : dispatch_range<1, grid_reg_max_seg(10)>(M, [&](auto seg) { launch(nc10, seg); });
+  if (!found) return MSNAP_EINVAL;
   MSNAP_HIP(ctx, hipGetLastError());
   return MSNAP_OK;
 }

@@ -23,7 +23,7 @@
 // lanes of a drone (no cross-lane traffic, no divergence: every lane runs the
 // same M-step recurrence).  The tile's inputs are staged in LDS by one
 // coalesced sweep.  The variants share the arithmetic (Sweep<K>::knot_geom / chain, recover_segment)
-// and are chosen per launch by launch_solve_k:
+// and are chosen per launch by plan_solve (msnap_solve_plan.h), which launch_solve_k carries out:
 //   solve_kernel_twist<K,H,M>  2 <= n_seg <= 24 (order 7) / 12 (order 9), batch up to one 8-drone
 //                              wavefront per SIMD: two-sided sweep (halves the dependent chain)
 //                              meeting at a shared knot, one straight-line instance per
@@ -37,6 +37,7 @@
 #include <cstdlib>
 
 #include "msnap_internal.h"
+#include "msnap_dispatch.h"
 #include "msnap_sweep.h"
 #include "msnap_rolled.h"
 
@@ -289,16 +290,7 @@ solve_kernel_reg(const double *__restrict__ wp, const double *__restrict__ tt, i
 // registers and ran at 83 us against solve_kernel_reg's 75 and this kernel's 57-60 at 65 536 x 10.)
 // ------------------------------------------------------------------------------------
 
-// Output transposition image of the twin kernel: 5 rows (coefficient pairs) of kTwinTrPitch 16-byte slots.  A lane
-// writes piece p at slot p * pitch + lane (8 contiguous lanes per LDS cycle: conflict-free for any pitch) and reads
-// back, with store q, piece (a2, j2) = ((4q + j) / 5, (4q + j) % 5) of its own block at slot j2 * pitch + 4 * blk + a2.
-// ds_read_b128 serves the lane groups {0-3, 12-15, 20-27}, ... (blocks 0, 3, 5, 6: all residues mod 4) and a slot
-// covers 4 of the 64 banks, so the 16 slots of a group must differ mod 16: with pitch = 1 (mod 16) they are
-// a2 + j2 + 4 * blk, distinct for every q (pitch 68 = 4 (mod 16), the one-sided kernels' choice for their flat
-// read-back order, made 4 of them collide here: SQ_LDS_BANK_CONFLICT 2.0 of 9.9 M LDS cycles per launch).
-constexpr int kTwinTrPitch = 65;
-constexpr int kTwinTrWords = 5 * kTwinTrPitch * 2;   // in doubles
-constexpr int kTwinDrones = 8;
+// (the output transposition image, kTwinTrPitch / kTwinTrWords, and kTwinDrones: msnap_solve_plan.h)
 
 // Output stores of the twin kernel.  The 4 axis lanes of a (drone, side) block hold the block's 320 bytes as
 // 4 x 5 pieces of 16 bytes (lane = axis, piece = coefficient pair).  Through the LDS image the pieces are
@@ -335,14 +327,6 @@ __device__ __forceinline__ void store_twin_coalesced(double2 *sTr, double *__res
   __builtin_amdgcn_wave_barrier();
 }
 
-inline size_t twin_lds_bytes(int khalf, int n_seg) {
-  const size_t h = (size_t)(n_seg - 2) - (size_t)(n_seg - 2) / 2;     // knots of the longer side
-  size_t g_words = h * (size_t)(khalf - 1) * kWave;           // h knots x NU rows x 16 (drone, side) blocks x 4 column slots
-  if (khalf == 4 && n_seg >= 17) g_words += 4 * (size_t)(khalf - 1) * kWave;   // z of the first knots (kTwinZInLds)
-  const size_t in_words = (size_t)kTwinDrones * (n_seg + 1) * 5;
-  const size_t body = (khalf == 5 ? (size_t)kTwinTrWords : 0) + g_words;
-  return (in_words > body ? in_words : body) * sizeof(double);
-}
 // waves per SIMD an instance is built for (registers: 512 / waves per lane)
 // (registers as built: order 7: 81 / 96 / 124 / 148 / 175 / 202 / 233 / 256 at 4 / 6 / ... / 18 segments; order 9:
 //  92 / 123 / 164 / 201 / 242 at 4 / 6 / 8 / 10 / 12)
@@ -750,7 +734,6 @@ solve_kernel_twin(const double *__restrict__ wp, const double *__restrict__ tt, 
 // outwards.  Side 1 obtains forward-time coefficients by recovering each piece with its two
 // end states swapped and the odd derivatives negated (p(t) = q(T - t)).
 // ------------------------------------------------------------------------------------
-constexpr int kTwistDrones = 8;
 constexpr int kTwistFenceHalf = 9;   // instances with this many knots per side fence the scheduler per knot
 
 // T > 0 and finite -- !(T > 0) | !finite64(T) exactly -- as one v_cmp_class_f64: positive normal or positive subnormal
@@ -1124,167 +1107,69 @@ solve_kernel_twist(const double *__restrict__ wp, const double *__restrict__ tt,
   }
 }
 
-constexpr int kTwistMaxSeg = 24;    // twisted variant, order 7: one instance per n_seg in 2..24
-constexpr int kTwistMaxSeg9 = 12;   // order 9: 2..12
+static SolveKnobs solve_knobs(const msnap_ctx *ctx) {
+  return {ctx->n_cu, ctx->no_twist, ctx->no_twin, ctx->twist_max_drones, ctx->twin_max_drones, ctx->twist_waves,
+          ctx->solve_grid_waves};
+}
 
-constexpr int kTwinMaxSeg = 20;    // order 9: solve_kernel_twin for 4..20 segments.  13..20 segments do not fit the 256 registers of two
-                                   // waves per SIMD (290..402 as built) and are instances for ONE wave per SIMD: the compiler keeps the
-                                   // excess in accumulation registers (10..146; no scratch).  Against solve_kernel_reg<5, 20> (also one wave
-                                   // per SIMD): 65 536 x 20: 136-143 against 187 us, 2^20 x 20: 1.80 against 2.32 ms = 54 % against 42 % of
-                                   // the HBM peak, 8192 x 20: 19.6 against 32.1 us (profiles/r04_order9_long.txt); 13 segments tie at 2^20
-constexpr int kTwinMaxSeg7 = 20;   // order 7 (19 and 20 segments: z of the first knots in LDS instead of registers)
-constexpr int kRegMaxSeg = 10;    // n_seg <= 10 takes the register-resident variant (2 waves per SIMD) ...
-constexpr int kRegMaxSeg2 = 20;   // ... 11 <= n_seg <= 20 a second instance at one wave per SIMD
-
+// plan (msnap_solve_plan.h: family, instance, geometry -- and why) -> slab -> name -> launch
 template <int K>
 static int launch_solve_k(msnap_ctx *ctx, int N, int M, const double *wp, const double *t, int shared,
                           double *coef, double *dur, int32_t *status) {
-  const int ntiles = (N + kDronesPerWave - 1) / kDronesPerWave;
-  const size_t tr_bytes = (size_t)K * kTrPitch * 16;   // output transpose image, NC/2 = K rows
-  // up to one 8-drone wavefront per SIMD the two-sided kernel wins (measured crossover 8-10 k drones on 256 CUs)
-  // (order 9 with an even segment count <= 10: the two-sided column-split throughput kernel already wins from one
-  // 8-drone wave per CU on -- 4096 x 10: 9.2 against 11.2 us, 8192 x 10: 11.0 against 16.3 -- the straight-line
-  // latency kernel below that: 1024 x 10: 7.1 against 7.4 us; tools/order_sizes.py)
-  // (order 7, tools/order_sizes.py with PROBE_ORDER=7, 10 segments: 4096 drones 7.4 us against 8.6 (small-batch
-  //  kernel) and 11.0 (solve_kernel_reg); 8192: 8.9 / 12.8 / 12.9; 16 384: 13.4 / - / 16.2; 32 768: 21.6 / - / 22.1;
-  //  65 536: 42.0 / - / 43.4 (eager launches); 2^20: 0.70 ms against 0.634 -- beyond 256 drones per CU the 16-drone
-  //  waves of solve_kernel_reg are ahead.  That holds for its two-waves-per-SIMD instance only: with 11..20 segments
-  //  solve_kernel_reg<4, 20> is one wave per SIMD and the column-split kernel stays ahead at every size -- 262 144 x 20:
-  //  335 against 370 us, 2^20 x 20: 1.357 against 1.407 ms (59 against 57 % of the HBM peak), 2^20 x 14: 0.941 against
-  //  1.020 ms (profiles/r04_order7_long.txt))
-  const bool twin_ok = (M >= 4 && M <= (K == 5 ? kTwinMaxSeg : kTwinMaxSeg7) && !ctx->no_twin &&
-                        (ctx->twin_max_drones > 0 ? N <= ctx->twin_max_drones
-                                                   : (K == 5 || N <= ctx->n_cu * 256 || M > kRegMaxSeg)));
-  const int twist_max = ctx->twist_max_drones > 0 ? ctx->twist_max_drones
-                                                  : ctx->n_cu * (twin_ok ? 1 : 4) * kTwistDrones;
-  if (M >= 2 && M <= (K == 4 ? kTwistMaxSeg : kTwistMaxSeg9) && N <= twist_max && !ctx->no_twist) {
-    // small batch: at most one wavefront per SIMD -- halve the dependent chain instead
-    const int nt8 = (N + kTwistDrones - 1) / kTwistDrones;
-    const int nR = (M - 2) - (M - 2) / 2;
-    // waves per tile (msnap_set_option admits 0, 1, 2 and 4 only).  Measured on 256 CUs, us per step, one / two /
-    // four waves (profiles/r05_twist_waves.txt): 256 x 10 (32 tiles) 4.41 / 4.31 / 4.30, 300 x 20 (38) 7.67 / 7.21 /
-    // 7.08, order 9 256 x 10 6.03 / 5.78 / 5.82 -- but 1024 x 24 (128 tiles) 9.85 / 9.59 / 9.85 and 2048 x 10 (256
-    // tiles) 5.71 / 5.89 / 6.06: four waves up to a quarter of the CUs' count in tiles, two up to half, one above
-    const int nw = ctx->twist_waves > 0 ? ctx->twist_waves : nt8 * 4 <= ctx->n_cu ? 4 : nt8 * 2 <= ctx->n_cu ? 2 : 1;
-    // inputs + z stash per wave (64 lanes x NU per knot; used by the long-path instances only, 4 x 16.5 KiB at M = 24)
-    const size_t lds_bytes = ((size_t)kTwistDrones * (M + 1) * 5 + (size_t)nw * 64 * (K - 1) * nR) * sizeof(double);
-    // grid == tile count: one workgroup of nw waves per 8-drone tile (the kernel has no tile loop and no tile guard,
-    // and no tile-count argument either: its seven arguments are exactly the 12 dwords the build preloads into SGPRs)
-#define MSNAP_TWIST_NW(MM, NWV)                                                                                    \
-  hipLaunchKernelGGL((solve_kernel_twist<K, (MM - 2) - (MM - 2) / 2, MM, NWV>), dim3(nt8), dim3(kWave * NWV),      \
-                     lds_bytes, ctx->stream, wp, t, shared, N, coef, dur, status)
-#define MSNAP_TWIST_EXACT(MM)                                                                          \
-  case MM:                                                                                             \
-    note_kernel(ctx, "msnap::solve_kernel_twist<%d, %d, %d>", K, (MM - 2) - (MM - 2) / 2, MM);         \
-    if (nw == 4) MSNAP_TWIST_NW(MM, 4);                                                                \
-    else if (nw == 2) MSNAP_TWIST_NW(MM, 2);                                                           \
-    else MSNAP_TWIST_NW(MM, 1);                                                                        \
-    break;
-    if constexpr (K == 4) {
-      switch (M) {   // 2 <= M <= kTwistMaxSeg
-        MSNAP_TWIST_EXACT(2) MSNAP_TWIST_EXACT(3) MSNAP_TWIST_EXACT(4) MSNAP_TWIST_EXACT(5)
-        MSNAP_TWIST_EXACT(6) MSNAP_TWIST_EXACT(7) MSNAP_TWIST_EXACT(8) MSNAP_TWIST_EXACT(9)
-        MSNAP_TWIST_EXACT(10) MSNAP_TWIST_EXACT(11) MSNAP_TWIST_EXACT(12) MSNAP_TWIST_EXACT(13)
-        MSNAP_TWIST_EXACT(14) MSNAP_TWIST_EXACT(15) MSNAP_TWIST_EXACT(16) MSNAP_TWIST_EXACT(17)
-        MSNAP_TWIST_EXACT(18) MSNAP_TWIST_EXACT(19) MSNAP_TWIST_EXACT(20) MSNAP_TWIST_EXACT(21)
-        MSNAP_TWIST_EXACT(22) MSNAP_TWIST_EXACT(23) MSNAP_TWIST_EXACT(24)
-        default: return MSNAP_EINVAL;   // unreachable: the range is checked above
-      }
-    } else {
-      switch (M) {   // 2 <= M <= kTwistMaxSeg9
-        MSNAP_TWIST_EXACT(2) MSNAP_TWIST_EXACT(3) MSNAP_TWIST_EXACT(4) MSNAP_TWIST_EXACT(5)
-        MSNAP_TWIST_EXACT(6) MSNAP_TWIST_EXACT(7) MSNAP_TWIST_EXACT(8) MSNAP_TWIST_EXACT(9)
-        MSNAP_TWIST_EXACT(10) MSNAP_TWIST_EXACT(11) MSNAP_TWIST_EXACT(12)
-        default: return MSNAP_EINVAL;
-      }
-    }
-#undef MSNAP_TWIST_EXACT
-#undef MSNAP_TWIST_NW
-    MSNAP_HIP(ctx, hipGetLastError());
-    return MSNAP_OK;
-  }
-  if (twin_ok) {
-    // large batch, even segment count: two-sided column-split kernel
-    const int nt8 = (N + kTwinDrones - 1) / kTwinDrones;
-    int grid = ctx->n_cu * 8 * 8;
-    if (ctx->solve_grid_waves > 0) grid = ctx->solve_grid_waves;
-    if (grid > nt8) grid = nt8;
-#define MSNAP_TWIN(MM)                                                                                            \
-  case MM:                                                                                                        \
-    note_kernel(ctx, "msnap::solve_kernel_twin<%d, %d>", K, MM);                                                  \
-    hipLaunchKernelGGL((solve_kernel_twin<K, MM>), dim3(grid), dim3(kWave), twin_lds_bytes(K, MM), ctx->stream,   \
-                       wp, t, shared, N, coef, dur, status, nt8);                                                 \
-    break;
-    if constexpr (K == 5) {
-      switch (M) {
-        MSNAP_TWIN(4) MSNAP_TWIN(5) MSNAP_TWIN(6) MSNAP_TWIN(7) MSNAP_TWIN(8) MSNAP_TWIN(9) MSNAP_TWIN(10)
-        MSNAP_TWIN(11) MSNAP_TWIN(12) MSNAP_TWIN(13) MSNAP_TWIN(14) MSNAP_TWIN(15) MSNAP_TWIN(16) MSNAP_TWIN(17)
-        MSNAP_TWIN(18) MSNAP_TWIN(19) MSNAP_TWIN(20)
-        default: return MSNAP_EINVAL;   // unreachable: the range is checked above
-      }
-    } else {
-      switch (M) {
-        MSNAP_TWIN(4) MSNAP_TWIN(5) MSNAP_TWIN(6) MSNAP_TWIN(7) MSNAP_TWIN(8) MSNAP_TWIN(9) MSNAP_TWIN(10)
-        MSNAP_TWIN(11) MSNAP_TWIN(12) MSNAP_TWIN(13) MSNAP_TWIN(14) MSNAP_TWIN(15) MSNAP_TWIN(16) MSNAP_TWIN(17)
-        MSNAP_TWIN(18) MSNAP_TWIN(19) MSNAP_TWIN(20)
-        default: return MSNAP_EINVAL;
-      }
-    }
-#undef MSNAP_TWIN
-    MSNAP_HIP(ctx, hipGetLastError());
-    return MSNAP_OK;
-  }
-  if (M >= 2 && M <= kRegMaxSeg2) {   // (one segment: the rolled kernel below)
-    const size_t nu = K - 1;
-    const size_t in_bytes = solve_input_words(M) * sizeof(double);
-    const size_t lds_bytes = (in_bytes > tr_bytes ? in_bytes : tr_bytes) +
-                             16 * nu * nu * (size_t)(M > 2 ? M - 2 : 0) * sizeof(double);
-    // persistent waves (all resident at once) so that tile k+1's inputs can be prefetched during tile k
-    const bool two_per_simd = (K <= 4 && M <= kRegMaxSeg);
-    // Waves beyond the resident set (8 or 4 per CU) are started by the hardware as others retire, which
-    // staggers the tiles' load / compute / store phases across the chip: 8x the resident set everywhere
-    // (2^19..2^20 drones, order 7 M <= 10: 0.681 -> 0.647 ms, 4 tiles per wave still leave the cross-tile
-    // prefetch its work; order 9 M > 10: 1.96 -> 1.55 ms; 65 536 drones, tools/reg_grid_probe.py: order 9
-    // M <= 10 73.5 -> 71 us, order 7 M > 10 106 -> 101 us; the saturated launches of those two do not care).
-    int grid = ctx->n_cu * (two_per_simd ? 8 : 4) * 8;
-    if (ctx->solve_grid_waves > 0) grid = ctx->solve_grid_waves;   // msnap_set_option: tests walk several tiles per wave
-    if (grid > ntiles) grid = ntiles;
-    note_kernel(ctx, "msnap::solve_kernel_reg<%d, %d>", K, M <= kRegMaxSeg ? kRegMaxSeg : kRegMaxSeg2);
-    if (M <= kRegMaxSeg)
-      hipLaunchKernelGGL((solve_kernel_reg<K, kRegMaxSeg>), dim3(grid), dim3(kWave), lds_bytes, ctx->stream,
-                         wp, t, shared, N, M, coef, dur, status, ntiles);
-    else
-      hipLaunchKernelGGL((solve_kernel_reg<K, kRegMaxSeg2>), dim3(grid), dim3(kWave), lds_bytes, ctx->stream,
-                         wp, t, shared, N, M, coef, dur, status, ntiles);
-    MSNAP_HIP(ctx, hipGetLastError());
-    return MSNAP_OK;
-  }
-  const size_t words = solve_scratch_words(K, M);
-  const size_t lds_bytes = tr_bytes + (words + solve_input_words(M)) * sizeof(double);
-  const size_t bytes = words * sizeof(double);
-  note_kernel(ctx, "msnap::solve_kernel<%d, %s>", K, lds_bytes <= kMaxLdsBytes ? "false" : "true");
-  if (lds_bytes <= kMaxLdsBytes) {
-    hipLaunchKernelGGL((solve_kernel<K, false>), dim3(ntiles), dim3(kWave), lds_bytes, ctx->stream, wp, t,
-                       shared, N, M, coef, dur, status, (double *)nullptr, ntiles);
-  } else {
-    // too many segments for LDS: same recurrence on a global scratch slab,
-    // persistent grid so the slab stays bounded
-    int grid = ctx->n_cu * 8;
-    if (grid > ntiles) grid = ntiles;
-    int rc = ensure(ctx, ctx->scratch, (size_t)grid * bytes);
+  const SolvePlan p = plan_solve(solve_knobs(ctx), K, N, M);
+  if (p.slab_bytes > 0) {
+    int rc = ensure(ctx, ctx->scratch, p.slab_bytes);
     if (rc) return rc;
-    hipLaunchKernelGGL((solve_kernel<K, true>), dim3(grid), dim3(kWave), tr_bytes, ctx->stream, wp, t,
-                       shared, N, M, coef, dur, status, (double *)ctx->scratch.p, ntiles);
   }
+  solve_plan_name(p, ctx->last_kernel, sizeof(ctx->last_kernel));   // (note_kernel's one formatting per launch)
+  const dim3 grid(p.grid), block(p.block);
+  bool found = true;
+  switch (p.family) {
+    case SolveFamily::twist:
+      // grid == tile count, and no tile-count argument: the kernel's seven arguments are exactly the 12 dwords the
+      // build preloads into SGPRs
+      found = dispatch_range<2, twist_max_seg(K)>(M, [&](auto seg) {
+        constexpr int MM = decltype(seg)::value;
+        auto launch = [&](auto waves) {
+          hipLaunchKernelGGL((solve_kernel_twist<K, twist_half(MM), MM, decltype(waves)::value>), grid, block,
+                             p.lds_bytes, ctx->stream, wp, t, shared, N, coef, dur, status);
+        };
+        if (p.waves == 4) launch(std::integral_constant<int, 4>{});
+        else if (p.waves == 2) launch(std::integral_constant<int, 2>{});
+        else launch(std::integral_constant<int, 1>{});
+      });
+      break;
+    case SolveFamily::twin:
+      found = dispatch_range<kTwinMinSeg, twin_max_seg(K)>(M, [&](auto seg) {
+        hipLaunchKernelGGL((solve_kernel_twin<K, decltype(seg)::value>), grid, block, p.lds_bytes, ctx->stream, wp, t,
+                           shared, N, coef, dur, status, p.tiles);
+      });
+      break;
+    case SolveFamily::reg:
+      if (p.seg == kRegMaxSeg)
+        hipLaunchKernelGGL((solve_kernel_reg<K, kRegMaxSeg>), grid, block, p.lds_bytes, ctx->stream, wp, t, shared, N, M,
+                           coef, dur, status, p.tiles);
+      else
+        hipLaunchKernelGGL((solve_kernel_reg<K, kRegMaxSeg2>), grid, block, p.lds_bytes, ctx->stream, wp, t, shared, N, M,
+                           coef, dur, status, p.tiles);
+      break;
+    case SolveFamily::rolled:
+      if (p.slab_bytes > 0)
+        hipLaunchKernelGGL((solve_kernel<K, true>), grid, block, p.lds_bytes, ctx->stream, wp, t, shared, N, M, coef, dur,
+                           status, (double *)ctx->scratch.p, p.tiles);
+      else
+        hipLaunchKernelGGL((solve_kernel<K, false>), grid, block, p.lds_bytes, ctx->stream, wp, t, shared, N, M, coef,
+                           dur, status, (double *)nullptr, p.tiles);
+      break;
+  }
+  if (!found) return MSNAP_EINVAL;   // unreachable: the plan's ranges are the dispatch's bounds
   MSNAP_HIP(ctx, hipGetLastError());
   return MSNAP_OK;
 }
 
+// one drone's plan: the slab does not depend on the batch size (msnap_solve_plan.h)
 bool solve_uses_global_scratch(const msnap_ctx *ctx, int n_seg) {
-  if (n_seg <= kRegMaxSeg2) return false;
-  const size_t tr_bytes = (size_t)ctx->khalf * kTrPitch * 16;
-  return tr_bytes + (solve_scratch_words(ctx->khalf, n_seg) + solve_input_words(n_seg)) * sizeof(double) >
-         kMaxLdsBytes;
+  return plan_solve(solve_knobs(ctx), ctx->khalf, 1, n_seg).slab_bytes > 0;
 }
 
 #ifdef MSNAP_TOOLS_TIMELINE

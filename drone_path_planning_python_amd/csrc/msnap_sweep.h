@@ -5,6 +5,7 @@
 
 #include "msnap_consts.h"
 #include "msnap_internal.h"
+#include "msnap_solve_plan.h"   // kTrPitch
 #include "msnap_energy.h"
 #include "msnap_wave.h"
 
@@ -255,8 +256,7 @@ __device__ __forceinline__ void taylor_shift(double (&c)[NC], double h) {
 // ds_read_b128 conflict-free for NC = 8) and leave as 16-B-per-lane stores that
 // are contiguous over each drone's 4*NC*8-byte block (256 B = two full lines).
 // LDS is in-order within a wave; the wavefront-scope fences only pin the
-// compiler's ordering (no vmcnt wait: output stores stay in flight).
-constexpr int kTrPitch = 68;
+// compiler's ordering (no vmcnt wait: output stores stay in flight).  (kTrPitch = 68: msnap_solve_plan.h)
 #define MSNAP_SEG_BASE(coef, tile, M, i, NC) ((coef) + ((size_t)(tile) * kDronesPerWave * (M) + (i)) * (4 * (NC)))
 #define MSNAP_SEG_STRIDE(M, NC) ((size_t)(M) * 4 * (NC))
 template <int NC>

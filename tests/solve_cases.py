@@ -1,8 +1,9 @@
-"""The table of K1 solve instances (msnap_solve.hip, launch_solve_k) that tests/test_solve_exact_gpu.py holds to the
+"""The table of K1 solve instances (csrc/msnap_solve_plan.h, plan_solve) that tests/test_solve_exact_gpu.py holds to the
 60-digit solutions of tests/solve_exact.py: one entry per kernel instance a small batch can reach, with the options
 that reach it and the msnap_last_kernel string it must report; the inputs every family of one (order, segment count)
-shares; the project's accuracy bars; the solve into sentinel-filled outputs.  tests/test_solve_exact_cpu.py holds the
-table to the launcher's own ranges without a GPU."""
+shares; the project's accuracy bars; the solve into sentinel-filled outputs.  The table is static (the GPU tests need no
+compiler); tests/test_solve_exact_cpu.py holds it, the restated ranges and formulas below included, to the launcher's
+executed decision without a GPU."""
 from collections import namedtuple
 
 import numpy as np
@@ -18,7 +19,7 @@ STRESS_TOL = {7: 1e-9, 9: 2e-8}    # tools/solve_stress.py's draw (durations U(0
 STRESS_MAX_SEG = {7: 24, 9: 20}
 
 # ---------------------------------------------------------------------------
-# the launcher's ranges (tests/test_solve_exact_cpu.py reads the same names out of msnap_solve.hip)
+# the launcher's ranges (tests/test_solve_exact_cpu.py holds them to what plan_solve sends where)
 # ---------------------------------------------------------------------------
 TWIST_SEG = {7: range(2, 25), 9: range(2, 13)}        # solve_kernel_twist<K, ., M, 1 | 2 | 4>: 2..kTwistMaxSeg[9]
 TWIN_SEG = {7: range(4, 21), 9: range(4, 21)}         # solve_kernel_twin<K, M>: 4..kTwinMaxSeg7 / kTwinMaxSeg
@@ -42,7 +43,7 @@ def khalf(order):
 
 
 def scratch_bytes(order, M, tr_pitch=68):
-    """launch_solve_k's dynamic LDS for solve_kernel<K, false>: transpose image + stash + input stage"""
+    """rolled_lds_bytes: the dynamic LDS of solve_kernel<K, false>, transpose image + stash + input stage"""
     K = khalf(order)
     nu = K - 1
     words = 16 * M + 16 * nu * nu * max(M - 1, 0) + 64 * nu * max(M - 1, 0)

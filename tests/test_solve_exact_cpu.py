@@ -1,12 +1,16 @@
 """tests/solve_exact.py (the 60-digit K1 reference with the start-row quirk) against everything that already pins the
 solve -- states_exact, the order-9 fixture, the reference's own outputs, the dense fp64 oracle -- and
-tests/solve_cases.py (the table of kernel instances) against the launcher's ranges in msnap_solve.hip.  No GPU.
+tests/solve_cases.py (the table of kernel instances) against the launcher's decision, executed on the host
+(csrc/msnap_solve_plan.h through tests/c_abi/solve_plan_dump.cpp).  No GPU.
 
 The 1e-11 bars are bars on the DENSE fp64 REFERENCE (a pivoted LU of the collocation system), not on a kernel: ten
 times the worst 1.0e-12 measured for it against 60 digits on the draw of tools/solve_stress.py (order 9, 10 segments;
 order 7 stays below 1e-13)."""
 import os
 import re
+import shutil
+import subprocess
+from collections import namedtuple
 
 import numpy as np
 import pytest
@@ -126,57 +130,144 @@ def test_dense_oracle_on_the_gpu_tests_grids(order, M, grid):
 
 
 # ---------------------------------------------------------------------------
-# the table against the launcher
+# the table against the launcher: its decision (csrc/msnap_solve_plan.h, plan_solve) is EXECUTED on the host by
+# tests/c_abi/solve_plan_dump.cpp -- for 256 CUs, over orders x drones x segments x option sets
 # ---------------------------------------------------------------------------
-def _consts():
-    csrc = os.path.join(ROOT, "drone_path_planning_python_amd", "csrc")
-    text = "".join(open(os.path.join(csrc, f)).read() for f in ("msnap_solve.hip", "msnap_sweep.h", "msnap_internal.h"))
-    out = {}
-    for name in ("kTwistMaxSeg", "kTwistMaxSeg9", "kTwinMaxSeg", "kTwinMaxSeg7", "kRegMaxSeg", "kRegMaxSeg2", "kTrPitch"):
-        m = re.findall(r"constexpr\s+int\s+%s\s*=\s*(\d+)\s*;" % name, text)
-        assert len(m) == 1, name
-        out[name] = int(m[0])
-    m = re.findall(r"constexpr\s+size_t\s+kMaxLdsBytes\s*=\s*(\d+)\s*\*\s*1024\s*;", text)
-    assert len(m) == 1
-    out["kMaxLdsBytes"] = int(m[0]) * 1024
-    return out, text
+CSRC = os.path.join(ROOT, "drone_path_planning_python_amd", "csrc")
+LLVM = "/opt/rocm/lib/llvm/bin"
+PlanRow = namedtuple("PlanRow", "order n m opts n_cu family name instance waves tiles grid block lds slab")
+PLAN_DRONES = (1, 3, 7, 8, 9, 16, 17, 255, 256, 257, 2048, 2049, 8192, 8193, 65536, 65537, 1048576)
+PLAN_OPTS = ("", "no_twist", "no_twist,no_twin", "twist_waves=1", "twist_waves=2", "twist_waves=4", "twist_max_drones=1",
+             "twist_max_drones=4096", "twin_max_drones=1", "twin_max_drones=1048576", "solve_grid_waves=1",
+             "solve_grid_waves=3", "no_twist,solve_grid_waves=3", "no_twist,no_twin,solve_grid_waves=3")
 
 
-def test_table_covers_exactly_the_launchers_ranges():
-    k, text = _consts()
+@pytest.fixture(scope="module")
+def plan(tmp_path_factory):
+    """(order, drones, segments, option set) -> PlanRow, and the constants of the dump's first line under "consts" """
+    gxx = shutil.which("g++")
+    if not gxx:
+        pytest.skip("no g++ here")
+    exe = str(tmp_path_factory.mktemp("solve_plan") / "solve_plan_dump")
+    subprocess.run([gxx, "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I", CSRC,
+                    os.path.join(ROOT, "tests", "c_abi", "solve_plan_dump.cpp"), "-o", exe], check=True, capture_output=True)
+    lines = subprocess.run([exe, "256"], check=True, capture_output=True, text=True).stdout.splitlines()
+    head = lines[0].split("\t")
+    assert head[0] == "consts"
+    out = {"consts": {k: int(v) for k, v in (f.split("=") for f in head[1:])}}
+    for ln in lines[1:]:
+        f = ln.split("\t")
+        assert len(f) == len(PlanRow._fields), ln
+        r = PlanRow(int(f[0]), int(f[1]), int(f[2]), f[3], int(f[4]), f[5], f[6], f[7], *map(int, f[8:]))
+        assert (r.order, r.n, r.m, r.opts) not in out
+        out[(r.order, r.n, r.m, r.opts)] = r
+    # the sweep the tests below rely on: every option set up to 64 segments, the default ones up to 200
+    assert len(out) - 1 == 2 * len(PLAN_DRONES) * (len(PLAN_OPTS) * 64 + 136)
+    assert all((o, n, 64, s) in out for o in (7, 9) for n in PLAN_DRONES for s in PLAN_OPTS)
+    return out
+
+
+def _labels(c):
+    """the option sets of the dump under which the GPU test runs a case"""
+    return ["", "twist_waves=1", "twist_waves=2", "twist_waves=4"] if c.family == "twist" else [",".join(c.opts)]
+
+
+def test_table_covers_exactly_the_launchers_ranges(plan):
     seg = lambda fam, order: sorted(c.M for c in SC.CASES if c.family == fam and c.order == order and not c.shared)  # noqa: E731
-    assert seg("twist", 7) == list(range(2, k["kTwistMaxSeg"] + 1))
-    assert seg("twist", 9) == list(range(2, k["kTwistMaxSeg9"] + 1))
-    assert seg("twin", 7) == list(range(4, k["kTwinMaxSeg7"] + 1))
-    assert seg("twin", 9) == list(range(4, k["kTwinMaxSeg"] + 1))
     for order in (7, 9):
-        assert seg("reg", order) == list(range(2, k["kRegMaxSeg2"] + 1))
+        for fam in ("twist", "twin", "reg"):
+            cases = [c for c in SC.CASES if c.family == fam and c.order == order]
+            assert len({(c.opts, c.n) for c in cases}) == 1
+            for label in _labels(cases[0]):
+                sent = [M for M in range(1, 65) if plan[(order, cases[0].n, M, label)].family == fam]
+                assert seg(fam, order) == sent, (fam, order, label)
+        assert seg("twist", order) == list(SC.TWIST_SEG[order]) and seg("twin", order) == list(SC.TWIN_SEG[order])
+        assert seg("reg", order) == list(SC.REG_SEG[order])
+        # the <K, 10> / <K, 20> split of the reg family falls at kRegMaxSeg
+        assert SC.REG_SPLIT == plan["consts"]["kRegMaxSeg"]
+        K = SC.khalf(order)
         for c in SC.CASES:
             if c.family == "reg" and c.order == order:
-                assert c.kernel.endswith(", %d>" % (k["kRegMaxSeg"] if c.M <= k["kRegMaxSeg"] else k["kRegMaxSeg2"]))
+                want = "msnap::solve_kernel_reg<%d, %d>" % (K, SC.REG_SPLIT if c.M <= SC.REG_SPLIT else SC.REG_SEG[order][-1])
+                assert plan[(order, c.n, c.M, ",".join(c.opts))].name == want == c.kernel
+        # the rolled kernel: one segment, and everything behind the reg family's range
         assert seg("generic", order) == list(SC.GENERIC_SEG[order])
-        assert seg("generic", order)[0] == 1 and seg("generic", order)[1] == k["kRegMaxSeg2"] + 1
-    # the launcher's switches hold one case label per instance of the table, and no other
-    assert len(re.findall(r"MSNAP_TWIST_EXACT\((\d+)\)", text)) == len(seg("twist", 7)) + len(seg("twist", 9))
-    assert len(re.findall(r"MSNAP_TWIN\((\d+)\)", text)) == len(seg("twin", 7)) + len(seg("twin", 9))
-    # the twin lower bound and the twist lower bound as the launcher states them
-    assert re.search(r"M >= 4 && M <= \(K == 5 \? kTwinMaxSeg : kTwinMaxSeg7\)", text)
-    assert re.search(r"M >= 2 && M <= \(K == 4 \? kTwistMaxSeg : kTwistMaxSeg9\)", text)
-    assert re.search(r"if \(M >= 2 && M <= kRegMaxSeg2\)", text)
-
-
-def test_global_scratch_threshold_is_the_tables():
-    k, _ = _consts()
-    for order in (7, 9):
-        gs = [M for M in range(k["kRegMaxSeg2"] + 1, 200)
-              if SC.scratch_bytes(order, M, k["kTrPitch"]) > k["kMaxLdsBytes"]]
-        assert gs[0] == SC.GS_MIN_SEG[order] and gs == list(range(gs[0], 200))
+        rolled = [M for M in range(1, 65) if plan[(order, SC.N_DRONES, M, "no_twist,no_twin")].family == "rolled"]
+        assert rolled == [1] + list(range(SC.REG_SEG[order][-1] + 1, 65))
+        assert seg("generic", order)[0] == 1 and seg("generic", order)[1] == rolled[1]
         for c in SC.CASES:
             if c.order == order and c.family in ("generic", "generic-GS"):
-                assert c.kernel == SC.generic_name(order, c.M, k["kMaxLdsBytes"])
-                assert c.kernel.endswith("true>") == (c.M >= SC.GS_MIN_SEG[order])
+                assert plan[(order, c.n, c.M, ",".join(c.opts))].family == "rolled"
+
+
+def test_every_case_reports_the_plans_kernel_name(plan):
+    for c in SC.CASES:
+        for label in _labels(c):
+            r = plan[(c.order, c.n, c.M, label)]
+            assert r.name == c.kernel, (SC.case_id(c), label)
+            assert r.family == {"generic": "rolled", "generic-GS": "rolled"}.get(c.family, c.family)
+            if label.startswith("twist_waves="):      # the wave count the GPU test asks for is the instance's
+                w = int(label.split("=")[1])
+                assert r.waves == w and r.instance == c.kernel[len("msnap::"):-1] + ", %d>" % w
+            elif c.family != "twist":
+                assert r.instance == c.kernel[len("msnap::"):]
+
+
+def test_global_scratch_threshold_is_the_tables(plan):
+    for order in (7, 9):
+        for n in PLAN_DRONES:
+            gs = [M for M in range(1, 201) if plan[(order, n, M, "")].slab > 0]
+            assert gs[0] == SC.GS_MIN_SEG[order] and gs == list(range(gs[0], 201)), (order, n)
+        for label in PLAN_OPTS:      # no other option set moves a slab below 65 segments either
+            for n in PLAN_DRONES:
+                assert [M for M in range(1, 65) if plan[(order, n, M, label)].slab > 0] == \
+                    list(range(SC.GS_MIN_SEG[order], 65))
+        for c in SC.CASES:
+            if c.order == order and c.family in ("generic", "generic-GS"):
+                r = plan[(order, c.n, c.M, ",".join(c.opts))]
+                assert c.kernel == SC.generic_name(order, c.M, plan["consts"]["kMaxLdsBytes"]) == r.name
+                assert c.kernel.endswith("true>") == (c.M >= SC.GS_MIN_SEG[order]) == (r.slab > 0)
         gsc = [c for c in SC.CASES if c.order == order and c.family == "generic-GS"]
         assert len(gsc) == 1 and gsc[0].M == SC.GS_MIN_SEG[order] and gsc[0].n == SC.N_DRONES_GS
+
+
+def test_plan_geometry_on_every_line(plan):
+    c = plan["consts"]
+    for key, r in plan.items():
+        if key == "consts":
+            continue
+        assert 0 <= r.lds <= c["kMaxLdsBytes"], r
+        assert 1 <= r.grid <= r.tiles, r
+        assert r.block == c["kWave"] * r.waves and r.waves in (1, 2, 4), r
+        assert r.tiles == -(-r.n // (8 if r.family in ("twist", "twin") else 16)), r
+        assert (r.slab > 0) == r.name.endswith("true>"), r
+        if r.family == "twist":
+            # one workgroup per 8-drone tile under every solve_grid_waves / twist_max_drones setting: the kernel has no
+            # tile loop (tests/test_twist_waves_gpu.py checks the same on the GPU)
+            assert r.grid == -(-r.n // 8), r
+        else:
+            assert r.waves == 1, r
+    twist = {r.opts for k, r in plan.items() if k != "consts" and r.family == "twist"}
+    assert {"", "solve_grid_waves=1", "solve_grid_waves=3", "twist_max_drones=1", "twist_max_drones=4096"} <= twist
+
+
+def test_code_object_holds_exactly_the_instances_the_plan_names(plan, tmp_path):
+    """The set of solve kernels in msnap_solve.o's gfx950 code object is what the plan can name over both orders, 1..64
+    segments, the dump's batch sizes and option sets (wave counts 1, 2 and 4 among them): no instance the launcher
+    cannot reach, none it would miss."""
+    obj = os.path.join(CSRC, "msnap_solve.o")
+    tools = [os.path.join(LLVM, t) for t in ("llvm-objcopy", "clang-offload-bundler", "llvm-readelf")]
+    if not os.path.exists(obj) or not all(os.path.exists(t) for t in tools):
+        pytest.skip("no object file / ROCm LLVM tools here")
+    fat, co = str(tmp_path / "fat"), str(tmp_path / "co")
+    subprocess.run([tools[0], "--dump-section=.hip_fatbin=" + fat, obj, str(tmp_path / "copy.o")], check=True)
+    subprocess.run([tools[1], "--unbundle", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--input=" + fat,
+                    "--output=" + co], check=True)
+    syms = subprocess.run([tools[2], "--symbols", "--demangle", co], check=True, capture_output=True, text=True).stdout
+    built = set(re.findall(r"\bFUNC\b.*\bvoid msnap::(solve_kernel(?:_twist|_twin|_reg)?<[^>]*>)\(", syms))
+    named = {r.instance for k, r in plan.items() if k != "consts" and r.m <= 64}
+    assert built == named, (sorted(built - named), sorted(named - built))
+    assert len(built) == sum(3 * len(SC.TWIST_SEG[o]) + len(SC.TWIN_SEG[o]) + 2 + 2 for o in (7, 9)) == 144
 
 
 def test_table_shape():
