@@ -158,11 +158,14 @@ int launch_eval_flat(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef
                      int n_samples, const double *ts, double *out);
 int launch_snap_cost(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur, double *cost);
 int launch_snap_cost_grad(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, double *grad);
-// time allocation (msnap_timeopt.hip): the whole iteration of a batch in one launch; cost, pg, iters may be null
+// time allocation (msnap_timeopt.hip): the whole iteration of a batch in one launch; cost, pg, iters may be null.
+// ends: from and to given end states (start / end: [n_drones][4][K-1] on the device, or null for rest)
 int launch_optimize_times(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, const double *t, int shared_times,
-                          const double *weights, double min_fraction, int max_iter, double tol, double *t_out,
-                          double *coef, double *dur, int32_t *status, double *cost, double *pg, int32_t *iters);
-int timeopt_max_segments(int khalf);   // largest n_seg whose per-tile state fits LDS (80 at order 7, 58 at order 9)
+                          bool ends, const double *start, const double *end, const double *weights,
+                          double min_fraction, int max_iter, double tol, double *t_out, double *coef, double *dur,
+                          int32_t *status, double *cost, double *pg, int32_t *iters);
+// largest n_seg whose per-tile state fits LDS (80 at order 7, 58 at order 9; with ends: see DESIGN.md K8)
+int timeopt_max_segments(int khalf, bool ends);
 // (the pairwise pass: msnap_collide.h)
 int launch_mesh_sweep(msnap_ctx *ctx, int n_drones, int n_samples, const double *pos, int n_tris,
                       const double *tris, double radius, double *min_dist, int32_t *hit);

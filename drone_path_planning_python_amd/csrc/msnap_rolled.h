@@ -20,6 +20,30 @@ struct RolledTile {
   double *sS0, *sS1;
 };
 
+// one coalesced pass over a tile's state block ([nvalid][4][NU], contiguous) into its LDS image [64][pitch]
+// (shared by states_solve_kernel and timeopt_kernel<K, true>, which passes its own tile's block and tile = 0)
+template <int NU, int PITCH>
+__device__ __forceinline__ void load_states(const double *__restrict__ src, int tile, int nvalid, int lane,
+                                            double (&v)[NU]) {
+  const double *s = src + (size_t)tile * kWave * NU;
+  const int cnt = nvalid * 4 * NU;
+#pragma unroll
+  for (int q = 0; q < NU; ++q) {
+    const int e = q * kWave + lane;
+    v[q] = s[e < cnt ? e : cnt - 1];
+  }
+}
+template <int NU, int PITCH>
+__device__ __forceinline__ void store_states(double *sS, int nvalid, int lane, const double (&v)[NU]) {
+  const int cnt = nvalid * 4 * NU;
+#pragma unroll
+  for (int q = 0; q < NU; ++q) {
+    const int e = q * kWave + lane;
+    const int l = e / NU;
+    if (e < cnt) sS[l * PITCH + (e - l * NU)] = v[q];
+  }
+}
+
 // One step of iterative refinement of the LAST segment's end conditions.  recover_segment's upper coefficients are
 // cancelling sums (constants of 10^2 .. 10^3) computed with 1/T rounded, so the polynomial it returns has the given
 // end state only to the accuracy of its coefficients.  Here the end values are evaluated with msnap_eval_state's own

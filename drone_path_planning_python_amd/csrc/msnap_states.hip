@@ -55,29 +55,6 @@ struct StatesLayout {
 static_assert(StatesLayout<4>::max_segments() == 47 && StatesLayout<5>::max_segments() == 32,
               "DESIGN.md K13 and include/msnap.h quote these");
 
-// one coalesced pass over a tile's state block ([nvalid][4][NU], contiguous) into its LDS image [64][pitch]
-template <int NU, int PITCH>
-__device__ __forceinline__ void load_states(const double *__restrict__ src, int tile, int nvalid, int lane,
-                                            double (&v)[NU]) {
-  const double *s = src + (size_t)tile * kWave * NU;
-  const int cnt = nvalid * 4 * NU;
-#pragma unroll
-  for (int q = 0; q < NU; ++q) {
-    const int e = q * kWave + lane;
-    v[q] = s[e < cnt ? e : cnt - 1];
-  }
-}
-template <int NU, int PITCH>
-__device__ __forceinline__ void store_states(double *sS, int nvalid, int lane, const double (&v)[NU]) {
-  const int cnt = nvalid * 4 * NU;
-#pragma unroll
-  for (int q = 0; q < NU; ++q) {
-    const int e = q * kWave + lane;
-    const int l = e / NU;
-    if (e < cnt) sS[l * PITCH + (e - l * NU)] = v[q];
-  }
-}
-
 template <int K>
 __global__ void __launch_bounds__(kWave)
 states_solve_kernel(const double *__restrict__ wp, const double *__restrict__ tt, int shared_times,

@@ -17,12 +17,19 @@
 // to make (__ballot), every lane runs its body, and what a finished drone would change is held back by selects -- no
 // loop the lanes leave one by one.  Cost and gradient are combined over the quad with quad_bcast in
 // the fixed order ((x + y) + z) + yaw, so the four lanes hold the same bits and take the same decisions.
+//
+// Given end states (msnap_optimize_times_states): timeopt_kernel<K, true>.  The end knots' derivative vectors are data
+// as in the boundary-state solve (msnap_rolled.h, ENDS); the gradient is the same expression -- the first and last
+// segment's outer end states are fixed either way.  What differs from the rest-to-rest instance is one `if constexpr`
+// each: the state images in LDS, their finiteness check, the seed of the sweep's carried term, the backward sweep from
+// u_M through the last knot's G, segment 0 from u_0, and refine_end on the last segment when the coefficients leave.
 #include <math.h>
 
 #include <type_traits>
 
 #include "msnap_api_util.h"
 #include "msnap_internal.h"
+#include "msnap_rolled.h"
 #include "msnap_sweep.h"
 
 namespace msnap {
@@ -43,6 +50,10 @@ struct TimeoptArgs {
   double *cost, *pg;
   int32_t *iters;
 };
+// ENDS: the tile's end states, [n_drones][4][K-1] each (msnap_solve_states's layout); a null block is rest
+struct TimeoptEndsArgs : TimeoptArgs {
+  const double *start, *end;
+};
 
 // w_0 v_0 + .. + w_3 v_3 over the quad, the same bits in its four lanes; an axis of weight 0 is not looked at
 __device__ __forceinline__ double quad_weighted_sum(double v, double wa) {
@@ -50,11 +61,13 @@ __device__ __forceinline__ double quad_weighted_sum(double v, double wa) {
   return ((quad_bcast<0>(p) + quad_bcast<1>(p)) + quad_bcast<2>(p)) + quad_bcast<3>(p);
 }
 
-template <int K>
+// ENDS: the end knots' derivative vectors u_0, u_M are data (msnap_optimize_times_states), as in rolled_solve_tile
+template <int K, bool ENDS>
 __global__ void __launch_bounds__(kWave)
-timeopt_kernel(const TimeoptArgs p) {
+timeopt_kernel(const std::conditional_t<ENDS, TimeoptEndsArgs, TimeoptArgs> p) {
   using SW = Sweep<K>;
-  constexpr int NU = SW::NU, NC = SW::NC;
+  using C = HermiteConsts<K>;
+  constexpr int NU = SW::NU, NC = SW::NC, KK = SW::KK, PM = SW::PM, PITCH = NU | 1;
 
   extern __shared__ __attribute__((aligned(16))) double lds[];
 
@@ -76,6 +89,7 @@ timeopt_kernel(const TimeoptArgs p) {
 
   // LDS: Tr (order 9 only: output transpose image) | Wraw[TD][(M+1)*4] | Traw[TD][M+1] (inputs, then the final knots)
   //      | Tc, Tt [M+1][TD] | Gc, Gt, D, X [M][TD] | G[knots][NU*NU][TD] | Z[knots][NU][4 TD]
+  //      | ENDS: S0, S1 [4 TD][PITCH] (start and end state of every lane, at K13's odd pitch)
   double2 *sTr = reinterpret_cast<double2 *>(lds);
   double *sWraw = lds + (NC == 8 ? 0 : (NC / 2) * kTrPitch * 2);
   double *sTraw = sWraw + TD * wpitch;
@@ -87,9 +101,25 @@ timeopt_kernel(const TimeoptArgs p) {
   double *sX = sD + TD * M;
   double *sG = sX + TD * M;
   double *sZ = sG + (size_t)TD * NU * NU * knots + ql;   // (this lane's column)
+  double *sS = sG + (size_t)TD * (NU * NU + 4 * NU) * knots;   // (ENDS only)
+  const double *sS0 = sS + ql * PITCH;                         // (this lane's rows)
+  const double *sS1 = sS0 + QL * PITCH;
 
+  // ENDS: the state blocks travel with the input stage, every load in flight before the first LDS store; a missing
+  // block is staged as zeros, so nothing below asks which were given
+  double v0[NU], v1[NU];
+  if constexpr (ENDS) {
+#pragma unroll
+    for (int q = 0; q < NU; ++q) v0[q] = v1[q] = 0.0;
+    if (p.start) load_states<NU, PITCH>(p.start + (size_t)tile * QL * NU, 0, nvalid, lane, v0);
+    if (p.end) load_states<NU, PITCH>(p.end + (size_t)tile * QL * NU, 0, nvalid, lane, v1);
+  }
   stage_inputs(p.wp + (size_t)tile * TD * wpitch, p.shared_times ? p.tt : p.tt + (size_t)tile * TD * tpitch,
                p.shared_times, 0, nvalid, wpitch, tpitch, sWraw, sTraw, lane);
+  if constexpr (ENDS) {
+    store_states<NU, PITCH>(sS, nvalid, lane, v0);
+    store_states<NU, PITCH>(sS + QL * PITCH, nvalid, lane, v1);
+  }
   __syncthreads();
   const double *lw = sWraw + dloc * wpitch + a;
   const double *lt = sTraw + (p.shared_times ? 0 : dloc * tpitch);
@@ -103,6 +133,10 @@ timeopt_kernel(const TimeoptArgs p) {
   for (int i = 0; i < M; ++i) {
     nonfinite |= !finite64(lt[i + 1]) | !finite64(lw[(i + 1) * 4]);
     badtime |= !(lt[i + 1] - lt[i] > 0.0);
+  }
+  if constexpr (ENDS) {      // data, and checked like every other input
+#pragma unroll
+    for (int q = 0; q < NU; ++q) nonfinite |= !finite64(sS0[q]) | !finite64(sS1[q]);
   }
   const double Tmin = p.min_fraction * ttotal / (double)M;
   // durations below the floor are raised to it; the others keep T_min plus their excess over it scaled by one factor
@@ -139,6 +173,18 @@ timeopt_kernel(const TimeoptArgs p) {
     sX[dloc] = x;
     SW sw;
     sw.init(x, wcur - lw[0]);
+    if constexpr (ENDS) {
+      // knot 1 sees the start state through the coupling block of segment 0: Otz = O_0^T u_0 (rolled_solve_tile)
+      double xp[PM + 1];
+      SW::powers(x, xp);
+#pragma unroll
+      for (int n = 0; n < NU; ++n) {
+        double w = 0.0;
+#pragma unroll
+        for (int q = 0; q < NU; ++q) w = __builtin_fma(C::HSE[q + 1][n + 1] * xp[KK - (q + 1) - (n + 1)], sS0[q], w);
+        sw.Otz[n] = w;
+      }
+    }
     for (int i = 1; i < M; ++i) {
       const double tnext = sT[(i + 1) * TD];
       const double wnext = lw[(i + 1) * 4];
@@ -161,8 +207,19 @@ timeopt_kernel(const TimeoptArgs p) {
 
     double un[NU];
 #pragma unroll
-    for (int r = 0; r < NU; ++r) un[r] = 0.0;
+    for (int r = 0; r < NU; ++r) {
+      if constexpr (ENDS) un[r] = sS1[r];      // the backward sweep starts from u_M
+      else un[r] = 0.0;
+    }
     double wn = wcur, tn = tcur;   // w_M, t_M
+    // ENDS: the local time msnap_eval_state evaluates the last segment at when asked for the sum of the durations --
+    // of the durations as they are stored, the differences of these knots
+    double tl_end = 0.0;
+    if constexpr (ENDS && EMIT) {
+      double tacc = 0.0;
+      for (int i = 0; i < M - 1; ++i) tacc = tacc + (sT[(i + 1) * TD] - sT[i * TD]);
+      tl_end = (tacc + (tn - sT[(M - 1) * TD])) - tacc;
+    }
     double Ja = 0.0;
     for (int i = M - 1; i >= 0; --i) {
       double u[NU];
@@ -172,11 +229,13 @@ timeopt_kernel(const TimeoptArgs p) {
 #pragma unroll
       for (int r = 0; r < NU; ++r) {
         double v = i >= 1 ? zz[r * QL] : 0.0;
-        if (i < M - 1) {
+        // (ENDS: the stash holds G of the last knot too, and with two segments the one knot receives both end terms)
+        if (ENDS || i < M - 1) {
 #pragma unroll
           for (int c = 0; c < NU; ++c) v = __builtin_fma(-(i >= 1 ? g[(r * NU + c) * TD] : 0.0), un[c], v);
         }
-        u[r] = i >= 1 ? v : 0.0;
+        if constexpr (ENDS) u[r] = i >= 1 ? v : sS0[r];      // segment 0 starts from u_0
+        else u[r] = i >= 1 ? v : 0.0;
       }
       const double wi = lw[i * 4];
       const double ti = sT[i * TD];
@@ -185,6 +244,11 @@ timeopt_kernel(const TimeoptArgs p) {
       Ja += segment_cost<K>(c, tn - ti);
       const double gi = -quad_weighted_sum(ostrogradsky_energy<K>(c), wa);
       if constexpr (EMIT) {
+        // the last segment leaves with one refinement step on its end conditions; cost and gradient above are the
+        // unrefined coefficients', as in every trial
+        if constexpr (ENDS) {
+          if (i == M - 1) refine_end<K>(c, tl_end, sX[i * TD + dloc], wn, un);
+        }
         double *base = p.coef + ((size_t)tile * TD * M + i) * (4 * NC);
         if constexpr (NC == 8) store_segment_quad8(base, MSNAP_SEG_STRIDE(M, NC), nvalid, lane, c, bad);
         else store_segment_coalesced<NC>(sTr, base, MSNAP_SEG_STRIDE(M, NC), nvalid, lane, c, bad);
@@ -340,42 +404,47 @@ timeopt_kernel(const TimeoptArgs p) {
   }
 }
 
-// doubles of LDS one tile of TD drones needs
-size_t timeopt_lds_words(int khalf, int M, int TD) {
+// doubles of LDS one tile of TD drones needs (ends: with the two state images)
+size_t timeopt_lds_words(int khalf, int M, int TD, bool ends) {
   const size_t nu = (size_t)khalf - 1, knots = (size_t)M - 1, m = (size_t)M;
   const size_t tr = khalf == 4 ? 0 : (size_t)khalf * kTrPitch * 2;
-  return tr + (size_t)TD * ((m + 1) * 4 + (m + 1) + 2 * (m + 1) + 4 * m + nu * nu * knots + 4 * nu * knots);
+  const size_t states = ends ? 2 * (size_t)TD * 4 * (nu | 1) : 0;
+  return tr + (size_t)TD * ((m + 1) * 4 + (m + 1) + 2 * (m + 1) + 4 * m + nu * nu * knots + 4 * nu * knots) + states;
 }
 
 }  // namespace
 
-int timeopt_max_segments(int khalf) {
+int timeopt_max_segments(int khalf, bool ends) {
   int m = 1;
-  while (m < 128 && timeopt_lds_words(khalf, m + 1, 8) * sizeof(double) <= kMaxLdsBytes) ++m;
+  while (m < 128 && timeopt_lds_words(khalf, m + 1, 8, ends) * sizeof(double) <= kMaxLdsBytes) ++m;
   return m;
 }
 
 // allow the full 160 KiB of dynamic LDS (once per context: a function attribute is a property of the device's module)
 static int timeopt_kernel_setup(msnap_ctx *ctx) {
   if (ctx->timeopt_ready) return MSNAP_OK;
-  MSNAP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&timeopt_kernel<4>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLdsBytes));
-  MSNAP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&timeopt_kernel<5>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLdsBytes));
+  for (const void *k : {reinterpret_cast<const void *>(&timeopt_kernel<4, false>),
+                        reinterpret_cast<const void *>(&timeopt_kernel<5, false>),
+                        reinterpret_cast<const void *>(&timeopt_kernel<4, true>),
+                        reinterpret_cast<const void *>(&timeopt_kernel<5, true>)})
+    MSNAP_HIP(ctx, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLdsBytes));
   ctx->timeopt_ready = 1;
   return MSNAP_OK;
 }
 
+// ends: msnap_optimize_times_states (start / end: device pointers or null); otherwise both are ignored
 int launch_optimize_times(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, const double *t, int shared_times,
-                          const double *weights, double min_fraction, int max_iter, double tol, double *t_out,
-                          double *coef, double *dur, int32_t *status, double *cost, double *pg, int32_t *iters) {
+                          bool ends, const double *start, const double *end, const double *weights,
+                          double min_fraction, int max_iter, double tol, double *t_out, double *coef, double *dur,
+                          int32_t *status, double *cost, double *pg, int32_t *iters) {
   if (n_drones == 0) return MSNAP_OK;
   // 16 drones per wave while their stash fits LDS, 8 above
-  const int TD = timeopt_lds_words(ctx->khalf, n_seg, kDronesPerWave) * sizeof(double) <= kMaxLdsBytes ? kDronesPerWave : 8;
-  const size_t lds_bytes = timeopt_lds_words(ctx->khalf, n_seg, TD) * sizeof(double);
+  const int TD =
+      timeopt_lds_words(ctx->khalf, n_seg, kDronesPerWave, ends) * sizeof(double) <= kMaxLdsBytes ? kDronesPerWave : 8;
+  const size_t lds_bytes = timeopt_lds_words(ctx->khalf, n_seg, TD, ends) * sizeof(double);
   if (lds_bytes > kMaxLdsBytes) return MSNAP_ESEGMENTS;
   if (int rc = timeopt_kernel_setup(ctx)) return rc;
-  TimeoptArgs a;
+  TimeoptEndsArgs a;
   a.wp = wp;
   a.tt = t;
   a.shared_times = shared_times;
@@ -393,11 +462,21 @@ int launch_optimize_times(msnap_ctx *ctx, int n_drones, int n_seg, const double 
   a.cost = cost;
   a.pg = pg;
   a.iters = iters;
+  a.start = start;
+  a.end = end;
+  const TimeoptArgs &rest = a;
   const int ntiles = (n_drones + TD - 1) / TD;
-  if (ctx->khalf == 4)
-    hipLaunchKernelGGL((timeopt_kernel<4>), dim3(ntiles), dim3(kWave), lds_bytes, ctx->stream, a);
-  else
-    hipLaunchKernelGGL((timeopt_kernel<5>), dim3(ntiles), dim3(kWave), lds_bytes, ctx->stream, a);
+  if (ends) {
+    if (ctx->khalf == 4)
+      hipLaunchKernelGGL((timeopt_kernel<4, true>), dim3(ntiles), dim3(kWave), lds_bytes, ctx->stream, a);
+    else
+      hipLaunchKernelGGL((timeopt_kernel<5, true>), dim3(ntiles), dim3(kWave), lds_bytes, ctx->stream, a);
+  } else {
+    if (ctx->khalf == 4)
+      hipLaunchKernelGGL((timeopt_kernel<4, false>), dim3(ntiles), dim3(kWave), lds_bytes, ctx->stream, rest);
+    else
+      hipLaunchKernelGGL((timeopt_kernel<5, false>), dim3(ntiles), dim3(kWave), lds_bytes, ctx->stream, rest);
+  }
   MSNAP_HIP(ctx, hipGetLastError());
   return MSNAP_OK;
 }
@@ -424,11 +503,11 @@ int msnap_snap_cost_grad(msnap_ctx *ctx, int n_drones, int n_seg, const double *
 // ------------------------------------------------------------------ time allocation (msnap_timeopt.hip)
 // weights is a host array in both versions; cost, pg and iters are optional
 namespace {
-int timeopt_args(const msnap_ctx *ctx, int n_drones, int n_seg, const double *weights, double min_fraction,
-                        int max_iter, double tol, std::initializer_list<const void *> ptrs) {
+int timeopt_args(const msnap_ctx *ctx, int n_drones, int n_seg, bool ends, const double *weights, double min_fraction,
+                 int max_iter, double tol, std::initializer_list<const void *> ptrs) {
   if (!ctx || n_drones < 0) return MSNAP_EINVAL;
   if (int rc = check_seg(ctx, n_seg)) return rc;
-  if (n_seg > timeopt_max_segments(ctx->khalf)) return MSNAP_ESEGMENTS;
+  if (n_seg > timeopt_max_segments(ctx->khalf, ends)) return MSNAP_ESEGMENTS;
   if (!weights || !(min_fraction > 0.0 && min_fraction <= 1.0) || max_iter < 0 || !(tol >= 0.0)) return MSNAP_EINVAL;
   for (int q = 0; q < 4; ++q)
     if (!(weights[q] >= 0.0) || !(weights[q] <= 1.79769313486231570815e308)) return MSNAP_EINVAL;   // negative, NaN, Inf
@@ -437,34 +516,73 @@ int timeopt_args(const msnap_ctx *ctx, int n_drones, int n_seg, const double *we
     if (!p) return MSNAP_EINVAL;
   return MSNAP_OK;
 }
+
+// the host entries: stage, launch, read back (start / end: host pointers or null, looked at with ends only)
+int optimize_times_host(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, const double *t, int shared_times,
+                        bool ends, const double *start, const double *end, const double *weights, double min_fraction,
+                        int max_iter, double tol, double *t_out, double *coef, double *dur, int32_t *status,
+                        double *cost, double *pg, int32_t *iters) {
+  const size_t n = (size_t)n_drones, m1 = (size_t)n_seg + 1;
+  const size_t b_s = n * 4 * (ctx->khalf - 1) * 8;
+  // (a region without a source is not copied: a NULL state stays NULL for the launcher)
+  return staged(ctx, {upload(wp, n * m1 * 4 * 8), upload(t, (shared_times ? 1 : n) * m1 * 8), download(t_out, n * m1 * 8),
+                      download(coef, coef_bytes(ctx, n_drones, n_seg)), download(dur, dur_bytes(n_drones, n_seg)),
+                      download(status, n * 4), download(cost, cost ? n * 16 : 0), download(pg, pg ? n * 8 : 0),
+                      download(iters, iters ? n * 4 : 0), upload(start, ends && start ? b_s : 0),
+                      upload(end, ends && end ? b_s : 0)},
+                [&](const DevPtr *d) {
+                  return launch_optimize_times(ctx, n_drones, n_seg, d[0], d[1], shared_times ? 1 : 0, ends,
+                                               ends && start ? (const double *)d[9] : nullptr,
+                                               ends && end ? (const double *)d[10] : nullptr, weights, min_fraction,
+                                               max_iter, tol, d[2], d[3], d[4], d[5], cost ? (double *)d[6] : nullptr,
+                                               pg ? (double *)d[7] : nullptr, iters ? (int32_t *)d[8] : nullptr);
+                });
+}
 }  // namespace
 
 int msnap_optimize_times_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, const double *t,
                                 int shared_times, const double weights[4], double min_fraction, int max_iter,
                                 double tol, double *t_out, double *coef, double *dur, int32_t *status, double *cost,
                                 double *pg, int32_t *iters) {
-  MSNAP_ENTER(ctx, timeopt_args(ctx, n_drones, n_seg, weights, min_fraction, max_iter, tol,
+  MSNAP_ENTER(ctx, timeopt_args(ctx, n_drones, n_seg, false, weights, min_fraction, max_iter, tol,
                                 {wp, t, t_out, coef, dur, status}));
-  return launch_optimize_times(ctx, n_drones, n_seg, wp, t, shared_times ? 1 : 0, weights, min_fraction, max_iter, tol,
-                               t_out, coef, dur, status, cost, pg, iters);
+  return launch_optimize_times(ctx, n_drones, n_seg, wp, t, shared_times ? 1 : 0, false, nullptr, nullptr, weights,
+                               min_fraction, max_iter, tol, t_out, coef, dur, status, cost, pg, iters);
 }
 
 int msnap_optimize_times(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, const double *t, int shared_times,
                          const double weights[4], double min_fraction, int max_iter, double tol, double *t_out,
                          double *coef, double *dur, int32_t *status, double *cost, double *pg, int32_t *iters) {
-  MSNAP_ENTER(ctx, timeopt_args(ctx, n_drones, n_seg, weights, min_fraction, max_iter, tol,
+  MSNAP_ENTER(ctx, timeopt_args(ctx, n_drones, n_seg, false, weights, min_fraction, max_iter, tol,
                                 {wp, t, t_out, coef, dur, status}));
-  const size_t n = (size_t)n_drones, m1 = (size_t)n_seg + 1;
-  return staged(ctx, {upload(wp, n * m1 * 4 * 8), upload(t, (shared_times ? 1 : n) * m1 * 8), download(t_out, n * m1 * 8),
-                      download(coef, coef_bytes(ctx, n_drones, n_seg)), download(dur, dur_bytes(n_drones, n_seg)),
-                      download(status, n * 4), download(cost, cost ? n * 16 : 0), download(pg, pg ? n * 8 : 0),
-                      download(iters, iters ? n * 4 : 0)},
-                [&](const DevPtr *d) {
-                  return launch_optimize_times(ctx, n_drones, n_seg, d[0], d[1], shared_times ? 1 : 0, weights,
-                                               min_fraction, max_iter, tol, d[2], d[3], d[4], d[5],
-                                               cost ? (double *)d[6] : nullptr, pg ? (double *)d[7] : nullptr,
-                                               iters ? (int32_t *)d[8] : nullptr);
-                });
+  return optimize_times_host(ctx, n_drones, n_seg, wp, t, shared_times, false, nullptr, nullptr, weights, min_fraction,
+                             max_iter, tol, t_out, coef, dur, status, cost, pg, iters);
+}
+
+int msnap_optimize_times_states_max_segments(int order) {
+  if (order != 7 && order != 9) return MSNAP_EORDER;
+  return timeopt_max_segments((order + 1) / 2, true);
+}
+
+int msnap_optimize_times_states_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, const double *t,
+                                       int shared_times, const double *start, const double *end,
+                                       const double weights[4], double min_fraction, int max_iter, double tol,
+                                       double *t_out, double *coef, double *dur, int32_t *status, double *cost,
+                                       double *pg, int32_t *iters) {
+  MSNAP_ENTER(ctx, timeopt_args(ctx, n_drones, n_seg, true, weights, min_fraction, max_iter, tol,
+                                {wp, t, t_out, coef, dur, status}));
+  return launch_optimize_times(ctx, n_drones, n_seg, wp, t, shared_times ? 1 : 0, true, start, end, weights,
+                               min_fraction, max_iter, tol, t_out, coef, dur, status, cost, pg, iters);
+}
+
+int msnap_optimize_times_states(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, const double *t,
+                                int shared_times, const double *start, const double *end, const double weights[4],
+                                double min_fraction, int max_iter, double tol, double *t_out, double *coef, double *dur,
+                                int32_t *status, double *cost, double *pg, int32_t *iters) {
+  MSNAP_ENTER(ctx, timeopt_args(ctx, n_drones, n_seg, true, weights, min_fraction, max_iter, tol,
+                                {wp, t, t_out, coef, dur, status}));
+  return optimize_times_host(ctx, n_drones, n_seg, wp, t, shared_times, true, start, end, weights, min_fraction,
+                             max_iter, tol, t_out, coef, dur, status, cost, pg, iters);
 }
 
 }  // extern "C"

@@ -287,6 +287,31 @@ class DeviceCompute:
                                          None if end is None else end.contiguous(), coef, dur, status)
         return coef, dur, status
 
+    def optimize_times_states(self, wp, t, start=None, end=None, weights=(1, 1, 1, 1), min_fraction=0.1, max_iter=200,
+                              tol=1e-4):
+        """(t_out, coef, dur, status, info) of the time allocation from and to given end states: arguments as
+        solve_states plus the four of Context.optimize_times; info = {"cost": [n, 2], "pg": [n], "iters": [n] int32}."""
+        torch = self.torch
+        n, m, _ = wp.shape
+        M = m - 1
+        nd = self.ctx.ncoef // 2 - 1
+        for name, x in (("start", start), ("end", end)):
+            if x is not None and (tuple(x.shape) != (n, 4, nd) or x.dtype != torch.float64):
+                raise ValueError(f"optimize_times_states: {name} must be a float64 tensor [n, 4, {nd}]")
+        t_out = self._out("optimize_times_states.t_out", (n, m), torch.float64)
+        coef = self._out("optimize_times_states.coef", (n, M, 4, self.ctx.ncoef), torch.float64)
+        dur = self._out("optimize_times_states.dur", (n, M), torch.float64)
+        status = self._out("optimize_times_states.status", (n,), torch.int32)
+        cost = self._out("optimize_times_states.cost", (n, 2), torch.float64)
+        pg = self._out("optimize_times_states.pg", (n,), torch.float64)
+        iters = self._out("optimize_times_states.iters", (n,), torch.int32)
+        if n:
+            self.ctx.optimize_times_states_device(n, M, wp.contiguous(), t.contiguous(), t.dim() == 1,
+                                                  None if start is None else start.contiguous(),
+                                                  None if end is None else end.contiguous(), weights, min_fraction,
+                                                  max_iter, tol, t_out, coef, dur, status, cost, pg, iters)
+        return t_out, coef, dur, status, {"cost": cost, "pg": pg, "iters": iters}
+
     def eval_state(self, coef, dur, tq):
         """(pos [n, 4], deriv [n, 4, K-1]) of each drone at its own time tq [n]: NaN outside its path."""
         torch = self.torch
@@ -957,7 +982,7 @@ def certify_geofence(compute, coef, dur, lo=None, hi=None, planes=None, radius: 
                           upper, box_lo, box_hi)
 
 
-def replan(compute, coef, dur, t_r, wp_new, t_new, end=None):
+def replan(compute, coef, dur, t_r, wp_new, t_new, end=None, optimize=None):
     """Replan a flying swarm: leave the paths `coef`, `dur` at time `t_r` and fly through new waypoints.
 
     `t_r` is a number or a tensor [N] (per drone, on the current paths' clock); `wp_new` [N, M', 4] are the waypoints
@@ -966,7 +991,11 @@ def replan(compute, coef, dur, t_r, wp_new, t_new, end=None):
     `compute.eval_state`, its position becomes the waypoint at time 0, its derivatives the start state of
     `compute.solve_states`.  Returns (coef, dur, status, (pos, deriv)) -- the new paths on a clock that starts at `t_r`,
     and the state they start from.  A drone whose `t_r` lies outside its path has a NaN state and comes back with
-    status 3 and NaN coefficients, as does one with bad times (status 2): nothing raises per drone."""
+    status 3 and NaN coefficients, as does one with bad times (status 2): nothing raises per drone.
+
+    `optimize`: None solves at `t_new` as given.  A dict with any of weights / min_fraction / max_iter / tol lets
+    `compute.optimize_times_states` move the interior times first (the state at `t_r`, the waypoints, `end` and the
+    last time are kept); the knots it chose are the running sum of the returned `dur`."""
     import torch
     n = dur.shape[0]
     dev = dur.device
@@ -981,7 +1010,13 @@ def replan(compute, coef, dur, t_r, wp_new, t_new, end=None):
     wp = torch.cat([pos[:, None, :], wp_new.to(torch.float64)], dim=1).contiguous()
     t = torch.cat([torch.zeros(t_new.shape[:-1] + (1,), dtype=torch.float64, device=dev), t_new.to(torch.float64)],
                   dim=-1).contiguous()
-    new_coef, new_dur, status = compute.solve_states(wp, t, start=deriv, end=end)
+    if optimize is None:
+        new_coef, new_dur, status = compute.solve_states(wp, t, start=deriv, end=end)
+    else:
+        unknown = set(optimize) - {"weights", "min_fraction", "max_iter", "tol"}
+        if unknown:
+            raise ValueError(f"replan: optimize takes weights, min_fraction, max_iter, tol, not {sorted(unknown)}")
+        _, new_coef, new_dur, status, _ = compute.optimize_times_states(wp, t, start=deriv, end=end, **optimize)
     return new_coef, new_dur, status, (pos, deriv)
 
 

@@ -661,6 +661,51 @@ int msnap_optimize_times_device(msnap_ctx *ctx, int n_drones, int n_seg, const d
                                 double tol, double *t_out, double *coef, double *dur, int32_t *status, double *cost,
                                 double *pg, int32_t *iters);
 
+/* msnap_optimize_times_states: the same time allocation from and to given end states -- the step a replan in flight
+ * lacks between msnap_eval_state and msnap_solve_states.  Arguments as msnap_optimize_times, with start and end after
+ * shared_times in msnap_solve_states's layout: [n_drones][4][K-1], K = (order + 1) / 2, entry q-1 the q-th time
+ * derivative at the first / last waypoint.  Either may be NULL: rest.  Objective, feasible set, floor (T_min =
+ * min_fraction * t[M] / M, inputs below it raised as above), direction, step rules, stopping measure, cost / pg /
+ * iters and the method are msnap_optimize_times's, word for word, with "the solve for T" read as msnap_solve_states's:
+ * dJ/dT_i = -sum_a weights[a] E_i,a holds for the first and last segment too, whose outer end states are data instead
+ * of stationary unknowns.
+ *   kept        the waypoints, both end states, t_out[0] == 0 and t_out[M] == t[M] bit for bit.  The total duration is
+ *               an input; it is not optimised (stretching a path changes no given end state, but choosing t[M] against
+ *               dynamic limits is not this entry's job);
+ *   coef, dur   the boundary-state solution for t_out: dur[i] = t_out[i+1] - t_out[i] bit for bit, coef what
+ *               msnap_solve_states returns for t_out to rounding (norm-relative 1e-9); coef[0][a][0] is wp[0][a] bit for
+ *               bit;
+ *   end state   as msnap_solve_states states it: msnap_eval_state returns the given start derivatives at tq = 0 within
+ *               4 * 2^-52 relative, and the given end derivatives at the sum of dur (as msnap_eval_flat accumulates it)
+ *               within 4 * 2^-52 of max(|value|, sum_j |d_j| T^j).  The last segment takes the same refinement step on
+ *               its end conditions, once, when the coefficients leave; cost, pg and the iteration's decisions are taken
+ *               from the unrefined coefficients (the refinement moves them by units in the last place);
+ *   status      MSNAP_ST_NONFINITE for NaN / Inf in wp, t or a state entry of that drone; MSNAP_ST_TIMES for times not
+ *               strictly increasing or t[0] != 0; MSNAP_ST_SINGULAR for a non-positive pivot or a cost that is not
+ *               finite at the (raised) input times.  A failed drone gets NaN coef, t_out, dur, cost, pg and iters 0; a
+ *               trial point whose solve fails is a rejected step.
+ * Guarantees as above: every dur[i] >= T_min (1 - 1e-12), cost[1] <= cost[0], max_iter = 0 returns the (raised) input
+ * times.  A drone's outputs are bit-identical whatever its place in the batch, the batch size, or host versus device
+ * entry; NULL and an array of zeros give the same bits.  With both blocks zero the problem is msnap_optimize_times's, and
+ * the two agree to rounding (not bit for bit: this entry applies the last knot's coupling block to a zero end state).
+ * n_seg: 1 (one Hermite segment, nothing to optimise: iters 0, t_out the input) ..
+ * msnap_optimize_times_states_max_segments(order) -- 79 at order 7, 57 at order 9: what an 8-drone tile's state and its
+ * two state images leave of 160 KiB of LDS -- and at most max_segments; MSNAP_ESEGMENTS above.  The query returns
+ * MSNAP_EORDER for any other order.  MSNAP_EINVAL as msnap_optimize_times; n_drones == 0 is a no-op.  The device
+ * version only launches (no synchronisation, no context buffer: the capture rules are msnap_optimize_times_device's).
+ */
+int msnap_optimize_times_states(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, const double *t,
+                                int shared_times, const double *start /* [n_drones][4][K-1] or NULL */,
+                                const double *end /* [n_drones][4][K-1] or NULL */, const double weights[4],
+                                double min_fraction, int max_iter, double tol, double *t_out, double *coef, double *dur,
+                                int32_t *status, double *cost, double *pg, int32_t *iters);
+int msnap_optimize_times_states_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, const double *t,
+                                       int shared_times, const double *start, const double *end,
+                                       const double weights[4], double min_fraction, int max_iter, double tol,
+                                       double *t_out, double *coef, double *dur, int32_t *status, double *cost,
+                                       double *pg, int32_t *iters);
+int msnap_optimize_times_states_max_segments(int order);     /* largest n_seg the entry takes; < 0: MSNAP_EORDER */
+
 /* ---- drone-vs-drone formation pass (new capability; no reference) -------
  * rows: the n_rows drones this caller owns (a shard), starting at global index
  * row_offset; cols: all n_cols drones (after the all-gather).  Spheres of `radius`.
