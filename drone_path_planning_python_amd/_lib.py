@@ -80,6 +80,9 @@ SIGNATURES = {
     "msnap_solve_states": (_I, [_VP, _I, _I, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP]),
     "msnap_solve_states_device": (_I, [_VP, _I, _I, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP]),
     "msnap_solve_states_max_segments": (_I, [_I]),
+    "msnap_solve_periodic": (_I, [_VP, _I, _I, _VP, _VP, _I, _VP, _VP, _VP]),
+    "msnap_solve_periodic_device": (_I, [_VP, _I, _I, _VP, _VP, _I, _VP, _VP, _VP]),
+    "msnap_solve_periodic_max_segments": (_I, [_I]),
     "msnap_optimize_times_states": (_I, [_VP, _I, _I, _VP, _VP, _I, _VP, _VP, _VP, _D, _I, _D, _VP, _VP, _VP, _VP, _VP,
                                          _VP, _VP]),
     "msnap_optimize_times_states_device": (_I, [_VP, _I, _I, _VP, _VP, _I, _VP, _VP, _VP, _D, _I, _D, _VP, _VP, _VP,

@@ -644,6 +644,37 @@ class Context:
                                                          int(bool(shared_times)), _ptr(start), _ptr(end), _ptr(coef),
                                                          _ptr(dur), _ptr(status)))
 
+    # ---- closed-loop paths (include/msnap.h) ----------------------------------------
+    def solve_periodic_max_segments(self) -> int:
+        """Largest segment count solve_periodic takes at this context's order (and at most max_segments)."""
+        return min(int(self._lib.msnap_solve_periodic_max_segments(self.order)), self.max_segments)
+
+    def solve_periodic(self, wp, t):
+        """The closed-loop minimum-snap solve (msnap_solve_periodic): wp [N, m, 4], t [N, m] or shared [m] with
+        t[0] == 0 and m >= 3; the last waypoint is joined to the first with derivatives 1 .. 2K-2 continuous, the period
+        is t[-1], wp[:, -1] - wp[:, 0] the lap offset -> coef [N, M, 4, ncoef], dur [N, M], status [N] int32."""
+        wp, pwp = _host(wp, np.float64)
+        t, pt = _host(t, np.float64)
+        if wp.ndim != 3 or wp.shape[2] != 4:
+            raise ValueError("wp must be [N, m, 4]")
+        N, m, _ = wp.shape
+        shared = int(t.ndim == 1)
+        if (shared and t.shape != (m,)) or (not shared and t.shape != (N, m)):
+            raise ValueError("t must be [N, m] or [m]")
+        M = m - 1
+        coef, dur, status = _out_arrays(None, ((N, max(M, 0), 4, self.ncoef), (N, max(M, 0)), (N,)))
+        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)      # noqa: E731
+        with self._lock:
+            self._ck(self._lib.msnap_solve_periodic(self._h, N, M, pwp, pt, shared, vp(coef), vp(dur), vp(status)))
+        return coef, dur, status
+
+    def solve_periodic_device(self, n_drones, n_seg, wp, t, shared_times, coef, dur, status):
+        """Device pointers, asynchronous on the context's stream."""
+        with self._lock:
+            self._ck(self._lib.msnap_solve_periodic_device(self._h, int(n_drones), int(n_seg), _ptr(wp), _ptr(t),
+                                                           int(bool(shared_times)), _ptr(coef), _ptr(dur),
+                                                           _ptr(status)))
+
     def optimize_times_states_max_segments(self) -> int:
         """Largest segment count optimize_times_states takes at this context's order (and at most max_segments)."""
         return min(int(self._lib.msnap_optimize_times_states_max_segments(self.order)), self.max_segments)

@@ -287,6 +287,19 @@ class DeviceCompute:
                                          None if end is None else end.contiguous(), coef, dur, status)
         return coef, dur, status
 
+    def solve_periodic(self, wp, t):
+        """(coef, dur, status) of the closed-loop solve: the last waypoint is joined to the first, the period is t[-1],
+        wp[:, -1] - wp[:, 0] the lap offset; t[0] must be 0."""
+        torch = self.torch
+        n, m, _ = wp.shape
+        M = m - 1
+        coef = self._out("solve_periodic.coef", (n, M, 4, self.ctx.ncoef), torch.float64)
+        dur = self._out("solve_periodic.dur", (n, M), torch.float64)
+        status = self._out("solve_periodic.status", (n,), torch.int32)
+        if n:
+            self.ctx.solve_periodic_device(n, M, wp.contiguous(), t.contiguous(), t.dim() == 1, coef, dur, status)
+        return coef, dur, status
+
     def optimize_times_states(self, wp, t, start=None, end=None, weights=(1, 1, 1, 1), min_fraction=0.1, max_iter=200,
                               tol=1e-4):
         """(t_out, coef, dur, status, info) of the time allocation from and to given end states: arguments as
@@ -1018,6 +1031,27 @@ def replan(compute, coef, dur, t_r, wp_new, t_new, end=None, optimize=None):
             raise ValueError(f"replan: optimize takes weights, min_fraction, max_iter, tol, not {sorted(unknown)}")
         _, new_coef, new_dur, status, _ = compute.optimize_times_states(wp, t, start=deriv, end=end, **optimize)
     return new_coef, new_dur, status, (pos, deriv)
+
+
+def join_loop(compute, coef, dur, t_r, loop_coef, loop_dur, wp_via, t_via, optimize=None):
+    """Park a flying swarm on holding loops: leave the paths `coef`, `dur` at time `t_r` and arrive on the loops
+    `loop_coef`, `loop_dur` (what `compute.solve_periodic` returned) at their first waypoint, in the loops' own state.
+
+    `wp_via` [N, V, 4] are waypoints to pass on the way (V may be 0); `t_via` [N, V + 1] or [V + 1] holds their times
+    and, last, the arrival time on the loop, all counted from `t_r`.  This is `replan` with the loop's first waypoint
+    appended as the last one and `end` taken from `compute.eval_state` of the loop at 0: positions and derivatives
+    1 .. K-1 are continuous at both hand-overs.  Returns what `replan` returns; `optimize` as there."""
+    import torch
+    n = dur.shape[0]
+    if loop_dur.shape[0] != n or loop_coef.shape[0] != n:
+        raise ValueError("join_loop: loop_coef, loop_dur hold one loop per drone")
+    if wp_via.dim() != 3 or wp_via.shape[0] != n or wp_via.shape[2] != 4:
+        raise ValueError("join_loop: wp_via must be [N, V, 4]")
+    zero = torch.zeros((n,), dtype=torch.float64, device=dur.device)
+    pos, deriv = compute.eval_state(loop_coef, loop_dur, zero)
+    # (replan evaluates too: with reuse_outputs the same tensors would come back)
+    wp_new = torch.cat([wp_via.to(torch.float64), pos[:, None, :]], dim=1)
+    return replan(compute, coef, dur, t_r, wp_new, t_via, end=deriv.clone(), optimize=optimize)
 
 
 # ---- certified clearance of replanned paths against the paths that stay, and against each other ---------------------

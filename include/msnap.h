@@ -571,6 +571,41 @@ int msnap_eval_state(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef
 int msnap_eval_state_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,
                             const double *tq, double *pos, double *deriv);
 
+/* ---- closed-loop paths: the periodic solve (new capability) ----
+ * Every other solve ends at rest or in a state the caller supplies; msnap_solve_periodic joins the last waypoint to the
+ * first, for holding patterns and repeating figures.  wp, t, shared_times, coef, dur, status as for msnap_solve_states.
+ * With K = (order + 1) / 2:
+ *   - the result interpolates every waypoint;
+ *   - among all such paths whose derivatives 1 .. K-1 at the last waypoint equal those at the first it minimises the
+ *     cost of msnap_solve_batch, the integral of (p^(K))^2 per axis.  The seam's derivatives are free: the minimisation
+ *     chooses them;
+ *   - consequently derivatives 1 .. 2K-2 are continuous across the seam, exactly as at an interior knot.  The period is
+ *     t[n_seg];
+ *   - wp[n_seg] need NOT equal wp[0].  The difference is the lap offset: 0 for a closed curve, 2 pi k in yaw for a
+ *     turning one, a constant step for a helix.  The library does not judge it;
+ *   - coef[i][a][0] is wp[i][a] bit for bit.
+ * Through the evaluator: msnap_eval_state at the sum of the durations (as msnap_eval_flat accumulates it) returns
+ * derivatives 1 .. K-1 equal to those it returns at tq = 0, and the position wp[n_seg], within the bound
+ * msnap_solve_states states for its end state -- 4 * 2^-52 of max(|value|, sum_j |d_j| T^j), d the coefficients of the
+ * derivative being evaluated on the last segment: that segment takes the same refinement step on its end conditions,
+ * with the solved seam state as its end vector.  Time is not wrapped anywhere: callers reduce t modulo the period.
+ *   status   MSNAP_ST_NONFINITE, MSNAP_ST_TIMES (times not strictly increasing, or t[0] != 0) and MSNAP_ST_SINGULAR
+ *            (the seam knot's pivots are tested like every other knot's) as in msnap_solve_states.  A failed drone gets
+ *            NaN coefficients; dur[i] = t[i+1] - t[i] is written for every drone.
+ *   n_seg    2 .. msnap_solve_periodic_max_segments(order) -- 27 at order 7, 18 at order 9: what a 16-drone tile's
+ *            stash (one more matrix and one more vector per knot than the boundary-state solve) leaves of 160 KiB of
+ *            LDS -- and at most max_segments.  One segment is excluded.  MSNAP_ESEGMENTS outside, and nothing is written.
+ *            msnap_solve_periodic_max_segments returns MSNAP_EORDER for any other order.
+ * MSNAP_EINVAL: a null context, a null wp, t, coef, dur or status, negative n_drones.  n_drones == 0 is a no-op.  A
+ * drone's outputs are bit-identical whatever its place in the batch, the batch size, and host versus device entry.  The
+ * device version only launches (no synchronisation, no context buffer, so no capture rules).
+ */
+int msnap_solve_periodic(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, const double *t, int shared_times,
+                         double *coef, double *dur, int32_t *status);
+int msnap_solve_periodic_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, const double *t,
+                                int shared_times, double *coef, double *dur, int32_t *status);
+int msnap_solve_periodic_max_segments(int order);   /* largest n_seg the entry takes; < 0: MSNAP_EORDER */
+
 /* ---- near pairs: every pair of a swarm whose sampled distance is below a per-pair limit ----
  * msnap_formation_collide names one partner per drone; msnap_formation_near_pairs lists every close pair, e.g. the
  * pairs msnap_pair_clearance has to see.  pos [n_drones][n_samples][3] as the sampler writes it; speed [n_drones] or
