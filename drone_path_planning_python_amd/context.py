@@ -725,6 +725,52 @@ class Context:
                 pw, float(min_fraction), int(max_iter), float(tol), _ptr(t_out), _ptr(coef), _ptr(dur), _ptr(status),
                 _ptr(cost), _ptr(pg), _ptr(iters)))
 
+    def optimize_times_periodic_max_segments(self) -> int:
+        """Largest segment count optimize_times_periodic takes at this context's order (and at most max_segments)."""
+        return min(int(self._lib.msnap_optimize_times_periodic_max_segments(self.order)), self.max_segments)
+
+    def optimize_times_periodic(self, wp, t, weights=(1, 1, 1, 1), min_fraction=0.1, max_iter=200, tol=1e-4):
+        """optimize_times on closed loops (msnap_optimize_times_periodic): wp, t (m >= 3 waypoints) as solve_periodic
+        takes them, the other arguments and the result tuple as optimize_times.  Waypoints and the period t[-1] are
+        kept; coef, dur are the periodic solution for t_out."""
+        wp, pwp = _host(wp, np.float64)
+        t, pt = _host(t, np.float64)
+        if wp.ndim != 3 or wp.shape[2] != 4:
+            raise ValueError("wp must be [N, m, 4]")
+        N, m, _ = wp.shape
+        shared = int(t.ndim == 1)
+        if (shared and t.shape != (m,)) or (not shared and t.shape != (N, m)):
+            raise ValueError("t must be [N, m] or [m]")
+        w, pw = _host(weights, np.float64)
+        if w.shape != (4,):
+            raise ValueError("weights must hold 4 values")
+        M = m - 1
+        t_out = np.empty((N, m), dtype=np.float64)
+        coef = np.empty((N, max(M, 0), 4, self.ncoef), dtype=np.float64)
+        dur = np.empty((N, max(M, 0)), dtype=np.float64)
+        status = np.empty((N,), dtype=np.int32)
+        cost = np.empty((N, 2), dtype=np.float64)
+        pg = np.empty((N,), dtype=np.float64)
+        iters = np.empty((N,), dtype=np.int32)
+        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)   # noqa: E731
+        with self._lock:
+            self._ck(self._lib.msnap_optimize_times_periodic(
+                self._h, N, M, pwp, pt, shared, pw, float(min_fraction), int(max_iter), float(tol), vp(t_out),
+                vp(coef), vp(dur), vp(status), vp(cost), vp(pg), vp(iters)))
+        return t_out, coef, dur, status, {"cost": cost, "pg": pg, "iters": iters}
+
+    def optimize_times_periodic_device(self, n_drones, n_seg, wp, t, shared_times, weights, min_fraction, max_iter, tol,
+                                       t_out, coef, dur, status, cost=None, pg=None, iters=None):
+        """Device pointers, asynchronous; `weights` is a host sequence of 4 (x, y, z, yaw)."""
+        w, pw = _host(weights, np.float64)
+        if w.shape != (4,):
+            raise ValueError("weights must hold 4 values")
+        with self._lock:
+            self._ck(self._lib.msnap_optimize_times_periodic_device(
+                self._h, int(n_drones), int(n_seg), _ptr(wp), _ptr(t), int(bool(shared_times)), pw,
+                float(min_fraction), int(max_iter), float(tol), _ptr(t_out), _ptr(coef), _ptr(dur), _ptr(status),
+                _ptr(cost), _ptr(pg), _ptr(iters)))
+
     def eval_state(self, coef, dur, tq):
         """Full state of each drone at its own time tq [N] (msnap_eval_state): pos [N, 4], deriv [N, 4, K-1] with
         entry q-1 the q-th derivative -- the layout solve_states takes as `start`.  NaN where tq is outside the path."""

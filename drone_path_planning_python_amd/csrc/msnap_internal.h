@@ -119,7 +119,7 @@ struct msnap_ctx {
   int mesh_waves_per_cu = 0;    // "mesh_waves_per_cu": wavefronts per CU the mesh sweep's grid is capped at (0: one workgroup per drone)
   int own_stream_priority = 0;  // "own_stream_priority": 0 default, 1 lowest, 2 highest (re-creates own_stream)
   msnap::RetiredBuf *retired = nullptr;   // blocks kept alive for graphs captured before they were outgrown
-  int timeopt_ready = 0;        // msnap_timeopt.hip: its kernels' dynamic-LDS limit has been raised on this context's device
+  int timeopt_ready = 0;        // msnap_timeopt_kernel.h: bit m set when mode m's kernels' dynamic-LDS limit has been raised on this context's device
   char hip_err[256] = {0};
   char last_kernel[96] = {0};   // msnap_last_kernel: the solve kernel instance the last solve entry point launched
 };
@@ -159,13 +159,19 @@ int launch_eval_flat(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef
 int launch_snap_cost(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur, double *cost);
 int launch_snap_cost_grad(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, double *grad);
 // time allocation (msnap_timeopt.hip): the whole iteration of a batch in one launch; cost, pg, iters may be null.
-// ends: from and to given end states (start / end: [n_drones][4][K-1] on the device, or null for rest)
+// mode 0: rest to rest; 1: from and to given end states (start / end: [n_drones][4][K-1] on the device, or null for
+// rest); 2: closed loop, the trial is the periodic solve
 int launch_optimize_times(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, const double *t, int shared_times,
-                          bool ends, const double *start, const double *end, const double *weights,
+                          int mode, const double *start, const double *end, const double *weights,
                           double min_fraction, int max_iter, double tol, double *t_out, double *coef, double *dur,
                           int32_t *status, double *cost, double *pg, int32_t *iters);
-// largest n_seg whose per-tile state fits LDS (80 at order 7, 58 at order 9; with ends: see DESIGN.md K8)
-int timeopt_max_segments(int khalf, bool ends);
+// (mode 2's instances and their launch: msnap_timeopt_periodic.hip)
+int launch_optimize_times_ring(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, const double *t,
+                               int shared_times, const double *weights, double min_fraction, int max_iter, double tol,
+                               double *t_out, double *coef, double *dur, int32_t *status, double *cost, double *pg,
+                               int32_t *iters);
+// largest n_seg whose per-tile state fits LDS (80 at order 7, 58 at order 9; mode 1: see DESIGN.md K8; mode 2: 48, 33)
+int timeopt_max_segments(int khalf, int mode);
 // (the pairwise pass: msnap_collide.h)
 int launch_mesh_sweep(msnap_ctx *ctx, int n_drones, int n_samples, const double *pos, int n_tris,
                       const double *tris, double radius, double *min_dist, int32_t *hit);

@@ -27,6 +27,7 @@
 //             returns at 0.
 // With two segments both couplings land on the one knot (Q_1 = G_1 + H_1) and the loops above run as written.
 #include "msnap_api_util.h"
+#include "msnap_ring.h"
 #include "msnap_rolled.h"
 
 namespace msnap {
@@ -54,19 +55,7 @@ static_assert(PeriodicLayout<4>::bytes(2) <= kMaxLdsBytes && PeriodicLayout<5>::
 static_assert(PeriodicLayout<4>::max_segments() == 27 && PeriodicLayout<5>::max_segments() == 18,
               "DESIGN.md K15 and include/msnap.h quote these");
 
-// (s + e) -= a b with the product and the sum error-free: s carries the running value, e collects what the roundings
-// dropped (two-product by fma, Knuth's two-sum)
-__device__ __forceinline__ void dd_submul(double &s, double &e, double a, double b) {
-#pragma clang fp contract(off)
-  const double p = a * b;
-  const double pe = __builtin_fma(a, b, -p);
-  const double t = s - p;
-  const double bb = t - s;
-  const double err = (s - (t - bb)) + (-p - bb);
-  s = t;
-  e = e + (err - pe);
-}
-
+// (dd_submul, the error-free multiply-subtract of the refinement pass: msnap_ring.h)
 template <int K>
 __global__ void __launch_bounds__(kWave)
 periodic_solve_kernel(const double *__restrict__ wp, const double *__restrict__ tt, int shared_times, int N, int M,

@@ -1,0 +1,438 @@
+// The ring elimination of K15 (msnap_periodic.hip has the derivation) as one device function over a
+// tile whose stash is drone-interleaved at a run-time tile size: the trial of the time allocation on closed loops,
+// timeopt_kernel<K, kTimeoptRing> (msnap_timeopt.hip).  lane = 4 drone + axis.
+//   forward   S_i = D_i - O_{i-1}^T G_{i-1}, G_i = S_i^-1 O_i, z_i = S_i^-1 (y_i - O_{i-1}^T z_{i-1}),
+//             H_1 = S_1^-1 O_0^T, H_i = -S_i^-1 O_{i-1}^T H_{i-1}                     u_i = z_i - G_i u_{i+1} - H_i u_0
+//   backward  p_{M-1} = z_{M-1}, Q_{M-1} = G_{M-1} + H_{M-1}, p_i = z_i - G_i p_{i+1}, Q_i = H_i - G_i Q_{i+1},
+//             over z and H                                                           u_i = p_i - Q_i u_0
+//   seam      (D_0 - O_{M-1}^T Q_{M-1} - O_0 Q_1) u_0 = y_0 - O_{M-1}^T p_{M-1} - O_0 p_1
+//   REFINE    K15's refinement step of all u_i (residual of the ring's rows with dd_submul, the same elimination for
+//             the correction with S_i factored again from the stashed G) and refine_end on the last segment
+//   recovery  recover_segment, last segment first, each handed to `seg`
+// dd_submul is K15's too and lives here for both.
+#pragma once
+
+#include "msnap_rolled.h"
+
+namespace msnap {
+
+// (s + e) -= a b with the product and the sum error-free: s carries the running value, e collects what the roundings
+// dropped (two-product by fma, Knuth's two-sum)
+__device__ __forceinline__ void dd_submul(double &s, double &e, double a, double b) {
+#pragma clang fp contract(off)
+  const double p = a * b;
+  const double pe = __builtin_fma(a, b, -p);
+  const double t = s - p;
+  const double bb = t - s;
+  const double err = (s - (t - bb)) + (-p - bb);
+  s = t;
+  e = e + (err - pe);
+}
+
+// One lane's view of its tile's stash, every pointer already at this lane's column:
+//   lw [(M+1)] at stride 4 (waypoints of this axis) | sT [M+1], sX [M] at stride TD (knots; 1/T, written here) |
+//   sG, sH [M-1][NU NU] at stride TD | sZ, sZ2 [M-1][NU] at stride 4 TD (sZ2: REFINE only)
+struct RingLane {
+  const double *lw, *sT;
+  double *sX, *sG, *sH, *sZ, *sZ2;
+  int TD;
+};
+
+// seg(i, c, T_i): segment i's coefficients, i = M-1 .. 0.  Returns true if a pivot, the seam block's included, is not
+// positive and finite.  The knots are taken as valid (increasing, finite): the caller has checked its inputs.
+template <int K, bool REFINE, class Seg>
+__device__ __forceinline__ bool ring_solve(const RingLane &p, int M, Seg &&seg) {
+  using SW = Sweep<K>;
+  using C = HermiteConsts<K>;
+  constexpr int NU = SW::NU, NC = SW::NC, KK = SW::KK, PM = SW::PM, NS = SW::NS;
+  const int TD = p.TD, QL = 4 * p.TD;
+  const double *lw = p.lw, *sT = p.sT;
+  double *sX = p.sX;
+  auto gslot = [&](double *base, int i) -> double * { return base + (size_t)(i - 1) * (NU * NU * TD); };   // knot i
+  auto zslot = [&](double *base, int i) -> double * { return base + (size_t)(i - 1) * (NU * QL); };
+
+  // ---------------- segment 0 ----------------
+  double tcur = sT[TD];
+  const double w0 = lw[0];
+  double wcur = lw[4];
+  double T = tcur - sT[0];
+  double x = rcp64(T);
+  const double x0 = x, dw0 = wcur - w0;
+  sX[0] = x;
+  SW sw;
+  sw.init(x, dw0);
+  // the carried right-hand side of H: O_0^T at knot 1, then -O_{i-1}^T H_{i-1}
+  double Cy[NU][NU];
+  {
+    double xp[PM + 1];
+    SW::powers(x, xp);
+#pragma unroll
+    for (int r = 0; r < NU; ++r)
+#pragma unroll
+      for (int c = 0; c < NU; ++c) Cy[r][c] = C::HSE[c + 1][r + 1] * xp[KK - (c + 1) - (r + 1)];
+  }
+
+  // ---------------- forward sweep over knots 1 .. M-1 ----------------
+  double tacc = 0.0;      // the durations before the current segment, summed as msnap_eval_flat sums them
+  for (int i = 1; i < M; ++i) {
+    const double tnext = sT[(i + 1) * TD];
+    const double wnext = lw[(i + 1) * 4];
+    tacc = tacc + T;
+    T = tnext - tcur;
+    x = rcp64(T);
+    sX[i * TD] = x;
+
+    typename SW::Knot k;
+    SW::knot_geom(x, wnext - wcur, sw.E, sw.re, k);
+    double S[NS], y[NU], dinv[NU];
+#pragma unroll
+    for (int n = 0; n < NU; ++n) {
+#pragma unroll
+      for (int m = 0; m <= n; ++m) S[sidx(n, m)] = k.D[sidx(n, m)] - sw.OtG[sidx(n, m)];
+      y[n] = -k.yb[n] - sw.Otz[n];
+    }
+    sw.singular |= SW::ldl_factor(S, dinv);
+
+    double *g = gslot(p.sG, i), *h = gslot(p.sH, i), *zz = zslot(p.sZ, i);
+    // G_i = S^-1 O_i column by column, and the Schur term O_i^T G_i (symmetric) for knot i+1
+    double G[NU][NU];
+#pragma unroll
+    for (int c = 0; c < NU; ++c) {
+      double v[NU];
+#pragma unroll
+      for (int r = 0; r < NU; ++r) v[r] = k.O[r][c];
+      SW::ldl_solve(S, dinv, v);
+#pragma unroll
+      for (int r = 0; r < NU; ++r) {
+        G[r][c] = v[r];
+        g[(r * NU + c) * TD] = v[r];
+      }
+    }
+    // z_i = S^-1 y_i
+    SW::ldl_solve(S, dinv, y);
+#pragma unroll
+    for (int r = 0; r < NU; ++r) zz[r * QL] = y[r];
+    // H_i = S^-1 Cy column by column; each column's carry -O_i^T H_i[:, c] replaces it
+#pragma unroll
+    for (int c = 0; c < NU; ++c) {
+      double v[NU];
+#pragma unroll
+      for (int r = 0; r < NU; ++r) v[r] = Cy[r][c];
+      SW::ldl_solve(S, dinv, v);
+#pragma unroll
+      for (int r = 0; r < NU; ++r) h[(r * NU + c) * TD] = v[r];
+#pragma unroll
+      for (int n = 0; n < NU; ++n) {
+        double w = 0.0;
+#pragma unroll
+        for (int q = 0; q < NU; ++q) w = __builtin_fma(-k.O[q][n], v[q], w);
+        Cy[n][c] = w;
+      }
+    }
+#pragma unroll
+    for (int n = 0; n < NU; ++n) {
+#pragma unroll
+      for (int m = 0; m <= n; ++m) {
+        double v = 0.0;
+#pragma unroll
+        for (int q = 0; q < NU; ++q) v = __builtin_fma(k.O[q][n], G[q][m], v);
+        sw.OtG[sidx(n, m)] = v;
+      }
+      double w = 0.0;
+#pragma unroll
+      for (int q = 0; q < NU; ++q) w = __builtin_fma(k.O[q][n], y[q], w);
+      sw.Otz[n] = w;
+    }
+#pragma unroll
+    for (int e = 0; e < NS; ++e) sw.E[e] = k.E[e];
+#pragma unroll
+    for (int r = 0; r < NU; ++r) sw.re[r] = k.re[r];
+    tcur = tnext;
+    wcur = wnext;
+  }
+  const double wM = wcur, tM = tcur;
+  // the local time msnap_eval_state evaluates the last segment at when asked for the sum of the durations
+  const double tl_end = (tacc + T) - tacc;
+
+  // ---------------- backward pass: u_i = p_i - Q_i u_0, p and Q over z and H ----------------
+  double pn[NU], Qn[NU][NU];      // of knot i+1
+  {
+    const double *g = gslot(p.sG, M - 1), *zz = zslot(p.sZ, M - 1);
+    double *h = gslot(p.sH, M - 1);
+#pragma unroll
+    for (int r = 0; r < NU; ++r) {
+      pn[r] = zz[r * QL];
+#pragma unroll
+      for (int c = 0; c < NU; ++c) {
+        Qn[r][c] = g[(r * NU + c) * TD] + h[(r * NU + c) * TD];
+        h[(r * NU + c) * TD] = Qn[r][c];
+      }
+    }
+  }
+  double pL[NU], QLm[NU][NU];      // of knot M-1, for the seam
+#pragma unroll
+  for (int r = 0; r < NU; ++r) {
+    pL[r] = pn[r];
+#pragma unroll
+    for (int c = 0; c < NU; ++c) QLm[r][c] = Qn[r][c];
+  }
+  for (int i = M - 2; i >= 1; --i) {
+    const double *g = gslot(p.sG, i);
+    double *h = gslot(p.sH, i), *zz = zslot(p.sZ, i);
+    double gq[NU][NU], pp[NU], Q[NU][NU];
+#pragma unroll
+    for (int r = 0; r < NU; ++r) {
+      pp[r] = zz[r * QL];
+#pragma unroll
+      for (int c = 0; c < NU; ++c) {
+        gq[r][c] = g[(r * NU + c) * TD];
+        Q[r][c] = h[(r * NU + c) * TD];
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < NU; ++r) {
+#pragma unroll
+      for (int q = 0; q < NU; ++q) {
+        pp[r] = __builtin_fma(-gq[r][q], pn[q], pp[r]);
+#pragma unroll
+        for (int c = 0; c < NU; ++c) Q[r][c] = __builtin_fma(-gq[r][q], Qn[q][c], Q[r][c]);
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < NU; ++r) {
+      zz[r * QL] = pp[r];
+      pn[r] = pp[r];
+#pragma unroll
+      for (int c = 0; c < NU; ++c) {
+        h[(r * NU + c) * TD] = Q[r][c];
+        Qn[r][c] = Q[r][c];
+      }
+    }
+  }
+  // (pn, Qn are knot 1's now; with two segments knot 1 is knot M-1)
+
+  // ---------------- the seam knot: left segment M-1, right segment 0 ----------------
+  double u0[NU];
+  typename SW::Knot k0;        // D_0 = E_{M-1} + SS_0, yb_0, O_0
+  double OL[NU][NU];           // O_{M-1}
+  double S0[NS], dinv0[NU];    // the seam block and its factor (REFINE: kept for the correction)
+  {
+    SW::knot_geom(x0, dw0, sw.E, sw.re, k0);
+    double xp[PM + 1];
+    SW::powers(x, xp);         // x = 1 / T_{M-1}
+#pragma unroll
+    for (int n = 0; n < NU; ++n)
+#pragma unroll
+      for (int m = 0; m < NU; ++m) OL[n][m] = C::HSE[n + 1][m + 1] * xp[KK - (n + 1) - (m + 1)];
+#pragma unroll
+    for (int n = 0; n < NU; ++n) {
+#pragma unroll
+      for (int m = 0; m <= n; ++m) {
+        double v = k0.D[sidx(n, m)];
+#pragma unroll
+        for (int q = 0; q < NU; ++q) v = __builtin_fma(-OL[q][n], QLm[q][m], v);
+#pragma unroll
+        for (int q = 0; q < NU; ++q) v = __builtin_fma(-k0.O[n][q], Qn[q][m], v);
+        S0[sidx(n, m)] = v;
+      }
+      double w = -k0.yb[n];
+#pragma unroll
+      for (int q = 0; q < NU; ++q) w = __builtin_fma(-OL[q][n], pL[q], w);
+#pragma unroll
+      for (int q = 0; q < NU; ++q) w = __builtin_fma(-k0.O[n][q], pn[q], w);
+      u0[n] = w;
+    }
+    sw.singular |= SW::ldl_factor(S0, dinv0);
+    SW::ldl_solve(S0, dinv0, u0);
+  }
+
+  // ---------------- REFINE: residual of the ring in extended precision, the same elimination ----------------
+  double du0[NU];
+#pragma unroll
+  for (int r = 0; r < NU; ++r) du0[r] = 0.0;
+  if constexpr (REFINE) {
+    // u_j of knot j from the stash (j = 0 and j = M: the seam)
+    auto knot_u = [&](int j, double (&u)[NU]) {
+      if (j >= 1 && j <= M - 1) {
+        const double *h = gslot(p.sH, j), *zz = zslot(p.sZ, j);
+#pragma unroll
+        for (int r = 0; r < NU; ++r) {
+          double v = zz[r * QL];
+#pragma unroll
+          for (int c = 0; c < NU; ++c) v = __builtin_fma(-h[(r * NU + c) * TD], u0[c], v);
+          u[r] = v;
+        }
+      } else {
+#pragma unroll
+        for (int r = 0; r < NU; ++r) u[r] = u0[r];
+      }
+    };
+    // r = y - OP^T up - D uc - ON un, row by row
+    auto residual = [&](const double (&yb)[NU], const double (&D)[NS], const double (&OP)[NU][NU],
+                        const double (&ON)[NU][NU], const double (&up)[NU], const double (&uc)[NU],
+                        const double (&un_)[NU], double (&r)[NU]) {
+#pragma unroll
+      for (int n = 0; n < NU; ++n) {
+        double s = -yb[n], e = 0.0;
+#pragma unroll
+        for (int q = 0; q < NU; ++q) dd_submul(s, e, OP[q][n], up[q]);
+#pragma unroll
+        for (int q = 0; q < NU; ++q) dd_submul(s, e, D[n >= q ? sidx(n, q) : sidx(q, n)], uc[q]);
+#pragma unroll
+        for (int q = 0; q < NU; ++q) dd_submul(s, e, ON[n][q], un_[q]);
+        r[n] = s + e;
+      }
+    };
+    SW s2;
+    s2.init(x0, dw0);          // the end side of segment 0 again; s2.Otz carries O_{i-1}^T z'_{i-1}
+    double OP[NU][NU];         // O_{i-1}
+#pragma unroll
+    for (int n = 0; n < NU; ++n)
+#pragma unroll
+      for (int m = 0; m < NU; ++m) OP[n][m] = k0.O[n][m];
+    double up[NU], uc[NU], un_[NU];
+    knot_u(0, up);
+    knot_u(1, uc);
+    double wc = lw[4];
+    for (int i = 1; i < M; ++i) {
+      const double wnx = lw[(i + 1) * 4];
+      const double xi = sX[i * TD];
+      knot_u(i + 1, un_);
+      typename SW::Knot k;
+      SW::knot_geom(xi, wnx - wc, s2.E, s2.re, k);
+      double S[NS], dinv[NU], r[NU];
+      if (i >= 2) {            // S_i = D_i - O_{i-1}^T G_{i-1} from the stash, as the forward sweep formed it
+        const double *g = gslot(p.sG, i - 1);
+        double G[NU][NU];
+#pragma unroll
+        for (int rr = 0; rr < NU; ++rr)
+#pragma unroll
+          for (int c = 0; c < NU; ++c) G[rr][c] = g[(rr * NU + c) * TD];
+#pragma unroll
+        for (int n = 0; n < NU; ++n)
+#pragma unroll
+          for (int m = 0; m <= n; ++m) {
+            double v = 0.0;
+#pragma unroll
+            for (int q = 0; q < NU; ++q) v = __builtin_fma(OP[q][n], G[q][m], v);
+            S[sidx(n, m)] = k.D[sidx(n, m)] - v;
+          }
+      } else {
+#pragma unroll
+        for (int e = 0; e < NS; ++e) S[e] = k.D[e] - 0.0;
+      }
+      SW::ldl_factor(S, dinv);
+      residual(k.yb, k.D, OP, k.O, up, uc, un_, r);
+#pragma unroll
+      for (int n = 0; n < NU; ++n) r[n] = r[n] - s2.Otz[n];
+      SW::ldl_solve(S, dinv, r);
+      double *z2 = zslot(p.sZ2, i);
+#pragma unroll
+      for (int n = 0; n < NU; ++n) z2[n * QL] = r[n];
+#pragma unroll
+      for (int n = 0; n < NU; ++n) {
+        double w = 0.0;
+#pragma unroll
+        for (int q = 0; q < NU; ++q) w = __builtin_fma(k.O[q][n], r[q], w);
+        s2.Otz[n] = w;
+      }
+#pragma unroll
+      for (int n = 0; n < NU; ++n) {
+#pragma unroll
+        for (int m = 0; m < NU; ++m) OP[n][m] = k.O[n][m];
+        up[n] = uc[n];
+        uc[n] = un_[n];
+      }
+#pragma unroll
+      for (int e = 0; e < NS; ++e) s2.E[e] = k.E[e];
+#pragma unroll
+      for (int rr = 0; rr < NU; ++rr) s2.re[rr] = k.re[rr];
+      wc = wnx;
+    }
+    // backward: p'_i = z'_i - G_i p'_{i+1} over z'
+    double qn[NU], qL[NU];     // p' of knot i+1, of knot M-1
+    {
+      const double *z2 = zslot(p.sZ2, M - 1);
+#pragma unroll
+      for (int r = 0; r < NU; ++r) qn[r] = qL[r] = z2[r * QL];
+    }
+    for (int i = M - 2; i >= 1; --i) {
+      const double *g = gslot(p.sG, i);
+      double *z2 = zslot(p.sZ2, i);
+      double q[NU];
+#pragma unroll
+      for (int r = 0; r < NU; ++r) {
+        double v = z2[r * QL];
+#pragma unroll
+        for (int c = 0; c < NU; ++c) v = __builtin_fma(-g[(r * NU + c) * TD], qn[c], v);
+        q[r] = v;
+      }
+#pragma unroll
+      for (int r = 0; r < NU; ++r) {
+        z2[r * QL] = q[r];
+        qn[r] = q[r];
+      }
+    }
+    // the seam row: left knot M-1, right knot 1 (up is u_{M-1} after the loop, uc is u_M = u_0)
+    double u1[NU];
+    knot_u(1, u1);
+    residual(k0.yb, k0.D, OL, k0.O, up, uc, u1, du0);
+#pragma unroll
+    for (int n = 0; n < NU; ++n) {
+      double w = du0[n];
+#pragma unroll
+      for (int q = 0; q < NU; ++q) w = __builtin_fma(-OL[q][n], qL[q], w);
+#pragma unroll
+      for (int q = 0; q < NU; ++q) w = __builtin_fma(-k0.O[n][q], qn[q], w);
+      du0[n] = w;
+    }
+    SW::ldl_solve(S0, dinv0, du0);
+  }
+  double us[NU];               // the seam state (REFINE: refined)
+#pragma unroll
+  for (int r = 0; r < NU; ++r) {
+    if constexpr (REFINE) us[r] = u0[r] + du0[r];
+    else us[r] = u0[r];
+  }
+
+  // ---------------- recovery, last segment first ----------------
+  double un[NU];
+#pragma unroll
+  for (int r = 0; r < NU; ++r) un[r] = us[r];      // u_M = u_0
+  double wn = wM, tn = tM;
+  for (int i = M - 1; i >= 0; --i) {
+    double u[NU];
+    const double wi = lw[i * 4];
+    const double ti = sT[i * TD];
+    const double xi = sX[i * TD];
+    const int kq = i >= 1 ? i : 1;      // (segment 0 starts from the seam state; its loads replay knot 1's)
+    const double *h = gslot(p.sH, kq), *zz = zslot(p.sZ, kq);
+#pragma unroll
+    for (int r = 0; r < NU; ++r) {
+      double v = zz[r * QL];
+#pragma unroll
+      for (int c = 0; c < NU; ++c) v = __builtin_fma(-h[(r * NU + c) * TD], u0[c], v);
+      if constexpr (REFINE) {
+        double dv = zslot(p.sZ2, kq)[r * QL];
+#pragma unroll
+        for (int c = 0; c < NU; ++c) dv = __builtin_fma(-h[(r * NU + c) * TD], du0[c], dv);
+        v = v + dv;
+      }
+      u[r] = i >= 1 ? v : us[r];
+    }
+    double c[NC];
+    recover_segment<K>(wi, wn - wi, xi, u, un, c);
+    if constexpr (REFINE) {
+      // the last segment takes one refinement step on its end conditions, the solved seam state as its end vector
+      if (i == M - 1) refine_end<K>(c, tl_end, xi, wn, un);
+    }
+    seg(i, c, tn - ti);
+#pragma unroll
+    for (int r = 0; r < NU; ++r) un[r] = u[r];
+    wn = wi;
+    tn = ti;
+  }
+  return sw.singular;
+}
+
+}  // namespace msnap

@@ -21,7 +21,7 @@ struct RolledTile {
 };
 
 // one coalesced pass over a tile's state block ([nvalid][4][NU], contiguous) into its LDS image [64][pitch]
-// (shared by states_solve_kernel and timeopt_kernel<K, true>, which passes its own tile's block and tile = 0)
+// (shared by states_solve_kernel and timeopt_kernel<K, kTimeoptEnds>, which passes its own tile's block and tile = 0)
 template <int NU, int PITCH>
 __device__ __forceinline__ void load_states(const double *__restrict__ src, int tile, int nvalid, int lane,
                                             double (&v)[NU]) {

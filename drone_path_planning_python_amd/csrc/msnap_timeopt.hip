@@ -1,484 +1,27 @@
 // K8 -- segment-time optimisation per drone, one launch for the whole iteration (include/msnap.h, "time allocation";
-// DESIGN.md §5 K8).
-//
-// Per drone: minimise J(T) = sum_a w_a J_a over the segment durations with sum T_i and the waypoints fixed,
-// T_i >= T_min.  dJ/dT_i = -sum_a w_a E_i,a with E the conserved Ostrogradsky energy of segment i (envelope theorem:
-// no adjoint sweep), so one block-LDL^T solve gives cost and gradient.  Method: projected gradient descent with Armijo
-// backtracking; the iterate is the knot times, a trial is "knots -> durations as the solve entries take them -> solve".
-//
-// Mapping as K1: lane = 4 * drone + axis, a wavefront carries one tile of 16 drones (8 when the 16-drone stash does
-// not fit LDS; lanes 32..63 then replay the tile's last drone as the lanes past a batch end always do).  The
-// arithmetic per knot and segment is Sweep<K> / recover_segment of msnap_sweep.h.  Everything a drone carries between
-// trials lives in LDS, drone-interleaved ([index][drone]): current and trial knots, the gradient at both, the descent
-// direction, 1/T, G_i, z_i.  The four axis lanes of a drone write the same bits to the same address, so nothing one
-// lane reads was written by another and no fence is needed after the input stage.
-//
-// Control flow.  Drones need different numbers of trials.  The trial loop runs while any lane of the wave has a trial
-// to make (__ballot), every lane runs its body, and what a finished drone would change is held back by selects -- no
-// loop the lanes leave one by one.  Cost and gradient are combined over the quad with quad_bcast in
-// the fixed order ((x + y) + z) + yaw, so the four lanes hold the same bits and take the same decisions.
-//
-// Given end states (msnap_optimize_times_states): timeopt_kernel<K, true>.  The end knots' derivative vectors are data
-// as in the boundary-state solve (msnap_rolled.h, ENDS); the gradient is the same expression -- the first and last
-// segment's outer end states are fixed either way.  What differs from the rest-to-rest instance is one `if constexpr`
-// each: the state images in LDS, their finiteness check, the seed of the sweep's carried term, the backward sweep from
-// u_M through the last knot's G, segment 0 from u_0, and refine_end on the last segment when the coefficients leave.
-#include <math.h>
-
-#include <type_traits>
-
-#include "msnap_api_util.h"
-#include "msnap_internal.h"
-#include "msnap_rolled.h"
-#include "msnap_sweep.h"
+// DESIGN.md §5 K8).  The kernel text, its LDS layout and the launcher are msnap_timeopt_kernel.h; this translation unit
+// instantiates the rest-to-rest and the end-state mode and holds every entry point, msnap_timeopt_periodic.hip the ring
+// mode (msnap_optimize_times_periodic).
+#include "msnap_timeopt_kernel.h"
 
 namespace msnap {
-namespace {
 
-constexpr double kArmijo = 1e-4;       // accept when J_new <= J - kArmijo * a * |P g|^2
-constexpr int kMaxHalvings = 30;       // rejected trials in a row after which the line search gives up
-constexpr double kBoundRel = 1e-9;     // a segment within T_min (1 + kBoundRel) is at its bound
+int timeopt_max_segments(int khalf, int mode) { return timeopt_tile_segments(khalf, 8, mode); }
 
-struct TimeoptArgs {
-  const double *wp, *tt;
-  int shared_times, N, M, TD;
-  double w[4];
-  double min_fraction, tol;
-  int max_iter;
-  double *t_out, *coef, *dur;
-  int32_t *status;
-  double *cost, *pg;
-  int32_t *iters;
-};
-// ENDS: the tile's end states, [n_drones][4][K-1] each (msnap_solve_states's layout); a null block is rest
-struct TimeoptEndsArgs : TimeoptArgs {
-  const double *start, *end;
-};
-
-// w_0 v_0 + .. + w_3 v_3 over the quad, the same bits in its four lanes; an axis of weight 0 is not looked at
-__device__ __forceinline__ double quad_weighted_sum(double v, double wa) {
-  const double p = wa == 0.0 ? 0.0 : wa * v;
-  return ((quad_bcast<0>(p) + quad_bcast<1>(p)) + quad_bcast<2>(p)) + quad_bcast<3>(p);
-}
-
-// ENDS: the end knots' derivative vectors u_0, u_M are data (msnap_optimize_times_states), as in rolled_solve_tile
-template <int K, bool ENDS>
-__global__ void __launch_bounds__(kWave)
-timeopt_kernel(const std::conditional_t<ENDS, TimeoptEndsArgs, TimeoptArgs> p) {
-  using SW = Sweep<K>;
-  using C = HermiteConsts<K>;
-  constexpr int NU = SW::NU, NC = SW::NC, KK = SW::KK, PM = SW::PM, PITCH = NU | 1;
-
-  extern __shared__ __attribute__((aligned(16))) double lds[];
-
-  const int lane = threadIdx.x;
-  const int dl = lane >> 2;
-  const int a = lane & 3;
-  const int M = p.M, TD = p.TD, QL = 4 * p.TD;
-  const int knots = M - 1;
-  const int wpitch = (M + 1) * 4;
-  const int tpitch = M + 1;
-  const int tile = blockIdx.x;
-  const int left = p.N - tile * TD;
-  const int nvalid = left < TD ? left : TD;
-  // lanes past the tile's drones replay its last one (and store on top of its results)
-  const bool live = dl < nvalid;
-  const int dloc = live ? dl : nvalid - 1;
-  const int ql = dloc * 4 + a;
-  const size_t d = (size_t)tile * TD + dloc;
-
-  // LDS: Tr (order 9 only: output transpose image) | Wraw[TD][(M+1)*4] | Traw[TD][M+1] (inputs, then the final knots)
-  //      | Tc, Tt [M+1][TD] | Gc, Gt, D, X [M][TD] | G[knots][NU*NU][TD] | Z[knots][NU][4 TD]
-  //      | ENDS: S0, S1 [4 TD][PITCH] (start and end state of every lane, at K13's odd pitch)
-  double2 *sTr = reinterpret_cast<double2 *>(lds);
-  double *sWraw = lds + (NC == 8 ? 0 : (NC / 2) * kTrPitch * 2);
-  double *sTraw = sWraw + TD * wpitch;
-  double *sTc = sTraw + TD * tpitch + dloc;          // (this drone's column)
-  double *sTt = sTc + TD * tpitch;                   // (this drone's column)
-  double *sGc = sTraw + 3 * TD * tpitch;
-  double *sGt = sGc + TD * M;
-  double *sD = sGt + TD * M;
-  double *sX = sD + TD * M;
-  double *sG = sX + TD * M;
-  double *sZ = sG + (size_t)TD * NU * NU * knots + ql;   // (this lane's column)
-  double *sS = sG + (size_t)TD * (NU * NU + 4 * NU) * knots;   // (ENDS only)
-  const double *sS0 = sS + ql * PITCH;                         // (this lane's rows)
-  const double *sS1 = sS0 + QL * PITCH;
-
-  // ENDS: the state blocks travel with the input stage, every load in flight before the first LDS store; a missing
-  // block is staged as zeros, so nothing below asks which were given
-  double v0[NU], v1[NU];
-  if constexpr (ENDS) {
-#pragma unroll
-    for (int q = 0; q < NU; ++q) v0[q] = v1[q] = 0.0;
-    if (p.start) load_states<NU, PITCH>(p.start + (size_t)tile * QL * NU, 0, nvalid, lane, v0);
-    if (p.end) load_states<NU, PITCH>(p.end + (size_t)tile * QL * NU, 0, nvalid, lane, v1);
-  }
-  stage_inputs(p.wp + (size_t)tile * TD * wpitch, p.shared_times ? p.tt : p.tt + (size_t)tile * TD * tpitch,
-               p.shared_times, 0, nvalid, wpitch, tpitch, sWraw, sTraw, lane);
-  if constexpr (ENDS) {
-    store_states<NU, PITCH>(sS, nvalid, lane, v0);
-    store_states<NU, PITCH>(sS + QL * PITCH, nvalid, lane, v1);
-  }
-  __syncthreads();
-  const double *lw = sWraw + dloc * wpitch + a;
-  const double *lt = sTraw + (p.shared_times ? 0 : dloc * tpitch);
-  const double wa = a == 0 ? p.w[0] : a == 1 ? p.w[1] : a == 2 ? p.w[2] : p.w[3];
-
-  // ---------------- input checks, the floor, the start point ----------------
-  const double t0 = lt[0];
-  const double ttotal = lt[M];
-  bool nonfinite = !finite64(t0) | !finite64(lw[0]);
-  bool badtime = t0 != 0.0;
-  for (int i = 0; i < M; ++i) {
-    nonfinite |= !finite64(lt[i + 1]) | !finite64(lw[(i + 1) * 4]);
-    badtime |= !(lt[i + 1] - lt[i] > 0.0);
-  }
-  if constexpr (ENDS) {      // data, and checked like every other input
-#pragma unroll
-    for (int q = 0; q < NU; ++q) nonfinite |= !finite64(sS0[q]) | !finite64(sS1[q]);
-  }
-  const double Tmin = p.min_fraction * ttotal / (double)M;
-  // durations below the floor are raised to it; the others keep T_min plus their excess over it scaled by one factor
-  // that pays for the raise: the sum is kept, nothing falls below the floor, and a feasible input is not touched
-  double excess = 0.0, slack = 0.0;
-  bool anybelow = false;
-  for (int i = 0; i < M; ++i) {
-    const double T = lt[i + 1] - lt[i];
-    const bool below = T < Tmin;
-    anybelow |= below;
-    excess += below ? Tmin - T : 0.0;
-    slack += below ? 0.0 : T - Tmin;
-  }
-  const double keep = slack > 0.0 ? fmax(1.0 - excess / slack, 0.0) : 0.0;
-  {
-    double t = 0.0;
-    sTc[0] = t0;
-    for (int i = 0; i < M; ++i) {
-      const double T = lt[i + 1] - lt[i];
-      const double Tn = T < Tmin ? Tmin : fma(T - Tmin, keep, Tmin);
-      const double tn = i == M - 1 ? ttotal : t + Tn;
-      sTc[(i + 1) * TD] = anybelow ? tn : lt[i + 1];
-      sD[i * TD + dloc] = 0.0;
-      t = tn;
-    }
-  }
-
-  // ---------------- one trial: solve for the knots sT, cost, gradient (EMIT: the coefficients leave) ----------------
-  auto trial = [&](auto emit, const double *sT, double *sGrad, bool bad, double &Jw, bool &singular) {
-    constexpr bool EMIT = decltype(emit)::value;
-    double tcur = sT[TD];
-    double wcur = lw[4];
-    double x = rcp64(tcur - sT[0]);
-    sX[dloc] = x;
-    SW sw;
-    sw.init(x, wcur - lw[0]);
-    if constexpr (ENDS) {
-      // knot 1 sees the start state through the coupling block of segment 0: Otz = O_0^T u_0 (rolled_solve_tile)
-      double xp[PM + 1];
-      SW::powers(x, xp);
-#pragma unroll
-      for (int n = 0; n < NU; ++n) {
-        double w = 0.0;
-#pragma unroll
-        for (int q = 0; q < NU; ++q) w = __builtin_fma(C::HSE[q + 1][n + 1] * xp[KK - (q + 1) - (n + 1)], sS0[q], w);
-        sw.Otz[n] = w;
-      }
-    }
-    for (int i = 1; i < M; ++i) {
-      const double tnext = sT[(i + 1) * TD];
-      const double wnext = lw[(i + 1) * 4];
-      x = rcp64(tnext - tcur);
-      sX[i * TD + dloc] = x;
-      double G[NU][NU], z[NU];
-      sw.step(x, wnext - wcur, G, z);
-      double *g = sG + (size_t)(i - 1) * (NU * NU * TD) + dloc;
-      double *zz = sZ + (size_t)(i - 1) * (NU * QL);
-#pragma unroll
-      for (int r = 0; r < NU; ++r) {
-#pragma unroll
-        for (int c = 0; c < NU; ++c) g[(r * NU + c) * TD] = G[r][c];
-        zz[r * QL] = z[r];
-      }
-      tcur = tnext;
-      wcur = wnext;
-    }
-    singular = sw.singular;
-
-    double un[NU];
-#pragma unroll
-    for (int r = 0; r < NU; ++r) {
-      if constexpr (ENDS) un[r] = sS1[r];      // the backward sweep starts from u_M
-      else un[r] = 0.0;
-    }
-    double wn = wcur, tn = tcur;   // w_M, t_M
-    // ENDS: the local time msnap_eval_state evaluates the last segment at when asked for the sum of the durations --
-    // of the durations as they are stored, the differences of these knots
-    double tl_end = 0.0;
-    if constexpr (ENDS && EMIT) {
-      double tacc = 0.0;
-      for (int i = 0; i < M - 1; ++i) tacc = tacc + (sT[(i + 1) * TD] - sT[i * TD]);
-      tl_end = (tacc + (tn - sT[(M - 1) * TD])) - tacc;
-    }
-    double Ja = 0.0;
-    for (int i = M - 1; i >= 0; --i) {
-      double u[NU];
-      const int kq = i >= 1 ? i - 1 : 0;   // stash slot of knot i
-      const double *zz = sZ + (size_t)kq * (NU * QL);
-      const double *g = sG + (size_t)kq * (NU * NU * TD) + dloc;
-#pragma unroll
-      for (int r = 0; r < NU; ++r) {
-        double v = i >= 1 ? zz[r * QL] : 0.0;
-        // (ENDS: the stash holds G of the last knot too, and with two segments the one knot receives both end terms)
-        if (ENDS || i < M - 1) {
-#pragma unroll
-          for (int c = 0; c < NU; ++c) v = __builtin_fma(-(i >= 1 ? g[(r * NU + c) * TD] : 0.0), un[c], v);
-        }
-        if constexpr (ENDS) u[r] = i >= 1 ? v : sS0[r];      // segment 0 starts from u_0
-        else u[r] = i >= 1 ? v : 0.0;
-      }
-      const double wi = lw[i * 4];
-      const double ti = sT[i * TD];
-      double c[NC];
-      recover_segment<K>(wi, wn - wi, sX[i * TD + dloc], u, un, c);
-      Ja += segment_cost<K>(c, tn - ti);
-      const double gi = -quad_weighted_sum(ostrogradsky_energy<K>(c), wa);
-      if constexpr (EMIT) {
-        // the last segment leaves with one refinement step on its end conditions; cost and gradient above are the
-        // unrefined coefficients', as in every trial
-        if constexpr (ENDS) {
-          if (i == M - 1) refine_end<K>(c, tl_end, sX[i * TD + dloc], wn, un);
-        }
-        double *base = p.coef + ((size_t)tile * TD * M + i) * (4 * NC);
-        if constexpr (NC == 8) store_segment_quad8(base, MSNAP_SEG_STRIDE(M, NC), nvalid, lane, c, bad);
-        else store_segment_coalesced<NC>(sTr, base, MSNAP_SEG_STRIDE(M, NC), nvalid, lane, c, bad);
-      } else {
-        sGrad[i * TD + dloc] = gi;
-      }
-#pragma unroll
-      for (int r = 0; r < NU; ++r) un[r] = u[r];
-      wn = wi;
-      tn = ti;
-    }
-    Jw = quad_weighted_sum(Ja, wa);
-  };
-
-  // ---------------- the iteration ----------------
-  // Descent direction -P g at the current point (Tc, Gc) into D: the mean of g is removed over the free segments; a
-  // segment at its bound whose direction points below it leaves the free set, until none does (bitmask: n_seg <= 128).
-  // A pure function of (Tc, Gc): run again on an unchanged point it gives the same bits.
-  struct Direction {
-    double n2, dmax, Tsmall, cap;   // |P g|^2, max |d_i|, min T_i, the step that takes the first T_i to the floor
-  };
-  auto direction = [&]() -> Direction {
-    unsigned long long fix0 = 0, fix1 = 0;
-    double mean = 0.0;
-    bool changed = true;
-    while (__ballot(changed) != 0) {
-      double sum = 0.0;
-      int cnt = 0;
-      for (int i = 0; i < M; ++i) {
-        const bool fixed = (((i < 64 ? fix0 : fix1) >> (i & 63)) & 1ull) != 0;
-        sum += fixed ? 0.0 : sGc[i * TD + dloc];
-        cnt += fixed ? 0 : 1;
-      }
-      const double m = sum / (double)(cnt > 0 ? cnt : 1);
-      mean = cnt > 0 ? m : 0.0;
-      changed = false;
-      for (int i = 0; i < M; ++i) {
-        const bool fixed = (((i < 64 ? fix0 : fix1) >> (i & 63)) & 1ull) != 0;
-        const double T = sTc[(i + 1) * TD] - sTc[i * TD];
-        const bool leaves = !fixed & (T - Tmin <= kBoundRel * Tmin) & (mean - sGc[i * TD + dloc] < 0.0);
-        const unsigned long long bit = leaves ? 1ull << (i & 63) : 0ull;
-        fix0 |= i < 64 ? bit : 0ull;
-        fix1 |= i < 64 ? 0ull : bit;
-        changed |= leaves;
-      }
-    }
-    Direction r = {0.0, 0.0, ttotal, __builtin_inf()};
-    for (int i = 0; i < M; ++i) {
-      const bool fixed = (((i < 64 ? fix0 : fix1) >> (i & 63)) & 1ull) != 0;
-      const double di = fixed ? 0.0 : mean - sGc[i * TD + dloc];
-      const double T = sTc[(i + 1) * TD] - sTc[i * TD];
-      sD[i * TD + dloc] = di;
-      r.n2 = fma(di, di, r.n2);
-      r.dmax = fmax(r.dmax, fabs(di));
-      r.Tsmall = fmin(r.Tsmall, T);
-      const double reach = (T - Tmin) / (di < 0.0 ? -di : 1.0);
-      r.cap = fmin(r.cap, di < 0.0 ? reach : __builtin_inf());
-    }
-    return r;
-  };
-  // a trial counts when no pivot failed and its cost is finite: one answer for the four lanes
-  auto usable = [&](bool singular, double Jn) {
-    int f = (!singular & finite64(Jn)) ? 0 : 1;
-    f |= __shfl_xor(f, 1);
-    f |= __shfl_xor(f, 2);
-    return f == 0;
-  };
-  const double sqrtM = sqrt((double)M);
-  auto measure = [&](double n2, double Jc) {
-    const double v = sqrt(n2) * ttotal / (sqrtM * Jc);
-    return Jc > 0.0 ? v : 0.0;      // (a path that costs nothing is optimal)
-  };
-
-  // the start point
-  double J;
-  bool sing0;
-  trial(std::false_type{}, sTc, sGc, false, J, sing0);
-  const int st_in = drone_status(nonfinite, badtime, false);
-  const int st = st_in ? st_in : (usable(sing0, J) ? MSNAP_ST_OK : MSNAP_ST_SINGULAR);
-  const double J0 = J;
-  Direction dr = direction();
-  double pgm = measure(dr.n2, J);
-  // first proposal: a quarter of the smallest segment for the largest component; the step is the proposal, capped
-  double prop = 0.25 * dr.Tsmall / dr.dmax;
-  double step = fmin(prop, dr.cap);
-  int iters = 0, nback = 0;
-  bool run = (st == MSNAP_ST_OK) & (pgm > p.tol) & (p.max_iter > 0) & (dr.dmax > 0.0) & (step > 0.0);
-  while (__ballot(run) != 0) {
-    // trial knots: T_i + step * d_i, not below the floor, summed from 0; the last knot is the input's, bit for bit
-    {
-      double t = 0.0;
-      sTt[0] = sTc[0];
-      for (int i = 0; i < M; ++i) {
-        const double Tn = fmax(fma(step, sD[i * TD + dloc], sTc[(i + 1) * TD] - sTc[i * TD]), Tmin);
-        const double tn = i == M - 1 ? ttotal : t + Tn;
-        sTt[(i + 1) * TD] = tn;
-        t = tn;
-      }
-    }
-    double Jn;
-    bool singular;
-    trial(std::false_type{}, sTt, sGt, false, Jn, singular);
-    const bool accept = run & usable(singular, Jn) & (Jn <= J - kArmijo * step * dr.n2);
-    const bool capped = step >= dr.cap;
-    J = accept ? Jn : J;
-    iters += accept ? 1 : 0;
-    for (int i = 0; i < M; ++i) {
-      sTc[(i + 1) * TD] = accept ? sTt[(i + 1) * TD] : sTc[(i + 1) * TD];
-      sGc[i * TD + dloc] = accept ? sGt[i * TD + dloc] : sGc[i * TD + dloc];
-    }
-    dr = direction();          // (unchanged bits where the point did not move)
-    pgm = measure(dr.n2, J);
-    // next proposal: twice an accepted step (the proposal again when the floor cut the step short), half a rejected one
-    const double up = capped ? prop : 2.0 * step;
-    const double nprop = accept ? up : 0.5 * step;
-    nback = accept ? 0 : nback + 1;
-    const double next = fmin(nprop, dr.cap);
-    const bool done = accept ? (!(pgm > p.tol) | (iters >= p.max_iter) | !(dr.dmax > 0.0) | !(next > 0.0))
-                             : (nback >= kMaxHalvings);
-    step = run ? next : step;
-    prop = run ? nprop : prop;
-    run = run & !done;
-  }
-
-  // ---------------- results ----------------
-  const bool bad = st != MSNAP_ST_OK;
-  {
-    double Jf;
-    bool sf;
-    trial(std::true_type{}, sTc, sGt, bad, Jf, sf);
-  }
-  // the knots in drone-major order for the coalesced sweeps (Traw: the inputs are dead)
-  wave_lds_fence();
-  for (int i = 0; i <= M; ++i) sTraw[dloc * tpitch + i] = bad ? __builtin_nan("") : sTc[i * TD];
-  wave_lds_fence();
-  store_durations(sTraw, 0, tpitch, M, nvalid, lane, p.dur + (size_t)tile * TD * M);
-  {
-    const int cnt = nvalid * tpitch;
-    double *dst = p.t_out + (size_t)tile * TD * tpitch;
-    for (int e0 = 0; e0 < cnt; e0 += kWave) {      // (uniform_for of msnap_wave.h written out, as store_durations is:
-      const int e = e0 + lane;                      // the helper's inlining order moves instructions in this kernel)
-      if (e < cnt) dst[e] = sTraw[e];
-    }
-  }
-  if (live && a == 0) {
-    p.status[d] = st;
-    if (p.cost) {
-      p.cost[2 * d] = bad ? __builtin_nan("") : J0;
-      p.cost[2 * d + 1] = bad ? __builtin_nan("") : J;
-    }
-    if (p.pg) p.pg[d] = bad ? __builtin_nan("") : pgm;
-    if (p.iters) p.iters[d] = iters;
-  }
-}
-
-// doubles of LDS one tile of TD drones needs (ends: with the two state images)
-size_t timeopt_lds_words(int khalf, int M, int TD, bool ends) {
-  const size_t nu = (size_t)khalf - 1, knots = (size_t)M - 1, m = (size_t)M;
-  const size_t tr = khalf == 4 ? 0 : (size_t)khalf * kTrPitch * 2;
-  const size_t states = ends ? 2 * (size_t)TD * 4 * (nu | 1) : 0;
-  return tr + (size_t)TD * ((m + 1) * 4 + (m + 1) + 2 * (m + 1) + 4 * m + nu * nu * knots + 4 * nu * knots) + states;
-}
-
-}  // namespace
-
-int timeopt_max_segments(int khalf, bool ends) {
-  int m = 1;
-  while (m < 128 && timeopt_lds_words(khalf, m + 1, 8, ends) * sizeof(double) <= kMaxLdsBytes) ++m;
-  return m;
-}
-
-// allow the full 160 KiB of dynamic LDS (once per context: a function attribute is a property of the device's module)
-static int timeopt_kernel_setup(msnap_ctx *ctx) {
-  if (ctx->timeopt_ready) return MSNAP_OK;
-  for (const void *k : {reinterpret_cast<const void *>(&timeopt_kernel<4, false>),
-                        reinterpret_cast<const void *>(&timeopt_kernel<5, false>),
-                        reinterpret_cast<const void *>(&timeopt_kernel<4, true>),
-                        reinterpret_cast<const void *>(&timeopt_kernel<5, true>)})
-    MSNAP_HIP(ctx, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLdsBytes));
-  ctx->timeopt_ready = 1;
-  return MSNAP_OK;
-}
-
-// ends: msnap_optimize_times_states (start / end: device pointers or null); otherwise both are ignored
+// mode 0: msnap_optimize_times; 1: msnap_optimize_times_states (start / end: device pointers or null); 2:
+// msnap_optimize_times_periodic
 int launch_optimize_times(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, const double *t, int shared_times,
-                          bool ends, const double *start, const double *end, const double *weights,
+                          int mode, const double *start, const double *end, const double *weights,
                           double min_fraction, int max_iter, double tol, double *t_out, double *coef, double *dur,
                           int32_t *status, double *cost, double *pg, int32_t *iters) {
-  if (n_drones == 0) return MSNAP_OK;
-  // 16 drones per wave while their stash fits LDS, 8 above
-  const int TD =
-      timeopt_lds_words(ctx->khalf, n_seg, kDronesPerWave, ends) * sizeof(double) <= kMaxLdsBytes ? kDronesPerWave : 8;
-  const size_t lds_bytes = timeopt_lds_words(ctx->khalf, n_seg, TD, ends) * sizeof(double);
-  if (lds_bytes > kMaxLdsBytes) return MSNAP_ESEGMENTS;
-  if (int rc = timeopt_kernel_setup(ctx)) return rc;
-  TimeoptEndsArgs a;
-  a.wp = wp;
-  a.tt = t;
-  a.shared_times = shared_times;
-  a.N = n_drones;
-  a.M = n_seg;
-  a.TD = TD;
-  for (int q = 0; q < 4; ++q) a.w[q] = weights[q];
-  a.min_fraction = min_fraction;
-  a.tol = tol;
-  a.max_iter = max_iter;
-  a.t_out = t_out;
-  a.coef = coef;
-  a.dur = dur;
-  a.status = status;
-  a.cost = cost;
-  a.pg = pg;
-  a.iters = iters;
-  a.start = start;
-  a.end = end;
-  const TimeoptArgs &rest = a;
-  const int ntiles = (n_drones + TD - 1) / TD;
-  if (ends) {
-    if (ctx->khalf == 4)
-      hipLaunchKernelGGL((timeopt_kernel<4, true>), dim3(ntiles), dim3(kWave), lds_bytes, ctx->stream, a);
-    else
-      hipLaunchKernelGGL((timeopt_kernel<5, true>), dim3(ntiles), dim3(kWave), lds_bytes, ctx->stream, a);
-  } else {
-    if (ctx->khalf == 4)
-      hipLaunchKernelGGL((timeopt_kernel<4, false>), dim3(ntiles), dim3(kWave), lds_bytes, ctx->stream, rest);
-    else
-      hipLaunchKernelGGL((timeopt_kernel<5, false>), dim3(ntiles), dim3(kWave), lds_bytes, ctx->stream, rest);
-  }
-  MSNAP_HIP(ctx, hipGetLastError());
-  return MSNAP_OK;
+  if (mode == kTimeoptRing)
+    return launch_optimize_times_ring(ctx, n_drones, n_seg, wp, t, shared_times, weights, min_fraction, max_iter, tol,
+                                      t_out, coef, dur, status, cost, pg, iters);
+  if (mode == kTimeoptEnds)
+    return timeopt_launch<kTimeoptEnds>(ctx, n_drones, n_seg, wp, t, shared_times, start, end, weights, min_fraction,
+                                        max_iter, tol, t_out, coef, dur, status, cost, pg, iters);
+  return timeopt_launch<kTimeoptRest>(ctx, n_drones, n_seg, wp, t, shared_times, nullptr, nullptr, weights,
+                                      min_fraction, max_iter, tol, t_out, coef, dur, status, cost, pg, iters);
 }
 
 }  // namespace msnap
@@ -503,11 +46,12 @@ int msnap_snap_cost_grad(msnap_ctx *ctx, int n_drones, int n_seg, const double *
 // ------------------------------------------------------------------ time allocation (msnap_timeopt.hip)
 // weights is a host array in both versions; cost, pg and iters are optional
 namespace {
-int timeopt_args(const msnap_ctx *ctx, int n_drones, int n_seg, bool ends, const double *weights, double min_fraction,
+int timeopt_args(const msnap_ctx *ctx, int n_drones, int n_seg, int mode, const double *weights, double min_fraction,
                  int max_iter, double tol, std::initializer_list<const void *> ptrs) {
   if (!ctx || n_drones < 0) return MSNAP_EINVAL;
   if (int rc = check_seg(ctx, n_seg)) return rc;
-  if (n_seg > timeopt_max_segments(ctx->khalf, ends)) return MSNAP_ESEGMENTS;
+  if (n_seg > timeopt_max_segments(ctx->khalf, mode)) return MSNAP_ESEGMENTS;
+  if (mode == kTimeoptRing && n_seg < 2) return MSNAP_ESEGMENTS;      // (a loop has two segments at least)
   if (!weights || !(min_fraction > 0.0 && min_fraction <= 1.0) || max_iter < 0 || !(tol >= 0.0)) return MSNAP_EINVAL;
   for (int q = 0; q < 4; ++q)
     if (!(weights[q] >= 0.0) || !(weights[q] <= 1.79769313486231570815e308)) return MSNAP_EINVAL;   // negative, NaN, Inf
@@ -517,13 +61,14 @@ int timeopt_args(const msnap_ctx *ctx, int n_drones, int n_seg, bool ends, const
   return MSNAP_OK;
 }
 
-// the host entries: stage, launch, read back (start / end: host pointers or null, looked at with ends only)
+// the host entries: stage, launch, read back (start / end: host pointers or null, looked at with kTimeoptEnds only)
 int optimize_times_host(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, const double *t, int shared_times,
-                        bool ends, const double *start, const double *end, const double *weights, double min_fraction,
+                        int mode, const double *start, const double *end, const double *weights, double min_fraction,
                         int max_iter, double tol, double *t_out, double *coef, double *dur, int32_t *status,
                         double *cost, double *pg, int32_t *iters) {
   const size_t n = (size_t)n_drones, m1 = (size_t)n_seg + 1;
   const size_t b_s = n * 4 * (ctx->khalf - 1) * 8;
+  const bool ends = mode == kTimeoptEnds;
   // (a region without a source is not copied: a NULL state stays NULL for the launcher)
   return staged(ctx, {upload(wp, n * m1 * 4 * 8), upload(t, (shared_times ? 1 : n) * m1 * 8), download(t_out, n * m1 * 8),
                       download(coef, coef_bytes(ctx, n_drones, n_seg)), download(dur, dur_bytes(n_drones, n_seg)),
@@ -531,7 +76,7 @@ int optimize_times_host(msnap_ctx *ctx, int n_drones, int n_seg, const double *w
                       download(iters, iters ? n * 4 : 0), upload(start, ends && start ? b_s : 0),
                       upload(end, ends && end ? b_s : 0)},
                 [&](const DevPtr *d) {
-                  return launch_optimize_times(ctx, n_drones, n_seg, d[0], d[1], shared_times ? 1 : 0, ends,
+                  return launch_optimize_times(ctx, n_drones, n_seg, d[0], d[1], shared_times ? 1 : 0, mode,
                                                ends && start ? (const double *)d[9] : nullptr,
                                                ends && end ? (const double *)d[10] : nullptr, weights, min_fraction,
                                                max_iter, tol, d[2], d[3], d[4], d[5], cost ? (double *)d[6] : nullptr,
@@ -544,24 +89,24 @@ int msnap_optimize_times_device(msnap_ctx *ctx, int n_drones, int n_seg, const d
                                 int shared_times, const double weights[4], double min_fraction, int max_iter,
                                 double tol, double *t_out, double *coef, double *dur, int32_t *status, double *cost,
                                 double *pg, int32_t *iters) {
-  MSNAP_ENTER(ctx, timeopt_args(ctx, n_drones, n_seg, false, weights, min_fraction, max_iter, tol,
+  MSNAP_ENTER(ctx, timeopt_args(ctx, n_drones, n_seg, kTimeoptRest, weights, min_fraction, max_iter, tol,
                                 {wp, t, t_out, coef, dur, status}));
-  return launch_optimize_times(ctx, n_drones, n_seg, wp, t, shared_times ? 1 : 0, false, nullptr, nullptr, weights,
+  return launch_optimize_times(ctx, n_drones, n_seg, wp, t, shared_times ? 1 : 0, kTimeoptRest, nullptr, nullptr, weights,
                                min_fraction, max_iter, tol, t_out, coef, dur, status, cost, pg, iters);
 }
 
 int msnap_optimize_times(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, const double *t, int shared_times,
                          const double weights[4], double min_fraction, int max_iter, double tol, double *t_out,
                          double *coef, double *dur, int32_t *status, double *cost, double *pg, int32_t *iters) {
-  MSNAP_ENTER(ctx, timeopt_args(ctx, n_drones, n_seg, false, weights, min_fraction, max_iter, tol,
+  MSNAP_ENTER(ctx, timeopt_args(ctx, n_drones, n_seg, kTimeoptRest, weights, min_fraction, max_iter, tol,
                                 {wp, t, t_out, coef, dur, status}));
-  return optimize_times_host(ctx, n_drones, n_seg, wp, t, shared_times, false, nullptr, nullptr, weights, min_fraction,
+  return optimize_times_host(ctx, n_drones, n_seg, wp, t, shared_times, kTimeoptRest, nullptr, nullptr, weights, min_fraction,
                              max_iter, tol, t_out, coef, dur, status, cost, pg, iters);
 }
 
 int msnap_optimize_times_states_max_segments(int order) {
   if (order != 7 && order != 9) return MSNAP_EORDER;
-  return timeopt_max_segments((order + 1) / 2, true);
+  return timeopt_max_segments((order + 1) / 2, kTimeoptEnds);
 }
 
 int msnap_optimize_times_states_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, const double *t,
@@ -569,9 +114,9 @@ int msnap_optimize_times_states_device(msnap_ctx *ctx, int n_drones, int n_seg, 
                                        const double weights[4], double min_fraction, int max_iter, double tol,
                                        double *t_out, double *coef, double *dur, int32_t *status, double *cost,
                                        double *pg, int32_t *iters) {
-  MSNAP_ENTER(ctx, timeopt_args(ctx, n_drones, n_seg, true, weights, min_fraction, max_iter, tol,
+  MSNAP_ENTER(ctx, timeopt_args(ctx, n_drones, n_seg, kTimeoptEnds, weights, min_fraction, max_iter, tol,
                                 {wp, t, t_out, coef, dur, status}));
-  return launch_optimize_times(ctx, n_drones, n_seg, wp, t, shared_times ? 1 : 0, true, start, end, weights,
+  return launch_optimize_times(ctx, n_drones, n_seg, wp, t, shared_times ? 1 : 0, kTimeoptEnds, start, end, weights,
                                min_fraction, max_iter, tol, t_out, coef, dur, status, cost, pg, iters);
 }
 
@@ -579,10 +124,35 @@ int msnap_optimize_times_states(msnap_ctx *ctx, int n_drones, int n_seg, const d
                                 int shared_times, const double *start, const double *end, const double weights[4],
                                 double min_fraction, int max_iter, double tol, double *t_out, double *coef, double *dur,
                                 int32_t *status, double *cost, double *pg, int32_t *iters) {
-  MSNAP_ENTER(ctx, timeopt_args(ctx, n_drones, n_seg, true, weights, min_fraction, max_iter, tol,
+  MSNAP_ENTER(ctx, timeopt_args(ctx, n_drones, n_seg, kTimeoptEnds, weights, min_fraction, max_iter, tol,
                                 {wp, t, t_out, coef, dur, status}));
-  return optimize_times_host(ctx, n_drones, n_seg, wp, t, shared_times, true, start, end, weights, min_fraction,
+  return optimize_times_host(ctx, n_drones, n_seg, wp, t, shared_times, kTimeoptEnds, start, end, weights, min_fraction,
                              max_iter, tol, t_out, coef, dur, status, cost, pg, iters);
+}
+
+int msnap_optimize_times_periodic_max_segments(int order) {
+  if (order != 7 && order != 9) return MSNAP_EORDER;
+  return timeopt_max_segments((order + 1) / 2, kTimeoptRing);
+}
+
+int msnap_optimize_times_periodic_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, const double *t,
+                                         int shared_times, const double weights[4], double min_fraction, int max_iter,
+                                         double tol, double *t_out, double *coef, double *dur, int32_t *status,
+                                         double *cost, double *pg, int32_t *iters) {
+  MSNAP_ENTER(ctx, timeopt_args(ctx, n_drones, n_seg, kTimeoptRing, weights, min_fraction, max_iter, tol,
+                                {wp, t, t_out, coef, dur, status}));
+  return launch_optimize_times(ctx, n_drones, n_seg, wp, t, shared_times ? 1 : 0, kTimeoptRing, nullptr, nullptr,
+                               weights, min_fraction, max_iter, tol, t_out, coef, dur, status, cost, pg, iters);
+}
+
+int msnap_optimize_times_periodic(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, const double *t,
+                                  int shared_times, const double weights[4], double min_fraction, int max_iter,
+                                  double tol, double *t_out, double *coef, double *dur, int32_t *status, double *cost,
+                                  double *pg, int32_t *iters) {
+  MSNAP_ENTER(ctx, timeopt_args(ctx, n_drones, n_seg, kTimeoptRing, weights, min_fraction, max_iter, tol,
+                                {wp, t, t_out, coef, dur, status}));
+  return optimize_times_host(ctx, n_drones, n_seg, wp, t, shared_times, kTimeoptRing, nullptr, nullptr, weights,
+                             min_fraction, max_iter, tol, t_out, coef, dur, status, cost, pg, iters);
 }
 
 }  // extern "C"

@@ -300,6 +300,26 @@ class DeviceCompute:
             self.ctx.solve_periodic_device(n, M, wp.contiguous(), t.contiguous(), t.dim() == 1, coef, dur, status)
         return coef, dur, status
 
+    def optimize_times_periodic(self, wp, t, weights=(1, 1, 1, 1), min_fraction=0.1, max_iter=200, tol=1e-4):
+        """(t_out, coef, dur, status, info) of the time allocation on closed loops: wp, t as solve_periodic takes them
+        (the period t[-1] is kept), the rest as Context.optimize_times; info = {"cost": [n, 2], "pg": [n],
+        "iters": [n] int32}."""
+        torch = self.torch
+        n, m, _ = wp.shape
+        M = m - 1
+        t_out = self._out("optimize_times_periodic.t_out", (n, m), torch.float64)
+        coef = self._out("optimize_times_periodic.coef", (n, M, 4, self.ctx.ncoef), torch.float64)
+        dur = self._out("optimize_times_periodic.dur", (n, M), torch.float64)
+        status = self._out("optimize_times_periodic.status", (n,), torch.int32)
+        cost = self._out("optimize_times_periodic.cost", (n, 2), torch.float64)
+        pg = self._out("optimize_times_periodic.pg", (n,), torch.float64)
+        iters = self._out("optimize_times_periodic.iters", (n,), torch.int32)
+        if n:
+            self.ctx.optimize_times_periodic_device(n, M, wp.contiguous(), t.contiguous(), t.dim() == 1, weights,
+                                                    min_fraction, max_iter, tol, t_out, coef, dur, status, cost, pg,
+                                                    iters)
+        return t_out, coef, dur, status, {"cost": cost, "pg": pg, "iters": iters}
+
     def optimize_times_states(self, wp, t, start=None, end=None, weights=(1, 1, 1, 1), min_fraction=0.1, max_iter=200,
                               tol=1e-4):
         """(t_out, coef, dur, status, info) of the time allocation from and to given end states: arguments as

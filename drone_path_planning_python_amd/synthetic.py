@@ -22,6 +22,43 @@ def swarm(config_id: int, n_drones: int, n_seg: int, shared_times: bool = False,
     return wp, t
 
 
+def patrol_circuits(n_drones: int, n_seg: int, period: float = 12.0):
+    """Uneven closed circuits, one per drone (examples/12_loop_time_allocation.py and its test): a 5 x 2 m racetrack --
+    two straights and two half circles -- around centres 7 m apart on a grid four wide, with the waypoints crowded
+    into the bends: the legs differ in length by a factor of three to six.  z rises and falls by 0.4 m along the lap, yaw
+    follows the direction of travel and gains one turn per lap (the lap offset); x, y, z close bit for bit.
+    Returns wp [N, M+1, 4] and the evenly spaced shared grid t [M+1] with t[M] = period."""
+    M = n_seg
+    # arc-length fraction of the waypoints: dense around the bends' middles (0.37 and 0.87 of the lap), sparse between
+    u = np.arange(M + 1) / M
+    s = u - 0.06 * np.sin(4.0 * np.pi * (u - 0.37))
+    half, r = 1.5, 1.0                                   # half length of a straight, radius of a bend
+    lap = 4.0 * half + 2.0 * np.pi * r
+    a = (s % 1.0) * lap
+    x, y, yaw = np.empty(M + 1), np.empty(M + 1), np.empty(M + 1)
+    for i, ai in enumerate(a):
+        if ai < 2.0 * half:                              # lower straight, eastwards
+            x[i], y[i], yaw[i] = -half + ai, -r, 0.0
+        elif ai < 2.0 * half + np.pi * r:                # east bend
+            th = (ai - 2.0 * half) / r
+            x[i], y[i], yaw[i] = half + r * np.sin(th), -r * np.cos(th), th
+        elif ai < 4.0 * half + np.pi * r:                # upper straight, westwards
+            x[i], y[i], yaw[i] = half - (ai - 2.0 * half - np.pi * r), r, np.pi
+        else:                                            # west bend
+            th = (ai - 4.0 * half - np.pi * r) / r
+            x[i], y[i], yaw[i] = -half - r * np.sin(th), r * np.cos(th), np.pi + th
+    yaw[:M] = np.unwrap(yaw[:M])
+    yaw[M] = yaw[0] + 2.0 * np.pi
+    wp = np.empty((n_drones, M + 1, 4))
+    k = np.arange(n_drones)
+    wp[:, :, 0] = 7.0 * (k % 4)[:, None] + x[None, :]
+    wp[:, :, 1] = 7.0 * (k // 4)[:, None] + y[None, :] * (1.0 + 0.05 * k)[:, None]      # (no two circuits alike)
+    wp[:, :, 2] = 2.0 + 0.4 * np.sin(2.0 * np.pi * s)[None, :]
+    wp[:, :, 3] = yaw[None, :]
+    wp[:, M, :3] = wp[:, 0, :3]
+    return wp, period * np.arange(M + 1) / M
+
+
 def formation_swarm(config_id: int, n_groups: int, n_seg: int, offsets: np.ndarray, rank: int = 0):
     """Formation-like swarm: n_groups random rigid-body paths, each carrying the
     K body-frame `offsets` (scripts/drones_traj_generator.py:22-38 has K = 2 at

@@ -741,6 +741,44 @@ int msnap_optimize_times_states_device(msnap_ctx *ctx, int n_drones, int n_seg, 
                                        double *pg, int32_t *iters);
 int msnap_optimize_times_states_max_segments(int order);     /* largest n_seg the entry takes; < 0: MSNAP_EORDER */
 
+/* msnap_optimize_times_periodic: the same time allocation on closed loops.  Arguments as
+ * msnap_optimize_times; wp, t as msnap_solve_periodic takes them: wp[M] - wp[0] is the lap offset, t[M] the period.
+ * Objective, feasible set, floor (T_min = min_fraction * t[M] / M, inputs below it raised as above), direction, step
+ * rules, stopping measure, cost / pg / iters, the power-of-two scaling property and the method are
+ * msnap_optimize_times's, word for word, with "the solve for T" read as msnap_solve_periodic's: dJ/dT_i =
+ * -sum_a weights[a] E_i,a holds on the ring, the seam state being a stationary unknown like every interior knot.
+ *   kept        the waypoints, t_out[0] == 0 and t_out[M] == t[M] -- the period -- bit for bit;
+ *   coef, dur   the periodic solution for t_out: dur[i] = t_out[i+1] - t_out[i] bit for bit, coef what
+ *               msnap_solve_periodic returns for t_out to rounding (norm-relative 1e-9); coef[i][a][0] is wp[i][a] bit
+ *               for bit;
+ *   seam        as msnap_solve_periodic promises it: msnap_eval_state at the sum of dur returns derivatives 1 .. K-1
+ *               equal to those at 0, and the position wp[M], within 4 * 2^-52 of the evaluation scale.  The
+ *               coefficients that leave take msnap_solve_periodic's refinement step and the step on the last
+ *               segment's end conditions, once; the trials run unrefined, and cost, pg and the iteration's decisions
+ *               are taken from the unrefined coefficients, as in msnap_optimize_times_states;
+ *   status      MSNAP_ST_NONFINITE for NaN / Inf in wp or t; MSNAP_ST_TIMES for times not strictly increasing or
+ *               t[0] != 0; MSNAP_ST_SINGULAR for a non-positive pivot, the seam block's included, or a cost that is not
+ *               finite at the (raised) input times.  A failed drone gets NaN coef, t_out, dur, cost, pg and iters 0; a
+ *               trial point whose solve fails is a rejected step.
+ * Guarantees as above: every dur[i] >= T_min (1 - 1e-12), cost[1] <= cost[0], max_iter = 0 returns the (raised) input
+ * times.  A drone's outputs are bit-identical whatever its place in the batch, the batch size, or host versus device
+ * entry.  Where the loop is cut changes the result by rounding only.
+ * n_seg: 2 .. msnap_optimize_times_periodic_max_segments(order) -- 48 at order 7, 33 at order 9: what an 8-drone
+ * tile's state leaves of 160 KiB of LDS (16-drone tiles up to 24 and 17 segments); every loop msnap_solve_periodic
+ * takes (27, 18) can be allocated -- and at most max_segments; MSNAP_ESEGMENTS otherwise, nothing written.  The query
+ * returns MSNAP_EORDER for any other order.  MSNAP_EINVAL as msnap_optimize_times; n_drones == 0 is a no-op.  The device
+ * version only launches (no synchronisation, no context buffer: the capture rules are msnap_optimize_times_device's).
+ */
+int msnap_optimize_times_periodic(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, const double *t,
+                                  int shared_times, const double weights[4], double min_fraction, int max_iter,
+                                  double tol, double *t_out, double *coef, double *dur, int32_t *status, double *cost,
+                                  double *pg, int32_t *iters);
+int msnap_optimize_times_periodic_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, const double *t,
+                                         int shared_times, const double weights[4], double min_fraction, int max_iter,
+                                         double tol, double *t_out, double *coef, double *dur, int32_t *status,
+                                         double *cost, double *pg, int32_t *iters);
+int msnap_optimize_times_periodic_max_segments(int order);   /* largest n_seg the entry takes; < 0: MSNAP_EORDER */
+
 /* ---- drone-vs-drone formation pass (new capability; no reference) -------
  * rows: the n_rows drones this caller owns (a shard), starting at global index
  * row_offset; cols: all n_cols drones (after the all-gather).  Spheres of `radius`.
