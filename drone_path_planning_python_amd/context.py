@@ -771,6 +771,64 @@ class Context:
                 float(min_fraction), int(max_iter), float(tol), _ptr(t_out), _ptr(coef), _ptr(dur), _ptr(status),
                 _ptr(cost), _ptr(pg), _ptr(iters)))
 
+    def optimize_times_free_max_segments(self) -> int:
+        """Largest segment count optimize_times_free takes at this context's order (and at most max_segments)."""
+        return min(int(self._lib.msnap_optimize_times_free_max_segments(self.order)), self.max_segments)
+
+    def optimize_times_free(self, wp, t, start=None, end=None, weights=(1, 1, 1, 1), time_weight=1.0, min_fraction=0.1,
+                            max_iter=200, tol=1e-4):
+        """optimize_times_states with the total duration free (msnap_optimize_times_free): minimises
+        sum_a weights[a] J_a + time_weight * t_out[-1] over every segment duration.  time_weight > 0 is a number or
+        [N], one per drone; t[-1] is a starting guess and the floor's scale.  The result tuple is optimize_times's,
+        with info["cost"] the objective (time term included) at the raised input times and at t_out."""
+        wp, pwp = _host(wp, np.float64)
+        t, pt = _host(t, np.float64)
+        if wp.ndim != 3 or wp.shape[2] != 4:
+            raise ValueError("wp must be [N, m, 4]")
+        N, m, _ = wp.shape
+        shared = int(t.ndim == 1)
+        if (shared and t.shape != (m,)) or (not shared and t.shape != (N, m)):
+            raise ValueError("t must be [N, m] or [m]")
+        w, pw = _host(weights, np.float64)
+        if w.shape != (4,):
+            raise ValueError("weights must hold 4 values")
+        kt = np.asarray(time_weight, dtype=np.float64)
+        if kt.ndim == 0:
+            kt = np.full((N,), float(kt))
+        if kt.shape != (N,):
+            raise ValueError("time_weight must be a number or [N]")
+        kt, pk = _host(kt, np.float64)
+        start, ps = self._state_block(start, N, "start")
+        end, pe = self._state_block(end, N, "end")
+        M = m - 1
+        t_out = np.empty((N, m), dtype=np.float64)
+        coef = np.empty((N, max(M, 0), 4, self.ncoef), dtype=np.float64)
+        dur = np.empty((N, max(M, 0)), dtype=np.float64)
+        status = np.empty((N,), dtype=np.int32)
+        cost = np.empty((N, 2), dtype=np.float64)
+        pg = np.empty((N,), dtype=np.float64)
+        iters = np.empty((N,), dtype=np.int32)
+        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)   # noqa: E731
+        with self._lock:
+            self._ck(self._lib.msnap_optimize_times_free(
+                self._h, N, M, pwp, pt, shared, ps, pe, pw, pk, float(min_fraction), int(max_iter), float(tol),
+                vp(t_out), vp(coef), vp(dur), vp(status), vp(cost), vp(pg), vp(iters)))
+        return t_out, coef, dur, status, {"cost": cost, "pg": pg, "iters": iters}
+
+    def optimize_times_free_device(self, n_drones, n_seg, wp, t, shared_times, start, end, weights, time_weight,
+                                   min_fraction, max_iter, tol, t_out, coef, dur, status, cost=None, pg=None,
+                                   iters=None):
+        """Device pointers (start / end may be None: rest; time_weight [n_drones] float64 on the device),
+        asynchronous; `weights` is a host sequence of 4."""
+        w, pw = _host(weights, np.float64)
+        if w.shape != (4,):
+            raise ValueError("weights must hold 4 values")
+        with self._lock:
+            self._ck(self._lib.msnap_optimize_times_free_device(
+                self._h, int(n_drones), int(n_seg), _ptr(wp), _ptr(t), int(bool(shared_times)), _ptr(start), _ptr(end),
+                pw, _ptr(time_weight), float(min_fraction), int(max_iter), float(tol), _ptr(t_out), _ptr(coef),
+                _ptr(dur), _ptr(status), _ptr(cost), _ptr(pg), _ptr(iters)))
+
     def eval_state(self, coef, dur, tq):
         """Full state of each drone at its own time tq [N] (msnap_eval_state): pos [N, 4], deriv [N, 4, K-1] with
         entry q-1 the q-th derivative -- the layout solve_states takes as `start`.  NaN where tq is outside the path."""

@@ -170,6 +170,7 @@ int launch_optimize_times_ring(msnap_ctx *ctx, int n_drones, int n_seg, const do
                                int shared_times, const double *weights, double min_fraction, int max_iter, double tol,
                                double *t_out, double *coef, double *dur, int32_t *status, double *cost, double *pg,
                                int32_t *iters);
+// (mode 3, the free total of msnap_optimize_times_free: instances, launch and entries in msnap_timeopt_free.hip)
 // largest n_seg whose per-tile state fits LDS (80 at order 7, 58 at order 9; mode 1: see DESIGN.md K8; mode 2: 48, 33)
 int timeopt_max_segments(int khalf, int mode);
 // (the pairwise pass: msnap_collide.h)

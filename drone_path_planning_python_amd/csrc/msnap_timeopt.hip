@@ -1,7 +1,8 @@
 // K8 -- segment-time optimisation per drone, one launch for the whole iteration (include/msnap.h, "time allocation";
 // DESIGN.md §5 K8).  The kernel text, its LDS layout and the launcher are msnap_timeopt_kernel.h; this translation unit
-// instantiates the rest-to-rest and the end-state mode and holds every entry point, msnap_timeopt_periodic.hip the ring
-// mode (msnap_optimize_times_periodic).
+// instantiates the rest-to-rest and the end-state mode and holds the entry points of the three fixed-total modes,
+// msnap_timeopt_periodic.hip the ring mode (msnap_optimize_times_periodic), msnap_timeopt_free.hip the free-total mode
+// with its own entries (msnap_optimize_times_free).
 #include "msnap_timeopt_kernel.h"
 
 namespace msnap {
@@ -44,23 +45,9 @@ int msnap_snap_cost_grad(msnap_ctx *ctx, int n_drones, int n_seg, const double *
 }
 
 // ------------------------------------------------------------------ time allocation (msnap_timeopt.hip)
-// weights is a host array in both versions; cost, pg and iters are optional
+// weights is a host array in both versions; cost, pg and iters are optional (the argument check: timeopt_args of
+// msnap_timeopt_kernel.h)
 namespace {
-int timeopt_args(const msnap_ctx *ctx, int n_drones, int n_seg, int mode, const double *weights, double min_fraction,
-                 int max_iter, double tol, std::initializer_list<const void *> ptrs) {
-  if (!ctx || n_drones < 0) return MSNAP_EINVAL;
-  if (int rc = check_seg(ctx, n_seg)) return rc;
-  if (n_seg > timeopt_max_segments(ctx->khalf, mode)) return MSNAP_ESEGMENTS;
-  if (mode == kTimeoptRing && n_seg < 2) return MSNAP_ESEGMENTS;      // (a loop has two segments at least)
-  if (!weights || !(min_fraction > 0.0 && min_fraction <= 1.0) || max_iter < 0 || !(tol >= 0.0)) return MSNAP_EINVAL;
-  for (int q = 0; q < 4; ++q)
-    if (!(weights[q] >= 0.0) || !(weights[q] <= 1.79769313486231570815e308)) return MSNAP_EINVAL;   // negative, NaN, Inf
-  if (n_drones == 0) return kNoWork;
-  for (const void *p : ptrs)
-    if (!p) return MSNAP_EINVAL;
-  return MSNAP_OK;
-}
-
 // the host entries: stage, launch, read back (start / end: host pointers or null, looked at with kTimeoptEnds only)
 int optimize_times_host(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, const double *t, int shared_times,
                         int mode, const double *start, const double *end, const double *weights, double min_fraction,

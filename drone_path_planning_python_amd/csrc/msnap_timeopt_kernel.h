@@ -30,10 +30,17 @@
 // (the seam state is a stationary unknown like every interior knot), so input stage, floor, direction, step rules and
 // results are the lines below unchanged; the mode is one `if constexpr` around the trial's body.
 //
-// One kernel text, two translation units: msnap_timeopt.hip instantiates the rest-to-rest and end-state modes (and holds
-// every entry point), msnap_timeopt_periodic.hip the ring mode -- an object of its own, so that what is held of
-// msnap_timeopt.o (its instructions, its kernel count, no register-pressure copy) stays true.  Everything here has
-// internal linkage.
+// A free total duration (msnap_optimize_times_free): timeopt_kernel<K, kTimeoptFree>, the end-state
+// mode with F(T) = J(T) + k_T sum_i T_i in place of J and a time weight k_T per drone.  The envelope statement never
+// asked for a fixed sum, so dF/dT_i = k_T - sum_a w_a E_i,a comes out of the same solve and the projection goes: the
+// direction is -g off the floor, one pass.  What differs from kTimeoptEnds is one `if constexpr` each: the weight's
+// check, a raise of short durations nobody pays for, cost and gradient with the time term, the direction, a last knot
+// that moves, and the current total in the stopping measure.
+//
+// One kernel text, three translation units: msnap_timeopt.hip instantiates the rest-to-rest and end-state modes (and
+// holds their entry points), msnap_timeopt_periodic.hip the ring mode and msnap_timeopt_free.hip the free-total mode
+// with its entries -- objects of their own, so that what is held of msnap_timeopt.o (its instructions, its kernel
+// count, no register-pressure copy) stays true.  Everything here has internal linkage.
 #pragma once
 
 #include <math.h>
@@ -68,6 +75,10 @@ struct TimeoptArgs {
 struct TimeoptEndsArgs : TimeoptArgs {
   const double *start, *end;
 };
+// FREE: the price of a second per drone, [n_drones]
+struct TimeoptFreeArgs : TimeoptEndsArgs {
+  const double *time_weight;
+};
 
 // w_0 v_0 + .. + w_3 v_3 over the quad, the same bits in its four lanes; an axis of weight 0 is not looked at
 __device__ __forceinline__ double quad_weighted_sum(double v, double wa) {
@@ -75,14 +86,19 @@ __device__ __forceinline__ double quad_weighted_sum(double v, double wa) {
   return ((quad_bcast<0>(p) + quad_bcast<1>(p)) + quad_bcast<2>(p)) + quad_bcast<3>(p);
 }
 
-enum TimeoptMode : int { kTimeoptRest = 0, kTimeoptEnds = 1, kTimeoptRing = 2 };
+enum TimeoptMode : int { kTimeoptRest = 0, kTimeoptEnds = 1, kTimeoptRing = 2, kTimeoptFree = 3 };
+
+template <int MODE>
+using TimeoptArgsOf = std::conditional_t<MODE == kTimeoptFree, TimeoptFreeArgs,
+                                         std::conditional_t<MODE == kTimeoptEnds, TimeoptEndsArgs, TimeoptArgs>>;
 
 // ENDS: the end knots' derivative vectors u_0, u_M are data (msnap_optimize_times_states), as in rolled_solve_tile
 // RING: the last waypoint is joined to the first (msnap_optimize_times_periodic), the trial is ring_solve
+// FREE: ENDS with the total duration an unknown (msnap_optimize_times_free): F = J + k_T t[M], no projection
 template <int K, int MODE>
 __global__ void __launch_bounds__(kWave)
-timeopt_kernel(const std::conditional_t<MODE == kTimeoptEnds, TimeoptEndsArgs, TimeoptArgs> p) {
-  constexpr bool ENDS = MODE == kTimeoptEnds, RING = MODE == kTimeoptRing;
+timeopt_kernel(const TimeoptArgsOf<MODE> p) {
+  constexpr bool FREE = MODE == kTimeoptFree, ENDS = MODE == kTimeoptEnds || FREE, RING = MODE == kTimeoptRing;
   using SW = Sweep<K>;
   using C = HermiteConsts<K>;
   constexpr int NU = SW::NU, NC = SW::NC, KK = SW::KK, PM = SW::PM, PITCH = NU | 1;
@@ -157,6 +173,12 @@ timeopt_kernel(const std::conditional_t<MODE == kTimeoptEnds, TimeoptEndsArgs, T
 #pragma unroll
     for (int q = 0; q < NU; ++q) nonfinite |= !finite64(sS0[q]) | !finite64(sS1[q]);
   }
+  // FREE: the drone's time weight is data too; one that is not a positive number has no minimum to go to
+  double kT = 0.0;
+  if constexpr (FREE) {
+    kT = p.time_weight[d];
+    nonfinite |= !(finite64(kT) & (kT > 0.0));
+  }
   const double Tmin = p.min_fraction * ttotal / (double)M;
   // durations below the floor are raised to it; the others keep T_min plus their excess over it scaled by one factor
   // that pays for the raise: the sum is kept, nothing falls below the floor, and a feasible input is not touched
@@ -175,8 +197,9 @@ timeopt_kernel(const std::conditional_t<MODE == kTimeoptEnds, TimeoptEndsArgs, T
     sTc[0] = t0;
     for (int i = 0; i < M; ++i) {
       const double T = lt[i + 1] - lt[i];
-      const double Tn = T < Tmin ? Tmin : fma(T - Tmin, keep, Tmin);
-      const double tn = i == M - 1 ? ttotal : t + Tn;
+      // FREE: nothing pays for the raise -- every other duration is the input's and the sum grows
+      const double Tn = T < Tmin ? Tmin : FREE ? T : fma(T - Tmin, keep, Tmin);
+      const double tn = !FREE && i == M - 1 ? ttotal : t + Tn;
       sTc[(i + 1) * TD] = anybelow ? tn : lt[i + 1];
       sD[i * TD + dloc] = 0.0;
       t = tn;
@@ -291,7 +314,7 @@ timeopt_kernel(const std::conditional_t<MODE == kTimeoptEnds, TimeoptEndsArgs, T
         if constexpr (NC == 8) store_segment_quad8(base, MSNAP_SEG_STRIDE(M, NC), nvalid, lane, c, bad);
         else store_segment_coalesced<NC>(sTr, base, MSNAP_SEG_STRIDE(M, NC), nvalid, lane, c, bad);
       } else {
-        sGrad[i * TD + dloc] = gi;
+        sGrad[i * TD + dloc] = FREE ? kT + gi : gi;      // (FREE: dF/dT_i = k_T - sum_a w_a E_i,a)
       }
 #pragma unroll
       for (int r = 0; r < NU; ++r) un[r] = u[r];
@@ -299,6 +322,7 @@ timeopt_kernel(const std::conditional_t<MODE == kTimeoptEnds, TimeoptEndsArgs, T
       tn = ti;
     }
     Jw = quad_weighted_sum(Ja, wa);
+    if constexpr (FREE) Jw = Jw + kT * sT[M * TD];      // F = J + k_T sum_i T_i
   };
 
   // ---------------- the iteration ----------------
@@ -309,6 +333,24 @@ timeopt_kernel(const std::conditional_t<MODE == kTimeoptEnds, TimeoptEndsArgs, T
     double n2, dmax, Tsmall, cap;   // |P g|^2, max |d_i|, min T_i, the step that takes the first T_i to the floor
   };
   auto direction = [&]() -> Direction {
+    if constexpr (FREE) {
+      // no sum to keep, so no mean to remove and no free set to iterate: d = -g but on segments at their bound whose
+      // gradient points below it
+      Direction r = {0.0, 0.0, ttotal, __builtin_inf()};
+      for (int i = 0; i < M; ++i) {
+        const double gi = sGc[i * TD + dloc];
+        const double T = sTc[(i + 1) * TD] - sTc[i * TD];
+        const bool fixed = (T - Tmin <= kBoundRel * Tmin) & (gi > 0.0);
+        const double di = fixed ? 0.0 : -gi;
+        sD[i * TD + dloc] = di;
+        r.n2 = fma(di, di, r.n2);
+        r.dmax = fmax(r.dmax, fabs(di));
+        r.Tsmall = fmin(r.Tsmall, T);
+        const double reach = (T - Tmin) / (di < 0.0 ? -di : 1.0);
+        r.cap = fmin(r.cap, di < 0.0 ? reach : __builtin_inf());
+      }
+      return r;
+    }
     unsigned long long fix0 = 0, fix1 = 0;
     double mean = 0.0;
     bool changed = true;
@@ -356,7 +398,7 @@ timeopt_kernel(const std::conditional_t<MODE == kTimeoptEnds, TimeoptEndsArgs, T
   };
   const double sqrtM = sqrt((double)M);
   auto measure = [&](double n2, double Jc) {
-    const double v = sqrt(n2) * ttotal / (sqrtM * Jc);
+    const double v = sqrt(n2) * (FREE ? sTc[M * TD] : ttotal) / (sqrtM * Jc);      // (FREE: the current total)
     return Jc > 0.0 ? v : 0.0;      // (a path that costs nothing is optimal)
   };
 
@@ -381,7 +423,7 @@ timeopt_kernel(const std::conditional_t<MODE == kTimeoptEnds, TimeoptEndsArgs, T
       sTt[0] = sTc[0];
       for (int i = 0; i < M; ++i) {
         const double Tn = fmax(fma(step, sD[i * TD + dloc], sTc[(i + 1) * TD] - sTc[i * TD]), Tmin);
-        const double tn = i == M - 1 ? ttotal : t + Tn;
+        const double tn = !FREE && i == M - 1 ? ttotal : t + Tn;      // (FREE: the last knot moves with the rest)
         sTt[(i + 1) * TD] = tn;
         t = tn;
       }
@@ -446,7 +488,7 @@ timeopt_kernel(const std::conditional_t<MODE == kTimeoptEnds, TimeoptEndsArgs, T
 constexpr size_t timeopt_lds_words(int khalf, int M, int TD, int mode) {
   const size_t nu = (size_t)khalf - 1, knots = (size_t)M - 1, m = (size_t)M;
   const size_t tr = khalf == 4 ? 0 : (size_t)khalf * kTrPitch * 2;
-  const size_t states = mode == kTimeoptEnds ? 2 * (size_t)TD * 4 * (nu | 1) : 0;
+  const size_t states = mode == kTimeoptEnds || mode == kTimeoptFree ? 2 * (size_t)TD * 4 * (nu | 1) : 0;
   const size_t ring = mode == kTimeoptRing ? (size_t)TD * (nu * nu + 4 * nu) * knots : 0;
   return tr + (size_t)TD * ((m + 1) * 4 + (m + 1) + 2 * (m + 1) + 4 * m + nu * nu * knots + 4 * nu * knots) + states +
          ring;
@@ -465,12 +507,12 @@ static_assert(timeopt_tile_segments(4, 16, kTimeoptRing) == 24 && timeopt_tile_s
 
 // One mode's launch: the tile size, the kernels' dynamic-LDS limit (raised to the full 160 KiB once per context and
 // mode: a function attribute is a property of the device's module), the arguments.  start / end: device pointers or
-// null, looked at with kTimeoptEnds only.
+// null, looked at with kTimeoptEnds and kTimeoptFree only; time_weight: a device pointer, kTimeoptFree only.
 template <int MODE>
 int timeopt_launch(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, const double *t, int shared_times,
                    const double *start, const double *end, const double *weights, double min_fraction, int max_iter,
                    double tol, double *t_out, double *coef, double *dur, int32_t *status, double *cost, double *pg,
-                   int32_t *iters) {
+                   int32_t *iters, const double *time_weight = nullptr) {
   if (n_drones == 0) return MSNAP_OK;
   // 16 drones per wave while their stash fits LDS, 8 above
   const int TD =
@@ -483,7 +525,7 @@ int timeopt_launch(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, co
       MSNAP_HIP(ctx, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLdsBytes));
     ctx->timeopt_ready |= 1 << MODE;
   }
-  std::conditional_t<MODE == kTimeoptEnds, TimeoptEndsArgs, TimeoptArgs> a;
+  TimeoptArgsOf<MODE> a;
   a.wp = wp;
   a.tt = t;
   a.shared_times = shared_times;
@@ -501,16 +543,33 @@ int timeopt_launch(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, co
   a.cost = cost;
   a.pg = pg;
   a.iters = iters;
-  if constexpr (MODE == kTimeoptEnds) {
+  if constexpr (MODE == kTimeoptEnds || MODE == kTimeoptFree) {
     a.start = start;
     a.end = end;
   }
+  if constexpr (MODE == kTimeoptFree) a.time_weight = time_weight;
   const int ntiles = (n_drones + TD - 1) / TD;
   if (ctx->khalf == 4)
     hipLaunchKernelGGL((timeopt_kernel<4, MODE>), dim3(ntiles), dim3(kWave), lds_bytes, ctx->stream, a);
   else
     hipLaunchKernelGGL((timeopt_kernel<5, MODE>), dim3(ntiles), dim3(kWave), lds_bytes, ctx->stream, a);
   MSNAP_HIP(ctx, hipGetLastError());
+  return MSNAP_OK;
+}
+
+// The argument check every allocation entry and its _device twin make (ptrs: the pointers the entry requires)
+int timeopt_args(const msnap_ctx *ctx, int n_drones, int n_seg, int mode, const double *weights, double min_fraction,
+                 int max_iter, double tol, std::initializer_list<const void *> ptrs) {
+  if (!ctx || n_drones < 0) return MSNAP_EINVAL;
+  if (int rc = check_seg(ctx, n_seg)) return rc;
+  if (n_seg > timeopt_max_segments(ctx->khalf, mode)) return MSNAP_ESEGMENTS;
+  if (mode == kTimeoptRing && n_seg < 2) return MSNAP_ESEGMENTS;      // (a loop has two segments at least)
+  if (!weights || !(min_fraction > 0.0 && min_fraction <= 1.0) || max_iter < 0 || !(tol >= 0.0)) return MSNAP_EINVAL;
+  for (int q = 0; q < 4; ++q)
+    if (!(weights[q] >= 0.0) || !(weights[q] <= 1.79769313486231570815e308)) return MSNAP_EINVAL;   // negative, NaN, Inf
+  if (n_drones == 0) return kNoWork;
+  for (const void *p : ptrs)
+    if (!p) return MSNAP_EINVAL;
   return MSNAP_OK;
 }
 

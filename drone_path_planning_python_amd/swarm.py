@@ -345,6 +345,38 @@ class DeviceCompute:
                                                   max_iter, tol, t_out, coef, dur, status, cost, pg, iters)
         return t_out, coef, dur, status, {"cost": cost, "pg": pg, "iters": iters}
 
+    def optimize_times_free(self, wp, t, start=None, end=None, weights=(1, 1, 1, 1), time_weight=1.0, min_fraction=0.1,
+                            max_iter=200, tol=1e-4):
+        """(t_out, coef, dur, status, info) of the time allocation with a free total duration: arguments as
+        optimize_times_states plus `time_weight` > 0, a number or a float64 tensor [n] (one per drone); t[-1] is a
+        starting guess.  info as there, with "cost" the objective, time term included."""
+        torch = self.torch
+        n, m, _ = wp.shape
+        M = m - 1
+        nd = self.ctx.ncoef // 2 - 1
+        for name, x in (("start", start), ("end", end)):
+            if x is not None and (tuple(x.shape) != (n, 4, nd) or x.dtype != torch.float64):
+                raise ValueError(f"optimize_times_free: {name} must be a float64 tensor [n, 4, {nd}]")
+        if torch.is_tensor(time_weight):
+            if tuple(time_weight.shape) != (n,) or time_weight.dtype != torch.float64:
+                raise ValueError("optimize_times_free: time_weight must be a number or a float64 tensor [n]")
+            kt = time_weight.to(self.device).contiguous()
+        else:
+            kt = torch.full((n,), float(time_weight), dtype=torch.float64, device=self.device)
+        t_out = self._out("optimize_times_free.t_out", (n, m), torch.float64)
+        coef = self._out("optimize_times_free.coef", (n, M, 4, self.ctx.ncoef), torch.float64)
+        dur = self._out("optimize_times_free.dur", (n, M), torch.float64)
+        status = self._out("optimize_times_free.status", (n,), torch.int32)
+        cost = self._out("optimize_times_free.cost", (n, 2), torch.float64)
+        pg = self._out("optimize_times_free.pg", (n,), torch.float64)
+        iters = self._out("optimize_times_free.iters", (n,), torch.int32)
+        if n:
+            self.ctx.optimize_times_free_device(n, M, wp.contiguous(), t.contiguous(), t.dim() == 1,
+                                                None if start is None else start.contiguous(),
+                                                None if end is None else end.contiguous(), weights, kt, min_fraction,
+                                                max_iter, tol, t_out, coef, dur, status, cost, pg, iters)
+        return t_out, coef, dur, status, {"cost": cost, "pg": pg, "iters": iters}
+
     def eval_state(self, coef, dur, tq):
         """(pos [n, 4], deriv [n, 4, K-1]) of each drone at its own time tq [n]: NaN outside its path."""
         torch = self.torch
@@ -1028,7 +1060,25 @@ def replan(compute, coef, dur, t_r, wp_new, t_new, end=None, optimize=None):
 
     `optimize`: None solves at `t_new` as given.  A dict with any of weights / min_fraction / max_iter / tol lets
     `compute.optimize_times_states` move the interior times first (the state at `t_r`, the waypoints, `end` and the
-    last time are kept); the knots it chose are the running sum of the returned `dur`."""
+    last time are kept); the knots it chose are the running sum of the returned `dur`.  With "time_weight" in the dict
+    (a number or a tensor [N], > 0) `compute.optimize_times_free` moves every time, the last one too: `t_new[-1]` is
+    then a starting guess, and a larger weight buys a shorter path at a higher cost."""
+    wp, t, pos, deriv = _replan_inputs(compute, coef, dur, t_r, wp_new, t_new)
+    if optimize is None:
+        new_coef, new_dur, status = compute.solve_states(wp, t, start=deriv, end=end)
+    else:
+        unknown = set(optimize) - {"weights", "min_fraction", "max_iter", "tol", "time_weight"}
+        if unknown:
+            raise ValueError("replan: optimize takes weights, min_fraction, max_iter, tol, time_weight, not "
+                             f"{sorted(unknown)}")
+        entry = compute.optimize_times_free if "time_weight" in optimize else compute.optimize_times_states
+        _, new_coef, new_dur, status, _ = entry(wp, t, start=deriv, end=end, **optimize)
+    return new_coef, new_dur, status, (pos, deriv)
+
+
+def _replan_inputs(compute, coef, dur, t_r, wp_new, t_new):
+    """(wp [N, M' + 1, 4], t [N, M' + 1] or [M' + 1], pos, deriv) of a replan: the state at `t_r` in front of the new
+    waypoints, 0 in front of their times."""
     import torch
     n = dur.shape[0]
     dev = dur.device
@@ -1043,14 +1093,66 @@ def replan(compute, coef, dur, t_r, wp_new, t_new, end=None, optimize=None):
     wp = torch.cat([pos[:, None, :], wp_new.to(torch.float64)], dim=1).contiguous()
     t = torch.cat([torch.zeros(t_new.shape[:-1] + (1,), dtype=torch.float64, device=dev), t_new.to(torch.float64)],
                   dim=-1).contiguous()
-    if optimize is None:
-        new_coef, new_dur, status = compute.solve_states(wp, t, start=deriv, end=end)
-    else:
-        unknown = set(optimize) - {"weights", "min_fraction", "max_iter", "tol"}
-        if unknown:
-            raise ValueError(f"replan: optimize takes weights, min_fraction, max_iter, tol, not {sorted(unknown)}")
-        _, new_coef, new_dur, status, _ = compute.optimize_times_states(wp, t, start=deriv, end=end, **optimize)
-    return new_coef, new_dur, status, (pos, deriv)
+    return wp, t, pos, deriv
+
+
+def replan_within_limits(compute, coef, dur, t_r, wp_new, t_new, limits, end=None, rounds=8, optimize=None):
+    """`replan` with the total duration chosen per drone so that the new path keeps the dynamic `limits` (speed,
+    acceleration, jerk, yaw rate; 0 or inf: none) and is no slower than they ask: a search over the time weight of
+    `compute.optimize_times_free`.  A replanned path cannot be stretched afterwards (its start state is in physical
+    units), so the limits are met by the choice of the weight instead.
+
+    Each of the `rounds` rounds is one `optimize_times_free` launch, one `dynamic_peaks` launch and one synchronising
+    read.  Every drone starts at k_0 = (2k - 1) J(t_new) / t_new[-1], the weight at which the caller's total would be
+    stationary if the cost were homogeneous.  A drone whose certified peak upper bounds peak (1 + 2e-9) are all within
+    `limits` has its weight multiplied by 4, any other divided by 4; once a drone has both a feasible and a violating
+    weight, the next one is their geometric mean.  `optimize`: weights / min_fraction / max_iter / tol as `replan`.
+
+    Returns (coef, dur, status, (pos, deriv), info): per drone the path of the largest feasible weight tried, and info =
+    {"time_weight": [N] that weight, "violating_weight": [N] the smallest weight found to violate (inf: none),
+    "feasible": [N] bool (host arrays), "peaks": [N, 4] the kept path's peaks (device)}.  A drone with no feasible
+    weight in `rounds` rounds -- one whose start speed already exceeds the speed limit, say -- keeps feasible = False
+    and the path of the smallest weight tried."""
+    import torch
+    lim = check_limits(limits)
+    if rounds < 1:
+        raise ValueError("replan_within_limits: rounds must be at least 1")
+    opt = dict(optimize or {})
+    unknown = set(opt) - {"weights", "min_fraction", "max_iter", "tol"}
+    if unknown:
+        raise ValueError(f"replan_within_limits: optimize takes weights, min_fraction, max_iter, tol, not {sorted(unknown)}")
+    wp, t, pos, deriv = _replan_inputs(compute, coef, dur, t_r, wp_new, t_new)
+    n, dev = wp.shape[0], wp.device
+    order = compute.ctx.order                                  # 2k - 1
+    bound = torch.from_numpy(np.where((lim > 0.0) & np.isfinite(lim), lim, np.inf)).to(dev)
+    # J at the input times: the states entry at max_iter 0 (no synchronisation; a failed drone's NaN travels on)
+    rest = {k: v for k, v in opt.items() if k in ("weights", "min_fraction")}
+    _, _, _, _, at_input = compute.optimize_times_states(wp, t, start=deriv, end=end, max_iter=0, **rest)
+    k = (order * at_input["cost"][:, 0] / t[..., -1]).cpu().numpy()
+    k_feas, k_viol, k_low = np.zeros(n), np.full(n, np.inf), np.full(n, np.inf)
+    kept = None
+    for _ in range(rounds):
+        _, c, d, st, _ = compute.optimize_times_free(wp, t, start=deriv, end=end,
+                                                     time_weight=torch.from_numpy(k).to(dev), **opt)
+        peak, _, pst = compute.dynamic_peaks(c, d)
+        ok = ((st == 0) & (pst == 0) & (peak * (1.0 + PEAK_MARGIN) <= bound[None, :]).all(dim=1)).cpu().numpy()
+        # this round's path is kept by a drone it is the best feasible one of, or the slowest one of while none is
+        take = (ok & (k > k_feas)) | (~ok & (k_feas == 0.0) & (k < k_low))
+        k_feas = np.where(ok, np.maximum(k_feas, k), k_feas)
+        k_viol = np.where(ok, k_viol, np.minimum(k_viol, k))
+        k_low = np.minimum(k_low, k)
+        if kept is None:
+            kept = [c.clone(), d.clone(), st.clone(), peak.clone()]
+        else:
+            m = torch.from_numpy(take).to(dev)
+            for dst, src in zip(kept, (c, d, st, peak)):
+                dst.copy_(torch.where(m.reshape((n,) + (1,) * (src.dim() - 1)), src, dst))
+        both = (k_feas > 0.0) & np.isfinite(k_viol)
+        k = np.where(both, np.sqrt(k_feas * k_viol), np.where(k_feas > 0.0, 4.0 * k_feas, 0.25 * k_low))
+    feasible = k_feas > 0.0
+    info = {"time_weight": np.where(feasible, k_feas, k_low), "violating_weight": k_viol, "feasible": feasible,
+            "peaks": kept[3]}
+    return kept[0], kept[1], kept[2], (pos, deriv), info
 
 
 def join_loop(compute, coef, dur, t_r, loop_coef, loop_dur, wp_via, t_via, optimize=None):

@@ -779,6 +779,63 @@ int msnap_optimize_times_periodic_device(msnap_ctx *ctx, int n_drones, int n_seg
                                          double *cost, double *pg, int32_t *iters);
 int msnap_optimize_times_periodic_max_segments(int order);   /* largest n_seg the entry takes; < 0: MSNAP_EORDER */
 
+/* msnap_optimize_times_free: time allocation from and to given end states with the total duration free (DESIGN.md §5
+ * K17) -- what a replan in flight needs, whose start state is in physical units so that no uniform stretch
+ * (msnap_retime_to_limits) can follow.  Arguments as msnap_optimize_times_states with time_weight [n_drones] after
+ * weights: k_T > 0 per drone, the price of a second in units of the cost (a HOST array in the host version, a DEVICE
+ * array in the device version; weights stays a host array in both).  With M = n_seg and T_i the durations:
+ *   objective   F(T) = sum_a weights[a] * J_a(T) + k_T * sum_i T_i over ALL T_i, J_a as in msnap_optimize_times with
+ *               "the solve for T" read as msnap_solve_states's.  dJ/dT_i = -sum_a weights[a] E_i,a is the derivative of
+ *               segment i's cost at fixed end states and never asked for a fixed sum, so
+ *               g_i = dF/dT_i = k_T - sum_a weights[a] E_i,a comes out of the same solve and nothing is projected;
+ *   feasible    T_i >= T_min = min_fraction * t[M] / M, taken from the INPUT total.  Input durations below T_min are
+ *               raised to it; every other input duration is taken bit for bit (no factor pays for the raise: the sum
+ *               grows), and an input with no duration below T_min is taken bit for bit, knots included;
+ *   t_out [M+1] t_out[0] = 0; t_out[M], the total, is an output.  t[M] is a starting guess;
+ *   coef, dur   the msnap_solve_states solution for t_out: dur[i] = t_out[i+1] - t_out[i] bit for bit, coef what
+ *               msnap_solve_states returns for t_out to rounding (norm-relative 1e-9), coef[0][a][0] is wp[0][a] bit for
+ *               bit; the end states through msnap_eval_state as msnap_optimize_times_states promises them (the same
+ *               refinement step on the last segment, once, when the coefficients leave);
+ *   cost  [2]   F at the (raised) input times and at t_out;  pg [1] the stopping measure at t_out;  iters [1] accepted
+ *               steps.  cost, pg, iters may be NULL;
+ *   status      as msnap_optimize_times_states; a time_weight that is NaN, Inf or not > 0 gives that drone
+ *               MSNAP_ST_NONFINITE and NaN outputs (at 0 the optimum is at infinity).
+ * Method: gradient descent with Armijo backtracking, one launch.  Direction d_i = -g_i, and 0 on a segment within
+ * T_min (1 + 1e-9) with g_i > 0: no mean is removed and no free set iterated, one pass.  The step rules are
+ * msnap_optimize_times's word for word with J read as F and |P g| as |d|: first proposal 0.25 * min T / max |d|; the
+ * step is the proposal cut so that no T_i passes T_min; accepted when F_new <= F - 1e-4 * step * |d|^2, after which the
+ * proposal is twice the step (the same proposal again when the step had been cut); rejected otherwise, the proposal
+ * then half the step, at most 30 times in a row.  The trial knots are the running sum of max(T_i + step * d_i, T_min)
+ * from 0, the last knot included.  The run ends when
+ *               |d|_2 * T_cur / (sqrt(M) * F) <= tol,          T_cur the current total,
+ * after max_iter accepted steps, or when the line search cannot lower F any more.
+ * Guarantees: every dur[i] >= T_min (1 - 1e-12);  cost[1] <= cost[0];  t_out[M] <= cost[0] / time_weight (F only
+ * decreases and J >= 0);  max_iter = 0 returns the (raised) input times.  A drone's outputs are bit-identical whatever
+ * its place in the batch, the batch size, or host versus device entry; NULL and an array of zeros give the same bits.
+ * With both state blocks zero and no segment at the floor J is homogeneous of degree -(2k - 1) in the durations,
+ * k = (order + 1) / 2, so sum_i T_i g_i = k_T T - (2k - 1) J (Euler), and since |sum_i T_i g_i| <= |g|_2 T the
+ * stopping measure gives at a converged return |(2k - 1) J - k_T t_out[M]| <= tol * sqrt(M) * F; the ratios
+ * dur / t_out[M] are then those msnap_optimize_times finds on the same waypoints, to the tolerance.
+ * n_seg: 1 -- one duration between two given states, a real problem here: it iterates -- ..
+ * msnap_optimize_times_free_max_segments(order) = 79 at order 7, 57 at order 9 (the LDS of msnap_optimize_times_states;
+ * 16-drone tiles up to 39 and 28 segments), and at most max_segments; MSNAP_ESEGMENTS above.  The query returns
+ * MSNAP_EORDER for any other order.  MSNAP_EINVAL as msnap_optimize_times_states, and for a NULL time_weight;
+ * n_drones == 0 is a no-op.  The device version only launches (no synchronisation, no context buffer: the capture
+ * rules are msnap_optimize_times_device's).
+ */
+int msnap_optimize_times_free(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, const double *t,
+                              int shared_times, const double *start /* [n_drones][4][K-1] or NULL */,
+                              const double *end /* [n_drones][4][K-1] or NULL */, const double weights[4],
+                              const double *time_weight /* [n_drones] */, double min_fraction, int max_iter, double tol,
+                              double *t_out, double *coef, double *dur, int32_t *status, double *cost, double *pg,
+                              int32_t *iters);
+int msnap_optimize_times_free_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, const double *t,
+                                     int shared_times, const double *start, const double *end,
+                                     const double weights[4], const double *time_weight, double min_fraction,
+                                     int max_iter, double tol, double *t_out, double *coef, double *dur,
+                                     int32_t *status, double *cost, double *pg, int32_t *iters);
+int msnap_optimize_times_free_max_segments(int order);       /* largest n_seg the entry takes; < 0: MSNAP_EORDER */
+
 /* ---- drone-vs-drone formation pass (new capability; no reference) -------
  * rows: the n_rows drones this caller owns (a shard), starting at global index
  * row_offset; cols: all n_cols drones (after the all-gather).  Spheres of `radius`.

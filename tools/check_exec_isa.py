@@ -55,6 +55,7 @@ K12_OBJS = [os.path.join(CSRC, f) for f in ("msnap_extent.o",)]
 K13_OBJS = [os.path.join(CSRC, f) for f in ("msnap_states.o",)]
 K15_OBJS = [os.path.join(CSRC, f) for f in ("msnap_periodic.o",)]
 K16_OBJS = [os.path.join(CSRC, f) for f in ("msnap_timeopt_periodic.o",)]
+K17_OBJS = [os.path.join(CSRC, f) for f in ("msnap_timeopt_free.o",)]
 
 
 def disassemble(obj):
@@ -227,13 +228,13 @@ def check(obj):
 
 def main():
     if sys.argv[1:2] == ["--latches"]:      # the census: one line per kernel with a lane-retiring loop
-        for obj in sys.argv[2:] or DEFAULT_OBJS + MORE_OBJS + K11_OBJS + K12_OBJS + K13_OBJS + K15_OBJS + K16_OBJS:
+        for obj in sys.argv[2:] or DEFAULT_OBJS + MORE_OBJS + K11_OBJS + K12_OBJS + K13_OBJS + K15_OBJS + K16_OBJS + K17_OBJS:
             found = lane_latches(obj)
             print(f"check_exec_isa: {os.path.basename(obj)}: {sum(found.values())} lane-retiring loop latches in {len(found)} kernels")
             for k, n in sorted(found.items()):
                 print(f"    {n:3d}  {k}")
         return 0
-    objs = sys.argv[1:] or DEFAULT_OBJS + MORE_OBJS + K11_OBJS + K12_OBJS + K13_OBJS + K15_OBJS + K16_OBJS
+    objs = sys.argv[1:] or DEFAULT_OBJS + MORE_OBJS + K11_OBJS + K12_OBJS + K13_OBJS + K15_OBJS + K16_OBJS + K17_OBJS
     rc = 0
     for obj in objs:
         n_kernels, n_spill, bad = check(obj)
