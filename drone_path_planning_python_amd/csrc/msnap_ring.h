@@ -1,15 +1,34 @@
-// The ring elimination of K15 (msnap_periodic.hip has the derivation) as one device function over a
-// tile whose stash is drone-interleaved at a run-time tile size: the trial of the time allocation on closed loops,
-// timeopt_kernel<K, kTimeoptRing> (msnap_timeopt.hip).  lane = 4 drone + axis.
-//   forward   S_i = D_i - O_{i-1}^T G_{i-1}, G_i = S_i^-1 O_i, z_i = S_i^-1 (y_i - O_{i-1}^T z_{i-1}),
-//             H_1 = S_1^-1 O_0^T, H_i = -S_i^-1 O_{i-1}^T H_{i-1}                     u_i = z_i - G_i u_{i+1} - H_i u_0
-//   backward  p_{M-1} = z_{M-1}, Q_{M-1} = G_{M-1} + H_{M-1}, p_i = z_i - G_i p_{i+1}, Q_i = H_i - G_i Q_{i+1},
-//             over z and H                                                           u_i = p_i - Q_i u_0
-//   seam      (D_0 - O_{M-1}^T Q_{M-1} - O_0 Q_1) u_0 = y_0 - O_{M-1}^T p_{M-1} - O_0 p_1
-//   REFINE    K15's refinement step of all u_i (residual of the ring's rows with dd_submul, the same elimination for
-//             the correction with S_i factored again from the stashed G) and refine_end on the last segment
-//   recovery  recover_segment, last segment first, each handed to `seg`
-// dd_submul is K15's too and lives here for both.
+// The ring elimination of closed-loop paths as one device function, ring_solve, the one text of it:
+// periodic_solve_kernel<K> of msnap_periodic.hip (msnap_solve_periodic) runs it over a stash with the compile-time tile
+// of 16 drones, the trial of the time allocation on closed loops, timeopt_kernel<K, kTimeoptRing>
+// (msnap_timeopt_kernel.h), over one whose tile size is a run-time value.  lane = 4 drone + axis.
+//
+// The last waypoint is joined to the first.  The derivative vector of the seam, u_0 = u_M, is one more unknown, and the
+// seam one more knot whose left segment is M-1 and whose right segment is 0, so the Hermite-form system of DESIGN.md §3
+// becomes block CYCLIC tridiagonal:
+//     O_{i-1}^T u_{i-1} + D_i u_i + O_i u_{i+1} = y_i ,   i = 0..M-1,  indices mod M .
+// Sweep<K>'s geometry and LDL^T, recover_segment and refine_end are the open chain's (msnap_sweep.h, msnap_rolled.h);
+// the elimination goes around the ring in these passes:
+//   forward   knots 1..M-1 as the open chain does (S_i = D_i - O_{i-1}^T G_{i-1}, G_i = S_i^-1 O_i,
+//             z_i = S_i^-1 (y_i - O_{i-1}^T z_{i-1})), with one more matrix per knot for the coupling to the seam:
+//             H_1 = S_1^-1 O_0^T,  H_i = -S_i^-1 O_{i-1}^T H_{i-1},  so that  u_i = z_i - G_i u_{i+1} - H_i u_0.
+//             H depends on the times only, like G: the four lanes of a quad compute it redundantly and stash it at
+//             G's pitch.
+//   backward  p_{M-1} = z_{M-1}, Q_{M-1} = G_{M-1} + H_{M-1} (u_M is u_0);  p_i = z_i - G_i p_{i+1},
+//             Q_i = H_i - G_i Q_{i+1}, written over z and H:  u_i = p_i - Q_i u_0.
+//   seam      (D_0 - O_{M-1}^T Q_{M-1} - O_0 Q_1) u_0 = y_0 - O_{M-1}^T p_{M-1} - O_0 p_1 : one more symmetric positive
+//             definite block through ldl_factor / ldl_solve, its pivots tested like the others.
+//   REFINE    one step of iterative refinement of all u_i: the residual of the ring's rows, r_i = y_i - O_{i-1}^T u_{i-1}
+//             - D_i u_i - O_i u_{i+1}, accumulated with error-free products and sums (dd_submul), then the same
+//             elimination for the correction: z'_i = S_i^-1 (r_i - O_{i-1}^T z'_{i-1}) with S_i factored again from the
+//             stashed G, p'_i = z'_i - G_i p'_{i+1}, and the seam block's kept factor for du_0.  The ring has one more
+//             unknown block than the open chain and, with few segments, a worse condition: at order 9 with two segments
+//             the unrefined solve is 4 x further from the exact solution than msnap_solve_states given the exact seam
+//             state; the step brings every segment count to that solve's level (DESIGN.md K15 has the figures).
+//   recovery  u_i = (p_i - Q_i u_0) + (p'_i - Q_i du_0) (the second term with REFINE), recover_segment, last segment
+//             first, each handed to `seg`; with REFINE the last segment takes refine_end with the solved seam state as
+//             its end vector, so that msnap_eval_state at the sum of the durations returns what it returns at 0.
+// With two segments both couplings land on the one knot (Q_1 = G_1 + H_1) and the loops run as written.
 #pragma once
 
 #include "msnap_rolled.h"
@@ -29,33 +48,48 @@ __device__ __forceinline__ void dd_submul(double &s, double &e, double a, double
   e = e + (err - pe);
 }
 
-// One lane's view of its tile's stash, every pointer already at this lane's column:
-//   lw [(M+1)] at stride 4 (waypoints of this axis) | sT [M+1], sX [M] at stride TD (knots; 1/T, written here) |
-//   sG, sH [M-1][NU NU] at stride TD | sZ, sZ2 [M-1][NU] at stride 4 TD (sZ2: REFINE only)
+// One lane's view of its tile's stash, every pointer already at this lane's column.  TD is the tile size in drones:
+// the template argument TILE of ring_solve when that is given (K15: 16), this struct's field otherwise (K16).
+//   lw [(M+1)] at stride 4 (waypoints of this axis) | sT [M+1] (knots) at stride 1 with a compile-time tile (K15's
+//   staged row, shared or per drone), at stride TD otherwise (K16's drone-interleaved iterate) |
+//   sX [M] at stride TD (1/T, written here) | sG, sH [M-1][NU NU] at stride TD |
+//   sZ, sZ2 [M-1][NU] at stride 4 TD (sZ2: REFINE only)
 struct RingLane {
   const double *lw, *sT;
   double *sX, *sG, *sH, *sZ, *sZ2;
   int TD;
 };
 
-// seg(i, c, T_i): segment i's coefficients, i = M-1 .. 0.  Returns true if a pivot, the seam block's included, is not
-// positive and finite.  The knots are taken as valid (increasing, finite): the caller has checked its inputs.
-template <int K, bool REFINE, class Seg>
-__device__ __forceinline__ bool ring_solve(const RingLane &p, int M, Seg &&seg) {
+// seg(i, c, T_i): segment i's coefficients, i = M-1 .. 0.  `singular` is set before the first call of seg: true if a
+// pivot, the seam block's included, is not positive and finite.
+// see(t_{i+1}, w_{i+1}, T_i), i = 0 .. M-1: what the forward sweep reads of each segment, as it reads it, for a caller
+// that checks its inputs on the way (K15; a pass of its own over the staged row in front of the sweep cost 0.3-1.2 us
+// per launch, profiles/periodic_ring_ab.md) -- t_0 and w_0 are the caller's to look at.  The default sees nothing (K16
+// has checked the input times once, and its iterates are its own).
+// Nothing here acts on the knots' validity: through times that are not finite or not increasing the arithmetic runs on
+// (rcp64 of such a duration, NaN after it), every loop is bounded by M and wave-uniform, and the caller discards the
+// results.
+struct RingUnchecked {
+  __device__ __forceinline__ void operator()(double, double, double) const {}
+};
+template <int K, bool REFINE, int TILE = 0, class Seg, class See = RingUnchecked>
+__device__ __forceinline__ void ring_solve(const RingLane &p, int M, bool &singular, Seg &&seg, See &&see = See{}) {
   using SW = Sweep<K>;
   using C = HermiteConsts<K>;
   constexpr int NU = SW::NU, NC = SW::NC, KK = SW::KK, PM = SW::PM, NS = SW::NS;
-  const int TD = p.TD, QL = 4 * p.TD;
+  const int TD = TILE ? TILE : p.TD, QL = 4 * TD;
+  const int TS = TILE ? 1 : TD;      // the knots' stride
   const double *lw = p.lw, *sT = p.sT;
   double *sX = p.sX;
   auto gslot = [&](double *base, int i) -> double * { return base + (size_t)(i - 1) * (NU * NU * TD); };   // knot i
   auto zslot = [&](double *base, int i) -> double * { return base + (size_t)(i - 1) * (NU * QL); };
 
   // ---------------- segment 0 ----------------
-  double tcur = sT[TD];
+  double tcur = sT[TS];
   const double w0 = lw[0];
   double wcur = lw[4];
   double T = tcur - sT[0];
+  see(tcur, wcur, T);
   double x = rcp64(T);
   const double x0 = x, dw0 = wcur - w0;
   sX[0] = x;
@@ -75,10 +109,11 @@ __device__ __forceinline__ bool ring_solve(const RingLane &p, int M, Seg &&seg) 
   // ---------------- forward sweep over knots 1 .. M-1 ----------------
   double tacc = 0.0;      // the durations before the current segment, summed as msnap_eval_flat sums them
   for (int i = 1; i < M; ++i) {
-    const double tnext = sT[(i + 1) * TD];
+    const double tnext = sT[(i + 1) * TS];
     const double wnext = lw[(i + 1) * 4];
     tacc = tacc + T;
     T = tnext - tcur;
+    see(tnext, wnext, T);
     x = rcp64(T);
     sX[i * TD] = x;
 
@@ -245,6 +280,7 @@ __device__ __forceinline__ bool ring_solve(const RingLane &p, int M, Seg &&seg) 
     sw.singular |= SW::ldl_factor(S0, dinv0);
     SW::ldl_solve(S0, dinv0, u0);
   }
+  singular = sw.singular;
 
   // ---------------- REFINE: residual of the ring in extended precision, the same elimination ----------------
   double du0[NU];
@@ -403,7 +439,7 @@ __device__ __forceinline__ bool ring_solve(const RingLane &p, int M, Seg &&seg) 
   for (int i = M - 1; i >= 0; --i) {
     double u[NU];
     const double wi = lw[i * 4];
-    const double ti = sT[i * TD];
+    const double ti = sT[i * TS];
     const double xi = sX[i * TD];
     const int kq = i >= 1 ? i : 1;      // (segment 0 starts from the seam state; its loads replay knot 1's)
     const double *h = gslot(p.sH, kq), *zz = zslot(p.sZ, kq);
@@ -432,7 +468,6 @@ __device__ __forceinline__ bool ring_solve(const RingLane &p, int M, Seg &&seg) 
     wn = wi;
     tn = ti;
   }
-  return sw.singular;
 }
 
 }  // namespace msnap

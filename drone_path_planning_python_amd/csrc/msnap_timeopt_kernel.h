@@ -25,8 +25,9 @@
 // u_M through the last knot's G, segment 0 from u_0, and refine_end on the last segment when the coefficients leave.
 //
 // Closed loops (msnap_optimize_times_periodic): timeopt_kernel<K, kTimeoptRing>.  "The solve for T" is
-// msnap_solve_periodic's, so the trial is K15's ring elimination, ring_solve of msnap_ring.h, over a stash that is the
-// one below plus H and, for the coefficients that leave, the correction's z'.  The envelope gradient holds on the ring
+// msnap_solve_periodic's, so the trial is K15's ring elimination, ring_solve of msnap_ring.h -- the call K15's own
+// kernel makes, here at a run-time tile size -- over a stash that is the one below plus H and, for the coefficients
+// that leave, the correction's z'.  The envelope gradient holds on the ring
 // (the seam state is a stationary unknown like every interior knot), so input stage, floor, direction, step rules and
 // results are the lines below unchanged; the mode is one `if constexpr` around the trial's body.
 //
@@ -215,7 +216,7 @@ timeopt_kernel(const TimeoptArgsOf<MODE> p) {
       double *sZ2 = sS + (size_t)TD * NU * NU * knots + ql;
       const RingLane rl = {lw, sT, sX + dloc, sG + dloc, sS + dloc, sZ, sZ2, TD};
       double Ja = 0.0;
-      singular = ring_solve<K, EMIT>(rl, M, [&](int i, double (&c)[NC], double Ti) {
+      ring_solve<K, EMIT>(rl, M, singular, [&](int i, double (&c)[NC], double Ti) {
         if constexpr (EMIT) {
           double *base = p.coef + ((size_t)tile * TD * M + i) * (4 * NC);
           if constexpr (NC == 8) store_segment_quad8(base, MSNAP_SEG_STRIDE(M, NC), nvalid, lane, c, bad);

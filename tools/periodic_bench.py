@@ -31,8 +31,8 @@ from drone_path_planning_python_amd.swarm import DeviceCompute  # noqa: E402
 OUT = os.path.join(ROOT, "profiles", "periodic_bench.jsonl")
 SHAPES = [(7, 256, 10), (7, 4096, 10), (9, 256, 10), (9, 4096, 10)]
 # periodic_solve_kernel<K>: architectural / accumulation VGPRs, SGPRs, scratch bytes per lane, waves per SIMD by registers
-REGISTERS = {7: {"vgprs": 210, "agprs": 0, "sgprs": 70, "scratch": 0, "waves_per_simd": 2},
-             9: {"vgprs": 256, "agprs": 62, "sgprs": 97, "scratch": 0, "waves_per_simd": 1}}
+REGISTERS = {7: {"vgprs": 216, "agprs": 0, "sgprs": 58, "scratch": 0, "waves_per_simd": 2},
+             9: {"vgprs": 256, "agprs": 66, "sgprs": 90, "scratch": 0, "waves_per_simd": 1}}
 
 
 def time_shape(order, n, M):
