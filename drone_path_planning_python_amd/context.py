@@ -81,6 +81,30 @@ def _out_arrays(out, shapes):
     return tuple(out)
 
 
+def _waypoints_times(wp, t):
+    """Validated host (wp [N, m, 4], t [N, m] or shared [m]) -> wp, its pointer, t, its pointer, N, m, shared."""
+    wp, pwp = _host(wp, np.float64)
+    t, pt = _host(t, np.float64)
+    if wp.ndim != 3 or wp.shape[2] != 4:
+        raise ValueError("wp must be [N, m, 4]")
+    N, m, _ = wp.shape
+    shared = int(t.ndim == 1)
+    if (shared and t.shape != (m,)) or (not shared and t.shape != (N, m)):
+        raise ValueError("t must be [N, m] or [m]")
+    return wp, pwp, t, pt, N, m, shared
+
+
+def _weights(weights):
+    """The host array of the 4 axis weights (x, y, z, yaw) and its address; the caller holds the array while the
+    library reads it.  The address is taken as a number: `_host`'s `data_as` costs several times as much, on every
+    call of a device entry, and that pays for the frame the allocators' shared bodies add to such a call
+    (profiles/timeopt_call_record.md)."""
+    w = np.ascontiguousarray(weights, dtype=np.float64)
+    if w.shape != (4,):
+        raise ValueError("weights must hold 4 values")
+    return w, ctypes.c_void_p(w.ctypes.data)
+
+
 class Context:
     """One msnap context (include/msnap.h: msnap_create / msnap_destroy)."""
 
@@ -148,6 +172,52 @@ class Context:
                              f"order-{self.order} context, got {coef.shape}")
         return coef, pc, dur, pd, N, M
 
+    def _mode_max_segments(self, fn):
+        """What the library's `fn` (a *_max_segments entry) allows at this context's order, and at most max_segments."""
+        return min(int(fn(self.order)), self.max_segments)
+
+    def _optimize_times(self, entry, wp, t, states, weights, time_weight, min_fraction, max_iter, tol):
+        """The host allocators' one body: `entry` names the library's entry of the mode (looked up after the shape
+        checks, which need no library), `states` is its (start, end) and `time_weight` its (time_weight,) -- () where
+        it takes none; the other arguments and the result tuple as optimize_times."""
+        wp, pwp, t, pt, N, m, shared = _waypoints_times(wp, t)
+        w, pw = _weights(weights)
+        kts = []      # (the converted arrays and their pointers, as _host gives them)
+        for kt in time_weight:
+            kt = np.asarray(kt, dtype=np.float64)
+            if kt.ndim == 0:
+                kt = np.full((N,), float(kt))
+            if kt.shape != (N,):
+                raise ValueError("time_weight must be a number or [N]")
+            kts.append(_host(kt, np.float64))
+        ends = [self._state_block(x, N, name) for x, name in zip(states, ("start", "end"))]
+        M = m - 1
+        t_out = np.empty((N, m), dtype=np.float64)
+        coef = np.empty((N, max(M, 0), 4, self.ncoef), dtype=np.float64)
+        dur = np.empty((N, max(M, 0)), dtype=np.float64)
+        status = np.empty((N,), dtype=np.int32)
+        cost = np.empty((N, 2), dtype=np.float64)
+        pg = np.empty((N,), dtype=np.float64)
+        iters = np.empty((N,), dtype=np.int32)
+        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)   # noqa: E731
+        with self._lock:
+            self._ck(getattr(self._lib, entry)(
+                self._h, N, M, pwp, pt, shared, *(px for _, px in ends), pw, *(pk for _, pk in kts),
+                float(min_fraction), int(max_iter), float(tol), vp(t_out), vp(coef), vp(dur), vp(status), vp(cost),
+                vp(pg), vp(iters)))
+        return t_out, coef, dur, status, {"cost": cost, "pg": pg, "iters": iters}
+
+    def _optimize_times_device(self, entry, n_drones, n_seg, wp, t, shared_times, states, weights, time_weight,
+                               min_fraction, max_iter, tol, t_out, coef, dur, status, cost, pg, iters):
+        """The device allocators' one body: `entry` names the library's _device entry of the mode, `states` holds the
+        pointers of its (start, end) and `time_weight` that of its time weight -- () where it takes none."""
+        w, pw = _weights(weights)
+        with self._lock:
+            self._ck(getattr(self._lib, entry)(
+                self._h, int(n_drones), int(n_seg), _ptr(wp), _ptr(t), int(bool(shared_times)), *states, pw,
+                *time_weight, float(min_fraction), int(max_iter), float(tol), _ptr(t_out), _ptr(coef), _ptr(dur),
+                _ptr(status), _ptr(cost), _ptr(pg), _ptr(iters)))
+
     # ---- stream / timing ------------------------------------------------------
     def set_stream(self, hip_stream: int | None):
         """Launch on an external hipStream_t (0 / None = the HIP null stream)."""
@@ -178,14 +248,7 @@ class Context:
         """wp [N, m, 4], t [N, m] or shared [m] (host) ->
         coef [N, M, 4, ncoef], dur [N, M], status [N] int32.
         `out=(coef, dur, status)` writes into caller-owned arrays (e.g. from pinned_empty)."""
-        wp, pwp = _host(wp, np.float64)
-        t, pt = _host(t, np.float64)
-        if wp.ndim != 3 or wp.shape[2] != 4:
-            raise ValueError("wp must be [N, m, 4]")
-        N, m, _ = wp.shape
-        shared = int(t.ndim == 1)
-        if (shared and t.shape != (m,)) or (not shared and t.shape != (N, m)):
-            raise ValueError("t must be [N, m] or [m]")
+        wp, pwp, t, pt, N, m, shared = _waypoints_times(wp, t)
         M = m - 1
         coef, dur, status = _out_arrays(out, ((N, max(M, 0), 4, self.ncoef), (N, max(M, 0)), (N,)))
         with self._lock:
@@ -373,43 +436,13 @@ class Context:
         (msnap_optimize_times): wp [N, m, 4], t [N, m] or shared [m] with t[0] == 0 ->
         (t_out [N, m], coef [N, M, 4, ncoef], dur [N, M], status [N] int32, info) with info = {"cost": [N, 2] (at
         the input times, at t_out), "pg": [N] stopping measure, "iters": [N] accepted steps}."""
-        wp, pwp = _host(wp, np.float64)
-        t, pt = _host(t, np.float64)
-        if wp.ndim != 3 or wp.shape[2] != 4:
-            raise ValueError("wp must be [N, m, 4]")
-        N, m, _ = wp.shape
-        shared = int(t.ndim == 1)
-        if (shared and t.shape != (m,)) or (not shared and t.shape != (N, m)):
-            raise ValueError("t must be [N, m] or [m]")
-        w, pw = _host(weights, np.float64)
-        if w.shape != (4,):
-            raise ValueError("weights must hold 4 values")
-        M = m - 1
-        t_out = np.empty((N, m), dtype=np.float64)
-        coef = np.empty((N, max(M, 0), 4, self.ncoef), dtype=np.float64)
-        dur = np.empty((N, max(M, 0)), dtype=np.float64)
-        status = np.empty((N,), dtype=np.int32)
-        cost = np.empty((N, 2), dtype=np.float64)
-        pg = np.empty((N,), dtype=np.float64)
-        iters = np.empty((N,), dtype=np.int32)
-        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)   # noqa: E731
-        with self._lock:
-            self._ck(self._lib.msnap_optimize_times(
-                self._h, N, M, pwp, pt, shared, pw, float(min_fraction), int(max_iter), float(tol), vp(t_out),
-                vp(coef), vp(dur), vp(status), vp(cost), vp(pg), vp(iters)))
-        return t_out, coef, dur, status, {"cost": cost, "pg": pg, "iters": iters}
+        return self._optimize_times("msnap_optimize_times", wp, t, (), weights, (), min_fraction, max_iter, tol)
 
     def optimize_times_device(self, n_drones, n_seg, wp, t, shared_times, weights, min_fraction, max_iter, tol,
                               t_out, coef, dur, status, cost=None, pg=None, iters=None):
         """Device pointers, asynchronous; `weights` is a host sequence of 4 (x, y, z, yaw)."""
-        w, pw = _host(weights, np.float64)
-        if w.shape != (4,):
-            raise ValueError("weights must hold 4 values")
-        with self._lock:
-            self._ck(self._lib.msnap_optimize_times_device(
-                self._h, int(n_drones), int(n_seg), _ptr(wp), _ptr(t), int(bool(shared_times)), pw,
-                float(min_fraction), int(max_iter), float(tol), _ptr(t_out), _ptr(coef), _ptr(dur), _ptr(status),
-                _ptr(cost), _ptr(pg), _ptr(iters)))
+        self._optimize_times_device("msnap_optimize_times_device", n_drones, n_seg, wp, t, shared_times, (), weights, (),
+                                    min_fraction, max_iter, tol, t_out, coef, dur, status, cost, pg, iters)
 
     # ---- dynamic limits (include/msnap.h: certified peaks, uniform retiming) --------------
     @staticmethod
@@ -604,7 +637,7 @@ class Context:
     # ---- replanning in flight (include/msnap.h) -------------------------------------
     def solve_states_max_segments(self) -> int:
         """Largest segment count solve_states takes at this context's order (and at most max_segments)."""
-        return min(int(self._lib.msnap_solve_states_max_segments(self.order)), self.max_segments)
+        return self._mode_max_segments(self._lib.msnap_solve_states_max_segments)
 
     def _state_block(self, x, N, name):
         if x is None:
@@ -619,14 +652,7 @@ class Context:
         """solve_batch from and to given end states (msnap_solve_states): wp [N, m, 4], t [N, m] or shared [m] with
         t[0] == 0, start / end [N, 4, K-1] -- entry q-1 the q-th derivative at the first / last waypoint -- or None for
         rest -> coef [N, M, 4, ncoef], dur [N, M], status [N] int32."""
-        wp, pwp = _host(wp, np.float64)
-        t, pt = _host(t, np.float64)
-        if wp.ndim != 3 or wp.shape[2] != 4:
-            raise ValueError("wp must be [N, m, 4]")
-        N, m, _ = wp.shape
-        shared = int(t.ndim == 1)
-        if (shared and t.shape != (m,)) or (not shared and t.shape != (N, m)):
-            raise ValueError("t must be [N, m] or [m]")
+        wp, pwp, t, pt, N, m, shared = _waypoints_times(wp, t)
         M = m - 1
         start, ps = self._state_block(start, N, "start")
         end, pe = self._state_block(end, N, "end")
@@ -647,20 +673,13 @@ class Context:
     # ---- closed-loop paths (include/msnap.h) ----------------------------------------
     def solve_periodic_max_segments(self) -> int:
         """Largest segment count solve_periodic takes at this context's order (and at most max_segments)."""
-        return min(int(self._lib.msnap_solve_periodic_max_segments(self.order)), self.max_segments)
+        return self._mode_max_segments(self._lib.msnap_solve_periodic_max_segments)
 
     def solve_periodic(self, wp, t):
         """The closed-loop minimum-snap solve (msnap_solve_periodic): wp [N, m, 4], t [N, m] or shared [m] with
         t[0] == 0 and m >= 3; the last waypoint is joined to the first with derivatives 1 .. 2K-2 continuous, the period
         is t[-1], wp[:, -1] - wp[:, 0] the lap offset -> coef [N, M, 4, ncoef], dur [N, M], status [N] int32."""
-        wp, pwp = _host(wp, np.float64)
-        t, pt = _host(t, np.float64)
-        if wp.ndim != 3 or wp.shape[2] != 4:
-            raise ValueError("wp must be [N, m, 4]")
-        N, m, _ = wp.shape
-        shared = int(t.ndim == 1)
-        if (shared and t.shape != (m,)) or (not shared and t.shape != (N, m)):
-            raise ValueError("t must be [N, m] or [m]")
+        wp, pwp, t, pt, N, m, shared = _waypoints_times(wp, t)
         M = m - 1
         coef, dur, status = _out_arrays(None, ((N, max(M, 0), 4, self.ncoef), (N, max(M, 0)), (N,)))
         vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)      # noqa: E731
@@ -677,7 +696,7 @@ class Context:
 
     def optimize_times_states_max_segments(self) -> int:
         """Largest segment count optimize_times_states takes at this context's order (and at most max_segments)."""
-        return min(int(self._lib.msnap_optimize_times_states_max_segments(self.order)), self.max_segments)
+        return self._mode_max_segments(self._lib.msnap_optimize_times_states_max_segments)
 
     def optimize_times_states(self, wp, t, start=None, end=None, weights=(1, 1, 1, 1), min_fraction=0.1, max_iter=200,
                               tol=1e-4):
@@ -685,95 +704,36 @@ class Context:
         max_iter, tol and the result tuple as optimize_times; start / end [N, 4, K-1] as solve_states takes them, or
         None for rest.  Waypoints, both end states and the total duration are kept; coef, dur are the boundary-state
         solution for t_out."""
-        wp, pwp = _host(wp, np.float64)
-        t, pt = _host(t, np.float64)
-        if wp.ndim != 3 or wp.shape[2] != 4:
-            raise ValueError("wp must be [N, m, 4]")
-        N, m, _ = wp.shape
-        shared = int(t.ndim == 1)
-        if (shared and t.shape != (m,)) or (not shared and t.shape != (N, m)):
-            raise ValueError("t must be [N, m] or [m]")
-        w, pw = _host(weights, np.float64)
-        if w.shape != (4,):
-            raise ValueError("weights must hold 4 values")
-        start, ps = self._state_block(start, N, "start")
-        end, pe = self._state_block(end, N, "end")
-        M = m - 1
-        t_out = np.empty((N, m), dtype=np.float64)
-        coef = np.empty((N, max(M, 0), 4, self.ncoef), dtype=np.float64)
-        dur = np.empty((N, max(M, 0)), dtype=np.float64)
-        status = np.empty((N,), dtype=np.int32)
-        cost = np.empty((N, 2), dtype=np.float64)
-        pg = np.empty((N,), dtype=np.float64)
-        iters = np.empty((N,), dtype=np.int32)
-        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)   # noqa: E731
-        with self._lock:
-            self._ck(self._lib.msnap_optimize_times_states(
-                self._h, N, M, pwp, pt, shared, ps, pe, pw, float(min_fraction), int(max_iter), float(tol), vp(t_out),
-                vp(coef), vp(dur), vp(status), vp(cost), vp(pg), vp(iters)))
-        return t_out, coef, dur, status, {"cost": cost, "pg": pg, "iters": iters}
+        return self._optimize_times("msnap_optimize_times_states", wp, t, (start, end), weights, (),
+                                    min_fraction, max_iter, tol)
 
     def optimize_times_states_device(self, n_drones, n_seg, wp, t, shared_times, start, end, weights, min_fraction,
                                      max_iter, tol, t_out, coef, dur, status, cost=None, pg=None, iters=None):
         """Device pointers (start / end may be None: rest), asynchronous; `weights` is a host sequence of 4."""
-        w, pw = _host(weights, np.float64)
-        if w.shape != (4,):
-            raise ValueError("weights must hold 4 values")
-        with self._lock:
-            self._ck(self._lib.msnap_optimize_times_states_device(
-                self._h, int(n_drones), int(n_seg), _ptr(wp), _ptr(t), int(bool(shared_times)), _ptr(start), _ptr(end),
-                pw, float(min_fraction), int(max_iter), float(tol), _ptr(t_out), _ptr(coef), _ptr(dur), _ptr(status),
-                _ptr(cost), _ptr(pg), _ptr(iters)))
+        self._optimize_times_device("msnap_optimize_times_states_device", n_drones, n_seg, wp, t, shared_times,
+                                    (_ptr(start), _ptr(end)), weights, (), min_fraction, max_iter, tol, t_out, coef,
+                                    dur, status, cost, pg, iters)
 
     def optimize_times_periodic_max_segments(self) -> int:
         """Largest segment count optimize_times_periodic takes at this context's order (and at most max_segments)."""
-        return min(int(self._lib.msnap_optimize_times_periodic_max_segments(self.order)), self.max_segments)
+        return self._mode_max_segments(self._lib.msnap_optimize_times_periodic_max_segments)
 
     def optimize_times_periodic(self, wp, t, weights=(1, 1, 1, 1), min_fraction=0.1, max_iter=200, tol=1e-4):
         """optimize_times on closed loops (msnap_optimize_times_periodic): wp, t (m >= 3 waypoints) as solve_periodic
         takes them, the other arguments and the result tuple as optimize_times.  Waypoints and the period t[-1] are
         kept; coef, dur are the periodic solution for t_out."""
-        wp, pwp = _host(wp, np.float64)
-        t, pt = _host(t, np.float64)
-        if wp.ndim != 3 or wp.shape[2] != 4:
-            raise ValueError("wp must be [N, m, 4]")
-        N, m, _ = wp.shape
-        shared = int(t.ndim == 1)
-        if (shared and t.shape != (m,)) or (not shared and t.shape != (N, m)):
-            raise ValueError("t must be [N, m] or [m]")
-        w, pw = _host(weights, np.float64)
-        if w.shape != (4,):
-            raise ValueError("weights must hold 4 values")
-        M = m - 1
-        t_out = np.empty((N, m), dtype=np.float64)
-        coef = np.empty((N, max(M, 0), 4, self.ncoef), dtype=np.float64)
-        dur = np.empty((N, max(M, 0)), dtype=np.float64)
-        status = np.empty((N,), dtype=np.int32)
-        cost = np.empty((N, 2), dtype=np.float64)
-        pg = np.empty((N,), dtype=np.float64)
-        iters = np.empty((N,), dtype=np.int32)
-        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)   # noqa: E731
-        with self._lock:
-            self._ck(self._lib.msnap_optimize_times_periodic(
-                self._h, N, M, pwp, pt, shared, pw, float(min_fraction), int(max_iter), float(tol), vp(t_out),
-                vp(coef), vp(dur), vp(status), vp(cost), vp(pg), vp(iters)))
-        return t_out, coef, dur, status, {"cost": cost, "pg": pg, "iters": iters}
+        return self._optimize_times("msnap_optimize_times_periodic", wp, t, (), weights, (), min_fraction,
+                                    max_iter, tol)
 
     def optimize_times_periodic_device(self, n_drones, n_seg, wp, t, shared_times, weights, min_fraction, max_iter, tol,
                                        t_out, coef, dur, status, cost=None, pg=None, iters=None):
         """Device pointers, asynchronous; `weights` is a host sequence of 4 (x, y, z, yaw)."""
-        w, pw = _host(weights, np.float64)
-        if w.shape != (4,):
-            raise ValueError("weights must hold 4 values")
-        with self._lock:
-            self._ck(self._lib.msnap_optimize_times_periodic_device(
-                self._h, int(n_drones), int(n_seg), _ptr(wp), _ptr(t), int(bool(shared_times)), pw,
-                float(min_fraction), int(max_iter), float(tol), _ptr(t_out), _ptr(coef), _ptr(dur), _ptr(status),
-                _ptr(cost), _ptr(pg), _ptr(iters)))
+        self._optimize_times_device("msnap_optimize_times_periodic_device", n_drones, n_seg, wp, t, shared_times, (),
+                                    weights, (), min_fraction, max_iter, tol, t_out, coef, dur, status, cost, pg, iters)
 
     def optimize_times_free_max_segments(self) -> int:
         """Largest segment count optimize_times_free takes at this context's order (and at most max_segments)."""
-        return min(int(self._lib.msnap_optimize_times_free_max_segments(self.order)), self.max_segments)
+        return self._mode_max_segments(self._lib.msnap_optimize_times_free_max_segments)
 
     def optimize_times_free(self, wp, t, start=None, end=None, weights=(1, 1, 1, 1), time_weight=1.0, min_fraction=0.1,
                             max_iter=200, tol=1e-4):
@@ -781,53 +741,17 @@ class Context:
         sum_a weights[a] J_a + time_weight * t_out[-1] over every segment duration.  time_weight > 0 is a number or
         [N], one per drone; t[-1] is a starting guess and the floor's scale.  The result tuple is optimize_times's,
         with info["cost"] the objective (time term included) at the raised input times and at t_out."""
-        wp, pwp = _host(wp, np.float64)
-        t, pt = _host(t, np.float64)
-        if wp.ndim != 3 or wp.shape[2] != 4:
-            raise ValueError("wp must be [N, m, 4]")
-        N, m, _ = wp.shape
-        shared = int(t.ndim == 1)
-        if (shared and t.shape != (m,)) or (not shared and t.shape != (N, m)):
-            raise ValueError("t must be [N, m] or [m]")
-        w, pw = _host(weights, np.float64)
-        if w.shape != (4,):
-            raise ValueError("weights must hold 4 values")
-        kt = np.asarray(time_weight, dtype=np.float64)
-        if kt.ndim == 0:
-            kt = np.full((N,), float(kt))
-        if kt.shape != (N,):
-            raise ValueError("time_weight must be a number or [N]")
-        kt, pk = _host(kt, np.float64)
-        start, ps = self._state_block(start, N, "start")
-        end, pe = self._state_block(end, N, "end")
-        M = m - 1
-        t_out = np.empty((N, m), dtype=np.float64)
-        coef = np.empty((N, max(M, 0), 4, self.ncoef), dtype=np.float64)
-        dur = np.empty((N, max(M, 0)), dtype=np.float64)
-        status = np.empty((N,), dtype=np.int32)
-        cost = np.empty((N, 2), dtype=np.float64)
-        pg = np.empty((N,), dtype=np.float64)
-        iters = np.empty((N,), dtype=np.int32)
-        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)   # noqa: E731
-        with self._lock:
-            self._ck(self._lib.msnap_optimize_times_free(
-                self._h, N, M, pwp, pt, shared, ps, pe, pw, pk, float(min_fraction), int(max_iter), float(tol),
-                vp(t_out), vp(coef), vp(dur), vp(status), vp(cost), vp(pg), vp(iters)))
-        return t_out, coef, dur, status, {"cost": cost, "pg": pg, "iters": iters}
+        return self._optimize_times("msnap_optimize_times_free", wp, t, (start, end), weights, (time_weight,),
+                                    min_fraction, max_iter, tol)
 
     def optimize_times_free_device(self, n_drones, n_seg, wp, t, shared_times, start, end, weights, time_weight,
                                    min_fraction, max_iter, tol, t_out, coef, dur, status, cost=None, pg=None,
                                    iters=None):
         """Device pointers (start / end may be None: rest; time_weight [n_drones] float64 on the device),
         asynchronous; `weights` is a host sequence of 4."""
-        w, pw = _host(weights, np.float64)
-        if w.shape != (4,):
-            raise ValueError("weights must hold 4 values")
-        with self._lock:
-            self._ck(self._lib.msnap_optimize_times_free_device(
-                self._h, int(n_drones), int(n_seg), _ptr(wp), _ptr(t), int(bool(shared_times)), _ptr(start), _ptr(end),
-                pw, _ptr(time_weight), float(min_fraction), int(max_iter), float(tol), _ptr(t_out), _ptr(coef),
-                _ptr(dur), _ptr(status), _ptr(cost), _ptr(pg), _ptr(iters)))
+        self._optimize_times_device("msnap_optimize_times_free_device", n_drones, n_seg, wp, t, shared_times,
+                                    (_ptr(start), _ptr(end)), weights, (_ptr(time_weight),), min_fraction, max_iter,
+                                    tol, t_out, coef, dur, status, cost, pg, iters)
 
     def eval_state(self, coef, dur, tq):
         """Full state of each drone at its own time tq [N] (msnap_eval_state): pos [N, 4], deriv [N, 4, K-1] with

@@ -158,20 +158,36 @@ int launch_eval_flat(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef
                      int n_samples, const double *ts, double *out);
 int launch_snap_cost(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur, double *cost);
 int launch_snap_cost_grad(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, double *grad);
-// time allocation (msnap_timeopt.hip): the whole iteration of a batch in one launch; cost, pg, iters may be null.
-// mode 0: rest to rest; 1: from and to given end states (start / end: [n_drones][4][K-1] on the device, or null for
-// rest); 2: closed loop, the trial is the periodic solve
-int launch_optimize_times(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, const double *t, int shared_times,
-                          int mode, const double *start, const double *end, const double *weights,
-                          double min_fraction, int max_iter, double tol, double *t_out, double *coef, double *dur,
-                          int32_t *status, double *cost, double *pg, int32_t *iters);
-// (mode 2's instances and their launch: msnap_timeopt_periodic.hip)
-int launch_optimize_times_ring(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, const double *t,
-                               int shared_times, const double *weights, double min_fraction, int max_iter, double tol,
-                               double *t_out, double *coef, double *dur, int32_t *status, double *cost, double *pg,
-                               int32_t *iters);
-// (mode 3, the free total of msnap_optimize_times_free: instances, launch and entries in msnap_timeopt_free.hip)
-// largest n_seg whose per-tile state fits LDS (80 at order 7, 58 at order 9; mode 1: see DESIGN.md K8; mode 2: 48, 33)
+// time allocation (msnap_timeopt.hip): the whole iteration of a batch in one launch.  The modes: rest to rest
+// (msnap_optimize_times), from and to given end states (_states), closed loop, the trial being the periodic solve
+// (_periodic), end states with the total duration free (_free).
+enum TimeoptMode : int { kTimeoptRest = 0, kTimeoptEnds = 1, kTimeoptRing = 2, kTimeoptFree = 3 };
+// One allocation call, in the order of msnap_optimize_times_free's parameters.  Every mode reads all fields but these:
+// start / end ([n_drones][4][K-1], or null for rest) are read with kTimeoptEnds and kTimeoptFree only, time_weight
+// ([n_drones], required) with kTimeoptFree only; an entry whose mode has none leaves them null.  cost, pg, iters may be
+// null in every mode.  weights is a host array of 4; every other pointer is the host's in a host entry and the device's
+// from launch_optimize_times on.
+struct TimeoptCall {
+  int n_drones, n_seg;
+  const double *wp, *t;
+  int shared_times;
+  const double *start, *end, *weights, *time_weight;
+  double min_fraction;
+  int max_iter;
+  double tol;
+  double *t_out, *coef, *dur;
+  int32_t *status;
+  double *cost, *pg;
+  int32_t *iters;
+};
+// the one launch other code calls, asynchronous on ctx->stream
+int launch_optimize_times(msnap_ctx *ctx, int mode, const TimeoptCall &call);
+// (what it calls for the modes whose instances are objects of their own: msnap_timeopt_periodic.hip,
+// msnap_timeopt_free.hip)
+int launch_optimize_times_ring(msnap_ctx *ctx, const TimeoptCall &call);
+int launch_optimize_times_free(msnap_ctx *ctx, const TimeoptCall &call);
+// largest n_seg whose per-tile state fits LDS (80 at order 7, 58 at order 9; kTimeoptEnds: see DESIGN.md K8;
+// kTimeoptRing: 48, 33)
 int timeopt_max_segments(int khalf, int mode);
 // (the pairwise pass: msnap_collide.h)
 int launch_mesh_sweep(msnap_ctx *ctx, int n_drones, int n_samples, const double *pos, int n_tris,

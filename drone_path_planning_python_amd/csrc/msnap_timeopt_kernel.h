@@ -38,17 +38,18 @@
 // check, a raise of short durations nobody pays for, cost and gradient with the time term, the direction, a last knot
 // that moves, and the current total in the stopping measure.
 //
-// One kernel text, three translation units: msnap_timeopt.hip instantiates the rest-to-rest and end-state modes (and
-// holds their entry points), msnap_timeopt_periodic.hip the ring mode and msnap_timeopt_free.hip the free-total mode
-// with its entries -- objects of their own, so that what is held of msnap_timeopt.o (its instructions, its kernel
-// count, no register-pressure copy) stays true.  Everything here has internal linkage.
+// One kernel text, three translation units: msnap_timeopt.hip instantiates the rest-to-rest and end-state modes and
+// holds every mode's entry points and launch_optimize_times, the one launch function they call;
+// msnap_timeopt_periodic.hip instantiates the ring mode and msnap_timeopt_free.hip the free-total mode, each behind one
+// launch function of its own -- objects of their own, so that what is held of msnap_timeopt.o (its instructions, its
+// kernel count, no register-pressure copy) stays true.  Everything here has internal linkage.
 #pragma once
 
 #include <math.h>
 
+#include <initializer_list>
 #include <type_traits>
 
-#include "msnap_api_util.h"
 #include "msnap_internal.h"
 #include "msnap_ring.h"
 #include "msnap_rolled.h"
@@ -86,8 +87,6 @@ __device__ __forceinline__ double quad_weighted_sum(double v, double wa) {
   const double p = wa == 0.0 ? 0.0 : wa * v;
   return ((quad_bcast<0>(p) + quad_bcast<1>(p)) + quad_bcast<2>(p)) + quad_bcast<3>(p);
 }
-
-enum TimeoptMode : int { kTimeoptRest = 0, kTimeoptEnds = 1, kTimeoptRing = 2, kTimeoptFree = 3 };
 
 template <int MODE>
 using TimeoptArgsOf = std::conditional_t<MODE == kTimeoptFree, TimeoptFreeArgs,
@@ -506,19 +505,16 @@ static_assert(timeopt_tile_segments(4, 16, kTimeoptRing) == 24 && timeopt_tile_s
                   timeopt_tile_segments(4, 8, kTimeoptRing) == 48 && timeopt_tile_segments(5, 8, kTimeoptRing) == 33,
               "DESIGN.md K16 and include/msnap.h quote these");
 
-// One mode's launch: the tile size, the kernels' dynamic-LDS limit (raised to the full 160 KiB once per context and
-// mode: a function attribute is a property of the device's module), the arguments.  start / end: device pointers or
-// null, looked at with kTimeoptEnds and kTimeoptFree only; time_weight: a device pointer, kTimeoptFree only.
+// One mode's launch of a call whose pointers are the device's (TimeoptCall, msnap_internal.h): the tile size, the
+// kernels' dynamic-LDS limit (raised to the full 160 KiB once per context and mode: a function attribute is a property
+// of the device's module), the arguments.
 template <int MODE>
-int timeopt_launch(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, const double *t, int shared_times,
-                   const double *start, const double *end, const double *weights, double min_fraction, int max_iter,
-                   double tol, double *t_out, double *coef, double *dur, int32_t *status, double *cost, double *pg,
-                   int32_t *iters, const double *time_weight = nullptr) {
-  if (n_drones == 0) return MSNAP_OK;
+int timeopt_launch(msnap_ctx *ctx, const TimeoptCall &c) {
+  if (c.n_drones == 0) return MSNAP_OK;
   // 16 drones per wave while their stash fits LDS, 8 above
   const int TD =
-      timeopt_lds_words(ctx->khalf, n_seg, kDronesPerWave, MODE) * sizeof(double) <= kMaxLdsBytes ? kDronesPerWave : 8;
-  const size_t lds_bytes = timeopt_lds_words(ctx->khalf, n_seg, TD, MODE) * sizeof(double);
+      timeopt_lds_words(ctx->khalf, c.n_seg, kDronesPerWave, MODE) * sizeof(double) <= kMaxLdsBytes ? kDronesPerWave : 8;
+  const size_t lds_bytes = timeopt_lds_words(ctx->khalf, c.n_seg, TD, MODE) * sizeof(double);
   if (lds_bytes > kMaxLdsBytes) return MSNAP_ESEGMENTS;
   if (!(ctx->timeopt_ready & (1 << MODE))) {
     for (const void *k : {reinterpret_cast<const void *>(&timeopt_kernel<4, MODE>),
@@ -527,50 +523,34 @@ int timeopt_launch(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, co
     ctx->timeopt_ready |= 1 << MODE;
   }
   TimeoptArgsOf<MODE> a;
-  a.wp = wp;
-  a.tt = t;
-  a.shared_times = shared_times;
-  a.N = n_drones;
-  a.M = n_seg;
+  a.wp = c.wp;
+  a.tt = c.t;
+  a.shared_times = c.shared_times ? 1 : 0;
+  a.N = c.n_drones;
+  a.M = c.n_seg;
   a.TD = TD;
-  for (int q = 0; q < 4; ++q) a.w[q] = weights[q];
-  a.min_fraction = min_fraction;
-  a.tol = tol;
-  a.max_iter = max_iter;
-  a.t_out = t_out;
-  a.coef = coef;
-  a.dur = dur;
-  a.status = status;
-  a.cost = cost;
-  a.pg = pg;
-  a.iters = iters;
+  for (int q = 0; q < 4; ++q) a.w[q] = c.weights[q];
+  a.min_fraction = c.min_fraction;
+  a.tol = c.tol;
+  a.max_iter = c.max_iter;
+  a.t_out = c.t_out;
+  a.coef = c.coef;
+  a.dur = c.dur;
+  a.status = c.status;
+  a.cost = c.cost;
+  a.pg = c.pg;
+  a.iters = c.iters;
   if constexpr (MODE == kTimeoptEnds || MODE == kTimeoptFree) {
-    a.start = start;
-    a.end = end;
+    a.start = c.start;
+    a.end = c.end;
   }
-  if constexpr (MODE == kTimeoptFree) a.time_weight = time_weight;
-  const int ntiles = (n_drones + TD - 1) / TD;
+  if constexpr (MODE == kTimeoptFree) a.time_weight = c.time_weight;
+  const int ntiles = (c.n_drones + TD - 1) / TD;
   if (ctx->khalf == 4)
     hipLaunchKernelGGL((timeopt_kernel<4, MODE>), dim3(ntiles), dim3(kWave), lds_bytes, ctx->stream, a);
   else
     hipLaunchKernelGGL((timeopt_kernel<5, MODE>), dim3(ntiles), dim3(kWave), lds_bytes, ctx->stream, a);
   MSNAP_HIP(ctx, hipGetLastError());
-  return MSNAP_OK;
-}
-
-// The argument check every allocation entry and its _device twin make (ptrs: the pointers the entry requires)
-int timeopt_args(const msnap_ctx *ctx, int n_drones, int n_seg, int mode, const double *weights, double min_fraction,
-                 int max_iter, double tol, std::initializer_list<const void *> ptrs) {
-  if (!ctx || n_drones < 0) return MSNAP_EINVAL;
-  if (int rc = check_seg(ctx, n_seg)) return rc;
-  if (n_seg > timeopt_max_segments(ctx->khalf, mode)) return MSNAP_ESEGMENTS;
-  if (mode == kTimeoptRing && n_seg < 2) return MSNAP_ESEGMENTS;      // (a loop has two segments at least)
-  if (!weights || !(min_fraction > 0.0 && min_fraction <= 1.0) || max_iter < 0 || !(tol >= 0.0)) return MSNAP_EINVAL;
-  for (int q = 0; q < 4; ++q)
-    if (!(weights[q] >= 0.0) || !(weights[q] <= 1.79769313486231570815e308)) return MSNAP_EINVAL;   // negative, NaN, Inf
-  if (n_drones == 0) return kNoWork;
-  for (const void *p : ptrs)
-    if (!p) return MSNAP_EINVAL;
   return MSNAP_OK;
 }
 

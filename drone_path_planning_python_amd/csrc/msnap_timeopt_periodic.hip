@@ -2,17 +2,13 @@
 // mode of the one kernel text in msnap_timeopt_kernel.h, whose trial is ring_solve of msnap_ring.h.  The instances
 // live in this object of their own: at order 9 they fill the 256 architectural VGPRs and keep 166 values in
 // accumulation registers (no scratch), and msnap_timeopt.o is held to no such copy at all.  The entry points are
-// msnap_timeopt.hip's.
+// msnap_timeopt.hip's; they reach the instances through launch_optimize_times.
 #include "msnap_timeopt_kernel.h"
 
 namespace msnap {
 
-int launch_optimize_times_ring(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, const double *t,
-                               int shared_times, const double *weights, double min_fraction, int max_iter, double tol,
-                               double *t_out, double *coef, double *dur, int32_t *status, double *cost, double *pg,
-                               int32_t *iters) {
-  return timeopt_launch<kTimeoptRing>(ctx, n_drones, n_seg, wp, t, shared_times, nullptr, nullptr, weights,
-                                      min_fraction, max_iter, tol, t_out, coef, dur, status, cost, pg, iters);
+int launch_optimize_times_ring(msnap_ctx *ctx, const TimeoptCall &call) {
+  return timeopt_launch<kTimeoptRing>(ctx, call);
 }
 
 }  // namespace msnap

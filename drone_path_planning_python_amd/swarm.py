@@ -19,9 +19,17 @@ same three methods to exercise the exchange logic under gloo.
 """
 from __future__ import annotations
 
+import functools
 from dataclasses import dataclass
 
 import numpy as np
+
+
+@functools.lru_cache(maxsize=None)
+def _output_names(method: str) -> tuple:
+    """The names DeviceCompute._out keys a method's outputs by -- "<method>.coef", .dur, .status and, for an allocator,
+    .t_out, .cost, .pg, .iters -- built once per method: the same string objects on every call keep their hash."""
+    return tuple(f"{method}.{x}" for x in ("coef", "dur", "status", "t_out", "cost", "pg", "iters"))
 
 
 def shard_bounds(n: int, world: int, rank: int) -> tuple:
@@ -271,31 +279,21 @@ class DeviceCompute:
     def solve_states(self, wp, t, start=None, end=None):
         """(coef, dur, status) of the solve from and to given end states: `start` / `end` [n, 4, K-1] float64 -- entry
         q-1 the q-th derivative at the first / last waypoint -- or None for rest; t[0] must be 0."""
-        torch = self.torch
         n, m, _ = wp.shape
         M = m - 1
-        nd = self.ctx.ncoef // 2 - 1
-        for name, x in (("start", start), ("end", end)):
-            if x is not None and (tuple(x.shape) != (n, 4, nd) or x.dtype != torch.float64):
-                raise ValueError(f"solve_states: {name} must be a float64 tensor [n, 4, {nd}]")
-        coef = self._out("solve_states.coef", (n, M, 4, self.ctx.ncoef), torch.float64)
-        dur = self._out("solve_states.dur", (n, M), torch.float64)
-        status = self._out("solve_states.status", (n,), torch.int32)
+        start, end = self._end_states("solve_states", n, start, end)
+        coef, dur, status = self._solve_outs("solve_states", n, M)
         if n:
-            self.ctx.solve_states_device(n, M, wp.contiguous(), t.contiguous(), t.dim() == 1,
-                                         None if start is None else start.contiguous(),
-                                         None if end is None else end.contiguous(), coef, dur, status)
+            self.ctx.solve_states_device(n, M, wp.contiguous(), t.contiguous(), t.dim() == 1, start, end, coef, dur,
+                                         status)
         return coef, dur, status
 
     def solve_periodic(self, wp, t):
         """(coef, dur, status) of the closed-loop solve: the last waypoint is joined to the first, the period is t[-1],
         wp[:, -1] - wp[:, 0] the lap offset; t[0] must be 0."""
-        torch = self.torch
         n, m, _ = wp.shape
         M = m - 1
-        coef = self._out("solve_periodic.coef", (n, M, 4, self.ctx.ncoef), torch.float64)
-        dur = self._out("solve_periodic.dur", (n, M), torch.float64)
-        status = self._out("solve_periodic.status", (n,), torch.int32)
+        coef, dur, status = self._solve_outs("solve_periodic", n, M)
         if n:
             self.ctx.solve_periodic_device(n, M, wp.contiguous(), t.contiguous(), t.dim() == 1, coef, dur, status)
         return coef, dur, status
@@ -304,46 +302,17 @@ class DeviceCompute:
         """(t_out, coef, dur, status, info) of the time allocation on closed loops: wp, t as solve_periodic takes them
         (the period t[-1] is kept), the rest as Context.optimize_times; info = {"cost": [n, 2], "pg": [n],
         "iters": [n] int32}."""
-        torch = self.torch
-        n, m, _ = wp.shape
-        M = m - 1
-        t_out = self._out("optimize_times_periodic.t_out", (n, m), torch.float64)
-        coef = self._out("optimize_times_periodic.coef", (n, M, 4, self.ctx.ncoef), torch.float64)
-        dur = self._out("optimize_times_periodic.dur", (n, M), torch.float64)
-        status = self._out("optimize_times_periodic.status", (n,), torch.int32)
-        cost = self._out("optimize_times_periodic.cost", (n, 2), torch.float64)
-        pg = self._out("optimize_times_periodic.pg", (n,), torch.float64)
-        iters = self._out("optimize_times_periodic.iters", (n,), torch.int32)
-        if n:
-            self.ctx.optimize_times_periodic_device(n, M, wp.contiguous(), t.contiguous(), t.dim() == 1, weights,
-                                                    min_fraction, max_iter, tol, t_out, coef, dur, status, cost, pg,
-                                                    iters)
-        return t_out, coef, dur, status, {"cost": cost, "pg": pg, "iters": iters}
+        return self._optimize_times("optimize_times_periodic", self.ctx.optimize_times_periodic_device, wp, t, (),
+                                    weights, (), min_fraction, max_iter, tol)
 
     def optimize_times_states(self, wp, t, start=None, end=None, weights=(1, 1, 1, 1), min_fraction=0.1, max_iter=200,
                               tol=1e-4):
         """(t_out, coef, dur, status, info) of the time allocation from and to given end states: arguments as
         solve_states plus the four of Context.optimize_times; info = {"cost": [n, 2], "pg": [n], "iters": [n] int32}."""
-        torch = self.torch
-        n, m, _ = wp.shape
-        M = m - 1
-        nd = self.ctx.ncoef // 2 - 1
-        for name, x in (("start", start), ("end", end)):
-            if x is not None and (tuple(x.shape) != (n, 4, nd) or x.dtype != torch.float64):
-                raise ValueError(f"optimize_times_states: {name} must be a float64 tensor [n, 4, {nd}]")
-        t_out = self._out("optimize_times_states.t_out", (n, m), torch.float64)
-        coef = self._out("optimize_times_states.coef", (n, M, 4, self.ctx.ncoef), torch.float64)
-        dur = self._out("optimize_times_states.dur", (n, M), torch.float64)
-        status = self._out("optimize_times_states.status", (n,), torch.int32)
-        cost = self._out("optimize_times_states.cost", (n, 2), torch.float64)
-        pg = self._out("optimize_times_states.pg", (n,), torch.float64)
-        iters = self._out("optimize_times_states.iters", (n,), torch.int32)
-        if n:
-            self.ctx.optimize_times_states_device(n, M, wp.contiguous(), t.contiguous(), t.dim() == 1,
-                                                  None if start is None else start.contiguous(),
-                                                  None if end is None else end.contiguous(), weights, min_fraction,
-                                                  max_iter, tol, t_out, coef, dur, status, cost, pg, iters)
-        return t_out, coef, dur, status, {"cost": cost, "pg": pg, "iters": iters}
+        n, _, _ = wp.shape
+        states = self._end_states("optimize_times_states", n, start, end)
+        return self._optimize_times("optimize_times_states", self.ctx.optimize_times_states_device, wp, t, states,
+                                    weights, (), min_fraction, max_iter, tol)
 
     def optimize_times_free(self, wp, t, start=None, end=None, weights=(1, 1, 1, 1), time_weight=1.0, min_fraction=0.1,
                             max_iter=200, tol=1e-4):
@@ -351,30 +320,49 @@ class DeviceCompute:
         optimize_times_states plus `time_weight` > 0, a number or a float64 tensor [n] (one per drone); t[-1] is a
         starting guess.  info as there, with "cost" the objective, time term included."""
         torch = self.torch
-        n, m, _ = wp.shape
-        M = m - 1
-        nd = self.ctx.ncoef // 2 - 1
-        for name, x in (("start", start), ("end", end)):
-            if x is not None and (tuple(x.shape) != (n, 4, nd) or x.dtype != torch.float64):
-                raise ValueError(f"optimize_times_free: {name} must be a float64 tensor [n, 4, {nd}]")
+        n, _, _ = wp.shape
+        states = self._end_states("optimize_times_free", n, start, end)
         if torch.is_tensor(time_weight):
             if tuple(time_weight.shape) != (n,) or time_weight.dtype != torch.float64:
                 raise ValueError("optimize_times_free: time_weight must be a number or a float64 tensor [n]")
             kt = time_weight.to(self.device).contiguous()
         else:
             kt = torch.full((n,), float(time_weight), dtype=torch.float64, device=self.device)
-        t_out = self._out("optimize_times_free.t_out", (n, m), torch.float64)
-        coef = self._out("optimize_times_free.coef", (n, M, 4, self.ctx.ncoef), torch.float64)
-        dur = self._out("optimize_times_free.dur", (n, M), torch.float64)
-        status = self._out("optimize_times_free.status", (n,), torch.int32)
-        cost = self._out("optimize_times_free.cost", (n, 2), torch.float64)
-        pg = self._out("optimize_times_free.pg", (n,), torch.float64)
-        iters = self._out("optimize_times_free.iters", (n,), torch.int32)
+        return self._optimize_times("optimize_times_free", self.ctx.optimize_times_free_device, wp, t, states, weights,
+                                    (kt,), min_fraction, max_iter, tol)
+
+    def _end_states(self, method, n, start, end):
+        """`start` / `end` of `method` checked -- None, or a float64 tensor [n, 4, K-1] -- and contiguous."""
+        nd = self.ctx.ncoef // 2 - 1
+        for name, x in (("start", start), ("end", end)):
+            if x is not None and (tuple(x.shape) != (n, 4, nd) or x.dtype != self.torch.float64):
+                raise ValueError(f"{method}: {name} must be a float64 tensor [n, 4, {nd}]")
+        return None if start is None else start.contiguous(), None if end is None else end.contiguous()
+
+    def _solve_outs(self, method, n, M):
+        """coef, dur, status of `method` for n paths of M segments."""
+        torch = self.torch
+        coef, dur, status = _output_names(method)[:3]
+        return (self._out(coef, (n, M, 4, self.ctx.ncoef), torch.float64),
+                self._out(dur, (n, M), torch.float64), self._out(status, (n,), torch.int32))
+
+    def _optimize_times(self, method, device_entry, wp, t, states, weights, time_weight, min_fraction, max_iter, tol):
+        """The allocators' one body: `device_entry` is Context's `<method>_device`; `states` its checked (start, end)
+        and `time_weight` its (tensor [n],) -- () where it takes none."""
+        torch, out = self.torch, self._out
+        n, m, _ = wp.shape
+        M = m - 1
+        coef, dur, status, t_out, cost, pg, iters = _output_names(method)
+        t_out = out(t_out, (n, m), torch.float64)
+        coef = out(coef, (n, M, 4, self.ctx.ncoef), torch.float64)
+        dur = out(dur, (n, M), torch.float64)
+        status = out(status, (n,), torch.int32)
+        cost = out(cost, (n, 2), torch.float64)
+        pg = out(pg, (n,), torch.float64)
+        iters = out(iters, (n,), torch.int32)
         if n:
-            self.ctx.optimize_times_free_device(n, M, wp.contiguous(), t.contiguous(), t.dim() == 1,
-                                                None if start is None else start.contiguous(),
-                                                None if end is None else end.contiguous(), weights, kt, min_fraction,
-                                                max_iter, tol, t_out, coef, dur, status, cost, pg, iters)
+            device_entry(n, M, wp.contiguous(), t.contiguous(), t.dim() == 1, *states, weights, *time_weight,
+                         min_fraction, max_iter, tol, t_out, coef, dur, status, cost, pg, iters)
         return t_out, coef, dur, status, {"cost": cost, "pg": pg, "iters": iters}
 
     def eval_state(self, coef, dur, tq):

@@ -17,6 +17,7 @@ from conftest import GOLDEN_DIR, norm_rel
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import states_exact as SE  # noqa: E402
+import timeopt_entry_cases as E  # noqa: E402
 import timeopt_free_ref as FR  # noqa: E402
 import timeopt_ref as R  # noqa: E402
 
@@ -293,6 +294,11 @@ def test_position_independence_entries_and_capture(ctx7):
     zero = np.zeros_like(start[:17])
     a = ctx7.optimize_times_free(wp[:17], t[:17], None, None, W1, 300.0)
     assert _same(a, ctx7.optimize_times_free(wp[:17], t[:17], zero, zero, W1, np.full(17, 300.0)))
+    # the host entry without its optional outputs, each state block given and NULL, against the device entry (one full
+    # 16-drone tile and a tail of one)
+    w3, t3, s3, e3 = SE.case(7, 3, N=17)
+    for states in ((s3, e3), (s3, None), (None, e3), (None, None)):
+        E.assert_host_entry_without_optionals_is_the_device_entry(ctx7, "_free", w3, t3, states, (kt[:17].copy(),))
     # the device entry, eager and inside a captured graph, on a context of its own
     dev = torch.device("cuda", 0)
     n, m = 17, 10

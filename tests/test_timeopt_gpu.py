@@ -13,6 +13,7 @@ import pytest
 from conftest import GOLDEN_DIR, norm_rel
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import timeopt_entry_cases as E  # noqa: E402
 import timeopt_ref as R  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -199,6 +200,8 @@ def test_position_independence_entries_and_scaling(ctx7):
         ctx.optimize_times_device(1, 10, dw, dt, 0, W1, 0.1, 200, 1e-4, o_t, o_c, o_d, o_s)
         torch.cuda.synchronize()
         assert np.array_equal(o_c.cpu().numpy(), one[1])
+    # ... for the host entry too (one full 16-drone tile and a tail of one)
+    E.assert_host_entry_without_optionals_is_the_device_entry(ctx7, "", *_swarm(2, 17, 3))
     # waypoints times 4: every quantity scales by a power of two
     four = ctx7.optimize_times(4.0 * wp[5:6], t[5:6])
     assert np.array_equal(four[0], one[0]) and np.array_equal(four[2], one[2])

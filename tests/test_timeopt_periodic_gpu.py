@@ -18,6 +18,7 @@ from conftest import GOLDEN_DIR, norm_rel
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import periodic_exact as PE  # noqa: E402
 import states_exact as SE  # noqa: E402
+import timeopt_entry_cases as E  # noqa: E402
 import timeopt_periodic_ref as PR  # noqa: E402
 import timeopt_ref as R  # noqa: E402
 
@@ -329,6 +330,8 @@ def test_position_tile_entry_and_scale(ctx7, ctx9, order):
         dctx.sync()
     o = [x.cpu().numpy() for x in outs]
     assert _same(tuple(o[:4]) + ({"cost": o[4], "pg": o[5], "iters": o[6]},), whole)
+    # the host entry without its optional outputs against the device entry (one full 16-drone tile and a tail of one)
+    E.assert_host_entry_without_optionals_is_the_device_entry(ctx, "_periodic", *PE.case(order, 3, N=17))
 
 
 # ---- 8. failed drones --------------------------------------------------------------------------------------------------------

@@ -16,6 +16,7 @@ from conftest import GOLDEN_DIR, norm_rel
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import states_exact as SE  # noqa: E402
+import timeopt_entry_cases as E  # noqa: E402
 import timeopt_ref as R  # noqa: E402
 import timeopt_states_ref as S  # noqa: E402
 
@@ -314,6 +315,11 @@ def test_position_independence_entries_and_capture(ctx7):
         w2, t2, s2, e2 = wp[:n].copy(), t[:n].copy(), start[:n].copy(), end[:n].copy()
         w2[pos], t2[pos], s2[pos], e2[pos] = wp[5], t[5], start[5], end[5]
         assert _same(ctx7.optimize_times_states(w2, t2, s2, e2), one, slice(pos, pos + 1)), (n, pos)
+    # the host entry without its optional outputs, each state block given and NULL, against the device entry (one full
+    # 16-drone tile and a tail of one)
+    w3, t3, s3, e3 = SE.case(7, 3, N=17)
+    for states in ((s3, e3), (s3, None), (None, e3), (None, None)):
+        E.assert_host_entry_without_optionals_is_the_device_entry(ctx7, "_states", w3, t3, states)
     # the device entry, eager and inside a captured graph, on a context of its own
     dev = torch.device("cuda", 0)
     n, m = 17, 10
