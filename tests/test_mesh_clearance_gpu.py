@@ -16,19 +16,7 @@ pytestmark = pytest.mark.gpu
 WALL = np.array([[[0.0, -2.0, -2.0], [0.0, 3.0, -2.0], [0.0, 0.0, 3.0]]])
 
 
-def _sweep_at(ctx, coef, dur, tris, d, t):
-    """msnap_mesh_sweep of the single position msnap_eval_flat gives drone d at time t."""
-    out = ctx.eval_flat(coef[d:d + 1], dur[d:d + 1], np.array([t]))
-    md, _ = ctx.mesh_sweep(np.ascontiguousarray(out[:, :, :3]), tris, 0.1)
-    return md[0]
-
-
-def _check_attained(ctx, coef, dur, tris, md, tm, tri):
-    for d in range(len(md)):
-        assert _sweep_at(ctx, coef, dur, tris, d, tm[d]) == md[d], d
-        out = ctx.eval_flat(coef[d:d + 1], dur[d:d + 1], tm[d:d + 1])
-        each = np.array([ctx.mesh_sweep(np.ascontiguousarray(out[:, :, :3]), tris[k:k + 1], 0.1)[0][0] for k in range(len(tris))])
-        assert tri[d] == int(np.nanargmin(each)) and each[tri[d]] == md[d], (d, tri[d], each)
+_check_attained = MC.check_attained      # (shared with tests/test_mesh_clearance_edges_gpu.py)
 
 
 def test_the_drone_the_sampled_sweep_misses(ctx7):
