@@ -73,6 +73,11 @@ SIGNATURES = {
     "msnap_pair_clearance_device": (_I, [_VP, _I, _I, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP]),
     "msnap_cross_clearance": (_I, [_VP, _I, _I, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP]),
     "msnap_cross_clearance_device": (_I, [_VP, _I, _I, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP]),
+    "msnap_pair_conflict_window": (_I, [_VP, _I, _I, _VP, _VP, _I, _VP, _D, _D] + [_VP] * 7),
+    "msnap_pair_conflict_window_device": (_I, [_VP, _I, _I, _VP, _VP, _I, _VP, _D, _D] + [_VP] * 7),
+    "msnap_cross_conflict_window": (_I, [_VP, _I, _I, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _I, _VP, _D, _D] + [_VP] * 7),
+    "msnap_cross_conflict_window_device": (_I, [_VP, _I, _I, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _I, _VP, _D, _D]
+                                           + [_VP] * 7),
     "msnap_mesh_clearance": (_I, [_VP, _I, _I, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
     "msnap_mesh_clearance_device": (_I, [_VP, _I, _I, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
     "msnap_path_extent": (_I, [_VP, _I, _I, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP]),

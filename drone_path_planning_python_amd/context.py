@@ -580,6 +580,74 @@ class Context:
                                                             _ptr(dur_b), _ptr(t0_b), int(n_pairs), _ptr(pairs),
                                                             _ptr(min_dist), _ptr(t_min), _ptr(lower), _ptr(status)))
 
+    # ---- conflict windows: from when until when a pair is too close (include/msnap.h) ------
+    @staticmethod
+    def _window_outputs(P):
+        outs = [np.empty((P,), dtype=np.float64) for _ in range(6)] + [np.empty((P,), dtype=np.int32)]
+        return outs, [a.ctypes.data_as(ctypes.c_void_p) for a in outs]
+
+    def pair_conflict_window(self, coef, dur, pairs, threshold, t_res=1e-6):
+        """From when until when the listed pairs [P, 2] of one batch are closer than `threshold` [m]:
+        (t_clear_until, t_first, d_first, t_last, d_last, t_clear_from, status int32), each [P]
+        (msnap_pair_conflict_window).  Clear is proven on [0, t_clear_until) and (t_clear_from, window]; t_first /
+        t_last are the earliest / latest conflict found (+inf / -inf: none), to within `t_res` [s] of the proven
+        ranges when the search closes."""
+        coef, pc, dur, pd, N, M = self._coef_dur(coef, dur)
+        pr, ppr = _host(pairs, np.int32)
+        if pr.ndim != 2 or pr.shape[1] != 2:
+            raise ValueError("pairs must be [P, 2]")
+        P = pr.shape[0]
+        outs, ptrs = self._window_outputs(P)
+        with self._lock:
+            self._ck(self._lib.msnap_pair_conflict_window(self._h, N, M, pc, pd, P, ppr, float(threshold), float(t_res),
+                                                          *ptrs))
+        return tuple(outs)
+
+    def pair_conflict_window_device(self, n_drones, n_seg, coef, dur, n_pairs, pairs, threshold, t_res, t_clear_until,
+                                    t_first, d_first, t_last, d_last, t_clear_from, status):
+        """Device pointers (pairs int32 [n_pairs, 2]), asynchronous on the context's stream."""
+        with self._lock:
+            self._ck(self._lib.msnap_pair_conflict_window_device(
+                self._h, int(n_drones), int(n_seg), _ptr(coef), _ptr(dur), int(n_pairs), _ptr(pairs), float(threshold),
+                float(t_res), _ptr(t_clear_until), _ptr(t_first), _ptr(d_first), _ptr(t_last), _ptr(d_last),
+                _ptr(t_clear_from), _ptr(status)))
+
+    def cross_conflict_window(self, coef_a, dur_a, coef_b, dur_b, pairs, threshold, t_res=1e-6, t0_a=None, t0_b=None):
+        """pair_conflict_window for drone a of set A against drone b of set B on shifted clocks, as cross_clearance
+        (msnap_cross_conflict_window); the times are on the common clock."""
+        coef_a, pca, dur_a, pda, Na, Ma = self._coef_dur(coef_a, dur_a)
+        coef_b, pcb, dur_b, pdb, Nb, Mb = self._coef_dur(coef_b, dur_b)
+        pr, ppr = _host(pairs, np.int32)
+        if pr.ndim != 2 or pr.shape[1] != 2:
+            raise ValueError("pairs must be [P, 2]")
+        t0 = []
+        for name, x, n in (("t0_a", t0_a, Na), ("t0_b", t0_b, Nb)):
+            if x is None:
+                t0.append((None, None))
+                continue
+            x, px = _host(x, np.float64)
+            if x.shape != (n,):
+                raise ValueError(f"{name} must be [{n}]")
+            t0.append((x, px))
+        P = pr.shape[0]
+        outs, ptrs = self._window_outputs(P)
+        with self._lock:
+            self._ck(self._lib.msnap_cross_conflict_window(self._h, Na, Ma, pca, pda, t0[0][1], Nb, Mb, pcb, pdb,
+                                                           t0[1][1], P, ppr, float(threshold), float(t_res), *ptrs))
+        return tuple(outs)
+
+    def cross_conflict_window_device(self, n_a, n_seg_a, coef_a, dur_a, t0_a, n_b, n_seg_b, coef_b, dur_b, t0_b,
+                                     n_pairs, pairs, threshold, t_res, t_clear_until, t_first, d_first, t_last, d_last,
+                                     t_clear_from, status):
+        """Device pointers (t0_a / t0_b may be None: zeros; pairs int32 [n_pairs, 2]), asynchronous on the context's
+        stream."""
+        with self._lock:
+            self._ck(self._lib.msnap_cross_conflict_window_device(
+                self._h, int(n_a), int(n_seg_a), _ptr(coef_a), _ptr(dur_a), _ptr(t0_a), int(n_b), int(n_seg_b),
+                _ptr(coef_b), _ptr(dur_b), _ptr(t0_b), int(n_pairs), _ptr(pairs), float(threshold), float(t_res),
+                _ptr(t_clear_until), _ptr(t_first), _ptr(d_first), _ptr(t_last), _ptr(d_last), _ptr(t_clear_from),
+                _ptr(status)))
+
     # ---- mesh clearance in continuous time (include/msnap.h) ------------------------------
     def mesh_clearance(self, coef, dur, tris):
         """Certified distance of each drone's whole path to the mesh `tris` [T, 3, 3]: (min_dist [N], t_min [N],

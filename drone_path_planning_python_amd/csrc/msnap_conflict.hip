@@ -1,0 +1,318 @@
+// Conflict windows of two drones in continuous time: from when until when the pair is closer than a threshold
+// (include/msnap.h, "conflict windows").  Two entries, told apart by the template flag CROSS exactly as
+// msnap_clearance.hip's: msnap_pair_conflict_window (one batch, one clock) and msnap_cross_conflict_window (two sets on
+// shifted clocks).  The window [S, W], the knots, the slots, the tie order and the live / dead rules are K9's: the lane
+// set-up is msnap_pair_interval.h's lane_interval, the one text both lane kernels call.
+//
+// Lane.  g(u) = sum of the squares of the three difference polynomials on the lane's interval, L = threshold^2.  The
+// forward walk visits the dyadic nodes [a, a + hh] of u in [0, 1] left to right (msnap_walk.h, WalkNode::advance):
+//   1. shift_scale; the smallest Bernstein coefficient of g on the node (squares_bound<true>); g at 0, 1/2, 1;
+//   2. bound >= L: the node is proven clear -- on to the next sibling;
+//   3. else g(0) < L: the conflict begins at a (every earlier node was proven clear or noted as undecided): the walk ends;
+//   4. else h hh <= t_res or lvl == kMaxDepth: a leaf.  g(1/2) < L or g(1) < L: the earlier of the two is the first
+//      conflict found, the walk ends.  Otherwise the leaf is undecided: its a is kept if it is the earliest, and on;
+//   5. else split.
+// The node guard kMaxNodes ends the walk with everything from the current a on undecided.  A lane carries two numbers
+// per direction: the time of the conflict it found (none: +inf) and the time up to which it proved the pair clear -- the
+// smaller of the first undecided a and the a of the node that held the conflict (none of either: +inf).
+// The backward walk is the same body on e_s(1 - u) (a Taylor shift by 1, then the odd coefficients negated); its times
+// map back as E - h u, and its two numbers are the latest conflict found (none: -inf) and the time from which the pair
+// is proven clear (none: -inf).  There is no prune slack here: a node is clear when its fp64 bound says so, and the
+// header's allowance r covers the rounding of that bound.
+// A lane cannot know that an earlier slot already holds the first conflict: later slots are walked in full.
+//
+// Fold.  One thread per pair over its slots: the earliest and the latest conflict found in either direction (so that
+// t_first <= t_last whatever the rounding of the two walks), the earliest clear-until and the latest clear-from, clamped
+// to them; then the distances at t_first and t_last in the t domain (pair_distance_at: msnap_eval_flat reproduces them).
+// Status, W < S and W == S as pair_fold_kernel.  Nothing crosses lanes but the trip count.
+#include <math.h>
+
+#include "msnap_api_util.h"
+#include "msnap_pair_interval.h"
+#include "msnap_walk.h"
+#include "msnap_wave.h"
+
+namespace msnap {
+namespace {
+
+constexpr int kThreads = kClearanceThreads;
+constexpr int kLaneDoubles = 4;      // per lane: conflict found forward, clear until, conflict found backward, clear from
+
+// ctx->clearance_work: per-lane results [lanes][4] doubles, then the flags as msnap_clearance.hip lays them out
+inline size_t conflict_work_bytes(size_t lanes, size_t segs) {
+  return lanes * kLaneDoubles * sizeof(double) + segs * sizeof(int32_t);
+}
+
+// The walk for the first crossing of the level L from u = 0 on.  hit: the u of the conflict found (+inf: none); clear:
+// the u up to which g >= L is proven (+inf: the whole lane).  Every lane of the wave calls it.
+template <int D>
+__device__ __forceinline__ void first_crossing(const double (&e)[3][D + 1], bool ok, double h, double L, double t_res,
+                                               double &hit, double &clear) {
+  const double inf = __builtin_inf();
+  hit = inf;
+  clear = inf;
+  WalkNode node;
+  bool active = ok;
+  while (__ballot(active) != 0) {
+    const double hh = node.h(), a = node.a();
+    double f[3][D + 1];
+#pragma unroll
+    for (int s = 0; s < 3; ++s) shift_scale<D>(e[s], a, hh, f[s]);
+    const double bound = squares_bound<true, D>(f);
+    double g[3];
+    squares_at_ends_and_middle<D>(f, g);
+    const bool open = !(bound >= L);                                    // not proven clear (a NaN bound proves nothing)
+    const bool at_start = open && g[0] < L;
+    const bool leaf = h * hh <= t_res || node.lvl >= kMaxDepth;
+    const bool in_mid = g[1] < L, at_end = g[2] < L;
+    const bool found = at_start || (open && leaf && (in_mid || at_end));
+    const bool undecided = open && !found && leaf;
+    const bool split = open && !found && !leaf;
+    const double at = at_start ? a : (in_mid ? fma(0.5, hh, a) : a + hh);
+    const bool finished = node.advance(split, active);
+    const bool guard = !finished && node.nodes >= kMaxNodes;            // nodes are left unvisited: undecided from a on
+    if (active) {
+      hit = found ? at : hit;
+      clear = (found || undecided || guard) ? fmin(clear, a) : clear;
+    }
+    active = active && !(found || finished || guard);
+  }
+}
+
+// one lane per (pair, slot): work[4 item ..] = the four times of the head, on the common clock
+template <int NC, bool CROSS>
+__global__ void __launch_bounds__(kThreads)
+conflict_lane_kernel(const PathSet A, const PathSet B_, int n_pairs, const int32_t *__restrict__ pairs, double L,
+                     double t_res, double *__restrict__ work) {
+  constexpr int D = NC - 1;
+  const PathSet &B = CROSS ? B_ : A;
+  const double inf = __builtin_inf();
+  const size_t item = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool in_range = item < (size_t)n_pairs * (size_t)(A.m + B.m - 1);
+  double e[3][D + 1];
+  const LaneInterval iv = lane_interval<NC, CROSS>(A, B, n_pairs, pairs, item, e);
+
+  double out[kLaneDoubles];
+#pragma unroll 1
+  for (int dir = 0; dir < 2; ++dir) {
+    if (dir == 1) {
+      // e_s(1 - u): the Taylor shift by 1, then the odd coefficients negated
+#pragma unroll
+      for (int s = 0; s < 3; ++s) {
+#pragma unroll
+        for (int kk = 0; kk < D; ++kk)
+#pragma unroll
+          for (int j = D - 1; j >= kk; --j) e[s][j] = e[s][j + 1] + e[s][j];
+#pragma unroll
+        for (int j = 1; j <= D; j += 2) e[s][j] = -e[s][j];
+      }
+    }
+    double hit, clear;
+    first_crossing<D>(e, iv.ok, iv.h, L, t_res, hit, clear);
+    // u -> the common clock: start + h u forward, E - h u backward, kept inside the lane's interval
+    const double th = dir == 0 ? fmin(fma(iv.h, hit, iv.start), iv.E) : fmax(fma(-iv.h, hit, iv.E), iv.start);
+    const double tc = dir == 0 ? fmin(fma(iv.h, clear, iv.start), iv.E) : fmax(fma(-iv.h, clear, iv.E), iv.start);
+    const double none = dir == 0 ? inf : -inf;
+    out[2 * dir] = (iv.ok && hit < inf) ? th : none;
+    out[2 * dir + 1] = (iv.ok && clear < inf) ? tc : none;
+  }
+
+  if (!in_range) return;
+#pragma unroll
+  for (int q = 0; q < kLaneDoubles; ++q) work[kLaneDoubles * item + q] = out[q];
+}
+
+// one thread per pair: status, the window, the fold of the slots, the distances in the t domain
+template <int NC, bool CROSS>
+__global__ void __launch_bounds__(kThreads)
+conflict_fold_kernel(const PathSet A, const PathSet B_, const double *__restrict__ work, int n_pairs,
+                     const int32_t *__restrict__ pairs, double threshold, double *__restrict__ t_clear_until,
+                     double *__restrict__ t_first, double *__restrict__ d_first, double *__restrict__ t_last,
+                     double *__restrict__ d_last, double *__restrict__ t_clear_from, int32_t *__restrict__ status) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n_pairs) return;
+  const PathSet &B = CROSS ? B_ : A;
+  const double nan = __builtin_nan(""), inf = __builtin_inf();
+  const int a = pairs[2 * (size_t)p], b = pairs[2 * (size_t)p + 1];
+  const size_t da = (size_t)a * A.m, db = (size_t)b * B.m;
+  double ta, tb, totA, totB;      // (CROSS only: the clamp's)
+  const int st = pair_status<CROSS>(A, B, a, b, ta, tb, totA, totB);
+  double cu = nan, tf = nan, df = nan, tl = nan, dl = nan, cf = nan;
+  if (st == MSNAP_ST_OK) {
+    const double S = fmax(ta, tb), Wend = CROSS ? fmin(ta + totA, tb + totB) : inf;
+    cu = tf = inf;      // certified clear over the whole window
+    tl = cf = -inf;
+    const bool instant = CROSS && Wend == S;      // no slot is live: the one instant decides
+    if (instant) {
+      cu = tf = tl = cf = S;
+    } else if (!(Wend < S)) {
+      const int slots = A.m + B.m - 1;
+      const double *w = work + (size_t)p * slots * kLaneDoubles;
+      for (int k = 0; k < slots; ++k) {
+        tf = fmin(tf, w[kLaneDoubles * k]);
+        cu = fmin(cu, w[kLaneDoubles * k + 1]);
+        tl = fmax(tl, w[kLaneDoubles * k + 2]);
+        cf = fmax(cf, w[kLaneDoubles * k + 3]);
+      }
+      // one set of conflict times for both directions: a time found by either walk counts for both ends
+      const double lo = fmin(tf, tl > -inf ? tl : inf), hi = fmax(tl, tf < inf ? tf : -inf);
+      tf = lo;
+      tl = hi;
+      cu = fmin(cu, tf);
+      cf = fmax(cf, tl);
+    }
+    df = dl = inf;
+    if (tf < inf) {
+#pragma unroll 1
+      for (int q = 0; q < 2; ++q) {      // (one text of the evaluation for both ends)
+        const double d = pair_distance_at<NC, CROSS>(A, B, da, db, ta, tb, totA, totB, q == 0 ? tf : tl);
+        df = q == 0 ? d : df;
+        dl = q == 0 ? dl : d;
+      }
+    }
+    if (instant && !(df < threshold)) {      // clear at that instant: certified clear
+      cu = tf = df = dl = inf;
+      tl = cf = -inf;
+    }
+  }
+  t_clear_until[p] = cu;
+  t_first[p] = tf;
+  d_first[p] = df;
+  t_last[p] = tl;
+  d_last[p] = dl;
+  t_clear_from[p] = cf;
+  status[p] = st;
+}
+
+struct Outputs {
+  double *t_clear_until, *t_first, *d_first, *t_last, *d_last, *t_clear_from;
+  int32_t *status;
+};
+
+template <int NC, bool CROSS>
+int launch(msnap_ctx *ctx, PathSet A, PathSet B, int n_pairs, const int32_t *pairs, double threshold, double t_res,
+           void *scratch, const Outputs &o) {
+  const size_t lanes = clearance_lanes(n_pairs, A.m, B.m), segs_a = (size_t)A.n * A.m;
+  double *work = (double *)scratch;
+  int32_t *flags[2] = {(int32_t *)(work + kLaneDoubles * lanes), nullptr};
+  flags[1] = CROSS ? flags[0] + segs_a : flags[0];
+  PathSet *sets[2] = {&A, &B};
+  for (int s = 0; s < (CROSS ? 2 : 1); ++s) {
+    const size_t segs = (size_t)sets[s]->n * sets[s]->m;
+    if (!segs) continue;
+    hipLaunchKernelGGL((clearance_flags_kernel<NC>), dim3(blocks_of(segs, kThreads)), dim3(kThreads), 0, ctx->stream,
+                       sets[s]->coef, sets[s]->dur, segs, flags[s]);
+    MSNAP_HIP(ctx, hipGetLastError());
+  }
+  A.flags = flags[0];
+  B.flags = flags[1];
+  hipLaunchKernelGGL((conflict_lane_kernel<NC, CROSS>), dim3(blocks_of(lanes, kThreads)), dim3(kThreads), 0,
+                     ctx->stream, A, B, n_pairs, pairs, threshold * threshold, t_res, work);
+  MSNAP_HIP(ctx, hipGetLastError());
+  hipLaunchKernelGGL((conflict_fold_kernel<NC, CROSS>), dim3(blocks_of(n_pairs, kThreads)), dim3(kThreads), 0,
+                     ctx->stream, A, B, (const double *)work, n_pairs, pairs, threshold, o.t_clear_until, o.t_first,
+                     o.d_first, o.t_last, o.d_last, o.t_clear_from, o.status);
+  MSNAP_HIP(ctx, hipGetLastError());
+  return MSNAP_OK;
+}
+
+// cross = false: B is A given again (those instances read only A)
+int launch_conflict(msnap_ctx *ctx, bool cross, const PathSet &A, const PathSet &B, int n_pairs, const int32_t *pairs,
+                    double threshold, double t_res, const Outputs &o) {
+  const size_t segs = (size_t)A.n * A.m + (cross ? (size_t)B.n * B.m : 0);
+  const int rc = ensure(ctx, ctx->clearance_work, conflict_work_bytes(clearance_lanes(n_pairs, A.m, B.m), segs));
+  if (rc) return rc;
+  void *scratch = ctx->clearance_work.p;
+  if (ctx->order == 7)
+    return cross ? launch<8, true>(ctx, A, B, n_pairs, pairs, threshold, t_res, scratch, o)
+                 : launch<8, false>(ctx, A, B, n_pairs, pairs, threshold, t_res, scratch, o);
+  return cross ? launch<10, true>(ctx, A, B, n_pairs, pairs, threshold, t_res, scratch, o)
+               : launch<10, false>(ctx, A, B, n_pairs, pairs, threshold, t_res, scratch, o);
+}
+
+}  // namespace
+}  // namespace msnap
+
+using namespace msnap;
+
+extern "C" {
+
+static int conflict_args(const msnap_ctx *ctx, int n_a, int n_seg_a, int n_b, int n_seg_b, int n_pairs,
+                         double threshold, double t_res, std::initializer_list<const void *> ptrs) {
+  if (int rc = check_clearance_args(ctx, n_a, n_seg_a, n_b, n_seg_b, n_pairs)) return rc;
+  if (!(isfinite(threshold) && threshold >= 0.0) || !(isfinite(t_res) && t_res > 0.0)) return MSNAP_EINVAL;
+  if (n_pairs == 0) return kNoWork;
+  for (const void *p : ptrs)
+    if (!p) return MSNAP_EINVAL;
+  return MSNAP_OK;
+}
+
+int msnap_pair_conflict_window_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,
+                                      int n_pairs, const int32_t *pairs, double threshold, double t_res,
+                                      double *t_clear_until, double *t_first, double *d_first, double *t_last,
+                                      double *d_last, double *t_clear_from, int32_t *status) {
+  MSNAP_ENTER(ctx, conflict_args(ctx, n_drones, n_seg, n_drones, n_seg, n_pairs, threshold, t_res,
+                                 {coef, dur, pairs, t_clear_until, t_first, d_first, t_last, d_last, t_clear_from,
+                                  status}));
+  const PathSet A = {n_drones, n_seg, coef, dur, nullptr, nullptr};
+  return launch_conflict(ctx, false, A, A, n_pairs, pairs, threshold, t_res,
+                         {t_clear_until, t_first, d_first, t_last, d_last, t_clear_from, status});
+}
+
+int msnap_pair_conflict_window(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,
+                               int n_pairs, const int32_t *pairs, double threshold, double t_res,
+                               double *t_clear_until, double *t_first, double *d_first, double *t_last, double *d_last,
+                               double *t_clear_from, int32_t *status) {
+  MSNAP_ENTER(ctx, conflict_args(ctx, n_drones, n_seg, n_drones, n_seg, n_pairs, threshold, t_res,
+                                 {coef, dur, pairs, t_clear_until, t_first, d_first, t_last, d_last, t_clear_from,
+                                  status}));
+  const size_t b_out = (size_t)n_pairs * 8;
+  return staged(ctx, {upload(coef, coef_bytes(ctx, n_drones, n_seg)), upload(dur, dur_bytes(n_drones, n_seg)),
+                      upload(pairs, (size_t)n_pairs * 2 * 4), download(t_clear_until, b_out), download(t_first, b_out),
+                      download(d_first, b_out), download(t_last, b_out), download(d_last, b_out),
+                      download(t_clear_from, b_out), download(status, (size_t)n_pairs * 4)},
+                [&](const DevPtr *d) {
+                  const PathSet A = {n_drones, n_seg, d[0], d[1], nullptr, nullptr};
+                  return launch_conflict(ctx, false, A, A, n_pairs, d[2], threshold, t_res,
+                                         {d[3], d[4], d[5], d[6], d[7], d[8], d[9]});
+                });
+}
+
+int msnap_cross_conflict_window_device(msnap_ctx *ctx, int n_a, int n_seg_a, const double *coef_a, const double *dur_a,
+                                       const double *t0_a, int n_b, int n_seg_b, const double *coef_b,
+                                       const double *dur_b, const double *t0_b, int n_pairs, const int32_t *pairs,
+                                       double threshold, double t_res, double *t_clear_until, double *t_first,
+                                       double *d_first, double *t_last, double *d_last, double *t_clear_from,
+                                       int32_t *status) {
+  MSNAP_ENTER(ctx, conflict_args(ctx, n_a, n_seg_a, n_b, n_seg_b, n_pairs, threshold, t_res,
+                                 {coef_a, dur_a, coef_b, dur_b, pairs, t_clear_until, t_first, d_first, t_last, d_last,
+                                  t_clear_from, status}));
+  return launch_conflict(ctx, true, {n_a, n_seg_a, coef_a, dur_a, t0_a, nullptr},
+                         {n_b, n_seg_b, coef_b, dur_b, t0_b, nullptr}, n_pairs, pairs, threshold, t_res,
+                         {t_clear_until, t_first, d_first, t_last, d_last, t_clear_from, status});
+}
+
+int msnap_cross_conflict_window(msnap_ctx *ctx, int n_a, int n_seg_a, const double *coef_a, const double *dur_a,
+                                const double *t0_a, int n_b, int n_seg_b, const double *coef_b, const double *dur_b,
+                                const double *t0_b, int n_pairs, const int32_t *pairs, double threshold, double t_res,
+                                double *t_clear_until, double *t_first, double *d_first, double *t_last, double *d_last,
+                                double *t_clear_from, int32_t *status) {
+  MSNAP_ENTER(ctx, conflict_args(ctx, n_a, n_seg_a, n_b, n_seg_b, n_pairs, threshold, t_res,
+                                 {coef_a, dur_a, coef_b, dur_b, pairs, t_clear_until, t_first, d_first, t_last, d_last,
+                                  t_clear_from, status}));
+  const size_t b_out = (size_t)n_pairs * 8;
+  return staged(ctx, {upload(coef_a, coef_bytes(ctx, n_a, n_seg_a)), upload(dur_a, dur_bytes(n_a, n_seg_a)),
+                      upload(t0_a, t0_a ? (size_t)n_a * 8 : 0), upload(coef_b, coef_bytes(ctx, n_b, n_seg_b)),
+                      upload(dur_b, dur_bytes(n_b, n_seg_b)), upload(t0_b, t0_b ? (size_t)n_b * 8 : 0),
+                      upload(pairs, (size_t)n_pairs * 2 * 4), download(t_clear_until, b_out), download(t_first, b_out),
+                      download(d_first, b_out), download(t_last, b_out), download(d_last, b_out),
+                      download(t_clear_from, b_out), download(status, (size_t)n_pairs * 4)},
+                [&](const DevPtr *d) {
+                  const double *da = t0_a ? (const double *)d[2] : nullptr, *db = t0_b ? (const double *)d[5] : nullptr;
+                  return launch_conflict(ctx, true, {n_a, n_seg_a, d[0], d[1], da, nullptr},
+                                         {n_b, n_seg_b, d[3], d[4], db, nullptr}, n_pairs, d[6], threshold, t_res,
+                                         {d[7], d[8], d[9], d[10], d[11], d[12], d[13]});
+                });
+}
+
+}  // extern "C"

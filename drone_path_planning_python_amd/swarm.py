@@ -241,6 +241,48 @@ class DeviceCompute:
                                             pairs.contiguous(), md, tm, lower, status)
         return md, tm, lower, status
 
+    # ---- conflict windows: from when until when a pair is too close (include/msnap.h) -------------------------------
+    _WINDOW_OUTPUTS = ("t_clear_until", "t_first", "d_first", "t_last", "d_last", "t_clear_from")
+
+    def _window_out(self, name, P):
+        torch = self.torch
+        return ([self._out(f"{name}.{k}", (P,), torch.float64) for k in self._WINDOW_OUTPUTS]
+                + [self._out(f"{name}.status", (P,), torch.int32)])
+
+    def conflict_window(self, coef, dur, pairs, threshold, t_res=1e-6):
+        """(t_clear_until, t_first, d_first, t_last, d_last, t_clear_from, status int32), each [P], of the listed pairs
+        (int32 [P, 2], drone indices into the batch): from when until when the pair is closer than `threshold`, the
+        crossings located to `t_res` seconds (msnap_pair_conflict_window_device)."""
+        torch = self.torch
+        n, M = dur.shape
+        if pairs.dim() != 2 or pairs.shape[1] != 2 or pairs.dtype != torch.int32:
+            raise ValueError("conflict_window: pairs must be an int32 tensor [P, 2]")
+        P = pairs.shape[0]
+        outs = self._window_out("conflict_window", P)
+        if P:
+            self.ctx.pair_conflict_window_device(n, M, coef, dur, P, pairs.contiguous(), threshold, t_res, *outs)
+        return tuple(outs)
+
+    def cross_conflict_window(self, coef_a, dur_a, coef_b, dur_b, pairs, threshold, t_res=1e-6, t0_a=None, t0_b=None):
+        """conflict_window of drone a of set A against drone b of set B (int32 [P, 2]: index in A, index in B) on
+        shifted clocks, as cross_clearance; the times are on the common clock."""
+        torch = self.torch
+        (na, Ma), (nb, Mb) = dur_a.shape, dur_b.shape
+        if pairs.dim() != 2 or pairs.shape[1] != 2 or pairs.dtype != torch.int32:
+            raise ValueError("cross_conflict_window: pairs must be an int32 tensor [P, 2]")
+        for name, x, n in (("t0_a", t0_a, na), ("t0_b", t0_b, nb)):
+            if x is not None and (tuple(x.shape) != (n,) or x.dtype != torch.float64):
+                raise ValueError(f"cross_conflict_window: {name} must be a float64 tensor [{n}]")
+        P = pairs.shape[0]
+        outs = self._window_out("cross_conflict_window", P)
+        if P:
+            self.ctx.cross_conflict_window_device(na, Ma, coef_a.contiguous(), dur_a.contiguous(),
+                                                  None if t0_a is None else t0_a.contiguous(), nb, Mb,
+                                                  coef_b.contiguous(), dur_b.contiguous(),
+                                                  None if t0_b is None else t0_b.contiguous(), P, pairs.contiguous(),
+                                                  threshold, t_res, *outs)
+        return tuple(outs)
+
     # ---- mesh clearance in continuous time (include/msnap.h) --------------------------------------------------------
     def mesh_clearance(self, coef, dur, tris):
         """(min_dist [n], t_min [n], tri_min [n] int32, lower [n], status [n] int32): the certified distance of each
@@ -1180,6 +1222,31 @@ class ReplanClearanceResult:
     pair_lower: object        # [P]
 
 
+def _replan_pairs(who, dur, idx, t_r, new_coef, new_dur):
+    """The pair lists of a replan, shared by certify_replan and replan_conflict_windows: (idx [K] int64, t0 [K], no
+    [K (N - K), 2] int32 = (new i, old j) with j not in idx, nn [K (K - 1) / 2, 2] int32 = (new i, new j), i < j)."""
+    import torch
+    n, dev = dur.shape[0], dur.device
+    idx = torch.as_tensor(idx, dtype=torch.int64).to(dev).reshape(-1)
+    K = int(idx.numel())
+    if new_dur.shape[0] != K or new_coef.shape[0] != K:
+        raise ValueError(f"{who}: new_coef, new_dur hold one path per entry of idx")
+    if K and (int(idx.min()) < 0 or int(idx.max()) >= n or int(torch.unique(idx).numel()) != K):
+        raise ValueError(f"{who}: idx holds distinct drone indices of the swarm")
+    t0 = torch.as_tensor(t_r, dtype=torch.float64).to(dev)
+    t0 = t0.expand(K).contiguous() if t0.dim() == 0 else t0.contiguous()
+    if tuple(t0.shape) != (K,):
+        raise ValueError(f"{who}: t_r is a number or one value per replanned drone")
+    stays = torch.ones((n,), dtype=torch.bool, device=dev)
+    stays[idx] = False
+    old = torch.nonzero(stays, as_tuple=True)[0]
+    loc = torch.arange(K, device=dev)
+    no = torch.stack([loc.repeat_interleave(old.numel()), old.repeat(K)], dim=1).to(torch.int32).contiguous()
+    ii, jj = torch.triu_indices(K, K, offset=1, device=dev)
+    nn = torch.stack([ii, jj], dim=1).to(torch.int32).contiguous()
+    return idx, t0, no, nn
+
+
 def certify_replan(compute, coef, dur, idx, t_r, new_coef, new_dur, radius: float, new_status=None) -> ReplanClearanceResult:
     """Certify replanned paths next to the paths that stay, in continuous time.
 
@@ -1196,26 +1263,10 @@ def certify_replan(compute, coef, dur, idx, t_r, new_coef, new_dur, radius: floa
     import torch
     if not (radius >= 0.0):
         raise ValueError("certify_replan: radius >= 0")
-    n, dev = dur.shape[0], dur.device
-    idx = torch.as_tensor(idx, dtype=torch.int64).to(dev).reshape(-1)
-    K = int(idx.numel())
-    if new_dur.shape[0] != K or new_coef.shape[0] != K:
-        raise ValueError("certify_replan: new_coef, new_dur hold one path per entry of idx")
-    if K and (int(idx.min()) < 0 or int(idx.max()) >= n or int(torch.unique(idx).numel()) != K):
-        raise ValueError("certify_replan: idx holds distinct drone indices of the swarm")
     if new_status is not None and int(new_status.abs().sum()) != 0:
         raise ValueError("certify_replan: the replan reported failed drones (status != 0)")
-    t0 = torch.as_tensor(t_r, dtype=torch.float64).to(dev)
-    t0 = t0.expand(K).contiguous() if t0.dim() == 0 else t0.contiguous()
-    if tuple(t0.shape) != (K,):
-        raise ValueError("certify_replan: t_r is a number or one value per replanned drone")
-    stays = torch.ones((n,), dtype=torch.bool, device=dev)
-    stays[idx] = False
-    old = torch.nonzero(stays, as_tuple=True)[0]
-    loc = torch.arange(K, device=dev)
-    no = torch.stack([loc.repeat_interleave(old.numel()), old.repeat(K)], dim=1).to(torch.int32).contiguous()
-    ii, jj = torch.triu_indices(K, K, offset=1, device=dev)
-    nn = torch.stack([ii, jj], dim=1).to(torch.int32).contiguous()
+    idx, t0, no, nn = _replan_pairs("certify_replan", dur, idx, t_r, new_coef, new_dur)
+    K, dev = int(idx.numel()), dur.device
     outs = []
     if no.shape[0]:
         outs.append(tuple(x.clone() for x in compute.cross_clearance(new_coef, new_dur, coef, dur, no, t0_a=t0)))
@@ -1246,3 +1297,94 @@ def certify_replan(compute, coef, dur, idx, t_r, new_coef, new_dur, radius: floa
                        idx[nn.to(torch.int64)].reshape(-1, 2)]).to(torch.int32)
     new_new = torch.arange(pairs.shape[0], device=dev) >= P0
     return ReplanClearanceResult(certified, hit, undecided, pairs, new_new, md, tm, lower)
+
+
+# ---- conflict windows: from when a pair is too close, and the hand-over time of a replan that still avoids it --------
+@dataclass
+class ConflictWindowResult:
+    pairs: object             # [P, 2] int32, swarm indices: the pairs that went through the conflict-window entry
+    # per pair [P], msnap_pair_conflict_window's outputs (include/msnap.h): clear is proven on [S, t_clear_until) and
+    # (t_clear_from, W]; t_first / t_last are the earliest / latest conflict found (+inf / -inf: none)
+    t_clear_until: object
+    t_first: object
+    d_first: object
+    t_last: object
+    d_last: object
+    t_clear_from: object
+    # per drone (conflict_windows: [N]; replan_conflict_windows: [K], in the order of `idx`): the earliest t_clear_until
+    # over the drone's pairs -- until then the drone is proven clear of every listed partner --, +inf for a drone
+    # without a pair that is in conflict or undecided
+    first_conflict: object
+
+
+def _window_result(pairs, outs, who, n_who):
+    """ConflictWindowResult from the entry's outputs; `who` [Q] int64 indices into the per-drone array of length n_who
+    and the positions `take` [Q] of their pairs in the list."""
+    import torch
+    idx, take = who
+    cu = outs[0]
+    first = torch.full((n_who,), float("inf"), dtype=torch.float64, device=cu.device)
+    if idx.numel():
+        first.scatter_reduce_(0, idx, cu[take], reduce="amin", include_self=True)
+    return ConflictWindowResult(pairs, *outs[:6], first)
+
+
+def conflict_windows(compute, clearance_result, coef, dur, radius: float, t_res: float = 1e-6) -> ConflictWindowResult:
+    """From when the pairs that `certify_clearance` could not clear are closer than 2 radius.
+
+    The pairs of `clearance_result` (a ClearanceResult) whose `pair_lower` < 2 radius -- hits and undecided ones -- go
+    through `compute.conflict_window` (msnap_pair_conflict_window_device) with threshold = 2 radius.  `first_conflict`
+    [N] is per drone the earliest `t_clear_until` over its pairs: `latest_replan_time` turns it into a hand-over time."""
+    import torch
+    if not (radius >= 0.0):
+        raise ValueError("conflict_windows: radius >= 0")
+    n = dur.shape[0]
+    keep = clearance_result.pair_lower < 2.0 * radius
+    pairs = clearance_result.pairs[keep].to(torch.int32).contiguous()
+    outs = tuple(x.clone() for x in compute.conflict_window(coef, dur, pairs, 2.0 * radius, t_res))
+    if pairs.shape[0] and int(outs[6].abs().sum()) != 0:
+        raise ValueError("conflict_windows: msnap_pair_conflict_window reported failed pairs")
+    both = pairs.to(torch.int64).reshape(-1)                          # a0 b0 a1 b1 ...
+    take = torch.arange(pairs.shape[0], device=both.device).repeat_interleave(2)
+    return _window_result(pairs, outs, (both, take), n)
+
+
+def latest_replan_time(result: ConflictWindowResult, margin: float):
+    """Per drone the latest hand-over time t_r of a replan that starts `margin` seconds before the drone's first
+    conflict: first_conflict - margin, not below 0 (+inf for a drone without a conflict).  Hand it to `replan`."""
+    if not (margin >= 0.0):
+        raise ValueError("latest_replan_time: margin >= 0")
+    return (result.first_conflict - margin).clamp(min=0.0)
+
+
+def replan_conflict_windows(compute, coef, dur, idx, t_r, new_coef, new_dur, radius: float,
+                            t_res: float = 1e-6) -> ConflictWindowResult:
+    """`conflict_windows` beside `certify_replan`: the pairs of `certify_replan` (every (new i, old j), then every (new
+    i, new j) with i < j; swarm indices in `pairs`) through `compute.cross_conflict_window`
+    (msnap_cross_conflict_window_device) with the offsets `t_r` and threshold = 2 radius.  `first_conflict` [K] is per
+    replanned drone, on the swarm's clock."""
+    import torch
+    if not (radius >= 0.0):
+        raise ValueError("replan_conflict_windows: radius >= 0")
+    idx, t0, no, nn = _replan_pairs("replan_conflict_windows", dur, idx, t_r, new_coef, new_dur)
+    K, dev = int(idx.numel()), dur.device
+    outs = []
+    if no.shape[0]:
+        outs.append(tuple(x.clone() for x in compute.cross_conflict_window(new_coef, new_dur, coef, dur, no,
+                                                                           2.0 * radius, t_res, t0_a=t0)))
+    if nn.shape[0]:
+        outs.append(tuple(x.clone() for x in compute.cross_conflict_window(new_coef, new_dur, new_coef, new_dur, nn,
+                                                                           2.0 * radius, t_res, t0_a=t0, t0_b=t0)))
+    if not outs:
+        empty = torch.zeros((0,), dtype=torch.float64, device=dev)
+        return ConflictWindowResult(torch.zeros((0, 2), dtype=torch.int32, device=dev), *([empty] * 6),
+                                    torch.full((K,), float("inf"), dtype=torch.float64, device=dev))
+    cat = tuple(torch.cat([o[k] for o in outs]) for k in range(7))
+    if int(cat[6].abs().sum()) != 0:
+        raise ValueError("replan_conflict_windows: msnap_cross_conflict_window reported failed pairs")
+    P0, P = no.shape[0], no.shape[0] + nn.shape[0]
+    who = torch.cat([no[:, 0], nn[:, 0], nn[:, 1]]).to(torch.int64)
+    take = torch.cat([torch.arange(P, device=dev), torch.arange(P0, P, device=dev)])
+    pairs = torch.cat([torch.stack([idx[no[:, 0].to(torch.int64)], no[:, 1].to(torch.int64)], dim=1),
+                       idx[nn.to(torch.int64)].reshape(-1, 2)]).to(torch.int32)
+    return _window_result(pairs, cat, (who, take), K)

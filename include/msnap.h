@@ -436,6 +436,71 @@ int msnap_cross_clearance_device(msnap_ctx *ctx, int n_a, int n_seg_a, const dou
                                  const double *t0_b, int n_pairs, const int32_t *pairs, double *min_dist, double *t_min,
                                  double *lower, int32_t *status);
 
+/* ---- conflict windows: from when until when a pair is too close (new capability) ----
+ * msnap_pair_clearance / msnap_cross_clearance say that two paths come too close and where they are closest; t_min lies
+ * INSIDE the violation.  These entries certify the interval during which |p_a(t) - p_b(t)| < threshold: the latest safe
+ * hand-over time of a replan, how long one drone must wait for the other to pass, which of two conflicts comes first.
+ * msnap_pair_conflict_window takes both drones from one batch on one clock, msnap_cross_conflict_window drone a of set A
+ * and drone b of set B on shifted clocks.  The window [S, W], the clocks, the knots, the pair rules, the status
+ * precedence and the capture rules are exactly those of msnap_pair_clearance / msnap_cross_clearance.
+ *   threshold  a centre distance [m], finite and >= 0;   t_res  the time resolution [s], finite and > 0
+ *              (either outside its range: MSNAP_EINVAL).
+ * A pair is IN CONFLICT at t when its distance is < threshold (strict, as the sampled pass's md < 2 radius) and CLEAR at
+ * t when its distance is >= threshold.  Outputs, each [n_pairs]:
+ *   t_clear_until  proven: clear for every t in [S, t_clear_until);
+ *   t_first        the earliest time found at which the pair is in conflict (+inf: none found);
+ *   d_first        the distance at t_first, formed in the t domain exactly as the clearance entries form min_dist:
+ *                  msnap_eval_flat of the two drones at t_first (cross: at the clamped local times
+ *                  tau_x = min(max(fl(t_first - t0_x), 0), total_x)) gives positions whose
+ *                  sqrt(fma(dz, dz, fma(dy, dy, dx * dx))) is d_first bit for bit (+inf: no t_first);
+ *   t_last, d_last the latest such time and its distance (-inf / +inf: none);
+ *   t_clear_from   proven: clear for every t in (t_clear_from, W];
+ *   status         as for the clearance entries; every double output of a failed pair is NaN.
+ * Always S <= t_clear_until <= t_first <= t_last <= t_clear_from <= W, where the values are finite.  Verdicts:
+ *   certified clear over the whole window   t_clear_until = +inf, t_clear_from = -inf, t_first = +inf, t_last = -inf;
+ *   undecided        no conflict found, but t_clear_until is finite: a graze the search could not separate within its
+ *                    caps.  t_clear_until and t_clear_from still hold;
+ *   closed search    t_first - t_clear_until <= t_res and t_clear_from - t_last <= t_res: always so for a transversal
+ *                    crossing.  The caps are msnap_pair_clearance's: 40 bisections of an interval between knots, 4096
+ *                    nodes per interval.
+ *   W < S (cross): certified clear.  W == S: the one instant decides (in conflict: all four times are S).
+ * Rounding.  "Proven" and "in conflict" hold up to the rounding allowance r of the matching clearance entry
+ * (msnap_pair_clearance: r = 1e-13 + C_ROUND 2^-52 R; msnap_cross_clearance: r = 1e-13 + C_ROUND_CROSS 2^-52 R +
+ * C_CLOCK 2^-52 T_c R', with the constants, R, R' and T_c stated there).  For the exact real polynomials of the fp64
+ * coefficients:
+ *     distance >= threshold - r   at every t of [S, t_clear_until) and of (t_clear_from, W],
+ *     distance at t_first and at t_last  <  threshold + r.
+ * Bit identities.  A pair's outputs do not depend on its place in the list or on the list's length; host entry and
+ * device entry give the same bits; NULL and an array of zeros give the same bits; exchanging the two sets, with the
+ * pairs flipped, gives the same bits; with A == B, equal segment counts and zero offsets the cross entry gives the pair
+ * entry's bits; (b, a) gives the bits of (a, b).
+ * n_pairs == 0 is a no-op.  The device versions only launch; their scratch is a buffer of the context under the capture
+ * rules above (MSNAP_ECAPTURE: run the call once outside the capture first).
+ * (Method: per interval between consecutive knots, a time-ordered walk over dyadic sub-intervals in both directions --
+ * a node whose smallest Bernstein coefficient of |difference|^2 is >= threshold^2 is clear, a node that starts in
+ * conflict ends the walk, a node shorter than t_res is a leaf.  A later interval does not know that an earlier one
+ * already holds the first conflict: every interval is walked.)
+ */
+int msnap_pair_conflict_window(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,
+                               int n_pairs, const int32_t *pairs, double threshold, double t_res,
+                               double *t_clear_until, double *t_first, double *d_first, double *t_last, double *d_last,
+                               double *t_clear_from, int32_t *status);
+int msnap_pair_conflict_window_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,
+                                      int n_pairs, const int32_t *pairs, double threshold, double t_res,
+                                      double *t_clear_until, double *t_first, double *d_first, double *t_last,
+                                      double *d_last, double *t_clear_from, int32_t *status);
+int msnap_cross_conflict_window(msnap_ctx *ctx, int n_a, int n_seg_a, const double *coef_a, const double *dur_a,
+                                const double *t0_a, int n_b, int n_seg_b, const double *coef_b, const double *dur_b,
+                                const double *t0_b, int n_pairs, const int32_t *pairs, double threshold, double t_res,
+                                double *t_clear_until, double *t_first, double *d_first, double *t_last, double *d_last,
+                                double *t_clear_from, int32_t *status);
+int msnap_cross_conflict_window_device(msnap_ctx *ctx, int n_a, int n_seg_a, const double *coef_a, const double *dur_a,
+                                       const double *t0_a, int n_b, int n_seg_b, const double *coef_b,
+                                       const double *dur_b, const double *t0_b, int n_pairs, const int32_t *pairs,
+                                       double threshold, double t_res, double *t_clear_until, double *t_first,
+                                       double *d_first, double *t_last, double *d_last, double *t_clear_from,
+                                       int32_t *status);
+
 /* ---- mesh clearance in continuous time (new capability) ----
  * msnap_mesh_sweep takes the point-triangle distance on the sampling grid only, and an STL wall has no thickness: a
  * drone that passes it at 4 m/s has its 0.1 s samples 0.2 m either side of it.  msnap_mesh_clearance certifies the
