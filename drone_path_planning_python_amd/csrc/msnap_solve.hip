@@ -773,6 +773,65 @@ template <int S, int NW>   // S pieces per side (it = 0 .. S-1): the chunk of wa
 __device__ __forceinline__ constexpr int twist_chunk_lo(int w) {
   return w * (S / NW) + (w > NW - S % NW ? w - (NW - S % NW) : 0);
 }
+// the Hermite constants of the lean instances (msnap_twist_consts.h).  NOT const: a constant table would be folded back
+// into the literals it replaces.
+__constant__ TwistConstImage g_twist_consts = twist_const_image();
+
+// N doubles from `src` (wave-uniform) into scalar registers, in the fewest s_load_dwordx16 / x8 / x4 / x2.  Issued from
+// inline asm: written as plain loads the compiler sinks them, and their lgkmcnt wait, next to the first use -- onto the
+// dependent chain.  The compiler's wait-count pass does not see these loads; the caller retires them with
+// sload_wait() before the first use (cdna_hip_programming.md 5.7).  Scalar loads return out of order: only
+// lgkmcnt(0) retires them.
+typedef double f64x2 __attribute__((ext_vector_type(2)));
+typedef double f64x4 __attribute__((ext_vector_type(4)));
+typedef double f64x8 __attribute__((ext_vector_type(8)));
+template <int OFF, int N>
+__device__ __forceinline__ void sload_f64(const double *src, double (&dst)[N]) {
+  if constexpr (N - OFF >= 8) {
+    f64x8 v;
+    asm volatile("s_load_dwordx16 %0, %1, %2" : "=s"(v) : "s"(src), "i"(OFF * 8));
+#pragma unroll
+    for (int q = 0; q < 8; ++q) dst[OFF + q] = v[q];
+    sload_f64<OFF + 8>(src, dst);
+  } else if constexpr (N - OFF >= 4) {
+    f64x4 v;
+    asm volatile("s_load_dwordx8 %0, %1, %2" : "=s"(v) : "s"(src), "i"(OFF * 8));
+#pragma unroll
+    for (int q = 0; q < 4; ++q) dst[OFF + q] = v[q];
+    sload_f64<OFF + 4>(src, dst);
+  } else if constexpr (N - OFF >= 2) {
+    f64x2 v;
+    asm volatile("s_load_dwordx4 %0, %1, %2" : "=s"(v) : "s"(src), "i"(OFF * 8));
+    dst[OFF] = v[0];
+    dst[OFF + 1] = v[1];
+    sload_f64<OFF + 2>(src, dst);
+  } else if constexpr (N - OFF == 1) {
+    asm volatile("s_load_dwordx2 %0, %1, %2" : "=s"(dst[OFF]) : "s"(src), "i"(OFF * 8));
+  }
+}
+// one dword of each of the NL 64-byte lines at `src`: brings the lines into the scalar cache for a later sload_f64.
+// The registers stay pinned until touch_wait(), behind the wait that retires the loads (a register the compiler
+// believed free would be written by the returning load).
+template <int OFF, int NL>
+__device__ __forceinline__ void sload_touch(const double *src, unsigned (&t)[NL]) {
+  if constexpr (OFF < NL) {
+    asm volatile("s_load_dword %0, %1, %2" : "=s"(t[OFF]) : "s"(src), "i"(OFF * 64));
+    sload_touch<OFF + 1>(src, t);
+  }
+}
+template <int NL>
+__device__ __forceinline__ void touch_wait(unsigned (&t)[NL]) {
+#pragma unroll
+  for (int s = 0; s < NL; ++s) asm volatile("" : "+s"(t[s]));
+}
+template <int N>
+__device__ __forceinline__ void sload_wait(double (&v)[N]) {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  // live in scalar registers from here: no use is scheduled above the wait
+#pragma unroll
+  for (int s = 0; s < N; ++s) asm volatile("" : "+s"(v[s]));
+}
+
 template <int K, int MAXH, int M, int NW>
 __global__ void __launch_bounds__(kWave * NW)
 solve_kernel_twist(const double *__restrict__ wp, const double *__restrict__ tt, int shared_times,
@@ -812,6 +871,23 @@ solve_kernel_twist(const double *__restrict__ wp, const double *__restrict__ tt,
   // kernel fetch the count alone, wait, branch, and only then fetch its other arguments -- two dependent
   // scalar-cache round trips in front of the first load.
   const int tile = blockIdx.x;
+  // The lean instances (below) take their Hermite constants from g_twist_consts by scalar loads instead of two
+  // s_mov_b32 issue slots per constant: the sweep set is requested here, in front of the input loads, and its flight
+  // lies under theirs; the recovery set follows behind the last knot (its cache lines are touched here, so that the
+  // late request is a scalar-cache hit: the compiler schedules most of the merge in front of the request).
+  // (order 9 with 4 segments keeps its literals: with the sweep set resident two scalar registers spill to vector lanes)
+  constexpr bool kTab = MAXH * (K - 1) * (K - 1) <= 36 && !(K == 5 && M == 4);
+  // (order 9: both sets at once do not fit the 102 scalar registers, 2-9 of them spilled to vector lanes; its
+  //  recovery set stays literal)
+  constexpr bool kTabRec = kTab && K == 4;
+  using HC = std::conditional_t<kTab, TableHermite<K, kTabRec>, LiteralHermite<K>>;
+  HC hc;
+  constexpr int kRecLines = kTabRec ? (TwistConstLayout<K>::n_rec * 8 + 63) / 64 : 1;
+  unsigned rec_touch[kRecLines];
+  if constexpr (kTab) {
+    sload_f64<0>(g_twist_consts.v + TwistConstLayout<K>::sweep_at, hc.sw);
+    if constexpr (kTabRec) sload_touch<0>(g_twist_consts.v + TwistConstLayout<K>::rec_at, rec_touch);   // (the sets start on a line)
+  }
   // (pinning the three output pointers in SGPRs at the top -- the compiler re-fetches each right in front of its first
   //  use, a scalar-cache hit on the dependent chain -- was measured and LOST: 4.52 against 4.38 us per step; the kernel
   //  holds ~60 fp64 constants in scalar registers and six more live ones push some of them out)
@@ -861,6 +937,10 @@ solve_kernel_twist(const double *__restrict__ wp, const double *__restrict__ tt,
     }
     __syncthreads();
     MSNAP_TL(1);
+    if constexpr (kTab) {   // (the barrier's own wait has retired them: one slot)
+      sload_wait(hc.sw);
+      if constexpr (kTabRec) touch_wait(rec_touch);
+    }
 
     const int dloc = live ? dl : (N - 1 - tile * kTwistDrones);
     const double *lw = sWraw + dloc * wpitch + a;
@@ -900,7 +980,7 @@ solve_kernel_twist(const double *__restrict__ wp, const double *__restrict__ tt,
     }
     xreg[0] = rcp64(T0q);
     SW sw;
-    sw.init(xreg[0], wreg[1] - wreg[0]);
+    sw.init(xreg[0], wreg[1] - wreg[0], hc);
 
     // Per knot, the long dependent prefix that does not involve the recurrence -- inputs from LDS,
     // T, 1/T (reciprocal + Newton), its powers -- is prepared one knot AHEAD, inside the same
@@ -926,7 +1006,7 @@ solve_kernel_twist(const double *__restrict__ wp, const double *__restrict__ tt,
     auto knot_step = [&](int it) {
       double G[NU][NU], z[NU];
       typename SW::Knot k;
-      SW::knot_geom_xp(xpc, dwc, sw.E, sw.re, k);
+      SW::knot_geom_xp(xpc, dwc, sw.E, sw.re, k, hc);
       const bool ok = sw.chain(k, G, z);
       singular |= !ok & (it <= mside);
 #pragma unroll
@@ -969,6 +1049,8 @@ solve_kernel_twist(const double *__restrict__ wp, const double *__restrict__ tt,
     }
 
     MSNAP_TL(2);
+    // the recovery set: requested behind the last knot, retired in front of the back-substitution
+    if constexpr (kTabRec) sload_f64<0>(g_twist_consts.v + TwistConstLayout<K>::rec_at, hc.rc);
     // ---- the meeting knot: both sides' carried blocks add up to ONE symmetric positive definite
     // system,  S = (E - O^T G)_own + D (E - O^T G)_other D ,  y = -(re + O^T z)_own - D (re + O^T z)_other
     // (each side in its own orientation; D conjugates the other side's blocks).  One cross-lane
@@ -1043,6 +1125,7 @@ solve_kernel_twist(const double *__restrict__ wp, const double *__restrict__ tt,
     }
 
     MSNAP_TL(3);
+    if constexpr (kTabRec) sload_wait(hc.rc);
     // ---- outward back-substitution + recovery: side s owns its segments 0 .. mside; this wave recovers the
     // pieces lo .. hi of each side and back-substitutes out to lo (scalar bounds: wave-uniform branches) ----
     const int lo = twist_chunk_lo<MAXH + 1, NW>(wave), hi = twist_chunk_lo<MAXH + 1, NW>(wave + 1) - 1;
@@ -1078,7 +1161,15 @@ solve_kernel_twist(const double *__restrict__ wp, const double *__restrict__ tt,
         const double wa = side ? wreg[it + 1] : wreg[it];
         const double wb = side ? wreg[it] : wreg[it + 1];
         double c[NC];
-        recover_segment<K>(wa, wb - wa, xreg[it], ua, ub, c);
+        // The piece that side 1 alone owns (odd M) keeps the literals: there `side` is known, the compiler folds the
+        // reversal's negations into the constants themselves, and the sign bit of a failed drone's NaN coefficients
+        // follows that fold (tests/test_twist_bits_gpu.py holds it) -- a constant in a register cannot take it.
+        if constexpr (kTabRec) {
+          if (it <= nL) recover_segment<K>(wa, wb - wa, xreg[it], ua, ub, c, hc);
+          else recover_segment<K>(wa, wb - wa, xreg[it], ua, ub, c);
+        } else {
+          recover_segment<K>(wa, wb - wa, xreg[it], ua, ub, c);
+        }
         if (side == 0 && it == 0 && t0 != 0.0) taylor_shift<NC>(c, -t0);
         const int seg = side ? M - 1 - it : it;
         // a batch this small is latency bound, not store bound: plain per-lane stores.  Lanes past

@@ -4,6 +4,7 @@
 #pragma once
 
 #include "msnap_consts.h"
+#include "msnap_twist_consts.h"
 #include "msnap_internal.h"
 #include "msnap_solve_plan.h"   // kTrPitch
 #include "msnap_energy.h"
@@ -28,6 +29,38 @@ __device__ __forceinline__ double rcp64(double v) {
 
 __device__ __forceinline__ bool finite64(double v) { return __builtin_isfinite(v); }
 
+// Where knot_geom_xp / end_side / recover_segment take their Hermite constants from.  The default is the literal:
+// every kernel but the twisted one compiles exactly as if the bodies named HermiteConsts<K> themselves.
+template <int K>
+struct LiteralHermite {
+  using C = HermiteConsts<K>;
+  __device__ __forceinline__ double hss(int n, int m) const { return C::HSS[n][m]; }
+  __device__ __forceinline__ double hee(int n, int m) const { return C::HEE[n][m]; }
+  __device__ __forceinline__ double hse(int n, int m) const { return C::HSE[n][m]; }
+  __device__ __forceinline__ double cs(int m, int n) const { return C::CS[m][n]; }
+  __device__ __forceinline__ double ce(int m, int n) const { return C::CE[m][n]; }
+  __device__ __forceinline__ double invfact(int n) const { return C::INVFACT[n]; }
+};
+
+// The same constants held in (scalar) registers that the caller filled from the table of msnap_twist_consts.h:
+// `sw` the sweep set, `rc` the recovery set.  A code of 0 keeps the literal (inline operands).
+template <int K, bool REC = true>   // REC false: the recovery set stays literal (the registers do not hold both sets)
+struct TableHermite {
+  using C = HermiteConsts<K>;
+  using L = TwistConstLayout<K>;
+  static constexpr int NSW = L::n_sweep, NRC = REC ? L::n_rec : 0;
+  double sw[NSW], rc[REC ? L::n_rec : 1];
+  __device__ __forceinline__ static double pick(int code, double lit, const double *tab) {
+    return code == 0 ? lit : tab[code - 1];
+  }
+  __device__ __forceinline__ double hss(int n, int m) const { return pick(TwistMapOf<K>::map.hss[n][m], C::HSS[n][m], sw); }
+  __device__ __forceinline__ double hee(int n, int m) const { return pick(TwistMapOf<K>::map.hee[n][m], C::HEE[n][m], sw); }
+  __device__ __forceinline__ double hse(int n, int m) const { return pick(TwistMapOf<K>::map.hse[n][m], C::HSE[n][m], sw); }
+  __device__ __forceinline__ double cs(int m, int n) const { return pick(!REC ? 0 : TwistMapOf<K>::map.cs[m][n], C::CS[m][n], rc); }
+  __device__ __forceinline__ double ce(int m, int n) const { return pick(!REC ? 0 : TwistMapOf<K>::map.ce[m][n], C::CE[m][n], rc); }
+  __device__ __forceinline__ double invfact(int n) const { return pick(!REC ? 0 : TwistMapOf<K>::map.inv[n], C::INVFACT[n], rc); }
+};
+
 // ------------------------------------------------------------------------------------
 // the forward recurrence carried from knot to knot
 // ------------------------------------------------------------------------------------
@@ -51,20 +84,22 @@ struct Sweep {
     for (int p = 2; p <= PM; ++p) xp[p] = xp[p - 1] * x;
   }
 
-  __device__ __forceinline__ void end_side(const double (&xp)[PM + 1], double dw) {
+  template <class P = LiteralHermite<K>>
+  __device__ __forceinline__ void end_side(const double (&xp)[PM + 1], double dw, P hc = P()) {
 #pragma unroll
     for (int n = 1; n <= NU; ++n) {
 #pragma unroll
-      for (int m = 1; m <= n; ++m) E[sidx(n - 1, m - 1)] = C::HEE[n][m] * xp[KK - n - m];
-      re[n - 1] = (C::HEE[n][0] * xp[KK - n]) * dw;
+      for (int m = 1; m <= n; ++m) E[sidx(n - 1, m - 1)] = hc.hee(n, m) * xp[KK - n - m];
+      re[n - 1] = (hc.hee(n, 0) * xp[KK - n]) * dw;
     }
   }
 
   // segment 0 (x = 1/T_0, dw = w_1 - w_0): only its end side feeds knot 1
-  __device__ __forceinline__ void init(double x, double dw) {
+  template <class P = LiteralHermite<K>>
+  __device__ __forceinline__ void init(double x, double dw, P hc = P()) {
     double xp[PM + 1];
     powers(x, xp);
-    end_side(xp, dw);
+    end_side(xp, dw, hc);
     singular = false;
 #pragma unroll
     for (int r = 0; r < NU; ++r) Otz[r] = 0.0;
@@ -88,20 +123,21 @@ struct Sweep {
   }
 
   // the same from the powers of x = 1/T_i (for callers that prepare them ahead of the recurrence)
+  template <class P = LiteralHermite<K>>
   __device__ __forceinline__ static void knot_geom_xp(const double (&xp)[PM + 1], double dw,
                                                       const double (&Eprev)[NS], const double (&reprev)[NU],
-                                                      Knot &k) {
+                                                      Knot &k, P hc = P()) {
 #pragma unroll
     for (int n = 1; n <= NU; ++n) {
 #pragma unroll
       for (int m = 1; m <= n; ++m) {
-        k.D[sidx(n - 1, m - 1)] = __builtin_fma(C::HSS[n][m], xp[KK - n - m], Eprev[sidx(n - 1, m - 1)]);
-        k.E[sidx(n - 1, m - 1)] = C::HEE[n][m] * xp[KK - n - m];
+        k.D[sidx(n - 1, m - 1)] = __builtin_fma(hc.hss(n, m), xp[KK - n - m], Eprev[sidx(n - 1, m - 1)]);
+        k.E[sidx(n - 1, m - 1)] = hc.hee(n, m) * xp[KK - n - m];
       }
-      k.yb[n - 1] = __builtin_fma(C::HSE[n][0] * xp[KK - n], dw, reprev[n - 1]);
-      k.re[n - 1] = (C::HEE[n][0] * xp[KK - n]) * dw;
+      k.yb[n - 1] = __builtin_fma(hc.hse(n, 0) * xp[KK - n], dw, reprev[n - 1]);
+      k.re[n - 1] = (hc.hee(n, 0) * xp[KK - n]) * dw;
 #pragma unroll
-      for (int m = 1; m <= NU; ++m) k.O[n - 1][m - 1] = C::HSE[n][m] * xp[KK - n - m];
+      for (int m = 1; m <= NU; ++m) k.O[n - 1][m - 1] = hc.hse(n, m) * xp[KK - n - m];
     }
   }
 
@@ -208,17 +244,16 @@ struct Sweep {
 //   c_{K+m} = x^(K+m) [ CE_m0 dw + sum_n T^n (CS_mn u_n + CE_mn un_n) ]
 //           = x^(m+1) [ CE_m0 dw x^(K-1) + sum_n (CS_mn x^(K-1-n) u_n + CE_mn x^(K-1-n) un_n) ]
 // -- powers of x only, so callers need not keep T_i.
-template <int K>
+template <int K, class P = LiteralHermite<K>>
 __device__ __forceinline__ void recover_segment(double wi, double dwi, double xi, const double (&u)[K - 1],
-                                                const double (&un)[K - 1], double (&c)[2 * K]) {
-  using C = HermiteConsts<K>;
+                                                const double (&un)[K - 1], double (&c)[2 * K], P hc = P()) {
   double xq[K + 1];
   xq[0] = 1.0;
 #pragma unroll
   for (int m = 1; m <= K; ++m) xq[m] = xq[m - 1] * xi;
   c[0] = wi;
 #pragma unroll
-  for (int n = 1; n < K; ++n) c[n] = u[n - 1] * C::INVFACT[n];
+  for (int n = 1; n < K; ++n) c[n] = u[n - 1] * hc.invfact(n);
   double es[K], ee[K];
 #pragma unroll
   for (int n = 1; n < K; ++n) {
@@ -228,11 +263,11 @@ __device__ __forceinline__ void recover_segment(double wi, double dwi, double xi
   const double dwx = dwi * xq[K - 1];
 #pragma unroll
   for (int m = 0; m < K; ++m) {
-    double acc = C::CE[m][0] * dwx;
+    double acc = hc.ce(m, 0) * dwx;
 #pragma unroll
     for (int n = 1; n < K; ++n) {
-      acc = __builtin_fma(C::CS[m][n], es[n], acc);
-      acc = __builtin_fma(C::CE[m][n], ee[n], acc);
+      acc = __builtin_fma(hc.cs(m, n), es[n], acc);
+      acc = __builtin_fma(hc.ce(m, n), ee[n], acc);
     }
     c[K + m] = acc * xq[m + 1];
   }
