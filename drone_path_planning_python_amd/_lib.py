@@ -80,6 +80,8 @@ SIGNATURES = {
                                            + [_VP] * 7),
     "msnap_mesh_clearance": (_I, [_VP, _I, _I, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
     "msnap_mesh_clearance_device": (_I, [_VP, _I, _I, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "msnap_mesh_conflict_window": (_I, [_VP, _I, _I, _VP, _VP, _I, _VP, _D, _D] + [_VP] * 9),
+    "msnap_mesh_conflict_window_device": (_I, [_VP, _I, _I, _VP, _VP, _I, _VP, _D, _D] + [_VP] * 9),
     "msnap_path_extent": (_I, [_VP, _I, _I, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP]),
     "msnap_path_extent_device": (_I, [_VP, _I, _I, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP]),
     "msnap_solve_states": (_I, [_VP, _I, _I, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP]),

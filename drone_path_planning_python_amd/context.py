@@ -675,6 +675,34 @@ class Context:
                                                            int(n_tris), _ptr(tris), _ptr(min_dist), _ptr(t_min),
                                                            _ptr(tri_min), _ptr(lower), _ptr(status)))
 
+    # ---- mesh conflict windows (include/msnap.h) -------------------------------------------
+    def mesh_conflict_window(self, coef, dur, tris, threshold, t_res=1e-6):
+        """From when until when each drone is closer than `threshold` [m] to the mesh `tris` [T, 3, 3]:
+        (t_clear_until, t_first, d_first, tri_first int32, t_last, d_last, tri_last int32, t_clear_from, status int32),
+        each [N] (msnap_mesh_conflict_window).  Clear is proven on [0, t_clear_until) and (t_clear_from, total]; t_first
+        / t_last are the earliest / latest conflict found (+inf / -inf: none), to within `t_res` [s] of the proven
+        ranges when the search closes; d_* and tri_* are the sweep's distance and triangle there."""
+        coef, pc, dur, pd, N, M = self._coef_dur(coef, dur)
+        tr, ptr_ = _host(tris, np.float64)
+        if tr.ndim != 3 or tr.shape[1:] != (3, 3):
+            raise ValueError("tris must be [T, 3, 3]")
+        kinds = (np.float64, np.float64, np.float64, np.int32, np.float64, np.float64, np.int32, np.float64, np.int32)
+        outs = [np.empty((N,), dtype=k) for k in kinds]
+        with self._lock:
+            self._ck(self._lib.msnap_mesh_conflict_window(self._h, N, M, pc, pd, tr.shape[0], ptr_, float(threshold),
+                                                          float(t_res),
+                                                          *[a.ctypes.data_as(ctypes.c_void_p) for a in outs]))
+        return tuple(outs)
+
+    def mesh_conflict_window_device(self, n_drones, n_seg, coef, dur, n_tris, tris, threshold, t_res, t_clear_until,
+                                    t_first, d_first, tri_first, t_last, d_last, tri_last, t_clear_from, status):
+        """Device pointers (tri_first, tri_last, status int32), asynchronous on the context's stream."""
+        with self._lock:
+            self._ck(self._lib.msnap_mesh_conflict_window_device(
+                self._h, int(n_drones), int(n_seg), _ptr(coef), _ptr(dur), int(n_tris), _ptr(tris), float(threshold),
+                float(t_res), _ptr(t_clear_until), _ptr(t_first), _ptr(d_first), _ptr(tri_first), _ptr(t_last),
+                _ptr(d_last), _ptr(tri_last), _ptr(t_clear_from), _ptr(status)))
+
     # ---- path extent in continuous time (include/msnap.h) --------------------------------
     def path_extent(self, coef, dur, dirs):
         """Certified reach of each drone's whole path in the directions `dirs` [K, 3]: (ext [N, K], t_ext [N, K],

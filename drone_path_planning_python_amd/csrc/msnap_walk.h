@@ -2,7 +2,8 @@
 // supremum), pair_lane_kernel (msnap_clearance.hip, K9 and, with CROSS, K14: a minimum between two drones),
 // mesh_clearance_lane_kernel (msnap_mesh_clearance.hip, K11: a minimum against a mesh) and extent_lane_kernel
 // (msnap_extent.hip, K12: a supremum in a direction, walked as the minimum of the negated polynomial).  DESIGN.md §5 K7
-// has the method.
+// has the method.  The two time-ordered walks for a first crossing (msnap_conflict.hip, K18; msnap_mesh_conflict.hip,
+// K19) use WalkNode and the node helpers, not the bookkeeping of a minimum.
 //
 // Walk.  Branch and bound over the dyadic sub-intervals [idx 2^-lvl, (idx + 1) 2^-lvl] of u in [0, 1].  Per node:
 //   1. shift_scale: the Taylor shift of each component polynomial to the node's start, then the scaling by 2^-lvl

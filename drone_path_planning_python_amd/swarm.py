@@ -300,6 +300,26 @@ class DeviceCompute:
             self.ctx.mesh_clearance_device(n, M, coef, dur, tris.shape[0], tris.contiguous(), md, tm, tri, lower, status)
         return md, tm, tri, lower, status
 
+    # ---- mesh conflict windows: from when until when a path is too close to a mesh (include/msnap.h) ---------------
+    _MESH_WINDOW_OUTPUTS = (("t_clear_until", "float64"), ("t_first", "float64"), ("d_first", "float64"),
+                            ("tri_first", "int32"), ("t_last", "float64"), ("d_last", "float64"),
+                            ("tri_last", "int32"), ("t_clear_from", "float64"), ("status", "int32"))
+
+    def mesh_conflict_window(self, coef, dur, tris, threshold, t_res=1e-6):
+        """(t_clear_until, t_first, d_first, tri_first int32, t_last, d_last, tri_last int32, t_clear_from, status
+        int32), each [n]: from when until when each drone is closer than `threshold` to the mesh `tris` [T, 3, 3], the
+        crossings located to `t_res` seconds (msnap_mesh_conflict_window_device)."""
+        torch = self.torch
+        n, M = dur.shape
+        if tris.dim() != 3 or tuple(tris.shape[1:]) != (3, 3) or tris.dtype != torch.float64:
+            raise ValueError("mesh_conflict_window: tris must be a float64 tensor [T, 3, 3]")
+        outs = [self._out(f"mesh_conflict_window.{k}", (n,), getattr(torch, kind))
+                for k, kind in self._MESH_WINDOW_OUTPUTS]
+        if n:
+            self.ctx.mesh_conflict_window_device(n, M, coef, dur, tris.shape[0], tris.contiguous(), threshold, t_res,
+                                                 *outs)
+        return tuple(outs)
+
     # ---- path extent in continuous time (include/msnap.h) ------------------------------------------------------------
     def path_extent(self, coef, dur, dirs):
         """(ext [n, K], t_ext [n, K], upper [n, K], status [n] int32): the certified reach of each drone's whole path in
@@ -1349,9 +1369,10 @@ def conflict_windows(compute, clearance_result, coef, dur, radius: float, t_res:
     return _window_result(pairs, outs, (both, take), n)
 
 
-def latest_replan_time(result: ConflictWindowResult, margin: float):
+def latest_replan_time(result, margin: float):
     """Per drone the latest hand-over time t_r of a replan that starts `margin` seconds before the drone's first
-    conflict: first_conflict - margin, not below 0 (+inf for a drone without a conflict).  Hand it to `replan`."""
+    conflict: first_conflict - margin, not below 0 (+inf for a drone without a conflict).  Hand it to `replan`.
+    `result`: a ConflictWindowResult or a MeshConflictWindowResult."""
     if not (margin >= 0.0):
         raise ValueError("latest_replan_time: margin >= 0")
     return (result.first_conflict - margin).clamp(min=0.0)
@@ -1388,3 +1409,48 @@ def replan_conflict_windows(compute, coef, dur, idx, t_r, new_coef, new_dur, rad
     pairs = torch.cat([torch.stack([idx[no[:, 0].to(torch.int64)], no[:, 1].to(torch.int64)], dim=1),
                        idx[nn.to(torch.int64)].reshape(-1, 2)]).to(torch.int32)
     return _window_result(pairs, cat, (who, take), K)
+
+
+# ---- mesh conflict windows: from when a drone is too close to the mesh, for the same hand-over time --------------------
+@dataclass
+class MeshConflictWindowResult:
+    idx: object               # [K] int64: the drones that went through the mesh conflict-window entry
+    # per drone [N], msnap_mesh_conflict_window's outputs (include/msnap.h): clear is proven on [0, t_clear_until) and
+    # (t_clear_from, W]; t_first / t_last are the earliest / latest conflict found, d_* and tri_* the sweep's distance
+    # and triangle there.  A drone that did not go through the entry has the certified-clear values
+    # (+inf, +inf, +inf, -1, -inf, +inf, -1, -inf)
+    t_clear_until: object
+    t_first: object
+    d_first: object
+    tri_first: object
+    t_last: object
+    d_last: object
+    tri_last: object
+    t_clear_from: object
+    # [N]: t_clear_until -- until then the drone is proven clear of the mesh --, +inf for a drone without a conflict
+    # or an undecided graze.  `latest_replan_time` reads this field alone
+    first_conflict: object
+
+
+def mesh_conflict_windows(compute, mesh_result, coef, dur, tris, radius: float,
+                          t_res: float = 1e-6) -> MeshConflictWindowResult:
+    """From when until when the drones that `certify_mesh_clearance` could not clear are closer than radius to the mesh.
+
+    The drones of `mesh_result` (a MeshClearanceResult) whose `certified_lower` < radius -- hits and undecided ones -- go
+    through `compute.mesh_conflict_window` (msnap_mesh_conflict_window_device) with threshold = radius.
+    `first_conflict` [N] is the drone's `t_clear_until`: `latest_replan_time` turns it into a hand-over time."""
+    import torch
+    if not (radius >= 0.0):
+        raise ValueError("mesh_conflict_windows: radius >= 0")
+    n, dev = dur.shape[0], dur.device
+    idx = torch.nonzero(mesh_result.certified_lower < radius, as_tuple=True)[0]
+    inf = float("inf")
+    fills = (inf, inf, inf, -1, -inf, inf, -1, -inf)
+    full = [torch.full((n,), f, dtype=torch.int32 if isinstance(f, int) else torch.float64, device=dev) for f in fills]
+    if idx.numel():
+        outs = compute.mesh_conflict_window(coef[idx].contiguous(), dur[idx].contiguous(), tris, radius, t_res)
+        if int(outs[8].abs().sum()) != 0:
+            raise ValueError("mesh_conflict_windows: msnap_mesh_conflict_window reported failed drones")
+        for dst, src in zip(full, outs[:8]):
+            dst[idx] = src
+    return MeshConflictWindowResult(idx, *full, full[0].clone())

@@ -542,6 +542,68 @@ int msnap_mesh_clearance_device(msnap_ctx *ctx, int n_drones, int n_seg, const d
                                 int n_tris, const double *tris, double *min_dist, double *t_min, int32_t *tri_min,
                                 double *lower, int32_t *status);
 
+/* ---- mesh conflict windows: from when until when a path is too close to a mesh (new capability) ----
+ * msnap_mesh_clearance says that a path comes too close to the mesh and where it is closest; t_min lies INSIDE the
+ * violation.  This entry certifies the interval during which the distance is < threshold: from when a replan has to
+ * have taken over, and when the drone is out of the margin again.  It is msnap_pair_conflict_window with a mesh in the
+ * place of the second drone.  coef, dur, tris as for msnap_mesh_clearance; every output is [n_drones].  The window of a
+ * drone is [0, W], W the running fp64 sum of its durations as msnap_eval_flat accumulates it, each segment on its closed
+ * [0, T_i].  The distance is the sweep's: the minimum over the triangles with finite vertices; a triangle the sweep
+ * takes as degenerate counts as the union of its three edges; a triangle with a non-finite vertex is skipped.
+ *   threshold  a distance [m], finite and >= 0;   t_res  the time resolution [s], finite and > 0
+ *              (either outside its range: MSNAP_EINVAL, also with n_drones == 0).
+ * A drone is IN CONFLICT at t when its distance is < threshold (strict, as the sweep's min_dist < radius) and CLEAR at t
+ * when its distance is >= threshold.  Outputs:
+ *   t_clear_until  proven: clear for every t in [0, t_clear_until);
+ *   t_first        the earliest time found at which the drone is in conflict (+inf: none found);
+ *   d_first        the distance at t_first by msnap_mesh_clearance's rule for min_dist: msnap_mesh_sweep of the single
+ *                  position msnap_eval_flat gives at t_first, over the whole mesh, returns d_first bit for bit (+inf: no
+ *                  t_first);
+ *   tri_first      the lowest triangle index that attains d_first (-1: none);
+ *   t_last, d_last, tri_last   the latest such time, its distance and triangle (-inf / +inf / -1: none);
+ *   t_clear_from   proven: clear for every t in (t_clear_from, W];
+ *   status         as for msnap_mesh_clearance (MSNAP_ST_NONFINITE, then MSNAP_ST_TIMES); the six doubles of a failed
+ *                  drone are NaN, both triangle outputs -1.
+ * Always 0 <= t_clear_until <= t_first <= t_last <= t_clear_from <= W, where the values are finite.  Verdicts:
+ *   certified clear over the whole window   t_clear_until = t_first = d_first = +inf, tri_first = -1, t_last = -inf,
+ *                    d_last = +inf, tri_last = -1, t_clear_from = -inf.  n_tris == 0, or no finite triangle, gives this;
+ *   undecided        no conflict found, but t_clear_until is finite: a graze the search could not separate within its
+ *                    caps.  t_clear_until and t_clear_from still hold;
+ *   closed search    t_first - t_clear_until <= t_res and t_clear_from - t_last <= t_res: always so for a transversal
+ *                    entry and exit.  The caps are msnap_mesh_clearance's: 40 bisections of a segment, 4096 nodes per
+ *                    segment and direction.  Against a degenerate triangle of non-zero area the closing is not promised
+ *                    (the bound is the hull's, as there); the proven ranges still hold.
+ * Rounding.  "Proven" and "in conflict" hold up to an allowance of msnap_mesh_clearance's form,
+ *     r = 1e-13 + C_ROUND_MESH_WINDOW * 2^-52 * R   [m],   C_ROUND_MESH_WINDOW = 8,   R as for msnap_mesh_clearance.
+ * For the exact real polynomials of the fp64 coefficients:
+ *     distance >= threshold - r   at every t of [0, t_clear_until) and of (t_clear_from, W],
+ *     distance at t_first and at t_last  <  threshold + r.
+ * (The constant is ten times the worst deviation measured against an exact reference, 0.732, rounded up -- more than
+ * msnap_mesh_clearance's C_ROUND_MESH = 3, which that measurement does not stay below: DESIGN.md §5 K19.)
+ * An entry or exit that falls exactly on a boundary of the search's dyadic subdivision of a segment has the distance
+ * EQUAL to the threshold at a node's end; the last bit then decides whether that node is proven clear, and the gap on
+ * that side can be up to 2 t_res.
+ * n_drones == 0 is a no-op.  MSNAP_EINVAL, MSNAP_ESEGMENTS and the grid limit are msnap_mesh_clearance's.  A drone's
+ * outputs are bit-identical whatever its place in the batch, the batch size, and host versus device entry.  The device
+ * version only launches; its scratch is msnap_mesh_clearance's buffer of the context under the capture rules above
+ * (MSNAP_ECAPTURE: run the call once outside the capture first).
+ * (Method: per segment a time-ordered walk over dyadic sub-intervals in both directions.  A node whose support-plane
+ * bound, msnap_mesh_clearance's, is >= threshold is clear; a triangle whose bounding box lies threshold or more from the
+ * box of the node's control points is left out of the node; a node that starts in conflict ends the walk; a node
+ * shorter than t_res is a leaf.  A later segment does not know that an earlier one already holds the first conflict:
+ * every segment is walked.)
+ */
+int msnap_mesh_conflict_window(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,
+                               int n_tris, const double *tris, double threshold, double t_res,
+                               double *t_clear_until, double *t_first, double *d_first, int32_t *tri_first,
+                               double *t_last, double *d_last, int32_t *tri_last, double *t_clear_from,
+                               int32_t *status);
+int msnap_mesh_conflict_window_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,
+                                      int n_tris, const double *tris, double threshold, double t_res,
+                                      double *t_clear_until, double *t_first, double *d_first, int32_t *tri_first,
+                                      double *t_last, double *d_last, int32_t *tri_last, double *t_clear_from,
+                                      int32_t *status);
+
 /* ---- path extent in continuous time: the support function of a path (new capability) ----
  * The peaks, the pairwise clearance and the mesh clearance say nothing about WHERE a path goes, and a minimum-snap fit
  * through waypoints inside a workspace overshoots it between them.  msnap_path_extent certifies, per drone and per given
