@@ -84,6 +84,8 @@ SIGNATURES = {
     "msnap_mesh_conflict_window_device": (_I, [_VP, _I, _I, _VP, _VP, _I, _VP, _D, _D] + [_VP] * 9),
     "msnap_path_extent": (_I, [_VP, _I, _I, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP]),
     "msnap_path_extent_device": (_I, [_VP, _I, _I, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP]),
+    "msnap_halfspace_window": (_I, [_VP, _I, _I, _VP, _VP, _I, _VP, _I, _VP, _VP, _VP, _D] + [_VP] * 7),
+    "msnap_halfspace_window_device": (_I, [_VP, _I, _I, _VP, _VP, _I, _VP, _I, _VP, _VP, _VP, _D] + [_VP] * 7),
     "msnap_solve_states": (_I, [_VP, _I, _I, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP]),
     "msnap_solve_states_device": (_I, [_VP, _I, _I, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP]),
     "msnap_solve_states_max_segments": (_I, [_I]),

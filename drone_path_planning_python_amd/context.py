@@ -730,6 +730,46 @@ class Context:
                                                         int(n_dirs), _ptr(dirs), _ptr(ext), _ptr(t_ext), _ptr(upper),
                                                         _ptr(status)))
 
+    # ---- half-space windows: from when until when a path is outside a half-space (include/msnap.h) ----
+    def halfspace_window(self, coef, dur, planes, queries, t_res=1e-6, t_from=None, t_to=None):
+        """From when until when the drone of each query is outside the half-space of that query: `planes` [K, 4] =
+        (n, b), inside is n.x <= b; `queries` [Q, 2] = (drone, plane); `t_from` / `t_to` [Q] or None (0 / the whole
+        flight) give each query's range.  Returns (t_inside_until, t_first, v_first, t_last, v_last, t_inside_from,
+        status int32), each [Q] (msnap_halfspace_window): inside is proven on [S, t_inside_until) and
+        (t_inside_from, W]; t_first / t_last are the earliest / latest time found outside (+inf / -inf: none), to within
+        `t_res` [s] of the proven ranges when the search closes; v_* are n.p there."""
+        coef, pc, dur, pd, N, M = self._coef_dur(coef, dur)
+        pl, ppl = _host(planes, np.float64)
+        if pl.ndim != 2 or pl.shape[1] != 4:
+            raise ValueError("planes must be [K, 4]")
+        qr, pqr = _host(queries, np.int32)
+        if qr.ndim != 2 or qr.shape[1] != 2:
+            raise ValueError("queries must be [Q, 2]")
+        Q = qr.shape[0]
+        rng = []
+        for name, x in (("t_from", t_from), ("t_to", t_to)):
+            if x is None:
+                rng.append((None, None))
+                continue
+            x, px = _host(x, np.float64)
+            if x.shape != (Q,):
+                raise ValueError(f"{name} must be [{Q}]")
+            rng.append((x, px))
+        outs, ptrs = self._window_outputs(Q)
+        with self._lock:
+            self._ck(self._lib.msnap_halfspace_window(self._h, N, M, pc, pd, pl.shape[0], ppl, Q, pqr, rng[0][1], rng[1][1], float(t_res), *ptrs))
+        return tuple(outs)
+
+    def halfspace_window_device(self, n_drones, n_seg, coef, dur, n_planes, planes, n_queries, queries, t_from, t_to,
+                                t_res, t_inside_until, t_first, v_first, t_last, v_last, t_inside_from, status):
+        """Device pointers (planes float64 [n_planes, 4]; queries int32 [n_queries, 2]; t_from / t_to may be None: 0 /
+        the whole flight; status int32), asynchronous on the context's stream."""
+        with self._lock:
+            self._ck(self._lib.msnap_halfspace_window_device(
+                self._h, int(n_drones), int(n_seg), _ptr(coef), _ptr(dur), int(n_planes), _ptr(planes), int(n_queries),
+                _ptr(queries), _ptr(t_from), _ptr(t_to), float(t_res), _ptr(t_inside_until), _ptr(t_first),
+                _ptr(v_first), _ptr(t_last), _ptr(v_last), _ptr(t_inside_from), _ptr(status)))
+
     # ---- replanning in flight (include/msnap.h) -------------------------------------
     def solve_states_max_segments(self) -> int:
         """Largest segment count solve_states takes at this context's order (and at most max_segments)."""

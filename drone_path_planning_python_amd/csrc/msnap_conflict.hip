@@ -43,40 +43,21 @@ inline size_t conflict_work_bytes(size_t lanes, size_t segs) {
   return lanes * kLaneDoubles * sizeof(double) + segs * sizeof(int32_t);
 }
 
-// The walk for the first crossing of the level L from u = 0 on.  hit: the u of the conflict found (+inf: none); clear:
-// the u up to which g >= L is proven (+inf: the whole lane).  Every lane of the wave calls it.
+// The walk for the first crossing of the level L from u = 0 on (msnap_walk.h, first_crossing: the walk K20 shares) on
+// g = the sum of the squares of the three difference polynomials e.  hit: the u of the conflict found (+inf: none);
+// clear: the u up to which g >= L is proven (+inf: the whole lane).  Every lane of the wave calls it.
 template <int D>
 __device__ __forceinline__ void first_crossing(const double (&e)[3][D + 1], bool ok, double h, double L, double t_res,
                                                double &hit, double &clear) {
-  const double inf = __builtin_inf();
-  hit = inf;
-  clear = inf;
-  WalkNode node;
-  bool active = ok;
-  while (__ballot(active) != 0) {
-    const double hh = node.h(), a = node.a();
-    double f[3][D + 1];
+  first_crossing(
+      [&](double a, double hh, double &bound, double (&g)[3]) {
+        double f[3][D + 1];
 #pragma unroll
-    for (int s = 0; s < 3; ++s) shift_scale<D>(e[s], a, hh, f[s]);
-    const double bound = squares_bound<true, D>(f);
-    double g[3];
-    squares_at_ends_and_middle<D>(f, g);
-    const bool open = !(bound >= L);                                    // not proven clear (a NaN bound proves nothing)
-    const bool at_start = open && g[0] < L;
-    const bool leaf = h * hh <= t_res || node.lvl >= kMaxDepth;
-    const bool in_mid = g[1] < L, at_end = g[2] < L;
-    const bool found = at_start || (open && leaf && (in_mid || at_end));
-    const bool undecided = open && !found && leaf;
-    const bool split = open && !found && !leaf;
-    const double at = at_start ? a : (in_mid ? fma(0.5, hh, a) : a + hh);
-    const bool finished = node.advance(split, active);
-    const bool guard = !finished && node.nodes >= kMaxNodes;            // nodes are left unvisited: undecided from a on
-    if (active) {
-      hit = found ? at : hit;
-      clear = (found || undecided || guard) ? fmin(clear, a) : clear;
-    }
-    active = active && !(found || finished || guard);
-  }
+        for (int s = 0; s < 3; ++s) shift_scale<D>(e[s], a, hh, f[s]);
+        bound = squares_bound<true, D>(f);
+        squares_at_ends_and_middle<D>(f, g);
+      },
+      ok, h, L, t_res, hit, clear);
 }
 
 // one lane per (pair, slot): work[4 item ..] = the four times of the head, on the common clock

@@ -337,6 +337,33 @@ class DeviceCompute:
             self.ctx.path_extent_device(n, M, coef, dur, K, dirs.contiguous(), ext, t_ext, upper, status)
         return ext, t_ext, upper, status
 
+    # ---- half-space windows: from when until when a path is outside a half-space (include/msnap.h) -------------------
+    _HALFSPACE_OUTPUTS = ("t_inside_until", "t_first", "v_first", "t_last", "v_last", "t_inside_from")
+
+    def halfspace_window(self, coef, dur, planes, queries, t_res=1e-6, t_from=None, t_to=None):
+        """(t_inside_until, t_first, v_first, t_last, v_last, t_inside_from, status int32), each [Q], of the queries
+        (int32 [Q, 2]: drone, plane) against `planes` [K, 4] = (n, b), inside being n.x <= b, each on its range
+        [t_from, t_to] ([Q] float64 each, or None: 0 / the whole flight), the crossings located to `t_res` seconds
+        (msnap_halfspace_window_device)."""
+        torch = self.torch
+        n, M = dur.shape
+        if planes.dim() != 2 or planes.shape[1] != 4 or planes.dtype != torch.float64:
+            raise ValueError("halfspace_window: planes must be a float64 tensor [K, 4]")
+        if queries.dim() != 2 or queries.shape[1] != 2 or queries.dtype != torch.int32:
+            raise ValueError("halfspace_window: queries must be an int32 tensor [Q, 2]")
+        Q = queries.shape[0]
+        for name, x in (("t_from", t_from), ("t_to", t_to)):
+            if x is not None and (tuple(x.shape) != (Q,) or x.dtype != torch.float64):
+                raise ValueError(f"halfspace_window: {name} must be a float64 tensor [{Q}]")
+        outs = ([self._out(f"halfspace_window.{k}", (Q,), torch.float64) for k in self._HALFSPACE_OUTPUTS]
+                + [self._out("halfspace_window.status", (Q,), torch.int32)])
+        if Q:
+            self.ctx.halfspace_window_device(n, M, coef.contiguous(), dur.contiguous(), planes.shape[0],
+                                             planes.contiguous(), Q, queries.contiguous(),
+                                             None if t_from is None else t_from.contiguous(),
+                                             None if t_to is None else t_to.contiguous(), t_res, *outs)
+        return tuple(outs)
+
     # ---- replanning in flight (include/msnap.h) ----------------------------------------------------------------------
     def solve_states(self, wp, t, start=None, end=None):
         """(coef, dur, status) of the solve from and to given end states: `start` / `end` [n, 4, K-1] float64 -- entry
@@ -1372,7 +1399,9 @@ def conflict_windows(compute, clearance_result, coef, dur, radius: float, t_res:
 def latest_replan_time(result, margin: float):
     """Per drone the latest hand-over time t_r of a replan that starts `margin` seconds before the drone's first
     conflict: first_conflict - margin, not below 0 (+inf for a drone without a conflict).  Hand it to `replan`.
-    `result`: a ConflictWindowResult or a MeshConflictWindowResult."""
+    `result`: a ConflictWindowResult, a MeshConflictWindowResult or a GeofenceWindowResult (`geofence_windows`: there
+    first_conflict is the earliest time FOUND outside the fence, to within t_res of the proven `inside_until` when the
+    search closed; an undecided graze has +inf here and a finite `inside_until`)."""
     if not (margin >= 0.0):
         raise ValueError("latest_replan_time: margin >= 0")
     return (result.first_conflict - margin).clamp(min=0.0)
@@ -1454,3 +1483,219 @@ def mesh_conflict_windows(compute, mesh_result, coef, dur, tris, radius: float,
         for dst, src in zip(full, outs[:8]):
             dst[idx] = src
     return MeshConflictWindowResult(idx, *full, full[0].clone())
+
+
+# ---- half-space windows: when a path leaves a geofence, and a safe flight corridor as a chain of polytopes -------------
+@dataclass
+class GeofenceWindowResult:
+    idx: object               # [K] int64: the drones that went through the half-space window entry
+    queries: object           # [Q, 2] int32: (drone, constraint -- an index into the GeofenceResult's `normals`)
+    # per query [Q], msnap_halfspace_window's outputs (include/msnap.h): inside is proven on [0, t_inside_until) and
+    # (t_inside_from, total]; t_first / t_last are the earliest / latest time found outside (+inf / -inf: none), v_*
+    # the constraint's n.p there
+    t_inside_until: object
+    t_first: object
+    v_first: object
+    t_last: object
+    v_last: object
+    t_inside_from: object
+    # per drone [N]; a drone that did not go through the entry has (+inf, -inf, +inf, -inf, -1)
+    first_conflict: object    # the earliest t_first over the drone's constraints (+inf: none found): `latest_replan_time`
+    last_conflict: object     # the latest t_last (-inf: none found)
+    inside_until: object      # the earliest t_inside_until: until then the drone is proven inside every constraint
+    inside_from: object       # the latest t_inside_from: after it the drone is proven inside every constraint
+    first_broken: object      # int64: the constraint whose t_first is first_conflict (-1: none)
+
+
+def _drone_plane_queries(idx, first, count):
+    """int64 (row [Q], plane [Q]): for row r of `idx`, the `count[r]` planes from `first[r]` on; row indexes `idx`."""
+    import torch
+    total = int(count.sum())
+    row = torch.repeat_interleave(torch.arange(idx.numel(), device=idx.device), count, output_size=total)
+    within = torch.arange(total, device=idx.device) - (torch.cumsum(count, 0) - count)[row]
+    return row, first[row] + within
+
+
+def _earliest(values, row, n_rows, fill, largest=False):
+    """Per row the smallest (largest) of `values` [Q] and the first query that attains it (-1: the row has none)."""
+    import torch
+    Q = values.numel()
+    best = torch.full((n_rows,), fill, dtype=values.dtype, device=values.device)
+    arg = torch.full((n_rows,), -1, dtype=torch.int64, device=values.device)
+    if Q:
+        best.scatter_reduce_(0, row, values, reduce="amax" if largest else "amin", include_self=True)
+        at = torch.where(values == best[row], torch.arange(Q, device=values.device), torch.full_like(row, Q))
+        first = torch.full((n_rows,), Q, dtype=torch.int64, device=values.device)
+        first.scatter_reduce_(0, row, at, reduce="amin", include_self=True)
+        arg = torch.where(first < Q, first, arg)
+    return best, arg
+
+
+def geofence_windows(compute, geofence_result, coef, dur, t_res: float = 1e-6) -> GeofenceWindowResult:
+    """From when until when the drones that `certify_geofence` could not certify are outside the fence.
+
+    The `outside` and `undecided` drones of `geofence_result` (a GeofenceResult) go against every finite constraint of it
+    -- `normals` / `limits`, which carry the radius already -- through `compute.halfspace_window`
+    (msnap_halfspace_window_device) over their whole flight.  Per drone: `first_conflict` / `last_conflict`, the earliest
+    and latest time found outside any constraint; `inside_until` / `inside_from`, the proven ranges; `first_broken`, the
+    constraint that is broken first.  `latest_replan_time` turns `first_conflict` into a hand-over time."""
+    import torch
+    n, dev = dur.shape[0], dur.device
+    idx = torch.nonzero(geofence_result.outside | geofence_result.undecided, as_tuple=True)[0]
+    C = int(geofence_result.limits.numel())
+    planes = torch.cat([geofence_result.normals.reshape(-1, 3), geofence_result.limits.reshape(-1, 1)], dim=1).contiguous()
+    row, con = _drone_plane_queries(idx, torch.zeros_like(idx), torch.full_like(idx, C))
+    queries = torch.stack([idx[row], con], dim=1).to(torch.int32).contiguous()
+    outs = tuple(x.clone() for x in compute.halfspace_window(coef, dur, planes, queries, t_res))
+    if queries.shape[0] and int(outs[6].abs().sum()) != 0:
+        raise ValueError("geofence_windows: msnap_halfspace_window reported failed queries")
+    inf = float("inf")
+    who = idx[row]
+    first, arg = _earliest(outs[1], who, n, inf)
+    last, _ = _earliest(outs[3], who, n, -inf, largest=True)
+    until, _ = _earliest(outs[0], who, n, inf)
+    frm, _ = _earliest(outs[5], who, n, -inf, largest=True)
+    broken = torch.where(torch.isfinite(first) & (arg >= 0), con[arg.clamp(min=0)] if con.numel() else arg, torch.full_like(arg, -1))
+    return GeofenceWindowResult(idx, queries, *outs[:6], first, last, until, frm, broken)
+
+
+CORRIDOR_INSIDE, CORRIDOR_OUTSIDE, CORRIDOR_UNDECIDED, CORRIDOR_FAILED = 0, 1, 2, 3
+
+
+@dataclass
+class CorridorResult:
+    verdict: object           # [N] int8: CORRIDOR_INSIDE / _OUTSIDE / _UNDECIDED / _FAILED
+    proven_until: object      # [N] the time up to which the drone is proven inside the corridor (INSIDE: its total; NaN: failed)
+    stage: object             # [N] int64: the stage of the drone's chain at which it stopped (-1: inside or failed)
+    plane: object             # [N] int64: the plane (index into `planes`) that stopped it (-1: inside or failed)
+    first_conflict: object    # [N] that plane's t_first (+inf: none found, inside, failed)
+    value: object             # [N] its v_first, n.p at first_conflict (-inf: none found; NaN: inside, failed)
+    handover: object          # [N, L] h_i, the time from which stage i had to hold (NaN: the stage was not reached)
+
+
+def certify_corridor(compute, coef, dur, planes, poly_offsets, chain, radius: float = 0.0, t_res: float = 1e-6,
+                     status=None) -> CorridorResult:
+    """Certify in continuous time that every drone of `coef`, `dur` flies through a safe flight corridor: a chain of
+    overlapping convex polytopes of free space, in each of which the path must stay until it is inside the next.
+
+    `planes` [Q, 4] = (n, b), finite, meaning n.x <= b; polytope p is planes[poly_offsets[p]:poly_offsets[p + 1]] (an
+    empty polytope is all of space); `chain` is [L] (shared by all drones) or [N, L] int64 polytope ids, -1 padding the
+    tail, at least one stage per drone.  A drone is a sphere of `radius`, which moves each limit by radius |n|.
+    L rounds, each one call of `compute.halfspace_window` (msnap_halfspace_window_device) over the drones still running,
+    h_0 = 0.  In round i the planes of stage i are queried on [h_i, total]; stay_i is the smallest t_inside_until:
+      all +inf                       the drone is certified inside through the end: INSIDE;
+      some t_inside_until == h_i     the drone is not proven inside stage i at the hand-over: it stops.  What stopped it
+                                     is the plane of stage i - 1 that it left before it was inside stage i (i = 0: the
+                                     plane of stage 0 it starts outside of);
+      the last stage of its chain    it stops there, proven inside until stay_i;
+      otherwise                      h_{i+1} = max(h_i, stay_i - t_res), the latest time proven inside stage i -- the right
+                                     choice for a chain: stage i + 1 has to hold from there.
+    A drone that stopped names that `stage` and its `plane` with the smallest t_inside_until, whose t_first / v_first are
+    `first_conflict` / `value`.  It is OUTSIDE only when that is definite: the position of the drone at `first_conflict`
+    (compute.eval_state: msnap_eval_flat's lookup and arithmetic) violates at least one plane of EVERY polytope of its
+    chain, by the unfused (n_x x + n_y y) + n_z z > limit.  Any other drone that stopped is UNDECIDED.  FAILED is as in
+    certify_geofence: status != 0 (`status`: the solve's; or the entry's), nothing is certified.
+
+    One rank: every drone is checked on its own, so a sharded swarm calls this per shard."""
+    import torch
+    if not (radius >= 0.0):
+        raise ValueError("certify_corridor: radius >= 0")
+    if not (t_res > 0.0 and t_res < float("inf")):
+        raise ValueError("certify_corridor: t_res > 0 and finite")
+    n, dev = dur.shape[0], dur.device
+    f64 = dict(dtype=torch.float64, device=dev)
+    pl = torch.as_tensor(planes, dtype=torch.float64).to(dev).reshape(-1, 4).clone()
+    if not bool(torch.isfinite(pl).all()):
+        raise ValueError("certify_corridor: planes must be finite")
+    off = torch.as_tensor(poly_offsets, dtype=torch.int64).to(dev).reshape(-1)
+    if off.numel() < 2 or int(off[0]) != 0 or int(off[-1]) != pl.shape[0] or bool((off[1:] < off[:-1]).any()):
+        raise ValueError("certify_corridor: poly_offsets must rise from 0 to the number of planes")
+    n_poly = off.numel() - 1
+    ch = torch.as_tensor(chain, dtype=torch.int64).to(dev)
+    if ch.dim() == 1:
+        ch = ch[None, :].expand(n, -1)
+    if ch.dim() != 2 or ch.shape[0] != n or ch.shape[1] < 1:
+        raise ValueError("certify_corridor: chain must be [L] or [N, L] with L >= 1")
+    valid = ch >= 0
+    if bool((ch < -1).any() | (ch >= n_poly).any() | (valid[:, 1:] & ~valid[:, :-1]).any() | ~valid[:, 0].all()):
+        raise ValueError("certify_corridor: chain holds polytope ids, -1 only as padding of the tail, one stage at least")
+    L = ch.shape[1]
+    length = valid.sum(dim=1)
+    pl[:, 3] = pl[:, 3] - radius * torch.linalg.vector_norm(pl[:, :3], dim=1)
+    sizes = off[1:] - off[:-1]
+    total = torch.zeros((n,), **f64)
+    for k in range(dur.shape[1]):      # (the running sum, as msnap_eval_flat accumulates it)
+        total = total + dur[:, k]
+
+    bad = torch.zeros((n,), dtype=torch.bool, device=dev)
+    if status is not None:
+        bad |= torch.as_tensor(status).to(dev) != 0
+    inf, nan = float("inf"), float("nan")
+    h = torch.zeros((n,), **f64)
+    proven = torch.zeros((n,), **f64)
+    handover = torch.full((n, L), nan, **f64)
+    stage = torch.full((n,), -1, dtype=torch.int64, device=dev)
+    plane = torch.full((n,), -1, dtype=torch.int64, device=dev)
+    first = torch.full((n,), inf, **f64)
+    value = torch.full((n,), nan, **f64)
+    left_plane, left_first, left_value = plane.clone(), first.clone(), value.clone()      # of the stage a drone left last
+    inside = torch.zeros_like(bad)
+    run = ~bad
+    for i in range(L):
+        idx = torch.nonzero(run, as_tuple=True)[0]
+        if not idx.numel():
+            break
+        handover[idx, i] = h[idx]
+        poly = ch[idx, i]
+        row, qp = _drone_plane_queries(idx, off[poly], sizes[poly])
+        queries = torch.stack([idx[row], qp], dim=1).to(torch.int32).contiguous()
+        outs = compute.halfspace_window(coef, dur, pl, queries, t_res, t_from=h[idx][row].contiguous())
+        iu, tf, vf, st = outs[0].clone(), outs[1].clone(), outs[2].clone(), outs[6]
+        failed = torch.zeros((idx.numel(),), dtype=torch.bool, device=dev)
+        if queries.shape[0]:
+            failed.index_put_((row,), st != 0, accumulate=True)
+        iu = torch.where(torch.isnan(iu), torch.full_like(iu, inf), iu)
+        stay, arg = _earliest(iu, row, idx.numel(), inf)
+        hi = h[idx]
+        done = ~failed & torch.isinf(stay)
+        stop = ~failed & ~done & ((stay == hi) | (length[idx] - 1 == i))
+        go = ~failed & ~done & ~stop
+        bad[idx[failed]] = True
+        inside[idx[done]] = True
+        # what is proven: stage i up to stay_i, unless the drone is not inside it at the hand-over
+        adv = (go | stop) & (stay > hi)
+        proven[idx[adv]] = torch.maximum(proven[idx[adv]], stay[adv])
+        # where it stopped: this stage's plane with the smallest t_inside_until -- or, when the hand-over into this
+        # stage failed, the plane of the stage before that the drone left too early
+        back = stop & (stay == hi) & (i > 0)
+        here = stop & ~back
+        s_i, s_q = idx[here], arg[here]
+        stage[s_i], plane[s_i], first[s_i], value[s_i] = i, qp[s_q], tf[s_q], vf[s_q]
+        b_i = idx[back]
+        stage[b_i], plane[b_i], first[b_i], value[b_i] = i - 1, left_plane[b_i], left_first[b_i], left_value[b_i]
+        handover[b_i, i] = nan      # (stage i was not reached)
+        g_i, g_q = idx[go], arg[go]
+        left_plane[g_i], left_first[g_i], left_value[g_i] = qp[g_q], tf[g_q], vf[g_q]
+        h[g_i] = torch.maximum(hi[go], stay[go] - t_res)
+        run = torch.zeros_like(run)
+        run[idx[go]] = True
+
+    stopped = stage >= 0
+    outside = torch.zeros_like(bad)
+    sidx = torch.nonzero(stopped & torch.isfinite(first), as_tuple=True)[0]
+    if sidx.numel():
+        pos, _ = compute.eval_state(coef[sidx].contiguous(), dur[sidx].contiguous(), first[sidx].contiguous())
+        x, y, z = pos[:, 0:1], pos[:, 1:2], pos[:, 2:3]
+        val = (pl[None, :, 0] * x + pl[None, :, 1] * y) + pl[None, :, 2] * z      # [S, Q], every operation rounded once
+        viol = (val > pl[None, :, 3]).to(torch.float64)
+        pid = torch.repeat_interleave(torch.arange(n_poly, device=dev), sizes, output_size=pl.shape[0])
+        per_poly = torch.zeros((sidx.numel(), n_poly), **f64).index_add_(1, pid, viol) > 0
+        along = per_poly.gather(1, ch[sidx].clamp(min=0)) | ~valid[sidx]
+        outside[sidx] = along.all(dim=1)
+    verdict = torch.full((n,), CORRIDOR_UNDECIDED, dtype=torch.int8, device=dev)
+    verdict[inside], verdict[outside], verdict[bad] = CORRIDOR_INSIDE, CORRIDOR_OUTSIDE, CORRIDOR_FAILED
+    proven = torch.where(inside, total, proven)
+    proven = torch.where(bad, torch.full_like(proven, nan), proven)
+    for x, fill in ((stage, -1), (plane, -1), (first, inf), (value, nan)):
+        x[bad] = fill
+    return CorridorResult(verdict, proven, stage, plane, first, value, handover)

@@ -71,7 +71,7 @@ enum msnap_status {       /* per-drone, written to status[]                   */
   MSNAP_ST_TIMES = 2,     /* times not strictly increasing (or t[1] <= 2 t[0]) */
   MSNAP_ST_NONFINITE = 3, /* NaN / Inf in the waypoints or times               */
   MSNAP_ST_PAIR = 4       /* msnap_pair_clearance: a drone index outside [0, n_drones), or a == b; msnap_cross_clearance:
-                             an index outside its set */
+                             an index outside its set; msnap_halfspace_window: a drone or plane index out of range */
 };
 
 int msnap_version(void);                       /* 10000*major + 100*minor + patch */
@@ -646,6 +646,78 @@ int msnap_path_extent(msnap_ctx *ctx, int n_drones, int n_seg, const double *coe
 int msnap_path_extent_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,
                              int n_dirs, const double *dirs, double *ext, double *t_ext, double *upper,
                              int32_t *status);
+
+/* ---- half-space windows: from when until when a path is outside a half-space (new capability) ----
+ * msnap_path_extent reports one extreme per direction over the whole flight; it cannot say WHEN a path leaves a
+ * half-space n.x <= b or when it is back inside.  This entry certifies that, per query and from a start time of the
+ * query's own: what a safe flight corridor needs (a chain of overlapping convex polytopes; the path must stay in one
+ * until it is inside the next), and the time-resolved sibling of the geofence.  It is msnap_pair_conflict_window with a
+ * half-space in the place of the second drone.  coef, dur as everywhere else.
+ *   planes   [n_planes][4] = (n_x, n_y, n_z, b): inside is n.x <= b; the normals need not have unit length;
+ *   queries  int32 [n_queries][2] = (drone, plane): index into the batch, index into planes;
+ *   t_from, t_to  [n_queries] each, or NULL: the query's range is [S, W] = [max(t_from, 0), min(t_to, total)], total the
+ *            running fp64 sum of the drone's durations as msnap_eval_flat accumulates it.  NULL t_from means 0, NULL t_to
+ *            the whole flight; NULL gives the same bits as an array of zeros / of the totals;
+ *   t_res    the time resolution [s], finite and > 0 (else MSNAP_EINVAL, also with n_queries == 0).
+ * A query is OUTSIDE at t when n.p(t) > b (strict: a path that only touches a limit is not outside) and INSIDE at t when
+ * n.p(t) <= b.  Outputs, each [n_queries]:
+ *   t_inside_until  proven: inside for every t in [S, t_inside_until);
+ *   t_first         the earliest time found at which the path is outside (+inf: none found);
+ *   v_first         n.p at t_first, formed as msnap_path_extent forms ext: for the position (x, y, z) msnap_eval_flat
+ *                   gives at t_first, (n_x * x + n_y * y) + n_z * z -- every operation rounded once, in this order, none
+ *                   fused -- is v_first bit for bit (-inf: no t_first);
+ *   t_last, v_last  the latest such time and its value (-inf / -inf: none);
+ *   t_inside_from   proven: inside for every t in (t_inside_from, W];
+ *   status          msnap_status, first condition wins: MSNAP_ST_PAIR for a drone index outside [0, n_drones) or a plane
+ *                   index outside [0, n_planes) (nothing is read for such a query), else MSNAP_ST_NONFINITE for a NaN /
+ *                   Inf coefficient or duration of the drone or a NaN / Inf t_from or t_to of the query, else
+ *                   MSNAP_ST_TIMES for a duration <= 0.  The six doubles of a failed query are NaN.
+ * Always S <= t_inside_until <= t_first <= t_last <= t_inside_from <= W, where the values are finite.  Verdicts:
+ *   certified inside over the whole range   t_inside_until = t_first = +inf, t_last = t_inside_from = -inf;
+ *   undecided        nothing found outside, but t_inside_until is finite: a graze the search could not separate within
+ *                    its caps.  t_inside_until and t_inside_from still hold;
+ *   closed search    t_first - t_inside_until <= t_res and t_inside_from - t_last <= t_res: always so for a transversal
+ *                    crossing.  The caps are msnap_path_extent's: 40 bisections of a segment, 4096 nodes per segment and
+ *                    direction.
+ *   W < S: certified inside.  W == S: the one instant decides (outside: all four times are S).
+ * A plane with a non-finite entry gives NaN in the six doubles of its queries; their status is the drone's, unaffected
+ * (msnap_path_extent's rule for a non-finite direction).  A zero normal is inside when 0 <= b and outside at every
+ * instant otherwise (t_inside_until = t_first = S, t_last = t_inside_from = W, both values 0).
+ * Rounding.  "Proven" and "outside" hold up to msnap_path_extent's allowance, unchanged:
+ *     r = 1e-13 + C_ROUND_EXTENT * 2^-52 * R_k,   C_ROUND_EXTENT = 9,   R_k as stated there for (drone, n).
+ * For the exact real polynomials of the fp64 coefficients and the fp64 plane:
+ *     n.p(t) <= b + r   at every t of [S, t_inside_until) and of (t_inside_from, W],
+ *     n.p at t_first and at t_last  >  b - r.
+ * (Measured on the fp64 restatement of the method, not on the kernel, against an exact reference at t_res = 1e-14, both
+ * orders, paths shifted by up to 1e5 m: the worst deviation is 0.697 in units of 2^-52 R_k; ten times that
+ * stays below C_ROUND_EXTENT = 9, so the entry uses K12's r.  tools/halfspace_window_rounding.py)
+ * A crossing that falls exactly on a boundary of the search's dyadic subdivision has n.p EQUAL to b at a node's end;
+ * the last bit then decides whether that node is proven inside, and the gap on that side can be up to 2 t_res.
+ * Bit identities.  A query's outputs do not depend on its place in the list, on the list's length, on the plane's place
+ * in planes or on n_planes; nor on the batch size or the drone's place in the batch; host entry and device entry give
+ * the same bits.
+ * n_queries == 0 is a no-op.  MSNAP_EINVAL: a null context, a null array other than t_from / t_to, negative sizes, t_res
+ * not finite or <= 0, planes == NULL with n_planes > 0, n_queries * n_seg beyond what one launch covers.
+ * MSNAP_ESEGMENTS as everywhere.  Both orders, n_seg 1 .. max_segments.  The device version takes device pointers and
+ * only launches; its scratch is msnap_path_extent's buffer of the context under the capture rules above
+ * (MSNAP_ECAPTURE: run the call once outside the capture first).
+ * (Method: one lane per query and segment on the part of the segment inside the range: the scalar polynomial -(n.p),
+ * a time-ordered walk over dyadic sub-intervals in both directions against the level -b, which is never rounded into
+ * the coefficients -- a node whose smallest Bernstein coefficient is >= -b is proven inside, a node that starts outside
+ * ends the walk, a node shorter than t_res is a leaf.  A later segment does not know that an earlier one already holds
+ * the first exit: every segment is walked.)
+ */
+int msnap_halfspace_window(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur, int n_planes,
+                           const double *planes /* [n_planes][4] = (n, b): inside is n.x <= b */, int n_queries,
+                           const int32_t *queries /* [n_queries][2] = (drone, plane) */, const double *t_from,
+                           const double *t_to /* [n_queries] each, or NULL */, double t_res, double *t_inside_until,
+                           double *t_first, double *v_first, double *t_last, double *v_last, double *t_inside_from,
+                           int32_t *status);
+int msnap_halfspace_window_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,
+                                  int n_planes, const double *planes, int n_queries, const int32_t *queries,
+                                  const double *t_from, const double *t_to, double t_res, double *t_inside_until,
+                                  double *t_first, double *v_first, double *t_last, double *v_last,
+                                  double *t_inside_from, int32_t *status);
 
 /* ---- replanning in flight: solve from and to given end states (new capability) ----
  * Every other solve starts and ends at rest.  msnap_eval_state reads the full state of each drone on its current path

@@ -59,6 +59,7 @@ K16_OBJS = [os.path.join(CSRC, f) for f in ("msnap_timeopt_periodic.o",)]
 K17_OBJS = [os.path.join(CSRC, f) for f in ("msnap_timeopt_free.o",)]
 K18_OBJS = [os.path.join(CSRC, f) for f in ("msnap_conflict.o",)]
 K19_OBJS = [os.path.join(CSRC, f) for f in ("msnap_mesh_conflict.o",)]
+K20_OBJS = [os.path.join(CSRC, f) for f in ("msnap_halfspace.o",)]
 
 
 def disassemble(obj):
@@ -231,13 +232,13 @@ def check(obj):
 
 def main():
     if sys.argv[1:2] == ["--latches"]:      # the census: one line per kernel with a lane-retiring loop
-        for obj in sys.argv[2:] or DEFAULT_OBJS + MORE_OBJS + K11_OBJS + K12_OBJS + K13_OBJS + K15_OBJS + K16_OBJS + K17_OBJS + K18_OBJS + K19_OBJS:
+        for obj in sys.argv[2:] or DEFAULT_OBJS + MORE_OBJS + K11_OBJS + K12_OBJS + K13_OBJS + K15_OBJS + K16_OBJS + K17_OBJS + K18_OBJS + K19_OBJS + K20_OBJS:
             found = lane_latches(obj)
             print(f"check_exec_isa: {os.path.basename(obj)}: {sum(found.values())} lane-retiring loop latches in {len(found)} kernels")
             for k, n in sorted(found.items()):
                 print(f"    {n:3d}  {k}")
         return 0
-    objs = sys.argv[1:] or DEFAULT_OBJS + MORE_OBJS + K11_OBJS + K12_OBJS + K13_OBJS + K15_OBJS + K16_OBJS + K17_OBJS + K18_OBJS + K19_OBJS
+    objs = sys.argv[1:] or DEFAULT_OBJS + MORE_OBJS + K11_OBJS + K12_OBJS + K13_OBJS + K15_OBJS + K16_OBJS + K17_OBJS + K18_OBJS + K19_OBJS + K20_OBJS
     rc = 0
     for obj in objs:
         n_kernels, n_spill, bad = check(obj)
