@@ -89,6 +89,9 @@ SIGNATURES = {
     "msnap_solve_states": (_I, [_VP, _I, _I, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP]),
     "msnap_solve_states_device": (_I, [_VP, _I, _I, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP]),
     "msnap_solve_states_max_segments": (_I, [_I]),
+    "msnap_solve_gates": (_I, [_VP, _I, _I, _VP, _VP, _I] + [_VP] * 7),
+    "msnap_solve_gates_device": (_I, [_VP, _I, _I, _VP, _VP, _I] + [_VP] * 7),
+    "msnap_solve_gates_max_segments": (_I, [_I]),
     "msnap_solve_periodic": (_I, [_VP, _I, _I, _VP, _VP, _I, _VP, _VP, _VP]),
     "msnap_solve_periodic_device": (_I, [_VP, _I, _I, _VP, _VP, _I, _VP, _VP, _VP]),
     "msnap_solve_periodic_max_segments": (_I, [_I]),

@@ -806,6 +806,46 @@ class Context:
                                                          int(bool(shared_times)), _ptr(start), _ptr(end), _ptr(coef),
                                                          _ptr(dur), _ptr(status)))
 
+    # ---- gates: prescribed derivatives at interior waypoints (include/msnap.h) -------
+    def solve_gates_max_segments(self) -> int:
+        """Largest segment count solve_gates takes at this context's order (and at most max_segments)."""
+        return self._mode_max_segments(self._lib.msnap_solve_gates_max_segments)
+
+    def solve_gates(self, wp, t, start=None, end=None, fix=None, via=None):
+        """solve_states with prescribed derivatives at interior waypoints (msnap_solve_gates): fix [N, M-1] int32 --
+        bit q-1 of entry i-1: the q-th derivative at waypoint i is prescribed, on all four axes -- and via
+        [N, M-1, 4, K-1] the values (unused entries may be NaN).  fix None: no gates, solve_states' bits
+        -> coef [N, M, 4, ncoef], dur [N, M], status [N] int32."""
+        wp, pwp, t, pt, N, m, shared = _waypoints_times(wp, t)
+        M = m - 1
+        start, ps = self._state_block(start, N, "start")
+        end, pe = self._state_block(end, N, "end")
+        pf = pv = None
+        if fix is not None:
+            fix, pf = _host(fix, np.int32)
+            if fix.shape != (N, max(M - 1, 0)):
+                raise ValueError(f"fix must be [N, M-1] = {(N, max(M - 1, 0))}, got {fix.shape}")
+            if via is None:
+                raise ValueError("fix needs via")
+        if via is not None:
+            via, pv = _host(via, np.float64)
+            if via.shape != (N, max(M - 1, 0), 4, self.ncoef // 2 - 1):
+                raise ValueError(f"via must be [N, M-1, 4, {self.ncoef // 2 - 1}], got {via.shape}")
+        coef, dur, status = _out_arrays(None, ((N, max(M, 0), 4, self.ncoef), (N, max(M, 0)), (N,)))
+        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)      # noqa: E731
+        with self._lock:
+            self._ck(self._lib.msnap_solve_gates(self._h, N, M, pwp, pt, shared, ps, pe, pf, pv, vp(coef), vp(dur),
+                                                 vp(status)))
+        return coef, dur, status
+
+    def solve_gates_device(self, n_drones, n_seg, wp, t, shared_times, start, end, fix, via, coef, dur, status):
+        """Device pointers (start / end may be None: rest; fix None: no gates, via may then be None too), asynchronous
+        on the context's stream."""
+        with self._lock:
+            self._ck(self._lib.msnap_solve_gates_device(self._h, int(n_drones), int(n_seg), _ptr(wp), _ptr(t),
+                                                        int(bool(shared_times)), _ptr(start), _ptr(end), _ptr(fix),
+                                                        _ptr(via), _ptr(coef), _ptr(dur), _ptr(status)))
+
     # ---- closed-loop paths (include/msnap.h) ----------------------------------------
     def solve_periodic_max_segments(self) -> int:
         """Largest segment count solve_periodic takes at this context's order (and at most max_segments)."""

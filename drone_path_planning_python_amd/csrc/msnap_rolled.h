@@ -1,8 +1,9 @@
-// The rolled solve of one 16-drone tile: the body of solve_kernel<K, GS> (msnap_solve.hip, rest to rest) and of
-// states_solve_kernel<K> (msnap_states.hip, given end states).  lane = 4 drone + axis; the tile's inputs are staged in
+// The rolled solve of one 16-drone tile: the body of solve_kernel<K, GS> (msnap_solve.hip, rest to rest), of
+// states_solve_kernel<K> (msnap_states.hip, given end states) and of gates_solve_kernel<K> (msnap_gates.hip, prescribed
+// derivatives at interior knots as well).  lane = 4 drone + axis; the tile's inputs are staged in
 // LDS by the caller (GS: read from global memory here), the knot loops are rolled over Sweep<K>::step, X / G / Z are
 // stashed in LDS or on a global slab, and every segment leaves through recover_segment and the full-line stores.
-// The callers carve their own layouts -- they differ on purpose -- and pass the pointers; what the two solves do
+// The callers carve their own layouts -- they differ on purpose -- and pass the pointers; what the solves do
 // differently is one `if constexpr` each below.
 #pragma once
 
@@ -86,18 +87,29 @@ __device__ __forceinline__ void refine_end(double (&c)[2 * K], double tl, double
   }
 }
 
+// The gates of a batch (GATES; msnap_solve_gates), in global memory as the caller gave them:
+// fix[n_drones][M-1] the mask of interior knot i at [i-1] -- bit q-1: the q-th derivative is prescribed, on the
+// drone's four axes -- and via[n_drones][M-1][4][K-1] the values.  fix == nullptr (wave-uniform): no gates.
+struct RolledGates {
+  const int32_t *fix;
+  const double *via;
+};
+
 // GS: stash on a global slab, operands read from global memory, durations written here (nothing is staged).
 // ENDS: the end knots' derivative vectors u_0, u_M are data (has_start / has_end: wave-uniform, a missing one is rest).
-template <int K, bool GS, bool ENDS>
+// GATES (with ENDS): interior knots may carry prescribed derivatives; a knot's mask and values are fetched from global
+// memory one knot ahead, as tpre / wpre are from LDS, and the knot goes through Sweep<K>::step_masked.
+template <int K, bool GS, bool ENDS, bool GATES = false>
 __device__ __forceinline__ void rolled_solve_tile(const RolledTile &p, double2 *sTr, const double *__restrict__ wp,
                                                   const double *__restrict__ tt, int shared_times, bool has_start,
                                                   bool has_end, int M, int tile, int nvalid, int lane,
                                                   double *__restrict__ coef, double *__restrict__ dur,
-                                                  int32_t *__restrict__ status) {
+                                                  int32_t *__restrict__ status, RolledGates gates = {}) {
   using SW = Sweep<K>;
   using C = HermiteConsts<K>;
   constexpr int NU = SW::NU, NC = SW::NC, KK = SW::KK, PM = SW::PM, PITCH = NU | 1;
   static_assert(!(GS && ENDS), "the boundary-state solve has no slab variant");
+  static_assert(!GATES || ENDS, "gates ride on the boundary-state solve");
   const int dl = lane >> 2;
   const int a = lane & 3;
   const int wpitch = (M + 1) * 4;
@@ -115,6 +127,25 @@ __device__ __forceinline__ void rolled_solve_tile(const RolledTile &p, double2 *
   const double *lt = p.sTraw + (shared_times ? 0 : dloc * tpitch);
   auto Wv = [&](int i) -> double { if constexpr (GS) return wrow[(size_t)i * 4]; else return lw[i * 4]; };
   auto Tv = [&](int i) -> double { if constexpr (GS) return trow[i]; else return lt[i]; };
+
+  // GATES: the mask and the lane's NU values of the next knot (an unused value may be anything: it is only selected).
+  // Knot 1's are asked for here, ahead of everything: they come from global memory, the rest of the set-up from LDS.
+  [[maybe_unused]] const bool has_gates = GATES && gates.fix != nullptr && M >= 2;
+  [[maybe_unused]] const int32_t *frow = nullptr;
+  [[maybe_unused]] const double *grow = nullptr;
+  [[maybe_unused]] int mpre = 0;
+  [[maybe_unused]] double gpre[NU];
+  if constexpr (GATES) {
+#pragma unroll
+    for (int q = 0; q < NU; ++q) gpre[q] = 0.0;
+    if (has_gates) {
+      frow = gates.fix + (size_t)d * (size_t)(M - 1);
+      grow = gates.via + ((size_t)d * (size_t)(M - 1) * 4 + a) * NU;
+      mpre = frow[0];
+#pragma unroll
+      for (int q = 0; q < NU; ++q) gpre[q] = grow[q];
+    }
+  }
 
   // ---------------- start of the chain: the end knots' derivatives ----------------
   double u0[NU], uM[NU];
@@ -183,6 +214,24 @@ __device__ __forceinline__ void rolled_solve_tile(const RolledTile &p, double2 *
       tpre = Tv(ip);
       wpre = Wv(ip);
     }
+    [[maybe_unused]] unsigned mask = 0u;
+    [[maybe_unused]] double gv[NU];
+    if constexpr (GATES) {
+      const int mi = mpre;
+#pragma unroll
+      for (int q = 0; q < NU; ++q) gv[q] = gpre[q];
+      if (has_gates) {
+        const int kn = (i + 1 < M) ? i : M - 2;      // knot i+1 sits at [i]; the last knot is read twice
+        mpre = frow[kn];
+#pragma unroll
+        for (int q = 0; q < NU; ++q) gpre[q] = grow[(size_t)kn * (4 * NU) + q];
+      }
+      // a mask outside 0 .. 2^NU - 1, or a prescribed value that is not finite, fails the drone like any other input
+      nonfinite |= (mi < 0) | (mi >= (1 << NU));
+      mask = (unsigned)mi & ((1u << NU) - 1u);
+#pragma unroll
+      for (int q = 0; q < NU; ++q) nonfinite |= (bool)((mask >> q) & 1u) & !finite64(gv[q]);
+    }
     nonfinite |= !finite64(tnext) | !finite64(wnext);
     T = tnext - tcur;
     badtime |= !(T > 0.0);
@@ -192,7 +241,14 @@ __device__ __forceinline__ void rolled_solve_tile(const RolledTile &p, double2 *
     x = rcp64(T);
     sX[i * 16 + dl] = x;
     double G[NU][NU], z[NU];
-    sw.step(x, wnext - wcur, G, z);
+    if constexpr (GATES) {
+      // one wave-uniform test per knot: a knot no drone of the tile gates takes the plain step (the same bits as the
+      // masked one with empty masks, without its selects)
+      if (__builtin_amdgcn_ballot_w64(mask != 0u) != 0) sw.template step_masked<true>(x, wnext - wcur, mask, gv, G, z);
+      else sw.step(x, wnext - wcur, G, z);
+    } else {
+      sw.step(x, wnext - wcur, G, z);
+    }
     double *g = sG + (size_t)(i - 1) * (NU * NU * 16) + dl;
     double *zz = sZ + (size_t)(i - 1) * (NU * 64) + lane;
 #pragma unroll
@@ -284,5 +340,31 @@ __device__ __forceinline__ void rolled_solve_tile(const RolledTile &p, double2 *
     wn = wi;
   }
 }
+
+// LDS of one 16-drone tile of the boundary-state solves (states_solve_kernel, gates_solve_kernel), in doubles:
+//   Tr[NC/2][68][2] (order 9 only: the output transpose image) | Wraw[16][(M+1) 4] | Traw[16][M+1] |
+//   S0[64][pitch] | S1[64][pitch] (start and end state of every lane) |
+//   X[M][16] | G[M-1][NU NU][16] | Z[M-1][NU][64]
+// The state blocks keep a lane's NU values side by side at an odd pitch (3 at order 7, 5 at order 9): ds_read_b64
+// serves 32 lanes per cycle over 64 four-byte banks, and 2 pitch l mod 64 is one-to-one for l < 32 only if pitch is odd.
+template <int K>
+struct StatesLayout {
+  static constexpr int NU = K - 1, NC = 2 * K;
+  static constexpr int kPitch = NU | 1;
+  static constexpr size_t kTrWords = NC == 8 ? 0 : (size_t)(NC / 2) * kTrPitch * 2;
+  static constexpr size_t kStateWords = (size_t)kWave * kPitch;
+  static constexpr size_t words(int M) {
+    return kTrWords + (size_t)16 * (M + 1) * 5 + 2 * kStateWords + (size_t)16 * M +
+           (size_t)(M - 1) * (16 * NU * NU + 64 * NU);
+  }
+  static constexpr size_t bytes(int M) { return words(M) * sizeof(double); }
+  static constexpr int max_segments() {
+    int M = 1;
+    while (bytes(M + 1) <= kMaxLdsBytes) ++M;
+    return M;
+  }
+};
+static_assert(StatesLayout<4>::max_segments() == 47 && StatesLayout<5>::max_segments() == 32,
+              "DESIGN.md K13, K21 and include/msnap.h quote these");
 
 }  // namespace msnap

@@ -29,32 +29,7 @@
 namespace msnap {
 namespace {
 
-// LDS of one 16-drone tile, in doubles:
-//   Tr[NC/2][68][2] (order 9 only: the output transpose image) | Wraw[16][(M+1) 4] | Traw[16][M+1] |
-//   S0[64][pitch] | S1[64][pitch] (start and end state of every lane) |
-//   X[M][16] | G[M-1][NU NU][16] | Z[M-1][NU][64]
-// The state blocks keep a lane's NU values side by side at an odd pitch (3 at order 7, 5 at order 9): ds_read_b64
-// serves 32 lanes per cycle over 64 four-byte banks, and 2 pitch l mod 64 is one-to-one for l < 32 only if pitch is odd.
-template <int K>
-struct StatesLayout {
-  static constexpr int NU = K - 1, NC = 2 * K;
-  static constexpr int kPitch = NU | 1;
-  static constexpr size_t kTrWords = NC == 8 ? 0 : (size_t)(NC / 2) * kTrPitch * 2;
-  static constexpr size_t kStateWords = (size_t)kWave * kPitch;
-  static constexpr size_t words(int M) {
-    return kTrWords + (size_t)16 * (M + 1) * 5 + 2 * kStateWords + (size_t)16 * M +
-           (size_t)(M - 1) * (16 * NU * NU + 64 * NU);
-  }
-  static constexpr size_t bytes(int M) { return words(M) * sizeof(double); }
-  static constexpr int max_segments() {
-    int M = 1;
-    while (bytes(M + 1) <= kMaxLdsBytes) ++M;
-    return M;
-  }
-};
-static_assert(StatesLayout<4>::max_segments() == 47 && StatesLayout<5>::max_segments() == 32,
-              "DESIGN.md K13 and include/msnap.h quote these");
-
+// (StatesLayout<K>, the LDS of one 16-drone tile, is in msnap_rolled.h: gates_solve_kernel<K> carves the same)
 template <int K>
 __global__ void __launch_bounds__(kWave)
 states_solve_kernel(const double *__restrict__ wp, const double *__restrict__ tt, int shared_times,

@@ -184,12 +184,44 @@ struct Sweep {
   // the recurrence proper: S_i = D_i - O_{i-1}^T G_{i-1}, LDL^T, G_i = S_i^-1 O_i, z_i = S_i^-1 y_i,
   // and the Schur terms carried to knot i+1.  Returns false if a pivot is not positive and finite.
   __device__ __forceinline__ bool chain(const Knot &k, double (&G)[NU][NU], double (&z)[NU]) {
+    return chain_masked<false>(k, 0u, nullptr, G, z);
+  }
+
+  // The same with some components of u_i prescribed (GATED): bit c of `mask` fixes u_i[c] = g[c].
+  // The known column goes to the right-hand side of the free rows, row and column c of S become those of the identity
+  // and y[c] = g[c], and the G solves take O_i with row c zeroed -- so z[c] = g[c] and row c of G is zero exactly.  The
+  // carry keeps the whole O_i: knot i+1's equations hold O_i^T u_i in full.  Masked terms are selected, never multiplied
+  // in: an empty mask leaves every operation of chain() as it is, and g[c] under a clear bit is not used.
+  template <bool GATED>
+  __device__ __forceinline__ bool chain_masked(const Knot &k, unsigned mask, const double *g, double (&G)[NU][NU],
+                                               double (&z)[NU]) {
     double S[NS], y[NU];
 #pragma unroll
     for (int n = 0; n < NU; ++n) {
 #pragma unroll
       for (int m = 0; m <= n; ++m) S[sidx(n, m)] = k.D[sidx(n, m)] - OtG[sidx(n, m)];
       y[n] = -k.yb[n] - Otz[n];
+    }
+    if constexpr (GATED) {
+#pragma unroll
+      for (int c = 0; c < NU; ++c) {
+        const bool fc = (mask >> c) & 1u;
+#pragma unroll
+        for (int r = 0; r < NU; ++r) {
+          if (r == c) continue;
+          const bool fr = (mask >> r) & 1u;
+          const double s = S[r > c ? sidx(r, c) : sidx(c, r)];
+          y[r] = (fc & !fr) ? __builtin_fma(-s, g[c], y[r]) : y[r];
+        }
+      }
+#pragma unroll
+      for (int n = 0; n < NU; ++n) {
+        const bool fn = (mask >> n) & 1u;
+#pragma unroll
+        for (int m = 0; m < n; ++m) S[sidx(n, m)] = (fn | (bool)((mask >> m) & 1u)) ? 0.0 : S[sidx(n, m)];
+        S[sidx(n, n)] = fn ? 1.0 : S[sidx(n, n)];
+        y[n] = fn ? g[n] : y[n];
+      }
     }
 
     double dinv[NU];
@@ -201,6 +233,12 @@ struct Sweep {
       double v[NU];
 #pragma unroll
       for (int r = 0; r < NU; ++r) v[r] = (c < NU) ? k.O[r][c < NU ? c : 0] : y[r];
+      if constexpr (GATED) {
+        if (c < NU) {
+#pragma unroll
+          for (int r = 0; r < NU; ++r) v[r] = ((mask >> r) & 1u) ? 0.0 : v[r];
+        }
+      }
       ldl_solve(S, dinv, v);
 #pragma unroll
       for (int r = 0; r < NU; ++r) {
@@ -229,9 +267,14 @@ struct Sweep {
 
   // knot i with segment i (x = 1/T_i, dw = w_{i+1} - w_i) on its right: geometry, then recurrence
   __device__ __forceinline__ void step(double x, double dw, double (&G)[NU][NU], double (&z)[NU]) {
+    step_masked<false>(x, dw, 0u, nullptr, G, z);
+  }
+  template <bool GATED>
+  __device__ __forceinline__ void step_masked(double x, double dw, unsigned mask, const double *g, double (&G)[NU][NU],
+                                              double (&z)[NU]) {
     Knot k;
     knot_geom(x, dw, E, re, k);
-    singular |= !chain(k, G, z);
+    singular |= !chain_masked<GATED>(k, mask, g, G, z);
 #pragma unroll
     for (int e = 0; e < NS; ++e) E[e] = k.E[e];
 #pragma unroll

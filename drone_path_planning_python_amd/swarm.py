@@ -377,6 +377,31 @@ class DeviceCompute:
                                          status)
         return coef, dur, status
 
+    def solve_gates(self, wp, t, start=None, end=None, fix=None, via=None):
+        """(coef, dur, status) of solve_states with prescribed derivatives at interior waypoints: `fix` [n, M-1] int32
+        -- bit q-1 of entry i-1: the q-th derivative at waypoint i is prescribed, on all four axes -- and `via`
+        [n, M-1, 4, K-1] float64 the values (entries under a clear bit are not used).  fix None: no gates."""
+        torch = self.torch
+        n, m, _ = wp.shape
+        M = m - 1
+        start, end = self._end_states("solve_gates", n, start, end)
+        if fix is not None:
+            if tuple(fix.shape) != (n, max(M - 1, 0)) or fix.dtype != torch.int32:
+                raise ValueError("solve_gates: fix must be an int32 tensor [n, M-1]")
+            if via is None:
+                raise ValueError("solve_gates: fix needs via")
+            fix = fix.contiguous()
+        if via is not None:
+            nd = self.ctx.ncoef // 2 - 1
+            if tuple(via.shape) != (n, max(M - 1, 0), 4, nd) or via.dtype != torch.float64:
+                raise ValueError(f"solve_gates: via must be a float64 tensor [n, M-1, 4, {nd}]")
+            via = via.contiguous()
+        coef, dur, status = self._solve_outs("solve_gates", n, M)
+        if n:
+            self.ctx.solve_gates_device(n, M, wp.contiguous(), t.contiguous(), t.dim() == 1, start, end, fix, via, coef,
+                                        dur, status)
+        return coef, dur, status
+
     def solve_periodic(self, wp, t):
         """(coef, dur, status) of the closed-loop solve: the last waypoint is joined to the first, the period is t[-1],
         wp[:, -1] - wp[:, 0] the lap offset; t[0] must be 0."""
@@ -1124,7 +1149,7 @@ def certify_geofence(compute, coef, dur, lo=None, hi=None, planes=None, radius: 
                           upper, box_lo, box_hi)
 
 
-def replan(compute, coef, dur, t_r, wp_new, t_new, end=None, optimize=None):
+def replan(compute, coef, dur, t_r, wp_new, t_new, end=None, optimize=None, gates=None):
     """Replan a flying swarm: leave the paths `coef`, `dur` at time `t_r` and fly through new waypoints.
 
     `t_r` is a number or a tensor [N] (per drone, on the current paths' clock); `wp_new` [N, M', 4] are the waypoints
@@ -1139,9 +1164,18 @@ def replan(compute, coef, dur, t_r, wp_new, t_new, end=None, optimize=None):
     `compute.optimize_times_states` move the interior times first (the state at `t_r`, the waypoints, `end` and the
     last time are kept); the knots it chose are the running sum of the returned `dur`.  With "time_weight" in the dict
     (a number or a tensor [N], > 0) `compute.optimize_times_free` moves every time, the last one too: `t_new[-1]` is
-    then a starting guess, and a larger weight buys a shorter path at a higher cost."""
+    then a starting guess, and a larger weight buys a shorter path at a higher cost.
+
+    `gates`: (fix, via) as `compute.solve_gates` takes them -- fix [N, M' - 1] int32, via [N, M' - 1, 4, K-1], entry
+    i-1 for `wp_new[:, i-1]`, the new path's interior waypoint i; the last new waypoint takes `end`.  Time allocation
+    with gates is not built: `gates` together with `optimize` raises ValueError."""
+    if gates is not None and optimize is not None:
+        raise ValueError("replan: gates and optimize do not combine (time allocation with gates is not built)")
     wp, t, pos, deriv = _replan_inputs(compute, coef, dur, t_r, wp_new, t_new)
-    if optimize is None:
+    if gates is not None:
+        fix, via = gates
+        new_coef, new_dur, status = compute.solve_gates(wp, t, start=deriv, end=end, fix=fix, via=via)
+    elif optimize is None:
         new_coef, new_dur, status = compute.solve_states(wp, t, start=deriv, end=end)
     else:
         unknown = set(optimize) - {"weights", "min_fraction", "max_iter", "tol", "time_weight"}

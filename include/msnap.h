@@ -770,6 +770,43 @@ int msnap_eval_state(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef
 int msnap_eval_state_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,
                             const double *tq, double *pos, double *deriv);
 
+/* ---- gates: prescribed derivatives at interior waypoints (new capability) ----
+ * Every other solve treats an interior waypoint as a position only; its velocity, acceleration and jerk (snap too at
+ * order 9) are what the minimisation picks.  msnap_solve_gates is msnap_solve_states with any of those prescribed at any
+ * interior waypoint: "pass this gate at 3 m/s along its axis", "stop at waypoint 4, then go on", "hold zero
+ * acceleration where the payload is released".  wp, t, shared_times, start, end, coef, dur, status as for
+ * msnap_solve_states.  With K = (order + 1) / 2:
+ *   fix [n_drones][n_seg-1]           int32; entry i-1 is the mask of interior waypoint i (1 .. n_seg-1): bit q-1 set
+ *                                     means its q-th time derivative is prescribed, on all four axes of the drone.
+ *   via [n_drones][n_seg-1][4][K-1]   the values, per waypoint in the layout of start / end: entry [a][q-1] is the q-th
+ *                                     derivative of axis a.  An entry under a clear bit is never used and may be NaN.
+ * fix == NULL: no gates -- coef, dur and status are msnap_solve_states' bit for bit, and via may be NULL too; so are
+ * they with a mask of zeros.  The result minimises the same cost over the paths that interpolate the waypoints, have
+ * the given end states and the prescribed derivatives: derivatives 1 .. K-1 stay continuous at every waypoint, and
+ * at a gated one the continuity of derivative 2K-1-q is given up for each prescribed q.  On the segment that leaves a
+ * gated waypoint coef[i][a][q] * q! is the prescribed value within 4 * 2^-52 relative; on the segment that arrives it
+ * is met as every interior waypoint's continuity is met (DESIGN.md K21 has the figures).  A waypoint with every bit
+ * set decouples the two sides: the path is the two msnap_solve_states solutions of its halves, to rounding.
+ *   status   as msnap_solve_states, and MSNAP_ST_NONFINITE for a NaN / Inf via entry under a set bit or a fix entry that
+ *            is negative or >= 2^(K-1).  A failed drone gets NaN coefficients; dur is written for every drone.
+ *   n_seg    1 .. msnap_solve_gates_max_segments(order) -- 47 at order 7, 32 at order 9, msnap_solve_states' range: the
+ *            gates take no LDS -- and at most max_segments; MSNAP_ESEGMENTS above, and nothing is written.
+ *            msnap_solve_gates_max_segments returns MSNAP_EORDER for any other order.
+ * MSNAP_EINVAL: as msnap_solve_states, and fix given without via.  n_drones == 0 is a no-op.  A drone's outputs are
+ * bit-identical whatever its place in the batch, the batch size, and host versus device entry.  The device version
+ * only launches.  Masks are per drone, not per axis, and the end states are always whole; the time-allocation and
+ * periodic solves take no gates.
+ */
+int msnap_solve_gates(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, const double *t, int shared_times,
+                      const double *start, const double *end,          /* as msnap_solve_states */
+                      const int32_t *fix /* [n_drones][n_seg-1] or NULL */,
+                      const double *via /* [n_drones][n_seg-1][4][K-1] or NULL */,
+                      double *coef, double *dur, int32_t *status);
+int msnap_solve_gates_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, const double *t,
+                             int shared_times, const double *start, const double *end, const int32_t *fix,
+                             const double *via, double *coef, double *dur, int32_t *status);
+int msnap_solve_gates_max_segments(int order);      /* largest n_seg the entry takes; < 0: MSNAP_EORDER */
+
 /* ---- closed-loop paths: the periodic solve (new capability) ----
  * Every other solve ends at rest or in a state the caller supplies; msnap_solve_periodic joins the last waypoint to the
  * first, for holding patterns and repeating figures.  wp, t, shared_times, coef, dur, status as for msnap_solve_states.
