@@ -881,9 +881,7 @@ static int limits_args(const msnap_ctx *ctx, int n_drones, int n_seg, std::initi
   if (int rc = check_limits_args(ctx, n_drones, n_seg)) return rc;
   if (limits_rc) return limits_rc;
   if (n_drones == 0) return kNoWork;
-  for (const void *p : ptrs)
-    if (!p) return MSNAP_EINVAL;
-  return MSNAP_OK;
+  return all_required(ptrs);
 }
 
 int msnap_dynamic_peaks_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,

@@ -3,6 +3,8 @@
 // macro and the one staging helper every host-pointer call goes through.
 #pragma once
 
+#include <math.h>
+
 #include <initializer_list>
 
 #include "msnap_internal.h"
@@ -76,14 +78,24 @@ inline size_t coef_bytes(const msnap_ctx *ctx, int n_drones, int n_seg) {
 }
 inline size_t dur_bytes(int n_drones, int n_seg) { return (size_t)n_drones * n_seg * 8; }
 
+// every pointer of the list is required: the last step of an argument check
+inline int all_required(std::initializer_list<const void *> ptrs) {
+  for (const void *p : ptrs)
+    if (!p) return MSNAP_EINVAL;
+  return MSNAP_OK;
+}
+
 // a batch of n_drones paths of n_seg segments whose every pointer is required
 inline int batch_args(const msnap_ctx *ctx, int n_drones, int n_seg, std::initializer_list<const void *> ptrs) {
   if (!ctx || n_drones < 0) return MSNAP_EINVAL;
   if (int rc = check_seg(ctx, n_seg)) return rc;
   if (n_drones == 0) return kNoWork;
-  for (const void *p : ptrs)
-    if (!p) return MSNAP_EINVAL;
-  return MSNAP_OK;
+  return all_required(ptrs);
+}
+
+// the numbers of a window call (msnap_window.h): a time resolution > 0 and, where there is one, a threshold >= 0
+inline bool window_levels_valid(double t_res, double threshold = 0.0) {
+  return isfinite(threshold) && threshold >= 0.0 && isfinite(t_res) && t_res > 0.0;
 }
 
 }  // namespace msnap

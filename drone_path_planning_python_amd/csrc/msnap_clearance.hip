@@ -178,9 +178,7 @@ static int clearance_args(const msnap_ctx *ctx, int n_a, int n_seg_a, int n_b, i
                           std::initializer_list<const void *> ptrs) {
   if (int rc = check_clearance_args(ctx, n_a, n_seg_a, n_b, n_seg_b, n_pairs)) return rc;
   if (n_pairs == 0) return kNoWork;
-  for (const void *p : ptrs)
-    if (!p) return MSNAP_EINVAL;
-  return MSNAP_OK;
+  return all_required(ptrs);
 }
 
 int msnap_pair_clearance_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,

@@ -4,60 +4,29 @@
 // shifted clocks).  The window [S, W], the knots, the slots, the tie order and the live / dead rules are K9's: the lane
 // set-up is msnap_pair_interval.h's lane_interval, the one text both lane kernels call.
 //
-// Lane.  g(u) = sum of the squares of the three difference polynomials on the lane's interval, L = threshold^2.  The
-// forward walk visits the dyadic nodes [a, a + hh] of u in [0, 1] left to right (msnap_walk.h, WalkNode::advance):
-//   1. shift_scale; the smallest Bernstein coefficient of g on the node (squares_bound<true>); g at 0, 1/2, 1;
-//   2. bound >= L: the node is proven clear -- on to the next sibling;
-//   3. else g(0) < L: the conflict begins at a (every earlier node was proven clear or noted as undecided): the walk ends;
-//   4. else h hh <= t_res or lvl == kMaxDepth: a leaf.  g(1/2) < L or g(1) < L: the earlier of the two is the first
-//      conflict found, the walk ends.  Otherwise the leaf is undecided: its a is kept if it is the earliest, and on;
-//   5. else split.
-// The node guard kMaxNodes ends the walk with everything from the current a on undecided.  A lane carries two numbers
-// per direction: the time of the conflict it found (none: +inf) and the time up to which it proved the pair clear -- the
-// smaller of the first undecided a and the a of the node that held the conflict (none of either: +inf).
-// The backward walk is the same body on e_s(1 - u) (a Taylor shift by 1, then the odd coefficients negated); its times
-// map back as E - h u, and its two numbers are the latest conflict found (none: -inf) and the time from which the pair
-// is proven clear (none: -inf).  There is no prune slack here: a node is clear when its fp64 bound says so, and the
-// header's allowance r covers the rounding of that bound.
+// Lane.  g(u) = sum of the squares of the three difference polynomials on the lane's interval, L = threshold^2, for
+// the bound and for the attained values.  The walk in both directions, the node rule and the lane's four numbers are
+// msnap_window.h's (first_crossing, window_lane_tail); the node step here: shift_scale, the smallest Bernstein
+// coefficient of g on the node (squares_bound<true>), g at 0, 1/2, 1.
 // A lane cannot know that an earlier slot already holds the first conflict: later slots are walked in full.
 //
-// Fold.  One thread per pair over its slots: the earliest and the latest conflict found in either direction (so that
-// t_first <= t_last whatever the rounding of the two walks), the earliest clear-until and the latest clear-from, clamped
-// to them; then the distances at t_first and t_last in the t domain (pair_distance_at: msnap_eval_flat reproduces them).
-// Status, W < S and W == S as pair_fold_kernel.  Nothing crosses lanes but the trip count.
+// Fold.  One thread per pair over its slots (msnap_window.h, fold_window); then the distances at t_first and t_last in
+// the t domain (pair_distance_at: msnap_eval_flat reproduces them).  Status, W < S and W == S as pair_fold_kernel.
+// Nothing crosses lanes but the trip count.
 #include <math.h>
 
 #include "msnap_api_util.h"
 #include "msnap_pair_interval.h"
-#include "msnap_walk.h"
 #include "msnap_wave.h"
+#include "msnap_window.h"
 
 namespace msnap {
 namespace {
 
 constexpr int kThreads = kClearanceThreads;
-constexpr int kLaneDoubles = 4;      // per lane: conflict found forward, clear until, conflict found backward, clear from
-
 // ctx->clearance_work: per-lane results [lanes][4] doubles, then the flags as msnap_clearance.hip lays them out
 inline size_t conflict_work_bytes(size_t lanes, size_t segs) {
-  return lanes * kLaneDoubles * sizeof(double) + segs * sizeof(int32_t);
-}
-
-// The walk for the first crossing of the level L from u = 0 on (msnap_walk.h, first_crossing: the walk K20 shares) on
-// g = the sum of the squares of the three difference polynomials e.  hit: the u of the conflict found (+inf: none);
-// clear: the u up to which g >= L is proven (+inf: the whole lane).  Every lane of the wave calls it.
-template <int D>
-__device__ __forceinline__ void first_crossing(const double (&e)[3][D + 1], bool ok, double h, double L, double t_res,
-                                               double &hit, double &clear) {
-  first_crossing(
-      [&](double a, double hh, double &bound, double (&g)[3]) {
-        double f[3][D + 1];
-#pragma unroll
-        for (int s = 0; s < 3; ++s) shift_scale<D>(e[s], a, hh, f[s]);
-        bound = squares_bound<true, D>(f);
-        squares_at_ends_and_middle<D>(f, g);
-      },
-      ok, h, L, t_res, hit, clear);
+  return lanes * kWindowLaneDoubles * sizeof(double) + segs * sizeof(int32_t);
 }
 
 // one lane per (pair, slot): work[4 item ..] = the four times of the head, on the common clock
@@ -67,40 +36,26 @@ conflict_lane_kernel(const PathSet A, const PathSet B_, int n_pairs, const int32
                      double t_res, double *__restrict__ work) {
   constexpr int D = NC - 1;
   const PathSet &B = CROSS ? B_ : A;
-  const double inf = __builtin_inf();
   const size_t item = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const bool in_range = item < (size_t)n_pairs * (size_t)(A.m + B.m - 1);
   double e[3][D + 1];
   const LaneInterval iv = lane_interval<NC, CROSS>(A, B, n_pairs, pairs, item, e);
 
-  double out[kLaneDoubles];
-#pragma unroll 1
-  for (int dir = 0; dir < 2; ++dir) {
-    if (dir == 1) {
-      // e_s(1 - u): the Taylor shift by 1, then the odd coefficients negated
+  // the node step: g = the sum of the squares of the three difference polynomials, its smallest Bernstein coefficient
+  const auto values = [&](double a, double hh, bool, double &bound, double (&g)[3]) {
+    double f[3][D + 1];
 #pragma unroll
-      for (int s = 0; s < 3; ++s) {
-#pragma unroll
-        for (int kk = 0; kk < D; ++kk)
-#pragma unroll
-          for (int j = D - 1; j >= kk; --j) e[s][j] = e[s][j + 1] + e[s][j];
-#pragma unroll
-        for (int j = 1; j <= D; j += 2) e[s][j] = -e[s][j];
-      }
-    }
-    double hit, clear;
-    first_crossing<D>(e, iv.ok, iv.h, L, t_res, hit, clear);
-    // u -> the common clock: start + h u forward, E - h u backward, kept inside the lane's interval
-    const double th = dir == 0 ? fmin(fma(iv.h, hit, iv.start), iv.E) : fmax(fma(-iv.h, hit, iv.E), iv.start);
-    const double tc = dir == 0 ? fmin(fma(iv.h, clear, iv.start), iv.E) : fmax(fma(-iv.h, clear, iv.E), iv.start);
-    const double none = dir == 0 ? inf : -inf;
-    out[2 * dir] = (iv.ok && hit < inf) ? th : none;
-    out[2 * dir + 1] = (iv.ok && clear < inf) ? tc : none;
-  }
+    for (int s = 0; s < 3; ++s) shift_scale<D>(e[s], a, hh, f[s]);
+    bound = squares_bound<true, D>(f);
+    squares_at_ends_and_middle<D>(f, g);
+  };
+  const auto walk = [&](double &hit, double &clear) { first_crossing(values, iv.ok, iv.h, L, L, t_res, hit, clear); };
+  double out[kWindowLaneDoubles];
+  window_lane_tail(e, iv.ok, iv.h, iv.start, iv.E, walk, out);
 
   if (!in_range) return;
 #pragma unroll
-  for (int q = 0; q < kLaneDoubles; ++q) work[kLaneDoubles * item + q] = out[q];
+  for (int q = 0; q < kWindowLaneDoubles; ++q) work[kWindowLaneDoubles * item + q] = out[q];
 }
 
 // one thread per pair: status, the window, the fold of the slots, the distances in the t domain
@@ -128,19 +83,7 @@ conflict_fold_kernel(const PathSet A, const PathSet B_, const double *__restrict
       cu = tf = tl = cf = S;
     } else if (!(Wend < S)) {
       const int slots = A.m + B.m - 1;
-      const double *w = work + (size_t)p * slots * kLaneDoubles;
-      for (int k = 0; k < slots; ++k) {
-        tf = fmin(tf, w[kLaneDoubles * k]);
-        cu = fmin(cu, w[kLaneDoubles * k + 1]);
-        tl = fmax(tl, w[kLaneDoubles * k + 2]);
-        cf = fmax(cf, w[kLaneDoubles * k + 3]);
-      }
-      // one set of conflict times for both directions: a time found by either walk counts for both ends
-      const double lo = fmin(tf, tl > -inf ? tl : inf), hi = fmax(tl, tf < inf ? tf : -inf);
-      tf = lo;
-      tl = hi;
-      cu = fmin(cu, tf);
-      cf = fmax(cf, tl);
+      fold_window(work + (size_t)p * slots * kWindowLaneDoubles, slots, cu, tf, tl, cf);
     }
     df = dl = inf;
     if (tf < inf) {
@@ -175,7 +118,7 @@ int launch(msnap_ctx *ctx, PathSet A, PathSet B, int n_pairs, const int32_t *pai
            void *scratch, const Outputs &o) {
   const size_t lanes = clearance_lanes(n_pairs, A.m, B.m), segs_a = (size_t)A.n * A.m;
   double *work = (double *)scratch;
-  int32_t *flags[2] = {(int32_t *)(work + kLaneDoubles * lanes), nullptr};
+  int32_t *flags[2] = {(int32_t *)(work + kWindowLaneDoubles * lanes), nullptr};
   flags[1] = CROSS ? flags[0] + segs_a : flags[0];
   PathSet *sets[2] = {&A, &B};
   for (int s = 0; s < (CROSS ? 2 : 1); ++s) {
@@ -221,11 +164,9 @@ extern "C" {
 static int conflict_args(const msnap_ctx *ctx, int n_a, int n_seg_a, int n_b, int n_seg_b, int n_pairs,
                          double threshold, double t_res, std::initializer_list<const void *> ptrs) {
   if (int rc = check_clearance_args(ctx, n_a, n_seg_a, n_b, n_seg_b, n_pairs)) return rc;
-  if (!(isfinite(threshold) && threshold >= 0.0) || !(isfinite(t_res) && t_res > 0.0)) return MSNAP_EINVAL;
+  if (!window_levels_valid(t_res, threshold)) return MSNAP_EINVAL;
   if (n_pairs == 0) return kNoWork;
-  for (const void *p : ptrs)
-    if (!p) return MSNAP_EINVAL;
-  return MSNAP_OK;
+  return all_required(ptrs);
 }
 
 int msnap_pair_conflict_window_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,

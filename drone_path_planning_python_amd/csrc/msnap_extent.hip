@@ -199,9 +199,7 @@ static int path_extent_args(const msnap_ctx *ctx, int n_drones, int n_seg, int n
   if (int rc = check_seg(ctx, n_seg)) return rc;
   if (int rc = check_extent_grid(n_drones, n_seg, n_dirs)) return rc;
   if (n_drones == 0 || n_dirs == 0) return kNoWork;
-  for (const void *p : ptrs)
-    if (!p) return MSNAP_EINVAL;
-  return MSNAP_OK;
+  return all_required(ptrs);
 }
 
 int msnap_path_extent_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,

@@ -102,8 +102,7 @@ int solve_gates_args(const msnap_ctx *ctx, int n_drones, int n_seg, const void *
   if (int rc = check_seg(ctx, n_seg)) return rc;
   if (n_seg > gates_max_segments(ctx->khalf)) return MSNAP_ESEGMENTS;
   if (n_drones == 0) return kNoWork;
-  for (const void *p : ptrs)
-    if (!p) return MSNAP_EINVAL;
+  if (int rc = all_required(ptrs)) return rc;
   if (fix && !via) return MSNAP_EINVAL;
   return MSNAP_OK;
 }

@@ -5,34 +5,31 @@
 // Lane.  One per (query, segment), a query being a (drone, plane) with a range [S, W] of its own.  The lane's interval
 // is the part of its segment inside the range, [max(S, start_k), min(W, E_k)], of length h; m = -(n.p) on it in
 // u in [0, 1]: K12's fused dot product of the segment's coefficients, the Taylor shift to the interval's start, the
-// scaling by h^j (msnap_pair_interval.h's slots are rescaled the same way).  The walk is first_crossing (msnap_walk.h,
-// the one text K18 walks with) against the level L = -b, which never enters the coefficients: a node whose smallest
-// Bernstein coefficient of m is >= L is proven inside, a node with m(0) < L starts outside and ends the walk, a node
-// shorter than t_res or at depth kMaxDepth is a leaf.  The backward walk is the same body on m(1 - u).  A lane carries
-// two numbers per direction, as K18's.  A lane that has nothing to walk -- an index out of range, a failed drone, a
-// plane that is not finite, a segment outside the range -- carries the zero polynomial and keeps the loop's shape.
+// scaling by h^j (msnap_pair_interval.h's slots are rescaled the same way).  The walk in both directions, the node rule
+// and the lane's four numbers are msnap_window.h's (first_crossing, window_lane_tail), with "outside" for its conflict
+// and "inside" for its clear, against the level L = -b, which never enters the coefficients; the node step here: m at
+// the node's start, middle and end and its smallest Bernstein coefficient.  A lane that has nothing to walk -- an index
+// out of range, a failed drone, a plane that is not finite, a segment outside the range -- carries the zero polynomial
+// and keeps the loop's shape.
 // A lane cannot know that an earlier segment already holds the first exit: later segments are walked in full.
 //
-// Fold.  One thread per query over its segments: the earliest and the latest time found outside in either direction
-// (so that t_first <= t_last whatever the rounding of the two walks), the earliest inside-until and the latest
-// inside-from, clamped to them; then n.p at t_first and t_last in the t domain -- msnap_eval_flat's lookup and Horner,
-// then (n_x x + n_y y) + n_z z with every operation rounded once, as K12's fold forms ext.  Status, W < S and W == S as
-// conflict_fold_kernel.  Nothing crosses lanes but the trip count.
+// Fold.  One thread per query over its segments (msnap_window.h, fold_window); then n.p at t_first and t_last in the t
+// domain -- msnap_eval_flat's lookup and Horner, then (n_x x + n_y y) + n_z z with every operation rounded once, as
+// K12's fold forms ext.  Status, W < S and W == S as conflict_fold_kernel.  Nothing crosses lanes but the trip count.
 #include <math.h>
 
 #include "msnap_api_util.h"
-#include "msnap_walk.h"
+#include "msnap_window.h"
 
 namespace msnap {
 namespace {
 
 constexpr int kThreads = kClearanceThreads;
-constexpr int kLaneDoubles = 4;      // per lane: outside found forward, inside until, outside found backward, inside from
 
 inline size_t halfspace_lanes(int n_queries, int M) { return (size_t)n_queries * (size_t)M; }
-// ctx->extent_work: per-lane results [lanes][4] doubles, then the flags [N M] int32
+// ctx->extent_work: per-lane results [lanes][4] doubles (a conflict: outside; clear: inside), then the flags [N M] int32
 inline size_t halfspace_work_bytes(size_t lanes, size_t segs) {
-  return lanes * kLaneDoubles * sizeof(double) + segs * sizeof(int32_t);
+  return lanes * kWindowLaneDoubles * sizeof(double) + segs * sizeof(int32_t);
 }
 
 // what a call reads: the batch, the planes [K][4] = (n, b), the queries [Q][2] = (drone, plane), the ranges ([Q] each,
@@ -54,7 +51,6 @@ template <int NC>
 __global__ void __launch_bounds__(kThreads)
 halfspace_lane_kernel(const HalfspaceCall c, double t_res, double *__restrict__ work) {
   constexpr int D = NC - 1;       // degree of the positions
-  const double inf = __builtin_inf();
   const int M = c.M;
   const size_t item = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const bool in_range = item < (size_t)c.Q * (size_t)M;
@@ -85,67 +81,49 @@ halfspace_lane_kernel(const HalfspaceCall c, double t_res, double *__restrict__ 
   const double lo = fmax(S, start), hi = fmin(Wend, E), h = hi - lo;
   const bool ok = valid && h > 0.0;
 
-  // e[j]: m = -n.p on the interval, in u (zero polynomial: the lane walks nothing but keeps the loop's shape)
-  double e[D + 1];
+  // m = -n.p on the interval, in u (zero polynomial: the lane walks nothing but keeps the loop's shape)
+  double e[1][D + 1];
   {
+    double(&m)[D + 1] = e[0];
     const double *cf = c.coef + (d * M + (size_t)k) * 4 * NC;
     const double la = lo - start;
 #pragma unroll
-    for (int j = 0; j <= D; ++j) e[j] = ok ? fma(nz, cf[2 * NC + j], fma(ny, cf[NC + j], nx * cf[j])) : 0.0;
+    for (int j = 0; j <= D; ++j) m[j] = ok ? fma(nz, cf[2 * NC + j], fma(ny, cf[NC + j], nx * cf[j])) : 0.0;
 #pragma unroll
     for (int kk = 0; kk < D; ++kk)
 #pragma unroll
-      for (int j = D - 1; j >= kk; --j) e[j] = fma(la, e[j + 1], e[j]);
+      for (int j = D - 1; j >= kk; --j) m[j] = fma(la, m[j + 1], m[j]);
     double hp = 1.0;
 #pragma unroll
     for (int j = 0; j <= D; ++j) {
-      e[j] = ok ? -(e[j] * hp) : 0.0;
+      m[j] = ok ? -(m[j] * hp) : 0.0;
       hp *= h;
     }
   }
   const double L = -b;
 
-  double out[kLaneDoubles];
-#pragma unroll 1
-  for (int dir = 0; dir < 2; ++dir) {
-    if (dir == 1) {
-      // m(1 - u): the Taylor shift by 1, then the odd coefficients negated
+  // the node step: m at the node's start, middle and end, and its smallest Bernstein coefficient on the node
+  const auto values = [&](double a, double hh, bool, double &bound, double (&g)[3]) {
+    constexpr BernsteinWeights<D> Wb{};
+    double f[D + 1];
+    shift_scale<D>(e[0], a, hh, f);
+    values_at_ends_and_middle<D>(f, g);
+    bound = f[0];
 #pragma unroll
-      for (int kk = 0; kk < D; ++kk)
+    for (int i = 1; i <= D; ++i) {
+      double v = 0.0;
 #pragma unroll
-        for (int j = D - 1; j >= kk; --j) e[j] = e[j + 1] + e[j];
-#pragma unroll
-      for (int j = 1; j <= D; j += 2) e[j] = -e[j];
+      for (int j = 0; j <= i; ++j) v = fma(Wb.w[i][j], f[j], v);
+      bound = fmin(bound, v);
     }
-    double hit, clear;
-    first_crossing(
-        [&](double a, double hh, double &bound, double (&g)[3]) {
-          constexpr BernsteinWeights<D> Wb{};
-          double f[D + 1];
-          shift_scale<D>(e, a, hh, f);
-          values_at_ends_and_middle<D>(f, g);
-          // the smallest Bernstein coefficient of m on the node
-          bound = f[0];
-#pragma unroll
-          for (int i = 1; i <= D; ++i) {
-            double v = 0.0;
-#pragma unroll
-            for (int j = 0; j <= i; ++j) v = fma(Wb.w[i][j], f[j], v);
-            bound = fmin(bound, v);
-          }
-        },
-        ok, h, L, t_res, hit, clear);
-    // u -> absolute time: lo + h u forward, hi - h u backward, kept inside the lane's interval
-    const double th = dir == 0 ? fmin(fma(h, hit, lo), hi) : fmax(fma(-h, hit, hi), lo);
-    const double tc = dir == 0 ? fmin(fma(h, clear, lo), hi) : fmax(fma(-h, clear, hi), lo);
-    const double none = dir == 0 ? inf : -inf;
-    out[2 * dir] = (ok && hit < inf) ? th : none;
-    out[2 * dir + 1] = (ok && clear < inf) ? tc : none;
-  }
+  };
+  const auto walk = [&](double &hit, double &clear) { first_crossing(values, ok, h, L, L, t_res, hit, clear); };
+  double out[kWindowLaneDoubles];
+  window_lane_tail(e, ok, h, lo, hi, walk, out);
 
   if (!in_range) return;
 #pragma unroll
-  for (int j = 0; j < kLaneDoubles; ++j) work[kLaneDoubles * item + j] = out[j];
+  for (int j = 0; j < kWindowLaneDoubles; ++j) work[kWindowLaneDoubles * item + j] = out[j];
 }
 
 struct Outputs {
@@ -186,19 +164,7 @@ halfspace_fold_kernel(const HalfspaceCall c, const double *__restrict__ work, co
       if (instant) {
         iu = tf = tl = ifr = S;
       } else if (!(Wend < S)) {
-        const double *w = work + q * (size_t)M * kLaneDoubles;
-        for (int k = 0; k < M; ++k) {
-          tf = fmin(tf, w[kLaneDoubles * k]);
-          iu = fmin(iu, w[kLaneDoubles * k + 1]);
-          tl = fmax(tl, w[kLaneDoubles * k + 2]);
-          ifr = fmax(ifr, w[kLaneDoubles * k + 3]);
-        }
-        // one set of times for both directions: a time found by either walk counts for both ends
-        const double lo = fmin(tf, tl > -inf ? tl : inf), hi = fmax(tl, tf < inf ? tf : -inf);
-        tf = lo;
-        tl = hi;
-        iu = fmin(iu, tf);
-        ifr = fmax(ifr, tl);
+        fold_window(work + q * (size_t)M * kWindowLaneDoubles, M, iu, tf, tl, ifr);
       }
       vf = vl = -inf;
       if (tf < inf) {
@@ -230,7 +196,7 @@ template <int NC>
 int launch(msnap_ctx *ctx, HalfspaceCall c, double t_res, void *scratch, const Outputs &o) {
   const size_t lanes = halfspace_lanes(c.Q, c.M), segs = (size_t)c.N * c.M;
   double *work = (double *)scratch;
-  int32_t *flags = (int32_t *)(work + kLaneDoubles * lanes);
+  int32_t *flags = (int32_t *)(work + kWindowLaneDoubles * lanes);
   if (segs) {
     hipLaunchKernelGGL((clearance_flags_kernel<NC>), dim3(blocks_of(segs, kThreads)), dim3(kThreads), 0, ctx->stream,
                        c.coef, c.dur, segs, flags);
@@ -266,11 +232,9 @@ static int halfspace_args(const msnap_ctx *ctx, int n_drones, int n_seg, int n_p
   if (int rc = check_seg(ctx, n_seg)) return rc;
   if ((halfspace_lanes(n_queries, n_seg) + kThreads - 1) / kThreads > 0x7fffffffu) return MSNAP_EINVAL;   // grid size
   if (int rc = check_walk_grid(n_drones, n_seg)) return rc;
-  if (!(isfinite(t_res) && t_res > 0.0) || (n_planes > 0 && !planes)) return MSNAP_EINVAL;
+  if (!window_levels_valid(t_res) || (n_planes > 0 && !planes)) return MSNAP_EINVAL;
   if (n_queries == 0) return kNoWork;
-  for (const void *p : ptrs)
-    if (!p) return MSNAP_EINVAL;
-  return MSNAP_OK;
+  return all_required(ptrs);
 }
 
 int msnap_halfspace_window_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,

@@ -192,9 +192,7 @@ static int mesh_clearance_args(const msnap_ctx *ctx, int n_drones, int n_seg, in
   if (int rc = check_walk_grid(n_drones, n_seg)) return rc;
   if (n_drones == 0) return kNoWork;
   if (n_tris > 0 && !tris) return MSNAP_EINVAL;
-  for (const void *p : ptrs)
-    if (!p) return MSNAP_EINVAL;
-  return MSNAP_OK;
+  return all_required(ptrs);
 }
 
 int msnap_mesh_clearance_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,

@@ -3,28 +3,16 @@
 // K18 (msnap_conflict.hip): its time-ordered walk in both directions, with K11's distance, bound and lanes
 // (msnap_mesh_bound.h, the text msnap_mesh_clearance.hip calls as well).
 //
-// Lane.  One per (drone, segment): the segment's x, y, z scaled to u in [0, 1].  The forward walk visits the dyadic nodes
-// [a, a + hh] left to right (msnap_walk.h, WalkNode::advance):
+// Lane.  One per (drone, segment): the segment's x, y, z scaled to u in [0, 1].  The walk in both directions, the node
+// rule and the lane's four numbers are msnap_window.h's (first_crossing, window_lane_tail): the bound is a distance,
+// compared with the threshold; the attained values are squared distances, compared with threshold^2.  The node step here:
 //   1. node_points: the control points, their box, the path's points at the node's start, middle and end;
 //   2. the triangles in index order (wave-uniform: scalar loads).  One whose box lies threshold or more from the control
 //      points' box (box_tri_lb2 >= threshold^2) is proven far on the node and left out -- the threshold is fixed, so
 //      this needs no running best.  Of the others: the smallest support-plane bound (tri_node_bound) and the smallest
-//      attained squared distance at each of the three points;
-//   3. bound >= threshold: the node is proven clear -- on to the next sibling;
-//   4. else the start is in conflict (its squared distance < threshold^2): the conflict begins at a (every earlier
-//      node was proven clear or noted as undecided): the walk ends;
-//   5. else h hh <= t_res or lvl == kMaxDepth: a leaf.  Middle or end in conflict: the earlier of the two is the first
-//      conflict found, the walk ends.  Otherwise the leaf is undecided: its a is kept if it is the earliest, and on;
-//   6. else split.
-// The node guard kMaxNodes ends the walk with everything from the current a on undecided.  A lane carries two numbers
-// per direction, as K18's: the time of the conflict it found (none: +inf) and the time up to which it proved the drone
-// clear (none of an undecided node or a conflict: +inf).  The backward walk is the same body on e_s(1 - u) (a Taylor
-// shift by 1, then the odd coefficients negated); its times map back as E - T u, and its two numbers are the latest
-// conflict found and the time from which the drone is proven clear (none: -inf).  There is no prune slack: a node is
-// clear when its fp64 bound says so, and the header's allowance r covers the rounding of that bound.
+//      attained squared distance at each of the three points.
 //
-// Fold.  One thread per drone over its segments: the earliest and the latest conflict found in either direction, the
-// earliest clear-until and the latest clear-from, clamped to them (K18's fold); then the distance at t_first and at
+// Fold.  One thread per drone over its segments (msnap_window.h, fold_window); then the distance at t_first and at
 // t_last -- msnap_eval_flat's lookup and Horner, every triangle in index order through the sweep's functions, strict
 // `<` -- so that msnap_mesh_sweep of that one position returns d_first / d_last bit for bit and tri_first / tri_last
 // is the lowest index that attains it.  Nothing crosses lanes but the trip count.
@@ -32,64 +20,16 @@
 
 #include "msnap_api_util.h"
 #include "msnap_mesh_bound.h"
-#include "msnap_walk.h"
 #include "msnap_wave.h"
+#include "msnap_window.h"
 
 namespace msnap {
 namespace {
 
 constexpr int kThreads = kClearanceThreads;
-constexpr int kLaneDoubles = 4;      // per lane: conflict found forward, clear until, conflict found backward, clear from
-
 // ctx->mesh_clearance_work: per-lane results [N M][4] doubles, then the flags [N M] int32
 inline size_t mesh_conflict_work_bytes(int N, int M) {
-  return (size_t)N * M * (kLaneDoubles * sizeof(double) + sizeof(int32_t));
-}
-
-// The walk for the first time below the threshold from u = 0 on (L = threshold^2).  hit: the u of the conflict found
-// (+inf: none); clear: the u up to which distance >= threshold is proven (+inf: the whole lane).  Every lane of the
-// wave calls it.
-template <int D>
-__device__ __forceinline__ void first_crossing(const double (&e)[3][D + 1], bool ok, double h, double threshold, double L,
-                                               double t_res, int n_tris, const double *__restrict__ tris, double &hit,
-                                               double &clear) {
-  const double inf = __builtin_inf();
-  hit = inf;
-  clear = inf;
-  WalkNode node;
-  bool active = ok;
-  while (__ballot(active) != 0) {
-    const double hh = node.h(), a = node.a();
-    double b[3][D + 1], p[3][3], lo[3], hi[3];
-    node_points<D>(e, a, hh, b, p, lo, hi);
-    double bound = inf, g[3] = {inf, inf, inf};      // bound: a distance; g: squared distances at the three points
-    for (int t = 0; t < n_tris; ++t) {
-      const double *tri = tris + (size_t)t * 9;
-      if (!tri_finite(tri)) continue;
-      const bool need = active && !(box_tri_lb2(lo, hi, tri) >= L);      // not proven far on the node
-      if (__ballot(need) == 0) continue;
-      double d2[3];
-      const double tb = tri_node_bound<D>(tri, b, p, d2);
-      bound = need ? fmin(bound, tb) : bound;
-#pragma unroll
-      for (int q = 0; q < 3; ++q) g[q] = need ? fmin(g[q], d2[q]) : g[q];
-    }
-    const bool open = !(bound >= threshold);                            // not proven clear (a NaN bound proves nothing)
-    const bool at_start = open && g[0] < L;
-    const bool leaf = h * hh <= t_res || node.lvl >= kMaxDepth;
-    const bool in_mid = g[1] < L, at_end = g[2] < L;
-    const bool found = at_start || (open && leaf && (in_mid || at_end));
-    const bool undecided = open && !found && leaf;
-    const bool split = open && !found && !leaf;
-    const double at = at_start ? a : (in_mid ? fma(0.5, hh, a) : a + hh);
-    const bool finished = node.advance(split, active);
-    const bool guard = !finished && node.nodes >= kMaxNodes;            // nodes are left unvisited: undecided from a on
-    if (active) {
-      hit = found ? at : hit;
-      clear = (found || undecided || guard) ? fmin(clear, a) : clear;
-    }
-    active = active && !(found || finished || guard);
-  }
+  return (size_t)N * M * (kWindowLaneDoubles * sizeof(double) + sizeof(int32_t));
 }
 
 // one lane per (drone, segment): work[4 item ..] = the four times of the head, on the drone's clock
@@ -133,34 +73,31 @@ mesh_conflict_lane_kernel(const double *__restrict__ coef, const double *__restr
   }
 
   const double L = threshold * threshold;
-  double out[kLaneDoubles];
-#pragma unroll 1
-  for (int dir = 0; dir < 2; ++dir) {
-    if (dir == 1) {
-      // e_s(1 - u): the Taylor shift by 1, then the odd coefficients negated
+  // the node step: the smallest support-plane bound (a distance) and the smallest attained squared distances at the
+  // node's three points, over the triangles that are not proven far on the node
+  const auto values = [&](double a, double hh, bool active, double &bound, double (&g)[3]) {
+    double b[3][D + 1], p[3][3], lo[3], hi[3];
+    node_points<D>(e, a, hh, b, p, lo, hi);
+    bound = g[0] = g[1] = g[2] = inf;
+    for (int t = 0; t < n_tris; ++t) {
+      const double *tri = tris + (size_t)t * 9;
+      if (!tri_finite(tri)) continue;
+      const bool need = active && !(box_tri_lb2(lo, hi, tri) >= L);      // not proven far on the node
+      if (__ballot(need) == 0) continue;
+      double d2[3];
+      const double tb = tri_node_bound<D>(tri, b, p, d2);
+      bound = need ? fmin(bound, tb) : bound;
 #pragma unroll
-      for (int s = 0; s < 3; ++s) {
-#pragma unroll
-        for (int kk = 0; kk < D; ++kk)
-#pragma unroll
-          for (int j = D - 1; j >= kk; --j) e[s][j] = e[s][j + 1] + e[s][j];
-#pragma unroll
-        for (int j = 1; j <= D; j += 2) e[s][j] = -e[s][j];
-      }
+      for (int q = 0; q < 3; ++q) g[q] = need ? fmin(g[q], d2[q]) : g[q];
     }
-    double hit, clear;
-    first_crossing<D>(e, ok, T, threshold, L, t_res, n_tris, tris, hit, clear);
-    // u -> the drone's clock: start + T u forward, E - T u backward, kept inside the segment
-    const double th = dir == 0 ? fmin(fma(T, hit, start), E) : fmax(fma(-T, hit, E), start);
-    const double tc = dir == 0 ? fmin(fma(T, clear, start), E) : fmax(fma(-T, clear, E), start);
-    const double none = dir == 0 ? inf : -inf;
-    out[2 * dir] = (ok && hit < inf) ? th : none;
-    out[2 * dir + 1] = (ok && clear < inf) ? tc : none;
-  }
+  };
+  const auto walk = [&](double &hit, double &clear) { first_crossing(values, ok, T, threshold, L, t_res, hit, clear); };
+  double out[kWindowLaneDoubles];
+  window_lane_tail(e, ok, T, start, E, walk, out);
 
   if (!in_range) return;
 #pragma unroll
-  for (int q = 0; q < kLaneDoubles; ++q) work[kLaneDoubles * item + q] = out[q];
+  for (int q = 0; q < kWindowLaneDoubles; ++q) work[kWindowLaneDoubles * item + q] = out[q];
 }
 
 struct Outputs {
@@ -192,19 +129,7 @@ mesh_conflict_fold_kernel(const double *__restrict__ coef, const double *__restr
   if (st == MSNAP_ST_OK) {
     cu = tf = inf;      // certified clear over the whole window
     tl = cf = -inf;
-    const double *w = work + (size_t)d * M * kLaneDoubles;
-    for (int k = 0; k < M; ++k) {
-      tf = fmin(tf, w[kLaneDoubles * k]);
-      cu = fmin(cu, w[kLaneDoubles * k + 1]);
-      tl = fmax(tl, w[kLaneDoubles * k + 2]);
-      cf = fmax(cf, w[kLaneDoubles * k + 3]);
-    }
-    // one set of conflict times for both directions: a time found by either walk counts for both ends
-    const double lo = fmin(tf, tl > -inf ? tl : inf), hi = fmax(tl, tf < inf ? tf : -inf);
-    tf = lo;
-    tl = hi;
-    cu = fmin(cu, tf);
-    cf = fmax(cf, tl);
+    fold_window(work + (size_t)d * M * kWindowLaneDoubles, M, cu, tf, tl, cf);
     df = dl = inf;
     if (tf < inf) {
 #pragma unroll 1
@@ -236,7 +161,7 @@ int launch(msnap_ctx *ctx, int N, int M, const double *coef, const double *dur, 
            double threshold, double t_res, void *scratch, const Outputs &o) {
   const size_t segs = (size_t)N * M;
   double *work = (double *)scratch;
-  int32_t *flags = (int32_t *)(work + kLaneDoubles * segs);
+  int32_t *flags = (int32_t *)(work + kWindowLaneDoubles * segs);
   hipLaunchKernelGGL((clearance_flags_kernel<NC>), dim3(blocks_of(segs, kThreads)), dim3(kThreads), 0, ctx->stream,
                      coef, dur, segs, flags);
   MSNAP_HIP(ctx, hipGetLastError());
@@ -271,12 +196,10 @@ static int mesh_conflict_args(const msnap_ctx *ctx, int n_drones, int n_seg, int
   if (!ctx || n_drones < 0 || n_tris < 0) return MSNAP_EINVAL;
   if (int rc = check_seg(ctx, n_seg)) return rc;
   if (int rc = check_walk_grid(n_drones, n_seg)) return rc;
-  if (!(isfinite(threshold) && threshold >= 0.0) || !(isfinite(t_res) && t_res > 0.0)) return MSNAP_EINVAL;
+  if (!window_levels_valid(t_res, threshold)) return MSNAP_EINVAL;
   if (n_drones == 0) return kNoWork;
   if (n_tris > 0 && !tris) return MSNAP_EINVAL;
-  for (const void *p : ptrs)
-    if (!p) return MSNAP_EINVAL;
-  return MSNAP_OK;
+  return all_required(ptrs);
 }
 
 int msnap_mesh_conflict_window_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,

@@ -131,9 +131,7 @@ int solve_periodic_args(const msnap_ctx *ctx, int n_drones, int n_seg, std::init
   if (int rc = check_seg(ctx, n_seg)) return rc;
   if (n_seg < 2 || n_seg > periodic_max_segments(ctx->khalf)) return MSNAP_ESEGMENTS;
   if (n_drones == 0) return kNoWork;
-  for (const void *p : ptrs)
-    if (!p) return MSNAP_EINVAL;
-  return MSNAP_OK;
+  return all_required(ptrs);
 }
 
 }  // namespace

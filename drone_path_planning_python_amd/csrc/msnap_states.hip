@@ -176,9 +176,7 @@ int solve_states_args(const msnap_ctx *ctx, int n_drones, int n_seg, std::initia
   if (int rc = check_seg(ctx, n_seg)) return rc;
   if (n_seg > states_max_segments(ctx->khalf)) return MSNAP_ESEGMENTS;
   if (n_drones == 0) return kNoWork;
-  for (const void *p : ptrs)
-    if (!p) return MSNAP_EINVAL;
-  return MSNAP_OK;
+  return all_required(ptrs);
 }
 
 size_t state_bytes(const msnap_ctx *ctx, int n_drones) { return (size_t)n_drones * 4 * (ctx->khalf - 1) * 8; }

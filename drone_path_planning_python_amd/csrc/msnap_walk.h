@@ -3,8 +3,8 @@
 // mesh_clearance_lane_kernel (msnap_mesh_clearance.hip, K11: a minimum against a mesh) and extent_lane_kernel
 // (msnap_extent.hip, K12: a supremum in a direction, walked as the minimum of the negated polynomial).  DESIGN.md §5 K7
 // has the method.  The time-ordered walks for a first crossing use WalkNode and the node helpers, not the bookkeeping
-// of a minimum: first_crossing below is the walk of K18 (msnap_conflict.hip) and K20 (msnap_halfspace.hip);
-// msnap_mesh_conflict.hip (K19) has its own, with a triangle cull in the node.
+// of a minimum: msnap_window.h has that walk (first_crossing) and what else K18 (msnap_conflict.hip), K19
+// (msnap_mesh_conflict.hip) and K20 (msnap_halfspace.hip) share.
 //
 // Walk.  Branch and bound over the dyadic sub-intervals [idx 2^-lvl, (idx + 1) 2^-lvl] of u in [0, 1].  Per node:
 //   1. shift_scale: the Taylor shift of each component polynomial to the node's start, then the scaling by 2^-lvl
@@ -159,42 +159,6 @@ __device__ __forceinline__ double squares_bound(const double (&f)[3][D + 1]) {
     bound = is_min ? fmin(bound, b) : fmax(bound, b);
   }
   return bound;
-}
-
-// The time-ordered walk for the first crossing of the level L from u = 0 on, the one text of K18 (msnap_conflict.hip:
-// the squared distance of a pair) and K20 (msnap_halfspace.hip: a scalar polynomial); msnap_conflict.hip's head has the
-// node rule.  values(a, hh, bound, g): a proven lower bound of the quantity on the node [a, a + hh] and its attained
-// values g at the node's start, middle and end -- all that differs between the two.  h: the lane's length in seconds.
-// hit: the u of the crossing found (+inf: none); clear: the u up to which quantity >= L is proven (+inf: the whole
-// lane).  Every lane of the wave calls it.
-template <class Values>
-__device__ __forceinline__ void first_crossing(Values &&values, bool ok, double h, double L, double t_res, double &hit,
-                                               double &clear) {
-  const double inf = __builtin_inf();
-  hit = inf;
-  clear = inf;
-  WalkNode node;
-  bool active = ok;
-  while (__ballot(active) != 0) {
-    const double hh = node.h(), a = node.a();
-    double bound, g[3];
-    values(a, hh, bound, g);
-    const bool open = !(bound >= L);                                    // not proven clear (a NaN bound proves nothing)
-    const bool at_start = open && g[0] < L;
-    const bool leaf = h * hh <= t_res || node.lvl >= kMaxDepth;
-    const bool in_mid = g[1] < L, at_end = g[2] < L;
-    const bool found = at_start || (open && leaf && (in_mid || at_end));
-    const bool undecided = open && !found && leaf;
-    const bool split = open && !found && !leaf;
-    const double at = at_start ? a : (in_mid ? fma(0.5, hh, a) : a + hh);
-    const bool finished = node.advance(split, active);
-    const bool guard = !finished && node.nodes >= kMaxNodes;            // nodes are left unvisited: undecided from a on
-    if (active) {
-      hit = found ? at : hit;
-      clear = (found || undecided || guard) ? fmin(clear, a) : clear;
-    }
-    active = active && !(found || finished || guard);
-  }
 }
 
 // the attained values g at the start, middle and end of the node [a, a + hh] (earlier first) against the best so far:
