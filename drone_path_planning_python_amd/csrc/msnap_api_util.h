@@ -93,6 +93,19 @@ inline int batch_args(const msnap_ctx *ctx, int n_drones, int n_seg, std::initia
   return all_required(ptrs);
 }
 
+// The launch of a kernel that carries one tile of kDronesPerWave drones per wave in `lds_bytes` of dynamic LDS
+// (K13, K15, K21).  Beyond 64 KiB a kernel has to be told: an attribute of the function, no stream operation.
+template <class... P, class... A>
+int launch_tiles(msnap_ctx *ctx, void (*kernel)(P...), size_t lds_bytes, int n_drones, A... args) {
+  if (lds_bytes > 64 * 1024)
+    MSNAP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLdsBytes));
+  const int ntiles = (n_drones + kDronesPerWave - 1) / kDronesPerWave;
+  hipLaunchKernelGGL(kernel, dim3(ntiles), dim3(kWave), lds_bytes, ctx->stream, static_cast<P>(args)...);
+  MSNAP_HIP(ctx, hipGetLastError());
+  return MSNAP_OK;
+}
+
 // the numbers of a window call (msnap_window.h): a time resolution > 0 and, where there is one, a threshold >= 0
 inline bool window_levels_valid(double t_res, double threshold = 0.0) {
   return isfinite(threshold) && threshold >= 0.0 && isfinite(t_res) && t_res > 0.0;

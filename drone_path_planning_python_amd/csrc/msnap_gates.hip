@@ -9,6 +9,7 @@
 // same input stage, same end states and refine_end; the knot's mask and the lane's K-1 values come from global memory
 // one knot ahead of the sweep (no LDS of their own, so the segment range is msnap_solve_states').  A knot that no
 // drone of the tile gates takes the plain step behind one wave-uniform test: the same bits, without the selects.
+// (The entry points and their argument check are msnap_states.hip's, shared by the three tile solves.)
 #include "msnap_api_util.h"
 #include "msnap_rolled.h"
 
@@ -39,7 +40,6 @@ gates_solve_kernel(const double *__restrict__ wp, const double *__restrict__ tt,
   const int tile = blockIdx.x;
 
   RolledTile p;
-  double2 *sTr = reinterpret_cast<double2 *>(lds);
   p.sWraw = lds + L::kTrWords;
   p.sTraw = p.sWraw + 16 * wpitch;
   p.sS0 = p.sTraw + 16 * tpitch;
@@ -64,89 +64,19 @@ gates_solve_kernel(const double *__restrict__ wp, const double *__restrict__ tt,
   __syncthreads();
   store_durations(p.sTraw, shared_times, tpitch, M, nvalid, lane, dur + (size_t)tile * kDronesPerWave * M);
 
-  rolled_solve_tile<K, false, true, true>(p, sTr, wp, tt, shared_times, has_start, has_end, M, tile, nvalid, lane, coef,
+  rolled_solve_tile<K, false, true, true>(p, wp, tt, shared_times, has_start, has_end, M, tile, nvalid, lane, coef,
                                           dur, status, RolledGates{fix, via});
 }
 
-template <int K>
-int launch_gates_k(msnap_ctx *ctx, int N, int M, const double *wp, const double *t, int shared, const double *start,
-                   const double *end, const int32_t *fix, const double *via, double *coef, double *dur,
-                   int32_t *status) {
-  const size_t lds_bytes = StatesLayout<K>::bytes(M);
-  // (beyond 64 KiB of dynamic LDS a kernel has to be told; an attribute of the function, no stream operation)
-  if (lds_bytes > 64 * 1024)
-    MSNAP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&gates_solve_kernel<K>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLdsBytes));
-  const int ntiles = (N + kDronesPerWave - 1) / kDronesPerWave;
-  hipLaunchKernelGGL((gates_solve_kernel<K>), dim3(ntiles), dim3(kWave), lds_bytes, ctx->stream, wp, t, shared, start,
-                     end, fix, via, N, M, coef, dur, status);
-  MSNAP_HIP(ctx, hipGetLastError());
-  return MSNAP_OK;
-}
-
-int launch_solve_gates(msnap_ctx *ctx, int N, int M, const double *wp, const double *t, int shared,
-                       const double *start, const double *end, const int32_t *fix, const double *via, double *coef,
-                       double *dur, int32_t *status) {
-  return ctx->khalf == 4 ? launch_gates_k<4>(ctx, N, M, wp, t, shared, start, end, fix, via, coef, dur, status)
-                         : launch_gates_k<5>(ctx, N, M, wp, t, shared, start, end, fix, via, coef, dur, status);
-}
-
-int gates_max_segments(int khalf) {
-  return khalf == 4 ? StatesLayout<4>::max_segments() : StatesLayout<5>::max_segments();
-}
-
-// msnap_solve_states' checks, and a mask needs its values
-int solve_gates_args(const msnap_ctx *ctx, int n_drones, int n_seg, const void *fix, const void *via,
-                     std::initializer_list<const void *> ptrs) {
-  if (!ctx || n_drones < 0) return MSNAP_EINVAL;
-  if (int rc = check_seg(ctx, n_seg)) return rc;
-  if (n_seg > gates_max_segments(ctx->khalf)) return MSNAP_ESEGMENTS;
-  if (n_drones == 0) return kNoWork;
-  if (int rc = all_required(ptrs)) return rc;
-  if (fix && !via) return MSNAP_EINVAL;
-  return MSNAP_OK;
-}
-
 }  // namespace
+
+int launch_solve_gates(msnap_ctx *ctx, const SolveCall &c) {
+  auto go = [&](auto kernel, size_t lds_bytes) {
+    return launch_tiles(ctx, kernel, lds_bytes, c.n_drones, c.wp, c.t, c.shared_times ? 1 : 0, c.start, c.end, c.fix,
+                        c.via, c.n_drones, c.n_seg, c.coef, c.dur, c.status);
+  };
+  return ctx->khalf == 4 ? go(&gates_solve_kernel<4>, StatesLayout<4>::bytes(c.n_seg))
+                         : go(&gates_solve_kernel<5>, StatesLayout<5>::bytes(c.n_seg));
+}
+
 }  // namespace msnap
-
-using namespace msnap;
-
-extern "C" {
-
-int msnap_solve_gates_max_segments(int order) {
-  if (order != 7 && order != 9) return MSNAP_EORDER;
-  return gates_max_segments((order + 1) / 2);
-}
-
-int msnap_solve_gates_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, const double *t,
-                             int shared_times, const double *start, const double *end, const int32_t *fix,
-                             const double *via, double *coef, double *dur, int32_t *status) {
-  MSNAP_ENTER(ctx, solve_gates_args(ctx, n_drones, n_seg, fix, via, {wp, t, coef, dur, status}));
-  return launch_solve_gates(ctx, n_drones, n_seg, wp, t, shared_times != 0, start, end, fix, fix ? via : nullptr, coef,
-                            dur, status);
-}
-
-int msnap_solve_gates(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, const double *t, int shared_times,
-                      const double *start, const double *end, const int32_t *fix, const double *via, double *coef,
-                      double *dur, int32_t *status) {
-  MSNAP_ENTER(ctx, solve_gates_args(ctx, n_drones, n_seg, fix, via, {wp, t, coef, dur, status}));
-  const size_t b_t = (size_t)(shared_times ? 1 : n_drones) * (n_seg + 1) * 8;
-  const size_t b_s = (size_t)n_drones * 4 * (ctx->khalf - 1) * 8;
-  const size_t n_knots = (size_t)n_drones * (n_seg - 1);
-  // (a region without a source is not copied: a NULL state or mask stays NULL for the launcher)
-  return staged(ctx, {upload(wp, (size_t)n_drones * (n_seg + 1) * 4 * 8), upload(t, b_t), upload(start, start ? b_s : 0),
-                      upload(end, end ? b_s : 0), upload(fix, fix ? n_knots * 4 : 0),
-                      upload(via, fix ? n_knots * 4 * (ctx->khalf - 1) * 8 : 0),
-                      download(coef, coef_bytes(ctx, n_drones, n_seg)), download(dur, dur_bytes(n_drones, n_seg)),
-                      download(status, (size_t)n_drones * 4)},
-                [&](const DevPtr *d) {
-                  return launch_solve_gates(ctx, n_drones, n_seg, d[0], d[1], shared_times != 0,
-                                            start ? (const double *)d[2] : nullptr,
-                                            end ? (const double *)d[3] : nullptr,
-                                            fix ? (const int32_t *)d[4] : nullptr,
-                                            fix ? (const double *)d[5] : nullptr, d[6], d[7], d[8]);
-                });
-}
-
-}  // extern "C"

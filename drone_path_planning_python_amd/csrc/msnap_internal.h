@@ -189,6 +189,29 @@ int launch_optimize_times_free(msnap_ctx *ctx, const TimeoptCall &call);
 // largest n_seg whose per-tile state fits LDS (80 at order 7, 58 at order 9; kTimeoptEnds: see DESIGN.md K8;
 // kTimeoptRing: 48, 33)
 int timeopt_max_segments(int khalf, int mode);
+// The tile solves beside K1 (entries: msnap_states.hip): from and to given end states (msnap_solve_states), with
+// prescribed derivatives at interior knots as well (msnap_solve_gates), closed loop (msnap_solve_periodic).
+enum SolveMode : int { kSolveEnds = 0, kSolveGates = 1, kSolveRing = 2 };
+// One such call, in the order of msnap_solve_gates' parameters.  start / end ([n_drones][4][K-1], or null for rest) are
+// read with kSolveEnds and kSolveGates, fix / via ([n_drones][n_seg-1] masks and [..][4][K-1] values, fix null: no
+// gates) with kSolveGates; an entry whose mode has none leaves them null.  The pointers are the host's in a host entry
+// and the device's from the launchers on.
+struct SolveCall {
+  int n_drones, n_seg;
+  const double *wp, *t;
+  int shared_times;
+  const double *start, *end;
+  const int32_t *fix;
+  const double *via;
+  double *coef, *dur;
+  int32_t *status;
+};
+// each mode's kernels and launcher stay in their unit (msnap_states.hip, msnap_gates.hip, msnap_periodic.hip)
+int launch_solve_states(msnap_ctx *ctx, const SolveCall &call);
+int launch_solve_gates(msnap_ctx *ctx, const SolveCall &call);
+int launch_solve_periodic(msnap_ctx *ctx, const SolveCall &call);
+// the closed loop's cap from its own LDS layout (27 at order 7, 18 at order 9)
+int periodic_max_segments(int khalf);
 // (the pairwise pass: msnap_collide.h)
 int launch_mesh_sweep(msnap_ctx *ctx, int n_drones, int n_samples, const double *pos, int n_tris,
                       const double *tris, double radius, double *min_dist, int32_t *hit);

@@ -5,6 +5,7 @@
 // states_solve_kernel<K> (lane = 4 drone + axis, one wave per 16-drone tile, inputs staged in LDS, the full-line stores)
 // and is what stands around that call: stage the inputs, store the durations, check the inputs, hand ring_solve the
 // tile's stash at the compile-time tile size, store each segment as it comes back, write the status.
+// (The entry points and their argument check are msnap_states.hip's, shared by the three tile solves.)
 #include "msnap_api_util.h"
 #include "msnap_ring.h"
 #include "msnap_rolled.h"
@@ -100,68 +101,19 @@ periodic_solve_kernel(const double *__restrict__ wp, const double *__restrict__ 
   if (live && a == 0) status[tile * kDronesPerWave + dl] = st;
 }
 
-template <int K>
-int launch_periodic_k(msnap_ctx *ctx, int N, int M, const double *wp, const double *t, int shared, double *coef,
-                      double *dur, int32_t *status) {
-  const size_t lds_bytes = PeriodicLayout<K>::bytes(M);
-  // (beyond 64 KiB of dynamic LDS a kernel has to be told; an attribute of the function, no stream operation)
-  if (lds_bytes > 64 * 1024)
-    MSNAP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&periodic_solve_kernel<K>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLdsBytes));
-  const int ntiles = (N + kDronesPerWave - 1) / kDronesPerWave;
-  hipLaunchKernelGGL((periodic_solve_kernel<K>), dim3(ntiles), dim3(kWave), lds_bytes, ctx->stream, wp, t, shared, N, M,
-                     coef, dur, status);
-  MSNAP_HIP(ctx, hipGetLastError());
-  return MSNAP_OK;
-}
+}  // namespace
 
-int launch_solve_periodic(msnap_ctx *ctx, int N, int M, const double *wp, const double *t, int shared, double *coef,
-                          double *dur, int32_t *status) {
-  return ctx->khalf == 4 ? launch_periodic_k<4>(ctx, N, M, wp, t, shared, coef, dur, status)
-                         : launch_periodic_k<5>(ctx, N, M, wp, t, shared, coef, dur, status);
+int launch_solve_periodic(msnap_ctx *ctx, const SolveCall &c) {
+  auto go = [&](auto kernel, size_t lds_bytes) {
+    return launch_tiles(ctx, kernel, lds_bytes, c.n_drones, c.wp, c.t, c.shared_times ? 1 : 0, c.n_drones, c.n_seg,
+                        c.coef, c.dur, c.status);
+  };
+  return ctx->khalf == 4 ? go(&periodic_solve_kernel<4>, PeriodicLayout<4>::bytes(c.n_seg))
+                         : go(&periodic_solve_kernel<5>, PeriodicLayout<5>::bytes(c.n_seg));
 }
 
 int periodic_max_segments(int khalf) {
   return khalf == 4 ? PeriodicLayout<4>::max_segments() : PeriodicLayout<5>::max_segments();
 }
 
-// the periodic solve's own segment range (2 .. cap) on top of the context's
-int solve_periodic_args(const msnap_ctx *ctx, int n_drones, int n_seg, std::initializer_list<const void *> ptrs) {
-  if (!ctx || n_drones < 0) return MSNAP_EINVAL;
-  if (int rc = check_seg(ctx, n_seg)) return rc;
-  if (n_seg < 2 || n_seg > periodic_max_segments(ctx->khalf)) return MSNAP_ESEGMENTS;
-  if (n_drones == 0) return kNoWork;
-  return all_required(ptrs);
-}
-
-}  // namespace
 }  // namespace msnap
-
-using namespace msnap;
-
-extern "C" {
-
-int msnap_solve_periodic_max_segments(int order) {
-  if (order != 7 && order != 9) return MSNAP_EORDER;
-  return periodic_max_segments((order + 1) / 2);
-}
-
-int msnap_solve_periodic_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, const double *t,
-                                int shared_times, double *coef, double *dur, int32_t *status) {
-  MSNAP_ENTER(ctx, solve_periodic_args(ctx, n_drones, n_seg, {wp, t, coef, dur, status}));
-  return launch_solve_periodic(ctx, n_drones, n_seg, wp, t, shared_times != 0, coef, dur, status);
-}
-
-int msnap_solve_periodic(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, const double *t, int shared_times,
-                         double *coef, double *dur, int32_t *status) {
-  MSNAP_ENTER(ctx, solve_periodic_args(ctx, n_drones, n_seg, {wp, t, coef, dur, status}));
-  const size_t b_t = (size_t)(shared_times ? 1 : n_drones) * (n_seg + 1) * 8;
-  return staged(ctx, {upload(wp, (size_t)n_drones * (n_seg + 1) * 4 * 8), upload(t, b_t),
-                      download(coef, coef_bytes(ctx, n_drones, n_seg)), download(dur, dur_bytes(n_drones, n_seg)),
-                      download(status, (size_t)n_drones * 4)},
-                [&](const DevPtr *d) {
-                  return launch_solve_periodic(ctx, n_drones, n_seg, d[0], d[1], shared_times != 0, d[2], d[3], d[4]);
-                });
-}
-
-}  // extern "C"

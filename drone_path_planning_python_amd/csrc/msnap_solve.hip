@@ -67,7 +67,6 @@ solve_kernel(const double *__restrict__ wp, const double *__restrict__ tt, int s
   //      inputs Wraw[16][(M+1)*4] | Traw[16][M+1]
   // stash (LDS or global slab): X[M][16] | G[knots][NU*NU][16] | Z[knots][NU][64]
   RolledTile p;
-  double2 *sTr = reinterpret_cast<double2 *>(lds);
   p.sWraw = lds + (NC / 2) * kTrPitch * 2;
   p.sTraw = p.sWraw + 16 * wpitch;
   if constexpr (GS) {
@@ -88,7 +87,7 @@ solve_kernel(const double *__restrict__ wp, const double *__restrict__ tt, int s
       __syncthreads();
       store_durations(p.sTraw, shared_times, tpitch, M, nvalid, lane, dur + (size_t)tile * kDronesPerWave * M);
     }
-    rolled_solve_tile<K, GS, false>(p, sTr, wp, tt, shared_times, false, false, M, tile, nvalid, lane, coef, dur, status);
+    rolled_solve_tile<K, GS, false>(p, wp, tt, shared_times, false, false, M, tile, nvalid, lane, coef, dur, status);
   }
 }
 

@@ -6,20 +6,19 @@
 // as data they only move to the right-hand side of the block tridiagonal system
 //     O_{i-1}^T u_{i-1} + D_i u_i + O_i u_{i+1} = r_i ,   i = 1..M-1 .
 // states_solve_kernel<K> carves StatesLayout<K>, stages the inputs and the two state blocks in LDS, and solves its tile
-// with rolled_solve_tile<K, false, true> of msnap_rolled.h -- the body it shares with the generic solve_kernel<K, false>
-// of msnap_solve.hip.  ENDS = true turns on, in that body:
-//   start      u_0 / u_M are read from the state blocks (a missing one is rest) and checked for finiteness;
-//   segment 0  x = 1 / T_0, and the first time must be 0 (MSNAP_ST_TIMES otherwise): the reference's start-row quirk --
-//              segment 0's start rows taken at local time t[0] -- has no meaning for a path that starts from a moving
-//              state, so there is no Taylor shift here;
-//   knot 1     the sweep's carried term starts as Otz = O_0^T u_0 (y_1 = -yb_1 - Otz), not 0;
-//   forward    the durations before the current segment are summed as msnap_eval_flat sums them;
-//   knot M-1   the sweep stores G_{M-1} = S^-1 O_{M-1} for every knot, the last one included, and the backward sweep
-//              starts from un = u_M:  u_{M-1} = z_{M-1} - G_{M-1} u_M, which is S^-1 (y_{M-1} - O_{M-1} u_M).  With two
-//              segments the one knot receives both terms;
-//   recovery   segment M-1 ends in u_M, segment 0 starts from u_0; one segment is recover_segment alone.  The last
-//              segment then takes one refinement step on its end conditions (refine_end), so that msnap_eval_state at
-//              the sum of the durations returns the given end state to the evaluator's own rounding.
+// with rolled_solve_tile<K, false, true> of msnap_rolled.h -- the wrapper it shares with the generic solve_kernel<K, false>
+// of msnap_solve.hip around chain_solve, the one text of the open-chain elimination.  ENDS = true there: u_0 / u_M are
+// read from the state blocks (a missing one is rest) and checked; x = 1 / T_0 and the first time must be 0
+// (MSNAP_ST_TIMES otherwise; no Taylor shift: the reference's start-row quirk has no meaning for a path that starts
+// from a moving state); knot 1 sees u_0 through Otz = O_0^T u_0; the backward sweep starts from u_M through the last
+// knot's G, u_{M-1} = z_{M-1} - G_{M-1} u_M (with two segments the one knot receives both terms); and the last segment
+// takes refine_end, so that msnap_eval_state at the sum of the durations returns the given end state to the
+// evaluator's own rounding.
+//
+// Host side.  This unit also holds what the three tile solves beside K1 share above their kernels -- this one, the
+// gates (msnap_gates.hip) and the closed loop (msnap_periodic.hip): the argument check, the entry body with its staging
+// block and the entry points, over one call record (SolveCall, msnap_internal.h), as msnap_timeopt.hip does for the
+// allocators.  Each unit keeps its kernels and one launch_solve_* behind launch_tiles (msnap_api_util.h).
 //
 // Evaluator.  One thread per drone: msnap_eval_flat's piece lookup (t <= acc + T_i: a knot belongs to the earlier
 // segment) and horner_derivs' arithmetic of msnap_aux.hip carried to derivative K-1, no contraction.
@@ -47,7 +46,6 @@ states_solve_kernel(const double *__restrict__ wp, const double *__restrict__ tt
   const int tile = blockIdx.x;
 
   RolledTile p;
-  double2 *sTr = reinterpret_cast<double2 *>(lds);
   p.sWraw = lds + L::kTrWords;
   p.sTraw = p.sWraw + 16 * wpitch;
   p.sS0 = p.sTraw + 16 * tpitch;
@@ -72,7 +70,7 @@ states_solve_kernel(const double *__restrict__ wp, const double *__restrict__ tt
   __syncthreads();
   store_durations(p.sTraw, shared_times, tpitch, M, nvalid, lane, dur + (size_t)tile * kDronesPerWave * M);
 
-  rolled_solve_tile<K, false, true>(p, sTr, wp, tt, shared_times, has_start, has_end, M, tile, nvalid, lane, coef,
+  rolled_solve_tile<K, false, true>(p, wp, tt, shared_times, has_start, has_end, M, tile, nvalid, lane, coef,
                                     dur, status);
 }
 
@@ -131,27 +129,6 @@ state_eval_kernel(const double *__restrict__ coef, const double *__restrict__ du
       (size_t)blockIdx.x * blockDim.x);
 }
 
-template <int K>
-int launch_states_k(msnap_ctx *ctx, int N, int M, const double *wp, const double *t, int shared, const double *start,
-                    const double *end, double *coef, double *dur, int32_t *status) {
-  const size_t lds_bytes = StatesLayout<K>::bytes(M);
-  // (beyond 64 KiB of dynamic LDS a kernel has to be told; an attribute of the function, no stream operation)
-  if (lds_bytes > 64 * 1024)
-    MSNAP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&states_solve_kernel<K>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLdsBytes));
-  const int ntiles = (N + kDronesPerWave - 1) / kDronesPerWave;
-  hipLaunchKernelGGL((states_solve_kernel<K>), dim3(ntiles), dim3(kWave), lds_bytes, ctx->stream, wp, t, shared, start,
-                     end, N, M, coef, dur, status);
-  MSNAP_HIP(ctx, hipGetLastError());
-  return MSNAP_OK;
-}
-
-int launch_solve_states(msnap_ctx *ctx, int N, int M, const double *wp, const double *t, int shared,
-                        const double *start, const double *end, double *coef, double *dur, int32_t *status) {
-  return ctx->khalf == 4 ? launch_states_k<4>(ctx, N, M, wp, t, shared, start, end, coef, dur, status)
-                         : launch_states_k<5>(ctx, N, M, wp, t, shared, start, end, coef, dur, status);
-}
-
 int launch_eval_state(msnap_ctx *ctx, int N, int M, const double *coef, const double *dur, const double *tq,
                       double *pos, double *deriv) {
   unsigned blocks = blocks_of((size_t)N, kEvalThreads);
@@ -166,54 +143,130 @@ int launch_eval_state(msnap_ctx *ctx, int N, int M, const double *coef, const do
   return MSNAP_OK;
 }
 
-int states_max_segments(int khalf) {
+size_t state_bytes(const msnap_ctx *ctx, int n_drones) { return (size_t)n_drones * 4 * (ctx->khalf - 1) * 8; }
+
+// the cap of a mode from its LDS layout (the gates take no LDS: theirs is the boundary-state solve's)
+int solve_max_segments(int khalf, int mode) {
+  if (mode == kSolveRing) return periodic_max_segments(khalf);
   return khalf == 4 ? StatesLayout<4>::max_segments() : StatesLayout<5>::max_segments();
 }
 
-// the boundary-state solve's own segment range on top of the context's
-int solve_states_args(const msnap_ctx *ctx, int n_drones, int n_seg, std::initializer_list<const void *> ptrs) {
-  if (!ctx || n_drones < 0) return MSNAP_EINVAL;
-  if (int rc = check_seg(ctx, n_seg)) return rc;
-  if (n_seg > states_max_segments(ctx->khalf)) return MSNAP_ESEGMENTS;
-  if (n_drones == 0) return kNoWork;
-  return all_required(ptrs);
+int launch_solve(msnap_ctx *ctx, int mode, const SolveCall &c) {
+  switch (mode) {
+    case kSolveRing: return launch_solve_periodic(ctx, c);
+    case kSolveGates: return launch_solve_gates(ctx, c);
+    default: return launch_solve_states(ctx, c);
+  }
 }
 
-size_t state_bytes(const msnap_ctx *ctx, int n_drones) { return (size_t)n_drones * 4 * (ctx->khalf - 1) * 8; }
+// The argument check every tile-solve entry and its _device twin make: the mode's own segment range on top of the
+// context's, then the pointers every mode requires; a mask needs its values
+int solve_args(const msnap_ctx *ctx, int mode, const SolveCall &c) {
+  if (!ctx || c.n_drones < 0) return MSNAP_EINVAL;
+  if (int rc = check_seg(ctx, c.n_seg)) return rc;
+  if (c.n_seg > solve_max_segments(ctx->khalf, mode)) return MSNAP_ESEGMENTS;
+  if (mode == kSolveRing && c.n_seg < 2) return MSNAP_ESEGMENTS;      // (a loop has two segments at least)
+  if (c.n_drones == 0) return kNoWork;
+  if (int rc = all_required({c.wp, c.t, c.coef, c.dur, c.status})) return rc;
+  if (c.fix && !c.via) return MSNAP_EINVAL;
+  return MSNAP_OK;
+}
+
+// Every tile-solve entry: check, then launch on the caller's device pointers (on_device), or stage the caller's host
+// arrays, launch on the staged copies and read back.  (Values without a mask are not read: the kernel asks for the mask.)
+int solve_entry(msnap_ctx *ctx, int mode, const SolveCall &c, bool on_device) {
+  MSNAP_ENTER(ctx, solve_args(ctx, mode, c));
+  if (on_device) return launch_solve(ctx, mode, c);
+  const size_t n = (size_t)c.n_drones, m1 = (size_t)c.n_seg + 1, b_s = state_bytes(ctx, c.n_drones);
+  const size_t n_knots = c.fix ? n * (c.n_seg - 1) : 0;
+  // (a region without a source is not copied: a NULL state or mask stays NULL for the launcher)
+  return staged(ctx, {upload(c.wp, n * m1 * 4 * 8), upload(c.t, (c.shared_times ? 1 : n) * m1 * 8),
+                      upload(c.start, c.start ? b_s : 0), upload(c.end, c.end ? b_s : 0), upload(c.fix, n_knots * 4),
+                      upload(c.via, n_knots * 4 * (ctx->khalf - 1) * 8),
+                      download(c.coef, coef_bytes(ctx, c.n_drones, c.n_seg)),
+                      download(c.dur, dur_bytes(c.n_drones, c.n_seg)), download(c.status, n * 4)},
+                [&](const DevPtr *d) {
+                  SolveCall dev = c;
+                  dev.wp = d[0];
+                  dev.t = d[1];
+                  dev.start = c.start ? (const double *)d[2] : nullptr;
+                  dev.end = c.end ? (const double *)d[3] : nullptr;
+                  dev.fix = c.fix ? (const int32_t *)d[4] : nullptr;
+                  dev.via = c.fix ? (const double *)d[5] : nullptr;
+                  dev.coef = d[6];
+                  dev.dur = d[7];
+                  dev.status = d[8];
+                  return launch_solve(ctx, mode, dev);
+                });
+}
+
+int max_segments_entry(int order, int mode) {
+  if (order != 7 && order != 9) return MSNAP_EORDER;
+  return solve_max_segments((order + 1) / 2, mode);
+}
 
 }  // namespace
+
+int launch_solve_states(msnap_ctx *ctx, const SolveCall &c) {
+  auto go = [&](auto kernel, size_t lds_bytes) {
+    return launch_tiles(ctx, kernel, lds_bytes, c.n_drones, c.wp, c.t, c.shared_times ? 1 : 0, c.start, c.end,
+                        c.n_drones, c.n_seg, c.coef, c.dur, c.status);
+  };
+  return ctx->khalf == 4 ? go(&states_solve_kernel<4>, StatesLayout<4>::bytes(c.n_seg))
+                         : go(&states_solve_kernel<5>, StatesLayout<5>::bytes(c.n_seg));
+}
+
 }  // namespace msnap
 
 using namespace msnap;
 
 extern "C" {
 
-int msnap_solve_states_max_segments(int order) {
-  if (order != 7 && order != 9) return MSNAP_EORDER;
-  return states_max_segments((order + 1) / 2);
-}
+// The tile-solve entries fill the call record in its field order (a mode without end states or gates leaves them null)
+// and differ in the mode and in whose pointers they take.
+int msnap_solve_states_max_segments(int order) { return max_segments_entry(order, kSolveEnds); }
 
 int msnap_solve_states_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, const double *t,
                               int shared_times, const double *start, const double *end, double *coef, double *dur,
                               int32_t *status) {
-  MSNAP_ENTER(ctx, solve_states_args(ctx, n_drones, n_seg, {wp, t, coef, dur, status}));
-  return launch_solve_states(ctx, n_drones, n_seg, wp, t, shared_times != 0, start, end, coef, dur, status);
+  const SolveCall c = {n_drones, n_seg, wp, t, shared_times, start, end, nullptr, nullptr, coef, dur, status};
+  return solve_entry(ctx, kSolveEnds, c, true);
 }
 
 int msnap_solve_states(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, const double *t, int shared_times,
                        const double *start, const double *end, double *coef, double *dur, int32_t *status) {
-  MSNAP_ENTER(ctx, solve_states_args(ctx, n_drones, n_seg, {wp, t, coef, dur, status}));
-  const size_t b_t = (size_t)(shared_times ? 1 : n_drones) * (n_seg + 1) * 8;
-  const size_t b_s = state_bytes(ctx, n_drones);
-  // (a region without a source is not copied: a NULL state stays NULL for the launcher)
-  return staged(ctx, {upload(wp, (size_t)n_drones * (n_seg + 1) * 4 * 8), upload(t, b_t), upload(start, start ? b_s : 0),
-                      upload(end, end ? b_s : 0), download(coef, coef_bytes(ctx, n_drones, n_seg)),
-                      download(dur, dur_bytes(n_drones, n_seg)), download(status, (size_t)n_drones * 4)},
-                [&](const DevPtr *d) {
-                  return launch_solve_states(ctx, n_drones, n_seg, d[0], d[1], shared_times != 0,
-                                             start ? (const double *)d[2] : nullptr,
-                                             end ? (const double *)d[3] : nullptr, d[4], d[5], d[6]);
-                });
+  const SolveCall c = {n_drones, n_seg, wp, t, shared_times, start, end, nullptr, nullptr, coef, dur, status};
+  return solve_entry(ctx, kSolveEnds, c, false);
+}
+
+int msnap_solve_gates_max_segments(int order) { return max_segments_entry(order, kSolveGates); }
+
+int msnap_solve_gates_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, const double *t,
+                             int shared_times, const double *start, const double *end, const int32_t *fix,
+                             const double *via, double *coef, double *dur, int32_t *status) {
+  const SolveCall c = {n_drones, n_seg, wp, t, shared_times, start, end, fix, via, coef, dur, status};
+  return solve_entry(ctx, kSolveGates, c, true);
+}
+
+int msnap_solve_gates(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, const double *t, int shared_times,
+                      const double *start, const double *end, const int32_t *fix, const double *via, double *coef,
+                      double *dur, int32_t *status) {
+  const SolveCall c = {n_drones, n_seg, wp, t, shared_times, start, end, fix, via, coef, dur, status};
+  return solve_entry(ctx, kSolveGates, c, false);
+}
+
+int msnap_solve_periodic_max_segments(int order) { return max_segments_entry(order, kSolveRing); }
+
+int msnap_solve_periodic_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, const double *t,
+                                int shared_times, double *coef, double *dur, int32_t *status) {
+  const SolveCall c = {n_drones, n_seg, wp, t, shared_times, nullptr, nullptr, nullptr, nullptr, coef, dur, status};
+  return solve_entry(ctx, kSolveRing, c, true);
+}
+
+int msnap_solve_periodic(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, const double *t, int shared_times,
+                         double *coef, double *dur, int32_t *status) {
+  const SolveCall c = {n_drones, n_seg, wp, t, shared_times, nullptr, nullptr, nullptr, nullptr, coef, dur, status};
+  return solve_entry(ctx, kSolveRing, c, false);
 }
 
 int msnap_eval_state_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, const double *dur,

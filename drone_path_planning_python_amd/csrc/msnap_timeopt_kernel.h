@@ -8,7 +8,8 @@
 //
 // Mapping as K1: lane = 4 * drone + axis, a wavefront carries one tile of 16 drones (8 when the 16-drone stash does
 // not fit LDS; lanes 32..63 then replay the tile's last drone as the lanes past a batch end always do).  The
-// arithmetic per knot and segment is Sweep<K> / recover_segment of msnap_sweep.h.  Everything a drone carries between
+// solve of a trial is the solve entries' own text: chain_solve of msnap_rolled.h, the call rolled_solve_tile makes, here
+// at a run-time tile size (closed loops: ring_solve).  Everything a drone carries between
 // trials lives in LDS, drone-interleaved ([index][drone]): current and trial knots, the gradient at both, the descent
 // direction, 1/T, G_i, z_i.  The four axis lanes of a drone write the same bits to the same address, so nothing one
 // lane reads was written by another and no fence is needed after the input stage.
@@ -19,10 +20,10 @@
 // the fixed order ((x + y) + z) + yaw, so the four lanes hold the same bits and take the same decisions.
 //
 // Given end states (msnap_optimize_times_states): timeopt_kernel<K, kTimeoptEnds>.  The end knots' derivative vectors are data
-// as in the boundary-state solve (msnap_rolled.h, ENDS); the gradient is the same expression -- the first and last
+// as in the boundary-state solve (chain_solve's ENDS); the gradient is the same expression -- the first and last
 // segment's outer end states are fixed either way.  What differs from the rest-to-rest instance is one `if constexpr`
-// each: the state images in LDS, their finiteness check, the seed of the sweep's carried term, the backward sweep from
-// u_M through the last knot's G, segment 0 from u_0, and refine_end on the last segment when the coefficients leave.
+// each: the state images in LDS, their finiteness check, the end vectors handed to chain_solve, and its REFINE
+// (refine_end on the last segment) when the coefficients leave -- so coef is msnap_solve_states' at t_out, bit for bit.
 //
 // Closed loops (msnap_optimize_times_periodic): timeopt_kernel<K, kTimeoptRing>.  "The solve for T" is
 // msnap_solve_periodic's, so the trial is K15's ring elimination, ring_solve of msnap_ring.h -- the call K15's own
@@ -92,16 +93,14 @@ template <int MODE>
 using TimeoptArgsOf = std::conditional_t<MODE == kTimeoptFree, TimeoptFreeArgs,
                                          std::conditional_t<MODE == kTimeoptEnds, TimeoptEndsArgs, TimeoptArgs>>;
 
-// ENDS: the end knots' derivative vectors u_0, u_M are data (msnap_optimize_times_states), as in rolled_solve_tile
+// ENDS: the end knots' derivative vectors u_0, u_M are data (msnap_optimize_times_states); the trial is chain_solve
 // RING: the last waypoint is joined to the first (msnap_optimize_times_periodic), the trial is ring_solve
 // FREE: ENDS with the total duration an unknown (msnap_optimize_times_free): F = J + k_T t[M], no projection
 template <int K, int MODE>
 __global__ void __launch_bounds__(kWave)
 timeopt_kernel(const TimeoptArgsOf<MODE> p) {
   constexpr bool FREE = MODE == kTimeoptFree, ENDS = MODE == kTimeoptEnds || FREE, RING = MODE == kTimeoptRing;
-  using SW = Sweep<K>;
-  using C = HermiteConsts<K>;
-  constexpr int NU = SW::NU, NC = SW::NC, KK = SW::KK, PM = SW::PM, PITCH = NU | 1;
+  constexpr int NU = K - 1, NC = 2 * K, PITCH = NU | 1;
 
   extern __shared__ __attribute__((aligned(16))) double lds[];
 
@@ -209,117 +208,37 @@ timeopt_kernel(const TimeoptArgsOf<MODE> p) {
   // ---------------- one trial: solve for the knots sT, cost, gradient (EMIT: the coefficients leave) ----------------
   auto trial = [&](auto emit, const double *sT, double *sGrad, bool bad, double &Jw, bool &singular) {
     constexpr bool EMIT = decltype(emit)::value;
-    if constexpr (RING) {
-      // K15's elimination around the ring; per segment the same cost, gradient and stores as below.  The coefficients
-      // that leave take K15's refinement step and refine_end; cost and gradient are every trial's, the unrefined ones
-      double *sZ2 = sS + (size_t)TD * NU * NU * knots + ql;
-      const RingLane rl = {lw, sT, sX + dloc, sG + dloc, sS + dloc, sZ, sZ2, TD};
-      double Ja = 0.0;
-      ring_solve<K, EMIT>(rl, M, singular, [&](int i, double (&c)[NC], double Ti) {
-        if constexpr (EMIT) {
-          double *base = p.coef + ((size_t)tile * TD * M + i) * (4 * NC);
-          if constexpr (NC == 8) store_segment_quad8(base, MSNAP_SEG_STRIDE(M, NC), nvalid, lane, c, bad);
-          else store_segment_coalesced<NC>(sTr, base, MSNAP_SEG_STRIDE(M, NC), nvalid, lane, c, bad);
-        } else {
-          Ja += segment_cost<K>(c, Ti);
-          sGrad[i * TD + dloc] = -quad_weighted_sum(ostrogradsky_energy<K>(c), wa);
-        }
-      });
-      Jw = quad_weighted_sum(Ja, wa);
-      return;
-    }
-    double tcur = sT[TD];
-    double wcur = lw[4];
-    double x = rcp64(tcur - sT[0]);
-    sX[dloc] = x;
-    SW sw;
-    sw.init(x, wcur - lw[0]);
-    if constexpr (ENDS) {
-      // knot 1 sees the start state through the coupling block of segment 0: Otz = O_0^T u_0 (rolled_solve_tile)
-      double xp[PM + 1];
-      SW::powers(x, xp);
-#pragma unroll
-      for (int n = 0; n < NU; ++n) {
-        double w = 0.0;
-#pragma unroll
-        for (int q = 0; q < NU; ++q) w = __builtin_fma(C::HSE[q + 1][n + 1] * xp[KK - (q + 1) - (n + 1)], sS0[q], w);
-        sw.Otz[n] = w;
-      }
-    }
-    for (int i = 1; i < M; ++i) {
-      const double tnext = sT[(i + 1) * TD];
-      const double wnext = lw[(i + 1) * 4];
-      x = rcp64(tnext - tcur);
-      sX[i * TD + dloc] = x;
-      double G[NU][NU], z[NU];
-      sw.step(x, wnext - wcur, G, z);
-      double *g = sG + (size_t)(i - 1) * (NU * NU * TD) + dloc;
-      double *zz = sZ + (size_t)(i - 1) * (NU * QL);
-#pragma unroll
-      for (int r = 0; r < NU; ++r) {
-#pragma unroll
-        for (int c = 0; c < NU; ++c) g[(r * NU + c) * TD] = G[r][c];
-        zz[r * QL] = z[r];
-      }
-      tcur = tnext;
-      wcur = wnext;
-    }
-    singular = sw.singular;
-
-    double un[NU];
-#pragma unroll
-    for (int r = 0; r < NU; ++r) {
-      if constexpr (ENDS) un[r] = sS1[r];      // the backward sweep starts from u_M
-      else un[r] = 0.0;
-    }
-    double wn = wcur, tn = tcur;   // w_M, t_M
-    // ENDS: the local time msnap_eval_state evaluates the last segment at when asked for the sum of the durations --
-    // of the durations as they are stored, the differences of these knots
-    double tl_end = 0.0;
-    if constexpr (ENDS && EMIT) {
-      double tacc = 0.0;
-      for (int i = 0; i < M - 1; ++i) tacc = tacc + (sT[(i + 1) * TD] - sT[i * TD]);
-      tl_end = (tacc + (tn - sT[(M - 1) * TD])) - tacc;
-    }
+    // per segment, last first: cost and gradient of a trial, or the stores of the coefficients that leave.  Those take
+    // the solve entries' refinement (K15's step on the ring, refine_end on the last segment); cost and gradient are
+    // every trial's, the unrefined ones
     double Ja = 0.0;
-    for (int i = M - 1; i >= 0; --i) {
-      double u[NU];
-      const int kq = i >= 1 ? i - 1 : 0;   // stash slot of knot i
-      const double *zz = sZ + (size_t)kq * (NU * QL);
-      const double *g = sG + (size_t)kq * (NU * NU * TD) + dloc;
-#pragma unroll
-      for (int r = 0; r < NU; ++r) {
-        double v = i >= 1 ? zz[r * QL] : 0.0;
-        // (ENDS: the stash holds G of the last knot too, and with two segments the one knot receives both end terms)
-        if (ENDS || i < M - 1) {
-#pragma unroll
-          for (int c = 0; c < NU; ++c) v = __builtin_fma(-(i >= 1 ? g[(r * NU + c) * TD] : 0.0), un[c], v);
-        }
-        if constexpr (ENDS) u[r] = i >= 1 ? v : sS0[r];      // segment 0 starts from u_0
-        else u[r] = i >= 1 ? v : 0.0;
-      }
-      const double wi = lw[i * 4];
-      const double ti = sT[i * TD];
-      double c[NC];
-      recover_segment<K>(wi, wn - wi, sX[i * TD + dloc], u, un, c);
-      Ja += segment_cost<K>(c, tn - ti);
-      const double gi = -quad_weighted_sum(ostrogradsky_energy<K>(c), wa);
+    auto seg = [&](int i, double (&c)[NC], double Ti) {
       if constexpr (EMIT) {
-        // the last segment leaves with one refinement step on its end conditions; cost and gradient above are the
-        // unrefined coefficients', as in every trial
-        if constexpr (ENDS) {
-          if (i == M - 1) refine_end<K>(c, tl_end, sX[i * TD + dloc], wn, un);
-        }
         double *base = p.coef + ((size_t)tile * TD * M + i) * (4 * NC);
         if constexpr (NC == 8) store_segment_quad8(base, MSNAP_SEG_STRIDE(M, NC), nvalid, lane, c, bad);
         else store_segment_coalesced<NC>(sTr, base, MSNAP_SEG_STRIDE(M, NC), nvalid, lane, c, bad);
       } else {
+        Ja += segment_cost<K>(c, Ti);
+        const double gi = -quad_weighted_sum(ostrogradsky_energy<K>(c), wa);
         sGrad[i * TD + dloc] = FREE ? kT + gi : gi;      // (FREE: dF/dT_i = k_T - sum_a w_a E_i,a)
       }
+    };
+    if constexpr (RING) {
+      // K15's elimination around the ring
+      double *sZ2 = sS + (size_t)TD * NU * NU * knots + ql;
+      const RingLane rl = {lw, sT, sX + dloc, sG + dloc, sS + dloc, sZ, sZ2, TD};
+      ring_solve<K, EMIT>(rl, M, singular, seg);
+    } else {
+      // the open chain of the solve entries (the input stage has checked t[0] == 0, so rest to rest may take the
+      // start-row form as it is: T_0 - 0 and the shift that is skipped are the same bits)
+      double u0[NU], uM[NU];
 #pragma unroll
-      for (int r = 0; r < NU; ++r) un[r] = u[r];
-      wn = wi;
-      tn = ti;
+      for (int q = 0; q < NU; ++q) {
+        if constexpr (ENDS) u0[q] = sS0[q], uM[q] = sS1[q];
+        else u0[q] = uM[q] = 0.0;
+      }
+      const ChainLane cl = {lw, sT, sX + dloc, sG + dloc, sZ, TD};
+      chain_solve<K, ENDS, ENDS && EMIT>(cl, M, u0, uM, singular, seg);
     }
     Jw = quad_weighted_sum(Ja, wa);
     if constexpr (FREE) Jw = Jw + kT * sT[M * TD];      // F = J + k_T sum_i T_i

@@ -217,7 +217,8 @@ def test_one_and_two_segments_tiles_and_null_blocks(ctx7, ctx9, order):
         r = ctx.optimize_times_states(wp, t, start, end)
         assert (r[3] == 0).all() and (r[4]["cost"][:, 1] <= r[4]["cost"][:, 0]).all()
         ce, de, se = ctx.solve_states(wp, r[0], start, end)
-        assert np.array_equal(r[2], de) and norm_rel(r[1], ce) <= 1e-9, (M, norm_rel(r[1], ce))
+        # (the trial runs the solve entry's own elimination, chain_solve: the coefficients are its bits)
+        assert np.array_equal(r[2], de) and np.array_equal(r[1], ce), (M, norm_rel(r[1], ce))
         assert (r[4]["iters"] > 0).any()
         for d in (0, 15, 16):
             one = ctx.optimize_times_states(wp[d:d + 1], t[d:d + 1], start[d:d + 1], end[d:d + 1])
