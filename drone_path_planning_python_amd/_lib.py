@@ -110,6 +110,11 @@ SIGNATURES = {
     "msnap_optimize_times_free_device": (_I, [_VP, _I, _I, _VP, _VP, _I, _VP, _VP, _VP, _VP, _D, _I, _D, _VP, _VP, _VP,
                                               _VP, _VP, _VP, _VP]),
     "msnap_optimize_times_free_max_segments": (_I, [_I]),
+    "msnap_optimize_times_gates": (_I, [_VP, _I, _I, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _D, _I, _D, _VP, _VP, _VP,
+                                        _VP, _VP, _VP, _VP]),
+    "msnap_optimize_times_gates_device": (_I, [_VP, _I, _I, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _D, _I, _D, _VP, _VP,
+                                               _VP, _VP, _VP, _VP, _VP]),
+    "msnap_optimize_times_gates_max_segments": (_I, [_I]),
     "msnap_eval_state": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _VP]),
     "msnap_eval_state_device": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _VP]),
     "msnap_formation_near_pairs": (_I, [_VP, _I, _I, _VP, _D, _VP, _D, _D, _LL, _VP, _VP, _VP]),

@@ -176,10 +176,11 @@ class Context:
         """What the library's `fn` (a *_max_segments entry) allows at this context's order, and at most max_segments."""
         return min(int(fn(self.order)), self.max_segments)
 
-    def _optimize_times(self, entry, wp, t, states, weights, time_weight, min_fraction, max_iter, tol):
+    def _optimize_times(self, entry, wp, t, states, weights, time_weight, min_fraction, max_iter, tol, gates=()):
         """The host allocators' one body: `entry` names the library's entry of the mode (looked up after the shape
-        checks, which need no library), `states` is its (start, end) and `time_weight` its (time_weight,) -- () where
-        it takes none; the other arguments and the result tuple as optimize_times."""
+        checks, which need no library), `states` is its (start, end), `time_weight` its (time_weight,) and `gates` the
+        pointers of its (fix, via), behind the states in the call -- () where it takes none; the other arguments and
+        the result tuple as optimize_times."""
         wp, pwp, t, pt, N, m, shared = _waypoints_times(wp, t)
         w, pw = _weights(weights)
         kts = []      # (the converted arrays and their pointers, as _host gives them)
@@ -202,7 +203,7 @@ class Context:
         vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)   # noqa: E731
         with self._lock:
             self._ck(getattr(self._lib, entry)(
-                self._h, N, M, pwp, pt, shared, *(px for _, px in ends), pw, *(pk for _, pk in kts),
+                self._h, N, M, pwp, pt, shared, *(px for _, px in ends), *gates, pw, *(pk for _, pk in kts),
                 float(min_fraction), int(max_iter), float(tol), vp(t_out), vp(coef), vp(dur), vp(status), vp(cost),
                 vp(pg), vp(iters)))
         return t_out, coef, dur, status, {"cost": cost, "pg": pg, "iters": iters}
@@ -820,6 +821,16 @@ class Context:
         M = m - 1
         start, ps = self._state_block(start, N, "start")
         end, pe = self._state_block(end, N, "end")
+        (fix, pf), (via, pv) = self._gate_blocks(fix, via, N, M)
+        coef, dur, status = _out_arrays(None, ((N, max(M, 0), 4, self.ncoef), (N, max(M, 0)), (N,)))
+        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)      # noqa: E731
+        with self._lock:
+            self._ck(self._lib.msnap_solve_gates(self._h, N, M, pwp, pt, shared, ps, pe, pf, pv, vp(coef), vp(dur),
+                                                 vp(status)))
+        return coef, dur, status
+
+    def _gate_blocks(self, fix, via, N, M):
+        """fix / via of a gated entry as host arrays with their pointers (None, None where not given), checked."""
         pf = pv = None
         if fix is not None:
             fix, pf = _host(fix, np.int32)
@@ -831,12 +842,7 @@ class Context:
             via, pv = _host(via, np.float64)
             if via.shape != (N, max(M - 1, 0), 4, self.ncoef // 2 - 1):
                 raise ValueError(f"via must be [N, M-1, 4, {self.ncoef // 2 - 1}], got {via.shape}")
-        coef, dur, status = _out_arrays(None, ((N, max(M, 0), 4, self.ncoef), (N, max(M, 0)), (N,)))
-        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)      # noqa: E731
-        with self._lock:
-            self._ck(self._lib.msnap_solve_gates(self._h, N, M, pwp, pt, shared, ps, pe, pf, pv, vp(coef), vp(dur),
-                                                 vp(status)))
-        return coef, dur, status
+        return (fix, pf), (via, pv)
 
     def solve_gates_device(self, n_drones, n_seg, wp, t, shared_times, start, end, fix, via, coef, dur, status):
         """Device pointers (start / end may be None: rest; fix None: no gates, via may then be None too), asynchronous
@@ -928,6 +934,29 @@ class Context:
         self._optimize_times_device("msnap_optimize_times_free_device", n_drones, n_seg, wp, t, shared_times,
                                     (_ptr(start), _ptr(end)), weights, (_ptr(time_weight),), min_fraction, max_iter,
                                     tol, t_out, coef, dur, status, cost, pg, iters)
+
+    def optimize_times_gates_max_segments(self) -> int:
+        """Largest segment count optimize_times_gates takes at this context's order (and at most max_segments)."""
+        return self._mode_max_segments(self._lib.msnap_optimize_times_gates_max_segments)
+
+    def optimize_times_gates(self, wp, t, start=None, end=None, fix=None, via=None, weights=(1, 1, 1, 1),
+                             min_fraction=0.1, max_iter=200, tol=1e-4):
+        """optimize_times_states through gates (msnap_optimize_times_gates): fix [N, M-1] int32 and via [N, M-1, 4, K-1]
+        as solve_gates takes them (fix None: no gates, optimize_times_states' bits).  Waypoints, both end states, the
+        gate values in physical units and the total duration are kept; coef, dur are solve_gates' for t_out."""
+        N, m = _waypoints_times(wp, t)[4:6]
+        (fix, pf), (via, pv) = self._gate_blocks(fix, via, N, m - 1)      # (the arrays live until the call returns)
+        return self._optimize_times("msnap_optimize_times_gates", wp, t, (start, end), weights, (), min_fraction,
+                                    max_iter, tol, gates=(pf, pv))
+
+    def optimize_times_gates_device(self, n_drones, n_seg, wp, t, shared_times, start, end, fix, via, weights,
+                                    min_fraction, max_iter, tol, t_out, coef, dur, status, cost=None, pg=None,
+                                    iters=None):
+        """Device pointers (start / end may be None: rest; fix None: no gates, via may then be None too),
+        asynchronous; `weights` is a host sequence of 4."""
+        self._optimize_times_device("msnap_optimize_times_gates_device", n_drones, n_seg, wp, t, shared_times,
+                                    (_ptr(start), _ptr(end), _ptr(fix), _ptr(via)), weights, (), min_fraction,
+                                    max_iter, tol, t_out, coef, dur, status, cost, pg, iters)
 
     def eval_state(self, coef, dur, tq):
         """Full state of each drone at its own time tq [N] (msnap_eval_state): pos [N, 4], deriv [N, 4, K-1] with

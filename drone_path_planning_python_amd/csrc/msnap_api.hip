@@ -1,6 +1,6 @@
 // C-ABI of libmsnap.so (include/msnap.h): context management, host-pointer
 // wrappers, stream / timer plumbing.  All compute happens in the HIP kernels of the other translation units (SRCS of
-// the Makefile, one subsystem each).  The units of the later subsystems -- msnap_timeopt.hip for all four
+// the Makefile, one subsystem each).  The units of the later subsystems -- msnap_timeopt.hip for all five
 // time-allocation modes, msnap_clearance.hip, msnap_pairs.hip, msnap_mesh_clearance.hip, msnap_extent.hip,
 // msnap_states.hip, msnap_periodic.hip -- hold their own entry points, on the helpers of msnap_api_util.h; there is no
 // CPU fallback.

@@ -1,5 +1,5 @@
 // What the translation units that define C-ABI entry points share (msnap_api.hip and every unit that holds its own
-// subsystem's entries; msnap_timeopt.hip holds those of all four time-allocation modes): the argument checks, the entry
+// subsystem's entries; msnap_timeopt.hip holds those of all five time-allocation modes): the argument checks, the entry
 // macro and the one staging helper every host-pointer call goes through.
 #pragma once
 

@@ -160,12 +160,14 @@ int launch_snap_cost(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef
 int launch_snap_cost_grad(msnap_ctx *ctx, int n_drones, int n_seg, const double *coef, double *grad);
 // time allocation (msnap_timeopt.hip): the whole iteration of a batch in one launch.  The modes: rest to rest
 // (msnap_optimize_times), from and to given end states (_states), closed loop, the trial being the periodic solve
-// (_periodic), end states with the total duration free (_free).
-enum TimeoptMode : int { kTimeoptRest = 0, kTimeoptEnds = 1, kTimeoptRing = 2, kTimeoptFree = 3 };
-// One allocation call, in the order of msnap_optimize_times_free's parameters.  Every mode reads all fields but these:
-// start / end ([n_drones][4][K-1], or null for rest) are read with kTimeoptEnds and kTimeoptFree only, time_weight
-// ([n_drones], required) with kTimeoptFree only; an entry whose mode has none leaves them null.  cost, pg, iters may be
-// null in every mode.  weights is a host array of 4; every other pointer is the host's in a host entry and the device's
+// (_periodic), end states with the total duration free (_free), end states with prescribed derivatives at interior
+// waypoints (_gates).
+enum TimeoptMode : int { kTimeoptRest = 0, kTimeoptEnds = 1, kTimeoptRing = 2, kTimeoptFree = 3, kTimeoptGates = 4 };
+// One allocation call, in the order of msnap_optimize_times_free's parameters, the gates behind them.  Every mode reads
+// all fields but these: start / end ([n_drones][4][K-1], or null for rest) are read with kTimeoptEnds, kTimeoptFree and
+// kTimeoptGates only, time_weight ([n_drones], required) with kTimeoptFree only, fix / via ([n_drones][n_seg-1] masks
+// and [..][4][K-1] values, fix null: no gates) with kTimeoptGates only; an entry whose mode has none leaves them null.
+// cost, pg, iters may be null in every mode.  weights is a host array of 4; every other pointer is the host's in a host entry and the device's
 // from launch_optimize_times on.
 struct TimeoptCall {
   int n_drones, n_seg;
@@ -179,15 +181,18 @@ struct TimeoptCall {
   int32_t *status;
   double *cost, *pg;
   int32_t *iters;
+  const int32_t *fix = nullptr;
+  const double *via = nullptr;
 };
 // the one launch other code calls, asynchronous on ctx->stream
 int launch_optimize_times(msnap_ctx *ctx, int mode, const TimeoptCall &call);
 // (what it calls for the modes whose instances are objects of their own: msnap_timeopt_periodic.hip,
-// msnap_timeopt_free.hip)
+// msnap_timeopt_free.hip, msnap_timeopt_gates.hip)
 int launch_optimize_times_ring(msnap_ctx *ctx, const TimeoptCall &call);
 int launch_optimize_times_free(msnap_ctx *ctx, const TimeoptCall &call);
-// largest n_seg whose per-tile state fits LDS (80 at order 7, 58 at order 9; kTimeoptEnds: see DESIGN.md K8;
-// kTimeoptRing: 48, 33)
+int launch_optimize_times_gates(msnap_ctx *ctx, const TimeoptCall &call);
+// largest n_seg whose per-tile state fits LDS (80 at order 7, 58 at order 9; kTimeoptEnds and kTimeoptGates: see
+// DESIGN.md K8; kTimeoptRing: 48, 33)
 int timeopt_max_segments(int khalf, int mode);
 // The tile solves beside K1 (entries: msnap_states.hip): from and to given end states (msnap_solve_states), with
 // prescribed derivatives at interior knots as well (msnap_solve_gates), closed loop (msnap_solve_periodic).

@@ -39,11 +39,20 @@
 // check, a raise of short durations nobody pays for, cost and gradient with the time term, the direction, a last knot
 // that moves, and the current total in the stopping measure.
 //
-// One kernel text, three translation units: msnap_timeopt.hip instantiates the rest-to-rest and end-state modes and
+// Gates (msnap_optimize_times_gates): timeopt_kernel<K, kTimeoptGates>, the end-state mode whose
+// interior knots may carry prescribed derivatives.  A gated component of u_i is data instead of a stationary unknown,
+// which the envelope argument does not look at (as it does not look at the end states), so the gradient is the same
+// expression.  What differs from kTimeoptEnds is one `if constexpr`: the trial hands its lane's ChainGates to
+// chain_solve's GATES, which fetches masks and values from global memory one knot ahead as K21 does (no LDS of their
+// own: the segment caps are the end-state mode's), and the first trial's `invalid` joins the input checks.  GATES is
+// written beside FREE, not against it: a free total through gates is a matter of one more instance.
+//
+// One kernel text, four translation units: msnap_timeopt.hip instantiates the rest-to-rest and end-state modes and
 // holds every mode's entry points and launch_optimize_times, the one launch function they call;
-// msnap_timeopt_periodic.hip instantiates the ring mode and msnap_timeopt_free.hip the free-total mode, each behind one
-// launch function of its own -- objects of their own, so that what is held of msnap_timeopt.o (its instructions, its
-// kernel count, no register-pressure copy) stays true.  Everything here has internal linkage.
+// msnap_timeopt_periodic.hip instantiates the ring mode, msnap_timeopt_free.hip the free-total mode and
+// msnap_timeopt_gates.hip the gates mode, each behind one launch function of its own -- objects of their own, so that
+// what is held of msnap_timeopt.o (its instructions, its kernel count, no register-pressure copy) stays true.
+// Everything here has internal linkage.
 #pragma once
 
 #include <math.h>
@@ -82,6 +91,11 @@ struct TimeoptEndsArgs : TimeoptArgs {
 struct TimeoptFreeArgs : TimeoptEndsArgs {
   const double *time_weight;
 };
+// GATES: the masks [n_drones][M-1] and values [n_drones][M-1][4][K-1] (msnap_solve_gates' layout); fix null: no gates
+struct TimeoptGatesArgs : TimeoptEndsArgs {
+  const int32_t *fix;
+  const double *via;
+};
 
 // w_0 v_0 + .. + w_3 v_3 over the quad, the same bits in its four lanes; an axis of weight 0 is not looked at
 __device__ __forceinline__ double quad_weighted_sum(double v, double wa) {
@@ -90,16 +104,20 @@ __device__ __forceinline__ double quad_weighted_sum(double v, double wa) {
 }
 
 template <int MODE>
-using TimeoptArgsOf = std::conditional_t<MODE == kTimeoptFree, TimeoptFreeArgs,
-                                         std::conditional_t<MODE == kTimeoptEnds, TimeoptEndsArgs, TimeoptArgs>>;
+using TimeoptArgsOf = std::conditional_t<
+    MODE == kTimeoptGates, TimeoptGatesArgs,
+    std::conditional_t<MODE == kTimeoptFree, TimeoptFreeArgs,
+                       std::conditional_t<MODE == kTimeoptEnds, TimeoptEndsArgs, TimeoptArgs>>>;
 
 // ENDS: the end knots' derivative vectors u_0, u_M are data (msnap_optimize_times_states); the trial is chain_solve
 // RING: the last waypoint is joined to the first (msnap_optimize_times_periodic), the trial is ring_solve
 // FREE: ENDS with the total duration an unknown (msnap_optimize_times_free): F = J + k_T t[M], no projection
+// GATES: ENDS with prescribed derivatives at interior knots (msnap_optimize_times_gates): chain_solve's GATES
 template <int K, int MODE>
 __global__ void __launch_bounds__(kWave)
 timeopt_kernel(const TimeoptArgsOf<MODE> p) {
-  constexpr bool FREE = MODE == kTimeoptFree, ENDS = MODE == kTimeoptEnds || FREE, RING = MODE == kTimeoptRing;
+  constexpr bool FREE = MODE == kTimeoptFree, GATES = MODE == kTimeoptGates;
+  constexpr bool ENDS = MODE == kTimeoptEnds || FREE || GATES, RING = MODE == kTimeoptRing;
   constexpr int NU = K - 1, NC = 2 * K, PITCH = NU | 1;
 
   extern __shared__ __attribute__((aligned(16))) double lds[];
@@ -205,6 +223,18 @@ timeopt_kernel(const TimeoptArgsOf<MODE> p) {
     }
   }
 
+  // GATES: this lane's masks and values, in global memory as the caller gave them (the replayed drone's for lanes past
+  // the tile's end); gatefault: a trial met a mask out of range or a non-finite value under a set bit
+  [[maybe_unused]] const int32_t *frow = nullptr;
+  [[maybe_unused]] const double *grow = nullptr;
+  [[maybe_unused]] bool gatefault = false;
+  if constexpr (GATES) {
+    if (p.fix != nullptr && M >= 2) {
+      frow = p.fix + d * (size_t)knots;
+      grow = p.via + (d * (size_t)knots * 4 + a) * NU;
+    }
+  }
+
   // ---------------- one trial: solve for the knots sT, cost, gradient (EMIT: the coefficients leave) ----------------
   auto trial = [&](auto emit, const double *sT, double *sGrad, bool bad, double &Jw, bool &singular) {
     constexpr bool EMIT = decltype(emit)::value;
@@ -238,7 +268,13 @@ timeopt_kernel(const TimeoptArgsOf<MODE> p) {
         else u0[q] = uM[q] = 0.0;
       }
       const ChainLane cl = {lw, sT, sX + dloc, sG + dloc, sZ, TD};
-      chain_solve<K, ENDS, ENDS && EMIT>(cl, M, u0, uM, singular, seg);
+      if constexpr (GATES) {
+        ChainGates cg = {frow, grow, false};
+        chain_solve<K, true, EMIT, 0, true>(cl, M, u0, uM, singular, seg, ChainUnchecked{}, &cg);
+        gatefault |= cg.invalid;
+      } else {
+        chain_solve<K, ENDS, ENDS && EMIT>(cl, M, u0, uM, singular, seg);
+      }
     }
     Jw = quad_weighted_sum(Ja, wa);
     if constexpr (FREE) Jw = Jw + kT * sT[M * TD];      // F = J + k_T sum_i T_i
@@ -325,6 +361,7 @@ timeopt_kernel(const TimeoptArgsOf<MODE> p) {
   double J;
   bool sing0;
   trial(std::false_type{}, sTc, sGc, false, J, sing0);
+  if constexpr (GATES) nonfinite |= gatefault;      // (the gates are data, seen whole by this first solve)
   const int st_in = drone_status(nonfinite, badtime, false);
   const int st = st_in ? st_in : (usable(sing0, J) ? MSNAP_ST_OK : MSNAP_ST_SINGULAR);
   const double J0 = J;
@@ -403,11 +440,13 @@ timeopt_kernel(const TimeoptArgsOf<MODE> p) {
   }
 }
 
-// doubles of LDS one tile of TD drones needs (kTimeoptEnds: with the two state images; kTimeoptRing: with H and Z2)
+// doubles of LDS one tile of TD drones needs (kTimeoptEnds, kTimeoptFree, kTimeoptGates: with the two state images --
+// the gates stay in global memory; kTimeoptRing: with H and Z2)
 constexpr size_t timeopt_lds_words(int khalf, int M, int TD, int mode) {
   const size_t nu = (size_t)khalf - 1, knots = (size_t)M - 1, m = (size_t)M;
   const size_t tr = khalf == 4 ? 0 : (size_t)khalf * kTrPitch * 2;
-  const size_t states = mode == kTimeoptEnds || mode == kTimeoptFree ? 2 * (size_t)TD * 4 * (nu | 1) : 0;
+  const size_t states =
+      mode == kTimeoptEnds || mode == kTimeoptFree || mode == kTimeoptGates ? 2 * (size_t)TD * 4 * (nu | 1) : 0;
   const size_t ring = mode == kTimeoptRing ? (size_t)TD * (nu * nu + 4 * nu) * knots : 0;
   return tr + (size_t)TD * ((m + 1) * 4 + (m + 1) + 2 * (m + 1) + 4 * m + nu * nu * knots + 4 * nu * knots) + states +
          ring;
@@ -423,6 +462,12 @@ constexpr int timeopt_tile_segments(int khalf, int TD, int mode) {
 static_assert(timeopt_tile_segments(4, 16, kTimeoptRing) == 24 && timeopt_tile_segments(5, 16, kTimeoptRing) == 17 &&
                   timeopt_tile_segments(4, 8, kTimeoptRing) == 48 && timeopt_tile_segments(5, 8, kTimeoptRing) == 33,
               "DESIGN.md K16 and include/msnap.h quote these");
+// gates: no LDS of their own, so the end-state mode's caps
+static_assert(timeopt_tile_segments(4, 16, kTimeoptGates) == 39 && timeopt_tile_segments(5, 16, kTimeoptGates) == 28 &&
+                  timeopt_tile_segments(4, 8, kTimeoptGates) == 79 && timeopt_tile_segments(5, 8, kTimeoptGates) == 57 &&
+                  timeopt_tile_segments(4, 8, kTimeoptGates) == timeopt_tile_segments(4, 8, kTimeoptEnds) &&
+                  timeopt_tile_segments(5, 8, kTimeoptGates) == timeopt_tile_segments(5, 8, kTimeoptEnds),
+              "DESIGN.md K22 and include/msnap.h quote these");
 
 // One mode's launch of a call whose pointers are the device's (TimeoptCall, msnap_internal.h): the tile size, the
 // kernels' dynamic-LDS limit (raised to the full 160 KiB once per context and mode: a function attribute is a property
@@ -459,9 +504,13 @@ int timeopt_launch(msnap_ctx *ctx, const TimeoptCall &c) {
   a.cost = c.cost;
   a.pg = c.pg;
   a.iters = c.iters;
-  if constexpr (MODE == kTimeoptEnds || MODE == kTimeoptFree) {
+  if constexpr (MODE == kTimeoptEnds || MODE == kTimeoptFree || MODE == kTimeoptGates) {
     a.start = c.start;
     a.end = c.end;
+  }
+  if constexpr (MODE == kTimeoptGates) {
+    a.fix = c.fix;
+    a.via = c.via;
   }
   if constexpr (MODE == kTimeoptFree) a.time_weight = c.time_weight;
   const int ntiles = (c.n_drones + TD - 1) / TD;

@@ -381,21 +381,10 @@ class DeviceCompute:
         """(coef, dur, status) of solve_states with prescribed derivatives at interior waypoints: `fix` [n, M-1] int32
         -- bit q-1 of entry i-1: the q-th derivative at waypoint i is prescribed, on all four axes -- and `via`
         [n, M-1, 4, K-1] float64 the values (entries under a clear bit are not used).  fix None: no gates."""
-        torch = self.torch
         n, m, _ = wp.shape
         M = m - 1
         start, end = self._end_states("solve_gates", n, start, end)
-        if fix is not None:
-            if tuple(fix.shape) != (n, max(M - 1, 0)) or fix.dtype != torch.int32:
-                raise ValueError("solve_gates: fix must be an int32 tensor [n, M-1]")
-            if via is None:
-                raise ValueError("solve_gates: fix needs via")
-            fix = fix.contiguous()
-        if via is not None:
-            nd = self.ctx.ncoef // 2 - 1
-            if tuple(via.shape) != (n, max(M - 1, 0), 4, nd) or via.dtype != torch.float64:
-                raise ValueError(f"solve_gates: via must be a float64 tensor [n, M-1, 4, {nd}]")
-            via = via.contiguous()
+        fix, via = self._gates("solve_gates", n, M, fix, via)
         coef, dur, status = self._solve_outs("solve_gates", n, M)
         if n:
             self.ctx.solve_gates_device(n, M, wp.contiguous(), t.contiguous(), t.dim() == 1, start, end, fix, via, coef,
@@ -445,6 +434,34 @@ class DeviceCompute:
         return self._optimize_times("optimize_times_free", self.ctx.optimize_times_free_device, wp, t, states, weights,
                                     (kt,), min_fraction, max_iter, tol)
 
+    def optimize_times_gates(self, wp, t, start=None, end=None, fix=None, via=None, weights=(1, 1, 1, 1),
+                             min_fraction=0.1, max_iter=200, tol=1e-4):
+        """(t_out, coef, dur, status, info) of the time allocation through gates: arguments as solve_gates plus the
+        four of Context.optimize_times.  The gate values are kept in physical units while the knots move; coef is
+        solve_gates' at t_out; fix None is optimize_times_states.  info as there."""
+        n, m, _ = wp.shape
+        states = self._end_states("optimize_times_gates", n, start, end)
+        gates = self._gates("optimize_times_gates", n, m - 1, fix, via)
+        return self._optimize_times("optimize_times_gates", self.ctx.optimize_times_gates_device, wp, t,
+                                    states + gates, weights, (), min_fraction, max_iter, tol)
+
+    def _gates(self, method, n, M, fix, via):
+        """`fix` / `via` of `method` checked -- None, or an int32 tensor [n, M-1] with a float64 tensor
+        [n, M-1, 4, K-1] -- and contiguous."""
+        torch = self.torch
+        if fix is not None:
+            if tuple(fix.shape) != (n, max(M - 1, 0)) or fix.dtype != torch.int32:
+                raise ValueError(f"{method}: fix must be an int32 tensor [n, M-1]")
+            if via is None:
+                raise ValueError(f"{method}: fix needs via")
+            fix = fix.contiguous()
+        if via is not None:
+            nd = self.ctx.ncoef // 2 - 1
+            if tuple(via.shape) != (n, max(M - 1, 0), 4, nd) or via.dtype != torch.float64:
+                raise ValueError(f"{method}: via must be a float64 tensor [n, M-1, 4, {nd}]")
+            via = via.contiguous()
+        return fix, via
+
     def _end_states(self, method, n, start, end):
         """`start` / `end` of `method` checked -- None, or a float64 tensor [n, 4, K-1] -- and contiguous."""
         nd = self.ctx.ncoef // 2 - 1
@@ -462,7 +479,8 @@ class DeviceCompute:
 
     def _optimize_times(self, method, device_entry, wp, t, states, weights, time_weight, min_fraction, max_iter, tol):
         """The allocators' one body: `device_entry` is Context's `<method>_device`; `states` its checked (start, end)
-        and `time_weight` its (tensor [n],) -- () where it takes none."""
+        -- with (fix, via) behind them for the gates mode -- and `time_weight` its (tensor [n],); () where it takes
+        none."""
         torch, out = self.torch, self._out
         n, m, _ = wp.shape
         M = m - 1
@@ -1167,10 +1185,10 @@ def replan(compute, coef, dur, t_r, wp_new, t_new, end=None, optimize=None, gate
     then a starting guess, and a larger weight buys a shorter path at a higher cost.
 
     `gates`: (fix, via) as `compute.solve_gates` takes them -- fix [N, M' - 1] int32, via [N, M' - 1, 4, K-1], entry
-    i-1 for `wp_new[:, i-1]`, the new path's interior waypoint i; the last new waypoint takes `end`.  Time allocation
-    with gates is not built: `gates` together with `optimize` raises ValueError."""
+    i-1 for `wp_new[:, i-1]`, the new path's interior waypoint i; the last new waypoint takes `end`.  `gates`
+    together with `optimize` raises ValueError here: time allocation through gates is `replan_gated`."""
     if gates is not None and optimize is not None:
-        raise ValueError("replan: gates and optimize do not combine (time allocation with gates is not built)")
+        raise ValueError("replan: gates and optimize do not combine here; replan_gated allocates times through gates")
     wp, t, pos, deriv = _replan_inputs(compute, coef, dur, t_r, wp_new, t_new)
     if gates is not None:
         fix, via = gates
@@ -1184,6 +1202,28 @@ def replan(compute, coef, dur, t_r, wp_new, t_new, end=None, optimize=None, gate
                              f"{sorted(unknown)}")
         entry = compute.optimize_times_free if "time_weight" in optimize else compute.optimize_times_states
         _, new_coef, new_dur, status, _ = entry(wp, t, start=deriv, end=end, **optimize)
+    return new_coef, new_dur, status, (pos, deriv)
+
+
+def replan_gated(compute, coef, dur, t_r, wp_new, t_new, gates, end=None, optimize=None):
+    """`replan` through gates, with or without time allocation: arguments and the returned tuple as `replan`, `gates`
+    = (fix, via) as described there.  `optimize` None: `compute.solve_gates` at `t_new` as given.  A dict with any of
+    weights / min_fraction / max_iter / tol: `compute.optimize_times_gates` moves the interior times first -- the state
+    at `t_r`, the waypoints, `end`, the last time and the gate values in physical units are kept.  "time_weight" raises
+    ValueError: a free total duration through gates is not built."""
+    fix, via = gates
+    if optimize is not None:
+        if "time_weight" in optimize:
+            raise ValueError("replan_gated: time_weight (a free total duration) does not combine with gates: not built")
+        unknown = set(optimize) - {"weights", "min_fraction", "max_iter", "tol"}
+        if unknown:
+            raise ValueError(f"replan_gated: optimize takes weights, min_fraction, max_iter, tol, not {sorted(unknown)}")
+    wp, t, pos, deriv = _replan_inputs(compute, coef, dur, t_r, wp_new, t_new)
+    if optimize is None:
+        new_coef, new_dur, status = compute.solve_gates(wp, t, start=deriv, end=end, fix=fix, via=via)
+    else:
+        _, new_coef, new_dur, status, _ = compute.optimize_times_gates(wp, t, start=deriv, end=end, fix=fix, via=via,
+                                                                        **optimize)
     return new_coef, new_dur, status, (pos, deriv)
 
 

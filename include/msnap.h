@@ -794,8 +794,8 @@ int msnap_eval_state_device(msnap_ctx *ctx, int n_drones, int n_seg, const doubl
  *            msnap_solve_gates_max_segments returns MSNAP_EORDER for any other order.
  * MSNAP_EINVAL: as msnap_solve_states, and fix given without via.  n_drones == 0 is a no-op.  A drone's outputs are
  * bit-identical whatever its place in the batch, the batch size, and host versus device entry.  The device version
- * only launches.  Masks are per drone, not per axis, and the end states are always whole; the time-allocation and
- * periodic solves take no gates.
+ * only launches.  Masks are per drone, not per axis, and the end states are always whole; the time allocation
+ * through gates is msnap_optimize_times_gates, and the periodic solves take no gates.
  */
 int msnap_solve_gates(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, const double *t, int shared_times,
                       const double *start, const double *end,          /* as msnap_solve_states */
@@ -1071,6 +1071,55 @@ int msnap_optimize_times_free_device(msnap_ctx *ctx, int n_drones, int n_seg, co
                                      int max_iter, double tol, double *t_out, double *coef, double *dur,
                                      int32_t *status, double *cost, double *pg, int32_t *iters);
 int msnap_optimize_times_free_max_segments(int order);       /* largest n_seg the entry takes; < 0: MSNAP_EORDER */
+
+/* msnap_optimize_times_gates: time allocation through gates -- msnap_optimize_times_states on a path
+ * whose interior waypoints may carry prescribed derivatives.  A path with gates is where a guessed time grid costs
+ * most, and a uniform stretch (msnap_retime_to_limits) cannot mend it: it divides the prescribed velocities.
+ * Arguments as msnap_optimize_times_states with fix and via after end, in msnap_solve_gates' layout and meaning:
+ * fix [n_drones][n_seg-1] int32 masks (bit q-1: the q-th derivative at that interior waypoint is prescribed, on all four
+ * axes), via [n_drones][n_seg-1][4][K-1] the values, K = (order + 1) / 2; an entry under a clear bit is never used and
+ * may be NaN.  Objective, feasible set, floor, direction, step rules, stopping measure, cost / pg / iters and the method
+ * are msnap_optimize_times's, word for word, with "the solve for T" read as msnap_solve_gates's: in Hermite form
+ * J*(T) = min_u J(u, T), a gated component of u_i is data instead of a stationary unknown, which the envelope argument
+ * does not look at, so dJ/dT_i = -sum_a weights[a] E_i,a holds as it does with given end states.
+ *   kept        the waypoints, both end states, the gate values IN PHYSICAL UNITS (a velocity gate is met in m/s at
+ *               whatever time its waypoint is crossed), t_out[0] == 0 and t_out[M] == t[M] bit for bit;
+ *   moves       the interior knot times, and with them every derivative no gate prescribes;
+ *   coef, dur   dur[i] = t_out[i+1] - t_out[i] bit for bit; coef is what msnap_solve_gates returns for t_out (same fix,
+ *               via, start, end), bit for bit, so the gates are honoured as that entry states: on the segment that
+ *               leaves a gated waypoint coef[i][a][q] * q! is the prescribed value within 4 * 2^-52 relative, on the
+ *               segment that arrives it is met as every interior waypoint's continuity is met; the end states through
+ *               msnap_eval_state as msnap_optimize_times_states promises them (the same refinement step on the last
+ *               segment, once, when the coefficients leave; cost, pg and the decisions use the unrefined ones);
+ *   status      as msnap_optimize_times_states, and MSNAP_ST_NONFINITE for a NaN / Inf via entry under a set bit or a
+ *               fix entry that is negative or >= 2^(K-1): seen by the solve at the input times, before any step.  A
+ *               failed drone gets NaN coef, t_out, dur, cost, pg and iters 0, and disturbs no other drone.
+ * fix == NULL: no gates, via may be NULL too -- every output is msnap_optimize_times_states', bit for bit; so is it with
+ * a mask of zeros.  Guarantees as there: every dur[i] >= T_min (1 - 1e-12), cost[1] <= cost[0], max_iter = 0 returns the
+ * (raised) input times; a drone's outputs are bit-identical whatever its place in the batch, the batch size, or host
+ * versus device entry.  A waypoint with every bit set decouples its two sides; the times are still allocated over the
+ * whole path, since the sum is shared.
+ * n_seg: 1 .. msnap_optimize_times_gates_max_segments(order) = 79 at order 7, 57 at order 9 -- msnap_optimize_times_
+ * states' range (16-drone tiles up to 39 and 28 segments): masks and values stay in global memory and take no LDS --
+ * and at most max_segments; MSNAP_ESEGMENTS above.  Note that msnap_solve_gates itself ends at 47 / 32.  The query
+ * returns MSNAP_EORDER for any other order.  MSNAP_EINVAL as msnap_optimize_times_states, and for fix given without
+ * via; n_drones == 0 is a no-op.  The device version only launches (no synchronisation, no context buffer: the capture
+ * rules are msnap_optimize_times_device's).  Not built: a free total duration through gates, gates on closed loops,
+ * per-axis masks.
+ */
+int msnap_optimize_times_gates(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, const double *t,
+                               int shared_times, const double *start /* [n_drones][4][K-1] or NULL */,
+                               const double *end /* [n_drones][4][K-1] or NULL */,
+                               const int32_t *fix /* [n_drones][n_seg-1] or NULL */,
+                               const double *via /* [n_drones][n_seg-1][4][K-1] or NULL */, const double weights[4],
+                               double min_fraction, int max_iter, double tol, double *t_out, double *coef, double *dur,
+                               int32_t *status, double *cost, double *pg, int32_t *iters);
+int msnap_optimize_times_gates_device(msnap_ctx *ctx, int n_drones, int n_seg, const double *wp, const double *t,
+                                      int shared_times, const double *start, const double *end, const int32_t *fix,
+                                      const double *via, const double weights[4], double min_fraction, int max_iter,
+                                      double tol, double *t_out, double *coef, double *dur, int32_t *status,
+                                      double *cost, double *pg, int32_t *iters);
+int msnap_optimize_times_gates_max_segments(int order);      /* largest n_seg the entry takes; < 0: MSNAP_EORDER */
 
 /* ---- drone-vs-drone formation pass (new capability; no reference) -------
  * rows: the n_rows drones this caller owns (a shard), starting at global index

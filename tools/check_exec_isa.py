@@ -21,7 +21,7 @@ it is written again, so any vector instruction there is reported -- it can only 
                                                               msnap_limits.o msnap_timeopt.o msnap_clearance.o msnap_pairs.o msnap_mesh_clearance.o
                                                               msnap_extent.o msnap_states.o msnap_periodic.o msnap_timeopt_periodic.o
                                                               msnap_timeopt_free.o msnap_conflict.o msnap_mesh_conflict.o
-                                                              msnap_halfspace.o msnap_gates.o)
+                                                              msnap_halfspace.o msnap_gates.o msnap_timeopt_gates.o)
     python tools/check_exec_isa.py --latches [object files ...]      the kernels that still hold such a loop, with their latch counts
 """
 from __future__ import annotations
@@ -62,6 +62,7 @@ K18_OBJS = [os.path.join(CSRC, f) for f in ("msnap_conflict.o",)]
 K19_OBJS = [os.path.join(CSRC, f) for f in ("msnap_mesh_conflict.o",)]
 K20_OBJS = [os.path.join(CSRC, f) for f in ("msnap_halfspace.o",)]
 K21_OBJS = [os.path.join(CSRC, f) for f in ("msnap_gates.o",)]
+K22_OBJS = [os.path.join(CSRC, f) for f in ("msnap_timeopt_gates.o",)]
 
 
 def disassemble(obj):
@@ -234,13 +235,13 @@ def check(obj):
 
 def main():
     if sys.argv[1:2] == ["--latches"]:      # the census: one line per kernel with a lane-retiring loop
-        for obj in sys.argv[2:] or DEFAULT_OBJS + MORE_OBJS + K11_OBJS + K12_OBJS + K13_OBJS + K15_OBJS + K16_OBJS + K17_OBJS + K18_OBJS + K19_OBJS + K20_OBJS + K21_OBJS:
+        for obj in sys.argv[2:] or DEFAULT_OBJS + MORE_OBJS + K11_OBJS + K12_OBJS + K13_OBJS + K15_OBJS + K16_OBJS + K17_OBJS + K18_OBJS + K19_OBJS + K20_OBJS + K21_OBJS + K22_OBJS:
             found = lane_latches(obj)
             print(f"check_exec_isa: {os.path.basename(obj)}: {sum(found.values())} lane-retiring loop latches in {len(found)} kernels")
             for k, n in sorted(found.items()):
                 print(f"    {n:3d}  {k}")
         return 0
-    objs = sys.argv[1:] or DEFAULT_OBJS + MORE_OBJS + K11_OBJS + K12_OBJS + K13_OBJS + K15_OBJS + K16_OBJS + K17_OBJS + K18_OBJS + K19_OBJS + K20_OBJS + K21_OBJS
+    objs = sys.argv[1:] or DEFAULT_OBJS + MORE_OBJS + K11_OBJS + K12_OBJS + K13_OBJS + K15_OBJS + K16_OBJS + K17_OBJS + K18_OBJS + K19_OBJS + K20_OBJS + K21_OBJS + K22_OBJS
     rc = 0
     for obj in objs:
         n_kernels, n_spill, bad = check(obj)
