@@ -147,7 +147,7 @@ def one_drone(job):
         best = ta if Ja <= Jb else rb["t_out"]
         act = np.flatnonzero(np.diff(best) - Tmin <= 1e-6 * Tmin)
         out = dict(J0=J0, J_ref=Jref, J_slsqp=Ja, J_descent=Jb, J4=J4, gap4=(J4 - Jref) / Jref, conv4=r4["pg"] <= 1e-4,
-                   active=len(act), iters4=r4["iters"], solves4=r4["solves"], n_below=int((np.diff(t) < Tmin).sum()),
+                   active=len(act), act=act, iters4=r4["iters"], solves4=r4["solves"], n_below=int((np.diff(t) < Tmin).sum()),
                    p_t=[], p_iters=[], p_trials=[], p_margin=[], prefix_sens=[])
         for mi in (1, 3):
             r, trace = wide.prefix(wp, t, w, mf, mi, ncoef)
